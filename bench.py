@@ -2,7 +2,12 @@
 """bench.py -- images/sec of the u-LLaVA multimodal forward on MI355X through the HIP path, with the roofline of the dominant
 kernel and a CPU-oracle baseline.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps of each workload the run times, rank 0 writes what the last timed step returned (logits; for RES
+also the masks and boxes) to DIR/<workload>.<key>.npy as float32 (float64 for float64 / integer outputs), 60 MiB in all; an output larger
+than its share is written as a seeded stratified sample of its flattened elements (DIR/manifest.json: shapes, sample sizes, seed).  Inputs
+and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: this script launches N ranks itself (re-exec under `torch.distributed.run`, one rank per GPU, RCCL over xGMI) unless it
 is already running inside such a launch (WORLD_SIZE set by the driver's own `python -m torch.distributed.run ... bench.py`).
@@ -591,9 +596,68 @@ def check_finite(out):
         raise SystemExit("bench.py: the last timed step returned no tensor to check")
 
 
-def timed_steps(step, steps, warmup, dist, batch, device):
+DUMP_BUDGET = 60 * 2**20         # --dump-outputs: bytes of array data in all, below 64 MB with room for the .npy headers and manifest
+DUMP_SKIP = ("past_key_values", "hidden_states", "gt_masks", "gt_boxes")     # caches and echoed inputs, as in check_finite
+
+
+def output_arrays(out, prefix):
+    """(name, tensor) for every tensor the last step returned, in a fixed order: dict keys in insertion order, list items by index."""
+    found = []
+
+    def walk(o, name):
+        if isinstance(o, torch.Tensor):
+            found.append((name, o.detach()))
+        elif isinstance(o, dict):
+            for k, v in dict.items(o):
+                if k not in DUMP_SKIP and v is not None:
+                    walk(v, f"{name}.{k}")
+        elif isinstance(o, (list, tuple)):
+            for i, v in enumerate(o):
+                walk(v, f"{name}.{i}")
+
+    walk(out, prefix)
+    return found
+
+
+def sample_index(n, m, seed=0):
+    """m distinct sorted flat indices out of n: [0, n) cut into m equal strata, one seeded uniform pick in each."""
+    g = torch.Generator().manual_seed(seed)
+    edges = (torch.arange(m + 1, dtype=torch.float64) * (n / m)).floor().long()
+    edges[-1] = n
+    lo, width = edges[:-1], edges[1:] - edges[:-1]
+    return lo + (torch.rand(m, generator=g, dtype=torch.float64) * width).long().clamp_max_(width - 1)
+
+
+def dump_outputs(out, directory, prefix, budget):
+    """Write what one step returned as <directory>/<prefix>.<key>.npy (float64 for float64 / integer tensors, float32 otherwise) within
+    `budget` bytes: the smallest arrays first, each whole if it fits its share of what is left, else a seeded stratified sample of it
+    (flattened, 1-D).  Returns the manifest entries (shape, dtype, and which elements a sample holds)."""
+    import numpy as np
+    arrays = output_arrays(out, prefix)
+    os.makedirs(directory, exist_ok=True)
+    left, todo, manifest = budget, len(arrays), {}
+    for name, t in sorted(arrays, key=lambda nt: nt[1].numel()):
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        dt, item = (torch.float64, 8) if wide else (torch.float32, 4)
+        n, m = t.numel(), max(1, (left // todo) // item)
+        rec = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "saved_as": str(dt).replace("torch.", "")}
+        if n <= m:
+            host = t.to(dt).cpu()
+        else:
+            idx = sample_index(n, m)
+            host = t[torch.unravel_index(idx.to(t.device), t.shape)].to(dt).cpu()
+            rec["sample"] = {"elements": m, "of": n, "flat_index": "stratified: one uniform pick per stratum of n/m elements", "seed": 0}
+        np.save(os.path.join(directory, name + ".npy"), host.numpy())
+        left -= host.numel() * item
+        todo -= 1
+        manifest[name] = rec
+    return manifest
+
+
+def timed_steps(step, steps, warmup, dist, batch, device, keep=None):
     """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides; MAX elapsed over ranks and
-    SUM of images over ranks through the path's only collective (u-llava_amd.dist.global_rate)."""
+    SUM of images over ranks through the path's only collective (u-llava_amd.dist.global_rate).  keep(outputs of the last timed step) runs
+    after the timed region and before the host-enqueue probe steps, which may reuse the buffers those outputs live in."""
     D = importlib.import_module("u-llava_amd.dist")
     sync = torch.cuda.synchronize if device.type == "cuda" else (lambda: None)
     for _ in range(warmup):
@@ -613,6 +677,8 @@ def timed_steps(step, steps, warmup, dist, batch, device):
     sync()
     elapsed = time.perf_counter() - t0
     check_finite(last)                                                        # outside the timed region: the last step's outputs
+    if keep is not None:
+        keep(last)
     host_ms = None
     if device.type == "cuda":
         # host time to ENQUEUE one step (idle GPU, no synchronize inside): what a rank's Python thread costs per step -- eight of them share a
@@ -746,7 +812,12 @@ def main():
     ap.add_argument("--no-pin", action="store_true", help="do not pin ranks to CPU sets")
     ap.add_argument("--share-gpu", action="store_true", help="tests only: rank r computes on cuda:(r %% device_count); needs --backend gloo")
     ap.add_argument("--train-config", default="full", choices=sorted(TRAIN_CONFIGS), help="--workload train: which trainable set / batch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of each timed workload returned to DIR/<workload>.<key>.npy "
+                         "(float32 / float64; %d MiB in all, larger outputs as a seeded sample) plus DIR/manifest.json" % (DUMP_BUDGET >> 20))
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global DTYPE
     DTYPE = {"fp16": torch.float16, "fp32": torch.float32}.get(a.dtype, torch.bfloat16)
     if a.dtype != "bf16":                                         # the roofline / parity legs are bf16 records: not part of a side check
@@ -754,6 +825,7 @@ def main():
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)                                           # does not return
+    torch.manual_seed(0)                                         # the global generators too (LoRA dropout masks): same run, same inputs
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -792,6 +864,20 @@ def main():
         # what the collective layer itself reports: a SCALE record must show that RCCL saw N ranks, not what the launcher was asked for
         pg = {"backend": dist.get_backend(), "rccl_world_size": dist.get_world_size(), "rank": dist.get_rank()}
 
+    # --dump-outputs: rank 0 keeps the outputs of the last timed step of every workload this run times, each within an equal share
+    timed = [a.workload] + (["res"] + ([] if a.no_extra else ["c2", "c5"]) if a.workload == "c4" and not a.no_res and not a.stub else [])
+    manifest = {}
+
+    def keeper(name):
+        if a.dump_outputs is None or rank != 0:
+            return None
+
+        def keep(out):
+            manifest[name] = dump_outputs(out, a.dump_outputs, name, DUMP_BUDGET // len(timed))
+            with open(os.path.join(a.dump_outputs, "manifest.json"), "w") as f:
+                json.dump({"argv": sys.argv[1:], "outputs": manifest}, f, indent=1)
+        return keep
+
     def close_pg():
         """barrier + destroy: every timed region is over.  Rank 0's single-rank probes run AFTER this, on an otherwise idle node (in an
         N > 1 run ranks 1..N-1 have left; before round 5 they sat in a barrier while rank 0 probed between the C4 and RES timings)."""
@@ -806,7 +892,7 @@ def main():
         def step():
             time.sleep(0.01 * (1 + rank))                        # rank r is (r+1)x slower: the MAX over ranks must show
             return torch.zeros(1)
-        value, total_images, elapsed, spread = timed_steps(step, a.steps, a.warmup, dist, batch, dev)
+        value, total_images, elapsed, spread = timed_steps(step, a.steps, a.warmup, dist, batch, dev, keep=keeper(a.workload))
         close_pg()
         if rank == 0:
             import torch.distributed as dist_chk
@@ -830,7 +916,7 @@ def main():
 
     with (torch.enable_grad() if a.workload == "train" else torch.no_grad()):
         step, batch, S, cfg, desc, flops_img, model = workload_step(a.workload, dev, rank, a.batch, a.train_config)
-        value, total_images, elapsed, spread = timed_steps(step, a.steps, a.warmup, dist, batch, dev)
+        value, total_images, elapsed, spread = timed_steps(step, a.steps, a.warmup, dist, batch, dev, keep=keeper(a.workload))
         image_size, prompt = WORKLOADS[a.workload][:2]
         res_rec = None
         extra = {}
@@ -840,7 +926,7 @@ def main():
             torch.cuda.empty_cache()
             rstep, rbatch, rS, rcfg, rdesc, rflops, rmodel = workload_step("res", dev, rank)
             rsteps = max(3, min(a.steps, 10))
-            rvalue, rimgs, relapsed, rspread = timed_steps(rstep, rsteps, max(1, min(a.warmup, 2)), dist, rbatch, dev)
+            rvalue, rimgs, relapsed, rspread = timed_steps(rstep, rsteps, max(1, min(a.warmup, 2)), dist, rbatch, dev, keep=keeper("res"))
             res_rec = sub_record(rvalue, rsteps, relapsed, rspread, rbatch, rS, rdesc, rflops,
                                  sam_input="1024x1024 (valid 768x1024 -> 480x640 masks)", prompts_per_image=3)
             if not a.no_extra:
@@ -850,7 +936,7 @@ def main():
                 for wname in ("c2", "c5"):
                     wstep, wbatch, wS, _, wdesc, wflops, _ = workload_step(wname, dev, rank, model=rmodel.llm)
                     wsteps = max(3, min(a.steps, 5))
-                    wvalue, _, welapsed, wspread = timed_steps(wstep, wsteps, 2, dist, wbatch, dev)
+                    wvalue, _, welapsed, wspread = timed_steps(wstep, wsteps, 2, dist, wbatch, dev, keep=keeper(wname))
                     extra[wname] = sub_record(wvalue, wsteps, welapsed, wspread, wbatch, wS, wdesc, wflops)
                     del wstep
             del rmodel

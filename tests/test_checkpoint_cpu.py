@@ -50,6 +50,7 @@ def test_core_save_load_roundtrip(tmp_path, safe, shard_bytes):
 def test_core_load_reports_mismatches(tmp_path):
     C, M, K = pkg("configuration"), pkg("modeling_core"), pkg("checkpoint")
     m = M.UllavaCoreForCausalLM(C.UllavaCoreConfig(**_tiny_core_cfg()))
+    _randomize(m, 3)            # uninitialised storage can hold NaN, and torch.equal(NaN, NaN) is False
     d = str(tmp_path / "ckpt")
     m.save_pretrained(d, safe_serialization=False)
     sd = torch.load(os.path.join(d, "pytorch_model.bin"), weights_only=True)

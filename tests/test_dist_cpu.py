@@ -77,6 +77,59 @@ def test_bench_launches_n_ranks_itself_gloo_stub():
     assert abs(rec["value"] - rec["total_images"] / (rec["ms_per_step"] * 3e-3)) < 0.05 * rec["value"]
 
 
+def test_bench_dump_outputs_stub(tmp_path):
+    """`--dump-outputs DIR`: --steps sets the timed steps, the line carries ms_per_step, and what the last timed step returned lands in
+    DIR/<workload>.npy (float32) with a manifest (stub step, CPU)."""
+    import json
+    import subprocess
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--stub", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 4 and rec["total_images"] == 32 * 4 and rec["ms_per_step"] >= 10.0
+    assert sorted(os.listdir(d)) == ["c4.npy", "manifest.json"]
+    a = np.load(d / "c4.npy")
+    assert a.dtype == np.float32 and a.shape == (1,) and float(a[0]) == 0.0
+    assert json.load(open(d / "manifest.json"))["outputs"]["c4"]["c4"]["shape"] == [1]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--stub", "--steps", "0"], capture_output=True,
+                       text=True, timeout=120, env=env, cwd=ROOT)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """dump_outputs: the arrays a caller receives (not the KV cache), float32 / float64 only, the total within the budget, large arrays as a
+    seeded stratified sample that is the same on every call and that the manifest identifies."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    B = importlib.import_module("bench")
+    g = torch.Generator().manual_seed(7)
+    out = {"loss": torch.tensor(1.25), "logits": torch.randn(2, 300, 4001, generator=g).to(torch.bfloat16), "past_key_values": [torch.ones(5)],
+           "pred_masks": [torch.randn(3, 48, 64, generator=g), torch.zeros(0, 48, 64)], "ids": torch.arange(9), "f64": torch.randn(5, dtype=torch.float64)}
+    budget = 1 << 20
+    m1, m2 = B.dump_outputs(out, str(tmp_path / "a"), "c4", budget), B.dump_outputs(out, str(tmp_path / "b"), "c4", budget)
+    assert m1 == m2
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(f"c4.{k}.npy" for k in ("loss", "logits", "pred_masks.0", "pred_masks.1", "ids", "f64"))
+    data = 0
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+        data += x.nbytes
+    assert data <= budget
+    assert np.load(tmp_path / "a" / "c4.f64.npy").dtype == np.float64 and np.array_equal(np.load(tmp_path / "a" / "c4.ids.npy"), np.arange(9.0))
+    assert np.array_equal(np.load(tmp_path / "a" / "c4.pred_masks.0.npy"), out["pred_masks"][0].numpy())
+    s = m1["c4.logits"]["sample"]
+    assert "sample" not in m1["c4.pred_masks.0"] and s["of"] == out["logits"].numel() and 0 < s["elements"] < s["of"]
+    idx = B.sample_index(s["of"], s["elements"], s["seed"])
+    assert bool((idx[1:] > idx[:-1]).all()) and int(idx[0]) >= 0 and int(idx[-1]) < s["of"]
+    assert np.array_equal(np.load(tmp_path / "a" / "c4.logits.npy"), out["logits"].reshape(-1)[idx].float().numpy())
+
+
 def test_bench_rejects_world_size_mismatch():
     import subprocess
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")

@@ -705,6 +705,27 @@ def test_bench_runs_with_rccl_process_group_at_one_gpu():
     assert rec["config"]["per_gpu_batch"] == 4 and rec["value"] > 0 and abs(rec["value"] - 4 * 2 / (rec["ms_per_step"] * 2e-3)) < 0.05 * rec["value"]
 
 
+def test_bench_dump_outputs_c1(tmp_path):
+    """`bench.py --workload c1 --dump-outputs DIR`: the logits of the last timed step, whole (one image: 291 x 32011 fits the budget), as
+    float32, finite, with the manifest naming their shape; --steps is the number of timed steps of the line."""
+    import numpy as np
+    env = _env()
+    for k in ("MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k)
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c1", "--steps", "3", "--warmup", "1",
+                        "--no-cpu-baseline", "--no-roofline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and abs(rec["value"] - 1 * 3 / (rec["ms_per_step"] * 3e-3)) < 0.05 * rec["value"]
+    man = json.load(open(d / "manifest.json"))["outputs"]
+    assert list(man) == ["c1"] and man["c1"]["c1.logits"] == {"shape": [1, 291, 32011], "dtype": "bfloat16", "saved_as": "float32"}
+    assert sorted(os.listdir(d)) == ["c1.logits.npy", "manifest.json"]
+    lg = np.load(d / "c1.logits.npy")
+    assert lg.dtype == np.float32 and lg.shape == (1, 291, 32011) and np.isfinite(lg).all() and float(np.abs(lg).max()) > 0
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 * 10**6
+
+
 def test_bench_two_ranks_with_real_steps_on_one_gpu():
     """The N > 1 protocol of `bench.py` with REAL HIP steps: two ranks launched by the script itself (`--gpus 2`), both computing on cuda:0
     (`--share-gpu`; RCCL refuses two ranks on one device -- profiles/r04_rccl_two_ranks_one_gpu.txt -- so gloo carries the barriers and the

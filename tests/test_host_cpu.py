@@ -408,28 +408,11 @@ def test_alias_pack_leaves_externally_owned_parameters_alone():
     assert p2 is not None and w2[2].data_ptr() == p2.data_ptr() + 32 * 8 * 2
 
 
-REFERENCE = "/root/reference"
-
-
-def _reference_source_nodes():
-    """(find_linear_layers FunctionDef, the `if lora_r > 0:` block of train_ullava.main) parsed from the reference checkout when it is there
-    (the build container); the test executes THOSE lines against the shim -- nothing of the reference is kept in this repository."""
-    import ast
-    src = open(os.path.join(REFERENCE, "train_ullava.py")).read()
-    tree = ast.parse(src)
-    fn = next(n for n in ast.walk(tree) if isinstance(n, ast.FunctionDef) and n.name == "find_linear_layers")
-    blk = next(n for n in ast.walk(tree) if isinstance(n, ast.If) and isinstance(n.test, ast.Compare) and isinstance(n.test.left, ast.Name)
-               and n.test.left.id == "lora_r")
-    return fn, blk
-
-
 def test_peft_shim_runs_the_references_lora_call_sites(tmp_path, capsys):
-    """`from peft import LoraConfig, get_peft_model, PeftModel` resolves to u-llava_amd/shim/peft; the reference's own LoRA lines
+    """`from peft import LoraConfig, get_peft_model, PeftModel` resolves to u-llava_amd/shim/peft; the reference's LoRA call sites
     (train_ullava.py:88-113 find_linear_layers, :217-245 the lora_r > 0 block, :71-79 the is_peft state-dict filter, :291 save_pretrained,
-    inference_ullava.py:43 PeftModel.from_pretrained) run against it unchanged."""
-    import ast
+    inference_ullava.py:43 PeftModel.from_pretrained), restated here with the reference's arguments, run against it."""
     import sys
-    import types
     shim = os.path.join(ROOT, "u-llava_amd", "shim")
     saved_path, saved_mod = list(sys.path), sys.modules.pop("peft", None)
     sys.path.insert(0, shim)
@@ -452,18 +435,14 @@ def test_peft_shim_runs_the_references_lora_call_sites(tmp_path, capsys):
         model = build()
         assert isinstance(model.llm.model.layers[0].self_attn.q_proj, torch.nn.Linear)
         assert isinstance(model.llm.lm_head, torch.nn.Linear) and model.llm.lm_head.bias is None and "lm_head.bias" not in model.llm.state_dict()
-        ns = dict(torch=torch, LoraConfig=LoraConfig, get_peft_model=get_peft_model, print=print, model=model, lora_r=4,
-                  model_args=types.SimpleNamespace(lora_r=4, lora_alpha=8, lora_dropout=0.05, lora_target_modules="q_proj,v_proj"))
-        if os.path.isdir(REFERENCE):
-            fn, blk = _reference_source_nodes()
-            exec(compile(ast.Module(body=[fn], type_ignores=[]), "train_ullava.py", "exec"), ns)
-            names = ns["find_linear_layers"](model.llm, ["q_proj", "v_proj"])
-            assert names == sorted(f"model.layers.{i}.self_attn.{k}" for i in range(3) for k in ("q_proj", "v_proj"))
-            exec(compile(ast.Module(body=[blk], type_ignores=[]), "train_ullava.py", "exec"), ns)        # model.llm = get_peft_model(...); print_trainable...
-        else:
-            names = sorted(f"model.layers.{i}.self_attn.{k}" for i in range(3) for k in ("q_proj", "v_proj"))
-            model.llm = get_peft_model(model.llm, LoraConfig(r=4, lora_alpha=8, target_modules=names, lora_dropout=0.05, bias="none", task_type="CAUSAL_LM"))
-            model.llm.print_trainable_parameters()
+        names = sorted(f"model.layers.{i}.self_attn.{k}" for i in range(3) for k in ("q_proj", "v_proj"))
+        # find_linear_layers(model.llm, ["q_proj", "v_proj"]): the target Linear modules of the language model, the vision tower and
+        # projector left out, under the reference's names
+        found = sorted(n for n, mod in model.llm.named_modules() if isinstance(mod, torch.nn.Linear) and n.split(".")[-1] in ("q_proj", "v_proj")
+                       and n.split(".")[0] not in ("vision_encoder", "vision_projector"))
+        assert found == names
+        model.llm = get_peft_model(model.llm, LoraConfig(r=4, lora_alpha=8, target_modules=names, lora_dropout=0.05, bias="none", task_type="CAUSAL_LM"))
+        model.llm.print_trainable_parameters()
         out = capsys.readouterr().out
         assert "trainable params:" in out and "all params:" in out
         assert isinstance(model.llm, PeftModel) and isinstance(model.llm.get_base_model(), MC.UllavaCoreForCausalLM)
