@@ -105,6 +105,30 @@ int ull_gemv_qkv_rope_append_bf16(const void* X, int64_t ldx, const void* norm_w
                                   const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int64_t B, int64_t S, int64_t H,
                                   int64_t hd, int64_t K, int64_t smax, int64_t past, void* stream);
 
+/* ---- FP8 (e4m3) weight-only decode (bf16 build only: no *_f16 twins) ---------------------------------------------------------------
+ * UllavaCoreForCausalLM.quantize_weights("fp8_e4m3") stores every LLaMA Linear and lm_head as e4m3fn codes [N, K] (row pitch ldq bytes) plus
+ * one fp32 scale 2^s per row: s is the smallest integer with amax|w_row| * 2^-s <= 448 (all-zero row: s = 0), q = e4m3fn(w * 2^-s) rounded to
+ * nearest even.  dequant(q) = float(q) * 2^s is exactly a bf16 value, and every entry below computes exactly what the bf16 entry it replaces
+ * computes on the dequantized weight (same FMA / MFMA operands in the same order): bit-identical outputs, half the weight bytes. */
+/* Quantize W [N, K] (bf16, row pitch ldw) into codes [N, K] (pitch K bytes) + scales [N]; matches torch's CPU cast bit for bit.  K % 8 == 0. */
+int ull_quantize_rows_fp8_bf16(const void* W, int64_t ldw, int64_t N, int64_t K, void* codes, void* scales, void* stream);
+/* dequant(codes) into bf16: tiled = 0: row-major [N, K]; tiled = 1: the ULL_EPI_W_TILED layout of ull_gemm_bf16 (K % 64 == 0, ceil(N / 256) * 256
+ * rows, padding rows zero).  Replaces the bf16 weight (or its tile-major copy) of a prefill-shape ull_gemm_bf16 / ull_gemm_qkv_rope_bf16 call. */
+int ull_dequantize_rows_fp8_bf16(const void* codes, int64_t ldq, const void* scales, int64_t N, int64_t K, void* out, int tiled, void* stream);
+/* Replaces ull_gemv_bf16 on an fp8 weight. */
+int ull_gemv_w8_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc, const void* bias, const void* R,
+                     int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+/* Replaces ull_gemv_rmsnorm_bf16 on an fp8 weight. */
+int ull_gemv_rmsnorm_w8_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales, void* C,
+                             int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+/* Replaces ull_gemv_qkv_rope_append_bf16 on an fp8 q|k|v weight. */
+int ull_gemv_qkv_rope_append_w8_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales,
+                                     void* Q_out, int64_t ldq_out, const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int64_t B,
+                                     int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax, int64_t past, void* stream);
+/* Replaces ull_gemm_skinny_bf16 on an fp8 weight. */
+int ull_gemm_skinny_w8_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc, const void* bias,
+                            const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+
 /* y = w * bf16(x * rsqrt(mean(x^2) + eps)).  hf: LlamaRMSNorm.forward. */
 int ull_rmsnorm_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int64_t rows, int64_t D, float eps, void* stream);
 
@@ -469,6 +493,24 @@ int ull_llama_decode_layers_bf16(const ull_llama_layer* layers, int64_t n_layers
                                  void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
                                  void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax,
                                  int64_t past, float eps, const void* zeros, void* stream);
+
+/* Replaces ull_llama_decode_layers_bf16 on a model quantized to fp8 weights (the same launches through the *_w8_bf16 entries).  Every layer is
+ * checked before anything is enqueued: qkv [3D, D], o [D, D], gu [2I, D], down [D, I], I % 8 == 0 (ULL_ERR_SHAPE otherwise; null pointers:
+ * ULL_ERR_ARG).  An fp8 model's prefill takes the per-op path (ull_dequantize_rows_fp8_bf16 + ull_gemm_bf16). */
+typedef struct ull_linear_w8 {
+    const void* codes;   /* [n, k] e4m3fn, row pitch ld bytes */
+    const void* scales;  /* [n] fp32 powers of two */
+    int64_t n, k, ld;
+} ull_linear_w8;
+typedef struct ull_llama_layer_w8 {
+    const void* ln1;
+    const void* ln2;
+    ull_linear_w8 qkv, o, gu, down;
+} ull_llama_layer_w8;
+int ull_llama_decode_layers_w8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
+                                    void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
+                                    void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax,
+                                    int64_t past, float eps, const void* zeros, void* stream);
 
 /* hf CLIPEncoder.forward's layer loop (modeling_clip.py:353-384; models/ullava_core.py:146-158 reads hidden_states[-2], so the caller passes
  * the first 23 layers): h [T = n_img * S, D] is updated in place; h_mid [T, D], y [T, D], qkv [T, 3D], att [T, D], f [T, I] scratch.

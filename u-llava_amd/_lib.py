@@ -22,6 +22,14 @@ class LlamaLayer(ctypes.Structure):
     _fields_ = [("ln1", _ptr), ("ln2", _ptr), ("qkv", Linear), ("o", Linear), ("gu", Linear), ("down", Linear)]
 
 
+class LinearW8(ctypes.Structure):
+    _fields_ = [("codes", _ptr), ("scales", _ptr), ("n", _i64), ("k", _i64), ("ld", _i64)]
+
+
+class LlamaLayerW8(ctypes.Structure):
+    _fields_ = [("ln1", _ptr), ("ln2", _ptr), ("qkv", LinearW8), ("o", LinearW8), ("gu", LinearW8), ("down", LinearW8)]
+
+
 class ClipLayer(ctypes.Structure):
     _fields_ = [("ln1_w", _ptr), ("ln1_b", _ptr), ("ln2_w", _ptr), ("ln2_b", _ptr), ("qkv", Linear), ("out", Linear), ("fc1", Linear), ("fc2", Linear)]
 
@@ -118,6 +126,19 @@ SIGNATURES.update({name[:-4] + "f16": args for name, args in list(SIGNATURES.ite
 # fp32 build of the inference path (csrc/f32.hip): the same signatures as the bf16 entries of the same name
 F32_TWINS = ['ull_gemm', 'ull_attention', 'ull_transpose_v', 'ull_rmsnorm', 'ull_layernorm', 'ull_clip_embed_ln', 'ull_layernorm2d_cl', 'ull_rope_inplace', 'ull_rope_append', 'ull_im2col', 'ull_im2col3x3', 'ull_video_pool', 'ull_add_rows', 'ull_window_unpartition_add', 'ull_sam_relpos', 'ull_interp_rows_linear', 'ull_mask_matmul', 'ull_greedy_step', 'ull_shifted_cross_entropy']
 SIGNATURES.update({name + "_f32": SIGNATURES[name + "_bf16"] for name in F32_TWINS})
+
+# fp8 (e4m3) weight-only decode: bf16-only entry points (no fp16 twin)
+SIGNATURES.update({
+    "ull_quantize_rows_fp8_bf16": [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr],
+    "ull_dequantize_rows_fp8_bf16": [_ptr, _i64, _ptr, _i64, _i64, _ptr, _i32, _ptr],
+    "ull_gemv_w8_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
+    "ull_gemv_rmsnorm_w8_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
+    "ull_gemv_qkv_rope_append_w8_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64,
+                                         _i64, _i64, _ptr],
+    "ull_gemm_skinny_w8_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
+    "ull_llama_decode_layers_w8_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
+                                        _i64, _i64, _i64, _f32, _ptr, _ptr],
+})
 
 # fp16-only entry points (no bf16 twin): the fp32 neck of an fp16 SAM encoder (image_encoder.py:117-124)
 SIGNATURES["ull_neck_layernorm2d_f32in_f16"] = [_ptr, _ptr, _f32, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr]

@@ -6,6 +6,8 @@
 // At M <= 4 the op is a pure weight stream (LLaMA-7B: 13.5 GB per token), so there is no LDS staging and no MFMA: one wave
 // owns one output feature at a time, its 64 lanes stream that weight row with 16-byte loads (1 KiB per wave-instruction,
 // read exactly once), X comes from L1/L2, fp32 accumulation, wave reduction, same epilogues/rounding points as the GEMM.
+#include <type_traits>
+
 #include "ull_common.h"
 
 namespace {
@@ -40,14 +42,52 @@ ULL_DEV uint4 w_load16(const elem_t* p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
+// Weight formats of the decode kernels.  WF_ELEM: 16-bit rows (the model dtype).  WF_FP8 (bf16 build only): e4m3 code rows plus one fp32
+// power-of-two scale per row (ull_quantize_rows_fp8_bf16); a lane turns 8 codes into the 8 floats float(q) * 2^s -- exactly the bf16
+// values of the dequantized weight -- and feeds them to the same FMAs / MFMAs in the same order, so the result equals the 16-bit
+// kernel's on dequant(W) bit for bit.  The format is a template parameter: for WF_ELEM the pointer type below is the plain weight pointer,
+// so the existing instantiations keep their arguments and code.
+constexpr int WF_ELEM = 0, WF_FP8 = 1;
+
+struct W8Rows {
+    const uint8_t* codes;                    // [N][ldw] e4m3fn bytes
+    const float* scales;                     // [N] 2^s
+};
+template <int WF> struct WFmt {
+    typedef const elem_t* __restrict__ ptr_t;
+    typedef elem_t w_t;
+    ULL_DEV static const elem_t* rows(ptr_t W) { return W; }
+};
+template <> struct WFmt<WF_FP8> {
+    typedef W8Rows ptr_t;
+    typedef uint8_t w_t;
+    ULL_DEV static const uint8_t* rows(const W8Rows& W) { return W.codes; }
+};
+
+typedef uint32_t gv_u32x2_t __attribute__((ext_vector_type(2)));
+ULL_DEV uint2 w_load8(const uint8_t* p) {
+    const gv_u32x2_t v = __builtin_nontemporal_load((const gv_u32x2_t*)p);
+    return make_uint2(v.x, v.y);
+}
+
+// 8 e4m3fn codes (element j in byte j) -> 8 floats float(q_j) * s.  The conversion is exact and s is a power of two, so the product is
+// exact too (and representable in bf16: 4 significant bits).
+ULL_DEV void unpack8_w8(const uint2& v, float s, float* f) {
+    typedef float f2_t __attribute__((ext_vector_type(2)));
+    const f2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, true);
+    const f2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, true);
+    f[0] = a[0] * s; f[1] = a[1] * s; f[2] = b[0] * s; f[3] = b[1] * s;
+    f[4] = c[0] * s; f[5] = c[1] * s; f[6] = d[0] * s; f[7] = d[1] * s;
+}
+
 constexpr int XS_MAX_BYTES = 32 * 1024;     // X (optionally RMS-normalised) is staged in LDS when M * K * 2 fits in this
 
 // X staged in LDS (`staged`): every block first copies -- or, with norm_w, RMS-normalises (transformers LlamaRMSNorm:
 // w * bf16(x * rsqrt(mean(x^2) + eps)), the op that precedes the q/k/v and gate/up projections) -- the M activation rows,
 // which removes one tiny latency-bound kernel per projection from the decode step.  The weight stream keeps U 16-byte loads
-// per lane in flight (U KiB per wave).
-template <int M, int U>
-__global__ __launch_bounds__(256) void gemv_kernel(const elem_t* __restrict__ X, long ldx, const elem_t* __restrict__ W, long ldw, void* C,
+// per lane in flight (U KiB per wave); WF_FP8: U 8-byte loads of 8 codes, the same 8 elements per lane and chunk as the 16-byte form.
+template <int M, int U, int WF = WF_ELEM>
+__global__ __launch_bounds__(256) void gemv_kernel(const elem_t* __restrict__ X, long ldx, typename WFmt<WF>::ptr_t W, long ldw, void* C,
                                                    long ldc, const elem_t* __restrict__ bias, const elem_t* __restrict__ R, long ldr, int N, int K,
                                                    int flags, int n_out, const elem_t* __restrict__ norm_w, float eps, int staged, RopeAppend ra) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -118,26 +158,41 @@ __global__ __launch_bounds__(256) void gemv_kernel(const elem_t* __restrict__ X,
             row0 = (r_sec * ra.H + r_head) * ra.hd + r_i;
             row1_off = half;
         }
-        const elem_t* w0 = W + (long)row0 * ldw;
-        const elem_t* w1 = w0 + (long)row1_off * ldw;
+        const typename WFmt<WF>::w_t* w0 = WFmt<WF>::rows(W) + (long)row0 * ldw;
+        const typename WFmt<WF>::w_t* w1 = w0 + (long)row1_off * ldw;
+        float s0 = 1.f, s1 = 1.f;                                 // (WF_FP8) the two rows' scales
+        if constexpr (WF == WF_FP8) {
+            s0 = W.scales[row0];
+            if (swiglu) s1 = W.scales[row0 + row1_off];
+        }
         float a0[M], a1[M];
 #pragma unroll
         for (int m = 0; m < M; ++m) a0[m] = a1[m] = 0.f;
         for (int c0 = lane; c0 < nchunk; c0 += 64 * U) {
-            uint4 wq[U], uq[U];
+            typename std::conditional<WF == WF_FP8, uint2, uint4>::type wq[U], uq[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int c = c0 + 64 * u;
-                wq[u] = c < nchunk ? w_load16(w0 + c * 8) : make_uint4(0, 0, 0, 0);
-                if (swiglu) uq[u] = c < nchunk ? w_load16(w1 + c * 8) : make_uint4(0, 0, 0, 0);
+                if constexpr (WF == WF_FP8) {
+                    wq[u] = c < nchunk ? w_load8(w0 + c * 8) : make_uint2(0, 0);
+                    if (swiglu) uq[u] = c < nchunk ? w_load8(w1 + c * 8) : make_uint2(0, 0);
+                } else {
+                    wq[u] = c < nchunk ? w_load16(w0 + c * 8) : make_uint4(0, 0, 0, 0);
+                    if (swiglu) uq[u] = c < nchunk ? w_load16(w1 + c * 8) : make_uint4(0, 0, 0, 0);
+                }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int c = c0 + 64 * u;
                 if (c < nchunk) {
                     float wv[8], uv[8];
-                    unpack8(wq[u], wv);
-                    if (swiglu) unpack8(uq[u], uv);
+                    if constexpr (WF == WF_FP8) {
+                        unpack8_w8(wq[u], s0, wv);
+                        if (swiglu) unpack8_w8(uq[u], s1, uv);
+                    } else {
+                        unpack8(wq[u], wv);
+                        if (swiglu) unpack8(uq[u], uv);
+                    }
 #pragma unroll
                     for (int m = 0; m < M; ++m) {
                         float xv[8];
@@ -206,9 +261,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(const elem_t* __restrict__ X,
 // 64 bytes of each weight row: a block of 8 waves owns 16 features (SwiGLU: 16 gate + 16 up rows), every wave one eighth of K,
 // weight fragments straight from HBM (8 in flight per lane), X fragments from L2 (M x K x 2 bytes, shared by every block), partial
 // sums through LDS, then the GEMV's epilogue (same flags, same rounding points).  MFMA work is 16 / M times the useful flops and
-// still far below the stream's time.
-template <bool SW>
-__global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restrict__ X, long ldx, const elem_t* __restrict__ W, long ldw, void* C,
+// still far below the stream's time.  WF_FP8: 8 code bytes per lane and fragment, turned into the exact bf16 fragment of dequant(W).
+template <bool SW, int WF = WF_ELEM>
+__global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restrict__ X, long ldx, typename WFmt<WF>::ptr_t W, long ldw, void* C,
                                                           long ldc, const elem_t* __restrict__ bias, const elem_t* __restrict__ R, long ldr, int M,
                                                           int N, int K, int flags, int n_out) {
     __shared__ f32x4_t part[SW ? 2 : 1][8][64];
@@ -216,27 +271,48 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restri
     const int o0 = blockIdx.x * 16;                              // first output feature of the block
     // weight row of A-operand row fr: plain: o0 + fr; SwiGLU pack: gate rows (o0/16)*32 + fr, up rows 16 below
     const int wr0 = SW ? (o0 >> 4) * 32 + fr : min(o0 + fr, N - 1);
-    const elem_t* w0 = W + (long)wr0 * ldw + fg * 8;
-    const elem_t* w1 = w0 + 16 * ldw;
+    const typename WFmt<WF>::w_t* w0 = WFmt<WF>::rows(W) + (long)wr0 * ldw + fg * 8;
+    const typename WFmt<WF>::w_t* w1 = w0 + 16 * ldw;
+    float s0 = 1.f, s1 = 1.f;                                    // (WF_FP8) the scales of rows wr0 and wr0 + 16
+    if constexpr (WF == WF_FP8) {
+        s0 = W.scales[wr0];
+        if constexpr (SW) s1 = W.scales[wr0 + 16];
+    }
     const elem_t* xr = X + (long)min(fr, M - 1) * ldx + fg * 8;  // rows >= M repeat the last row: those accumulator columns are not stored
     const int nks = K >> 5;                                      // 32-wide k-steps
     const int ks0 = (int)((long)nks * wave / 8), ks1 = (int)((long)nks * (wave + 1) / 8);
     f32x4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
     constexpr int U = SW ? 4 : 8;              // (SwiGLU streams two weight rows per fragment: 8 would cost the second block per CU its registers)
     for (int k0 = ks0; k0 < ks1; k0 += U) {
-        uint4 wq[U], uq[U], xq[U];
+        typename std::conditional<WF == WF_FP8, uint2, uint4>::type wq[U], uq[U];
+        uint4 xq[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int ks = min(k0 + u, ks1 - 1);                 // past the end: a repeated, unused fragment
-            wq[u] = *(const uint4*)(w0 + ks * 32);
-            if constexpr (SW) uq[u] = *(const uint4*)(w1 + ks * 32);
+            if constexpr (WF == WF_FP8) {
+                wq[u] = *(const uint2*)(w0 + ks * 32);
+                if constexpr (SW) uq[u] = *(const uint2*)(w1 + ks * 32);
+            } else {
+                wq[u] = *(const uint4*)(w0 + ks * 32);
+                if constexpr (SW) uq[u] = *(const uint4*)(w1 + ks * 32);
+            }
             xq[u] = *(const uint4*)(xr + ks * 32);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (k0 + u < ks1) {
-                a0 = mfma16(wq[u], xq[u], a0);
-                if constexpr (SW) a1 = mfma16(uq[u], xq[u], a1);
+                if constexpr (WF == WF_FP8) {
+                    float f[8];
+                    unpack8_w8(wq[u], s0, f);
+                    a0 = mfma16(pack8(f), xq[u], a0);
+                    if constexpr (SW) {
+                        unpack8_w8(uq[u], s1, f);
+                        a1 = mfma16(pack8(f), xq[u], a1);
+                    }
+                } else {
+                    a0 = mfma16(wq[u], xq[u], a0);
+                    if constexpr (SW) a1 = mfma16(uq[u], xq[u], a1);
+                }
             }
         }
     }
@@ -284,8 +360,9 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restri
     }
 }
 
+// scales != nullptr: W holds e4m3 codes (row pitch ldw bytes) with one fp32 scale per row (WF_FP8, bf16 build only).
 int launch_skinny(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr,
-                  int64_t M, int64_t N, int64_t K, int flags, void* stream) {
+                  int64_t M, int64_t N, int64_t K, int flags, void* stream, const float* scales = nullptr) {
     if (!X || !W || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
     if (M > 16 || (K & 31) || (ldx & 7) || (ldw & 7)) return ULL_ERR_SHAPE;
     if ((flags & EPI_BIAS) && !bias) return ULL_ERR_ARG;
@@ -294,6 +371,20 @@ int launch_skinny(const void* X, int64_t ldx, const void* W, int64_t ldw, void* 
     const int n_out = (int)((flags & EPI_SWIGLU) ? N / 2 : N);
     const unsigned blocks = (unsigned)((n_out + 15) / 16);
     hipStream_t st = (hipStream_t)stream;
+    if (scales) {
+#ifdef ULL_ELEM_F16
+        return ULL_ERR_ARG;
+#else
+        const W8Rows w8{(const uint8_t*)W, scales};
+        if (flags & EPI_SWIGLU)
+            hipLaunchKernelGGL((skinny_gemm_kernel<true, WF_FP8>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, w8, ldw, C, ldc,
+                               (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
+        else
+            hipLaunchKernelGGL((skinny_gemm_kernel<false, WF_FP8>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, w8, ldw, C, ldc,
+                               (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
+        return ull_check_launch();
+#endif
+    }
     if (flags & EPI_SWIGLU)
         hipLaunchKernelGGL(skinny_gemm_kernel<true>, dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, (const elem_t*)W, ldw, C, ldc,
                            (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
@@ -303,8 +394,10 @@ int launch_skinny(const void* X, int64_t ldx, const void* W, int64_t ldw, void* 
     return ull_check_launch();
 }
 
+// scales != nullptr: W holds e4m3 codes, as in launch_skinny.
 int launch_gemv(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr,
-                int64_t M, int64_t N, int64_t K, int flags, const void* norm_w, float eps, void* stream, const RopeAppend* rope = nullptr) {
+                int64_t M, int64_t N, int64_t K, int flags, const void* norm_w, float eps, void* stream, const RopeAppend* rope = nullptr,
+                const float* scales = nullptr) {
     if (!X || !W || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
     if ((flags & EPI_ROPE_APPEND) && (!rope || flags != EPI_ROPE_APPEND || (N & 1))) return ULL_ERR_ARG;   // (not part of the public flags)
     const RopeAppend ra = rope ? *rope : RopeAppend{};
@@ -321,6 +414,31 @@ int launch_gemv(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C,
     if (staged && blocks > 1024) blocks = 1024;
     if (blocks > 8192) blocks = 8192;
     hipStream_t st = (hipStream_t)stream;
+    if (scales) {
+#ifdef ULL_ELEM_F16
+        return ULL_ERR_ARG;
+#else
+        // Half the bytes per row make a row's latency, not the stream, the limit: more waves in flight (a 1536-block grid where the
+        // 16-bit form has 1024) and fewer registers per wave (4 loads per lane in flight at M = 1) -- measured on the LLaMA-7B decode step
+        // (tools/fp8_decode_bench.py, batch 1): U = 16 / 1024 blocks 3.06 ms, U = 8 / 2048 blocks 2.66, U = 4 / 2048 2.56, U = 4 / 1536
+        // 2.46, U = 4 / 1280 2.45, U = 4 / 1024 2.51, U = 2 / 2048 2.60 (bf16: 3.37).
+        const W8Rows w8{(const uint8_t*)W, scales};
+        int blocks8 = (n_out + 3) / 4;
+        if (staged && blocks8 > 1536) blocks8 = 1536;
+        if (blocks8 > 8192) blocks8 = 8192;
+#define ULL_GV8(MM, UU)                                                                                                                   \
+    hipLaunchKernelGGL((gemv_kernel<MM, UU, WF_FP8>), dim3(blocks8), dim3(256), lds, st, (const elem_t*)X, ldx, w8, ldw, C, ldc,           \
+                       (const elem_t*)bias, (const elem_t*)R, ldr, (int)N, (int)K, flags, n_out, (const elem_t*)norm_w, eps, staged, ra)
+        switch ((int)M) {
+            case 1: ULL_GV8(1, 4); break;
+            case 2: ULL_GV8(2, 8); break;
+            case 3: ULL_GV8(3, 8); break;
+            default: ULL_GV8(4, 8); break;
+        }
+#undef ULL_GV8
+        return ull_check_launch();
+#endif
+    }
 #define ULL_GV(MM, UU)                                                                                                                    \
     hipLaunchKernelGGL((gemv_kernel<MM, UU>), dim3(blocks), dim3(256), lds, st, (const elem_t*)X, ldx, (const elem_t*)W, ldw, C, ldc,     \
                        (const elem_t*)bias, (const elem_t*)R, ldr, (int)N, (int)K, flags, n_out, (const elem_t*)norm_w, eps, staged, ra)
@@ -370,3 +488,128 @@ extern "C" int ULL_FN(ull_gemm_skinny_)(const void* X, int64_t ldx, const void* 
                                     int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
     return launch_skinny(X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, stream);
 }
+
+// ---- FP8 (e4m3) weight-only decode: bf16 build only ------------------------------------------------------------------------------
+// A weight W [N, K] is stored as e4m3fn codes q [N, K] plus one fp32 scale 2^s per row, s the smallest integer with amax|w| * 2^-s <= 448
+// (all-zero row: s = 0), q = e4m3fn(w * 2^-s) rounded to nearest even.  dequant(q) = float(q) * 2^s is exactly representable in bf16, so
+// the fp8 kernels above compute exactly what the 16-bit kernels compute on dequant(W).
+#ifndef ULL_ELEM_F16
+namespace {
+
+// one row per wave: amax, the power-of-two scale, then the codes (8 per lane and chunk, like the GEMV's weight chunks)
+__global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const elem_t* __restrict__ W, long ldw, int N, int K, uint8_t* __restrict__ codes,
+                                                                float* __restrict__ scales) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const elem_t* w = W + (long)row * ldw;
+    const int nchunk = K >> 3;
+    float amax = 0.f;
+    for (int c = lane; c < nchunk; c += 64) {
+        float v[8];
+        unpack8(*(const uint4*)(w + c * 8), v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+    }
+    amax = wave_max(amax);
+    int s = 0;
+    if (amax > 0.f) {
+        int e;
+        frexpf(amax, &e);                                  // amax in [2^(e-1), 2^e): s is e - 9 or e - 8, settled exactly below
+        s = e - 9;
+        while (amax > ldexpf(448.f, s)) ++s;
+        while (amax <= ldexpf(448.f, s - 1)) --s;
+    }
+    if (lane == 0) scales[row] = ldexpf(1.f, s);
+    uint8_t* q = codes + (long)row * K;
+    for (int c = lane; c < nchunk; c += 64) {
+        float v[8];
+        unpack8(*(const uint4*)(w + c * 8), v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = ldexpf(v[j], -s);     // exact; |v| <= 448: the conversion cannot overflow
+        int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
+        int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], 0, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
+        *(uint2*)(q + c * 8) = make_uint2((uint32_t)lo, (uint32_t)hi);
+    }
+}
+
+// codes -> dequant(W) in bf16, row-major [N, K] or (tiled) the ULL_EPI_W_TILED layout [ceil(N/256)][K/64][256][64] of ull_gemm_bf16
+// with the padding rows zeroed.  One thread per 8 elements.
+__global__ __launch_bounds__(256) void dequantize_rows_fp8_kernel(const uint8_t* __restrict__ codes, long ldq, const float* __restrict__ scales,
+                                                                  int N, int K, elem_t* __restrict__ out, int tiled, long total) {
+    const int g8 = K >> 3;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int n = (int)(i / g8), k = (int)(i - (long)n * g8) * 8;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (n < N) {
+            float f[8];
+            unpack8_w8(*(const uint2*)(codes + (long)n * ldq + k), scales[n], f);
+            v = pack8(f);
+        }
+        const long o = tiled ? (((long)(n >> 8) * (K >> 6) + (k >> 6)) * 256 + (n & 255)) * 64 + (k & 63) : (long)n * K + k;
+        *(uint4*)(out + o) = v;
+    }
+}
+
+}  // namespace
+
+// Per-row e4m3 quantization (see above) of a bf16 weight W [N, K] (row pitch ldw): codes [N, K] (pitch K bytes), scales [N] fp32.
+// Bit-identical to torch's CPU cast (w.float() * 2^-s).to(torch.float8_e4m3fn).  K % 8 == 0.
+extern "C" int ULL_FN(ull_quantize_rows_fp8_)(const void* W, int64_t ldw, int64_t N, int64_t K, void* codes, void* scales, void* stream) {
+    if (!W || !codes || !scales || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if ((K & 7) || (ldw & 7) || ldw < K || N > (1 << 28)) return ULL_ERR_SHAPE;
+    hipLaunchKernelGGL(quantize_rows_fp8_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const elem_t*)W, (long)ldw,
+                       (int)N, (int)K, (uint8_t*)codes, (float*)scales);
+    return ull_check_launch();
+}
+
+// dequant(codes) into a bf16 buffer: tiled = 0: row-major [N, K]; tiled = 1: ull_gemm_bf16's ULL_EPI_W_TILED layout (K % 64 == 0;
+// out holds ceil(N / 256) * 256 * K elements).  The prefill path of an fp8 weight: this, then the unchanged 16-bit GEMM.
+extern "C" int ULL_FN(ull_dequantize_rows_fp8_)(const void* codes, int64_t ldq, const void* scales, int64_t N, int64_t K, void* out, int tiled,
+                                                void* stream) {
+    if (!codes || !scales || !out || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if ((K & 7) || (ldq & 7) || ldq < K || (tiled && (K & 63))) return ULL_ERR_SHAPE;
+    const long rows = tiled ? (N + 255) / 256 * 256 : N;
+    const long total = rows * (K >> 3);
+    const long blocks = std::min<long>((total + 255) / 256, 16384);
+    hipLaunchKernelGGL(dequantize_rows_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)codes, (long)ldq,
+                       (const float*)scales, (int)N, (int)K, (elem_t*)out, tiled, total);
+    return ull_check_launch();
+}
+
+// ull_gemv_bf16 / ull_gemv_rmsnorm_bf16 / ull_gemv_qkv_rope_append_bf16 / ull_gemm_skinny_bf16 on an fp8 weight: Q = e4m3 codes (row pitch
+// ldq bytes), scales [N] fp32.  Same contract and bits as the bf16 entry on dequant(Q).
+extern "C" int ULL_FN(ull_gemv_w8_)(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc, const void* bias,
+                                const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
+    if (!scales) return ULL_ERR_ARG;
+    return launch_gemv(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, nullptr, 0.f, stream, nullptr, (const float*)scales);
+}
+
+extern "C" int ULL_FN(ull_gemv_rmsnorm_w8_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales,
+                                        void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
+                                        void* stream) {
+    if (!norm_w || !scales) return ULL_ERR_ARG;
+    return launch_gemv(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, norm_w, eps, stream, nullptr, (const float*)scales);
+}
+
+extern "C" int ULL_FN(ull_gemv_qkv_rope_append_w8_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq,
+                                                const void* scales, void* Q_out, int64_t ldq_out, const void* cos_tab, const void* sin_tab,
+                                                void* k_cache, void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax,
+                                                int64_t past, void* stream) {
+    if (!scales || !cos_tab || !sin_tab || !k_cache || !vt_cache || B <= 0 || S <= 0 || H <= 0) return ULL_ERR_ARG;
+    if (hd <= 0 || (hd & 1) || past < 0 || past + S > smax || ldq_out < H * hd) return ULL_ERR_SHAPE;
+    RopeAppend ra;
+    ra.cs = (const elem_t*)cos_tab; ra.sn = (const elem_t*)sin_tab; ra.kc = (elem_t*)k_cache; ra.vtc = (elem_t*)vt_cache;
+    ra.S = (int)S; ra.H = (int)H; ra.hd = (int)hd; ra.smax = (int)smax; ra.past = (int)past;
+    return launch_gemv(X, ldx, Q, ldq, Q_out, ldq_out, nullptr, nullptr, 0, B * S, 3 * H * hd, K, EPI_ROPE_APPEND, norm_w, norm_w ? eps : 0.f, stream,
+                       &ra, (const float*)scales);
+}
+
+extern "C" int ULL_FN(ull_gemm_skinny_w8_)(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc,
+                                       const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
+    if (!scales) return ULL_ERR_ARG;
+    return launch_skinny(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, stream, (const float*)scales);
+}
+#endif  // !ULL_ELEM_F16

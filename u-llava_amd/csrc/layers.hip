@@ -129,6 +129,62 @@ extern "C" int FN(ull_llama_decode_layers_)(const ull_llama_layer* layers, int64
     return ULL_OK;
 }
 
+#ifndef ULL_ELEM_F16
+namespace {
+
+// lin_decode on an fp8 weight: the same GEMV / skinny choice and RMSNorm placement, the fp8 forms of the entries
+inline int lin_decode_w8(const void* x, int64_t ldx, const void* rms_w, float eps, void* xn_scratch, const ull_linear_w8* L, void* out, int64_t ldc,
+                         const void* R, int64_t ldr, int64_t M, int flags, void* stream) {
+    const bool skinny = M >= 3 && L->k % 32 == 0 && L->n * L->k >= ((int64_t)1 << 22) && L->ld % 8 == 0;
+    if (R) flags |= ULL_EPI_RESID;
+    if (rms_w && (skinny || !(L->k % 8 == 0 && M * L->k <= 16384))) {
+        TRY(FN(ull_rmsnorm_)(x, ldx, rms_w, xn_scratch, L->k, M, L->k, eps, stream));
+        x = xn_scratch;
+        ldx = L->k;
+        rms_w = nullptr;
+    }
+    if (skinny) return ull_gemm_skinny_w8_bf16(x, ldx, L->codes, L->ld, L->scales, out, ldc, nullptr, R, ldr, M, L->n, L->k, flags, stream);
+    if (rms_w) return ull_gemv_rmsnorm_w8_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, out, ldc, nullptr, R, ldr, M, L->n, L->k, flags, stream);
+    return ull_gemv_w8_bf16(x, ldx, L->codes, L->ld, L->scales, out, ldc, nullptr, R, ldr, M, L->n, L->k, flags, stream);
+}
+
+}  // namespace
+
+// ull_llama_decode_layers_bf16 on fp8 weights: the same launches with the fp8 entries; every layer's shapes are checked before anything is
+// enqueued.
+extern "C" int ull_llama_decode_layers_w8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid,
+                                               void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
+                                               const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H,
+                                               int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
+    if (!layers || !x_in || !x_out || !x_mid || !xn || !q || !att || !act || !rope_cos || !rope_sin || !k_cache || !vt_cache || !zeros || n_layers <= 0)
+        return ULL_ERR_ARG;
+    const int64_t D = H * hd, T = B * S;
+    if (T > 4 || T <= 0 || past <= 0 || (hd & 1) || D % 8 || I <= 0 || I % 8 || T * D * 2 > 32768 || past + S > smax) return ULL_ERR_SHAPE;
+    for (int64_t l = 0; l < n_layers; ++l) {
+        const ull_llama_layer_w8& w = layers[l];
+        if (w.qkv.n != 3 * D || w.qkv.k != D || w.o.n != D || w.o.k != D || w.gu.n != 2 * I || w.gu.k != D || w.down.n != D || w.down.k != I)
+            return ULL_ERR_SHAPE;
+        for (const ull_linear_w8* L : {&w.qkv, &w.o, &w.gu, &w.down})
+            if (!L->codes || !L->scales || L->ld < L->k) return ULL_ERR_ARG;
+        if (!w.ln1 || !w.ln2 || !k_cache[l] || !vt_cache[l] || !x_out[l]) return ULL_ERR_ARG;
+    }
+    const float scale = 1.0f / sqrtf((float)hd);
+    const void* x = x_in;
+    for (int64_t l = 0; l < n_layers; ++l) {
+        const ull_llama_layer_w8& w = layers[l];
+        TRY(ull_gemv_qkv_rope_append_w8_bf16(x, D, w.ln1, eps, w.qkv.codes, w.qkv.ld, w.qkv.scales, q, D, rope_cos, rope_sin, k_cache[l], vt_cache[l], B, S,
+                                             H, hd, D, smax, past, stream));
+        TRY(FN(ull_attention_)(q, S * D, hd, D, k_cache[l], H * smax * hd, smax * hd, hd, vt_cache[l], H * hd * smax, hd * smax, smax, smax, att, S * D, hd, D,
+                               key_mask, B, H, S, past + S, hd, 1, 1, scale, 1.0f, nullptr, nullptr, 0, 0, 0, zeros, stream));
+        TRY(lin_decode_w8(att, D, nullptr, 0.f, xn, &w.o, x_mid, D, x, D, T, 0, stream));
+        TRY(lin_decode_w8(x_mid, D, w.ln2, eps, xn, &w.gu, act, I, nullptr, 0, T, ULL_EPI_SWIGLU, stream));
+        TRY(lin_decode_w8(act, I, nullptr, 0.f, xn, &w.down, x_out[l], D, x_mid, D, T, 0, stream));
+        x = x_out[l];
+    }
+    return ULL_OK;
+}
+#endif  // !ULL_ELEM_F16
+
 extern "C" int FN(ull_clip_layers_)(const ull_clip_layer* layers, int64_t n_layers, void* h, void* h_mid, void* y, void* qkv, void* att, void* f,
                                     int64_t n_img, int64_t S, int64_t H, int64_t hd, int64_t I, float eps, void* ws, int64_t ws_bytes,
                                     int64_t sk_min_k, const void* zeros, void* stream) {

@@ -306,6 +306,7 @@ def sampling_probs(logits: torch.Tensor, temperature: float, top_k: Optional[int
 # ----------------------------------------------------------------------------------------------------------
 class UllavaCoreForCausalLM(nn.Module):
     config_class = UllavaCoreConfig
+    weight_quantization = None             # "fp8_e4m3" after quantize_weights()
 
     def __init__(self, config: UllavaCoreConfig, device=None, dtype=BF16):
         super().__init__()
@@ -352,6 +353,9 @@ class UllavaCoreForCausalLM(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         """.to() / .cuda() / .half() / .bfloat16(): the MI355X re-layouts (fused QKV, interleaved gate/up, tile-major copies) are
         derived from the parameters and are rebuilt from the moved / cast ones on the next forward."""
+        if self.weight_quantization is not None:
+            self._refuse_cast(fn)
+            return super()._apply(fn, *args, **kwargs)
         out = super()._apply(fn, *args, **kwargs)
         self._packed = None
         _clear_transposes()          # cached W^T copies of the training path describe the old weights
@@ -363,6 +367,23 @@ class UllavaCoreForCausalLM(nn.Module):
     def get_input_embeddings(self):
         return self.model.embed_tokens
 
+    def _refuse_quantized(self, what: str):
+        raise NotImplementedError(f"{what} is not supported on a model quantized with quantize_weights('{self.weight_quantization}'): its LLaMA "
+                                  "Linear weights exist only as fp8 codes and scales (inference only; load the bf16 model for this)")
+
+    def _refuse_cast(self, fn):
+        """_apply on a quantized model: the fp8 packs are the only copy of the LLaMA weights, so a cast or a move has nothing to rebuild
+        them from; a no-op (.to(the same device)) is allowed."""
+        probe = torch.empty(0, device=self.device, dtype=self.dtype)
+        moved = fn(probe)
+        if not isinstance(moved, torch.Tensor) or moved.dtype != probe.dtype or moved.device != probe.device:
+            self._refuse_quantized("changing the dtype or device (.to / .half / .float / .cpu)")
+
+    def state_dict(self, *args, **kwargs):
+        if self.weight_quantization is not None:
+            self._refuse_quantized("state_dict() export")
+        return super().state_dict(*args, **kwargs)
+
     def resize_token_embeddings(self, new_num_tokens=None, pad_to_multiple_of=None):
         """PreTrainedModel.resize_token_embeddings as the reference's callers use it (train_ullava.py:212, models/tools.py:45,72,
         102,108): grow (or shrink) embed_tokens and lm_head to `new_num_tokens` rows, old rows kept, new rows ~ N(0, 0.02)
@@ -370,6 +391,8 @@ class UllavaCoreForCausalLM(nn.Module):
         emb = self.model.embed_tokens
         if new_num_tokens is None:
             return emb
+        if self.weight_quantization is not None:
+            self._refuse_quantized("resize_token_embeddings")
         if pad_to_multiple_of:
             new_num_tokens = -(-new_num_tokens // pad_to_multiple_of) * pad_to_multiple_of
         old = emb.weight.shape[0]
@@ -402,10 +425,14 @@ class UllavaCoreForCausalLM(nn.Module):
         return core_from_pretrained(cls, pretrained_model_name_or_path, torch_dtype, device, **kwargs)
 
     def save_pretrained(self, save_directory, **kwargs):
+        if self.weight_quantization is not None:
+            self._refuse_quantized("save_pretrained")
         from .checkpoint import save_pretrained
         return save_pretrained(self, save_directory, **kwargs)
 
     def load_state_dict(self, state_dict, strict=True, assign=False):
+        if self.weight_quantization is not None:
+            self._refuse_quantized("load_state_dict")
         # transformers 4.29.1 checkpoints nest the CLIP tower under `vision_encoder.vision_model.`
         sd = {k.replace("vision_encoder.vision_model.", "vision_encoder."): v for k, v in state_dict.items()}
         sd = {k: v for k, v in sd.items() if not k.endswith("position_ids") and "rotary_emb.inv_freq" not in k}
@@ -416,6 +443,8 @@ class UllavaCoreForCausalLM(nn.Module):
     # -- weight re-layout ----------------------------------------------------------------------------------
     def pack_weights(self, free_originals: bool = False):
         """Build the MI355X layouts.  Call again after changing parameters."""
+        if self.weight_quantization is not None:
+            self._refuse_quantized("pack_weights")
         cfg = self.config
         pk = {"llama": [], "clip": []}
         lora = getattr(self, "_lora", None)
@@ -467,6 +496,77 @@ class UllavaCoreForCausalLM(nn.Module):
             for l in self.model.layers:
                 for mod in (l.self_attn.q_proj, l.self_attn.k_proj, l.self_attn.v_proj, l.mlp.gate_proj, l.mlp.up_proj):
                     mod.weight.data = torch.empty(0, device=mod.weight.device, dtype=mod.weight.dtype)
+        return self
+
+    def quantize_weights(self, fmt: str = "fp8_e4m3"):
+        """FP8 (e4m3) weight-only inference: store every LLaMA Linear (q/k/v/o/gate/up/down_proj of every layer) and lm_head as e4m3fn
+        codes with one power-of-two fp32 scale per output row (ops.quantize_fp8); activations stay bf16, accumulation fp32.  Everything
+        else (embeddings, norms, CLIP, projector) keeps its dtype.  Returns self.
+
+        The result is exactly the bf16 model whose LLaMA Linear weights are replaced by dequant(codes) = float(code) * scale (a bf16 value):
+        logits, hidden states and generated ids equal that twin's bit for bit.  The decode steps stream half the weight bytes (fp8 forms of
+        the GEMV / skinny kernels); prefill shapes dequantize each weight into a bf16 scratch and run the bf16 GEMM.  The bf16 LLaMA
+        weights and their tile-major copies are released: the fp8 packs become the only copy (like pack_weights(free_originals=True)),
+        so the model can no longer train, take LoRA adapters, be saved, exported through state_dict() or cast.  bf16 models only;
+        call merge_lora() first when adapters are attached."""
+        if fmt != "fp8_e4m3":
+            raise ValueError(f"quantize_weights: unknown format {fmt!r} (supported: 'fp8_e4m3')")
+        if self.weight_quantization is not None:
+            if self.weight_quantization == fmt:
+                return self
+            self._refuse_quantized(f"quantize_weights({fmt!r})")
+        if self.dtype != BF16:
+            raise NotImplementedError(f"quantize_weights('fp8_e4m3') covers bf16 models only (this one is {self.dtype}): for fp16 the dequantized "
+                                      "weights are not always representable, and fp32 has no fp8 kernels")
+        if getattr(self, "_lora", None) is not None:
+            raise NotImplementedError("quantize_weights: LoRA adapters are attached -- call merge_lora() first")
+        if not self.lm_head.weight.is_cuda:
+            raise RuntimeError("quantize_weights: move the model to the GPU first (the quantization runs there)")
+        cfg = self.config
+        if cfg.hidden_size % 32 or cfg.intermediate_size % 32:
+            raise NotImplementedError("quantize_weights: hidden_size and intermediate_size must be multiples of 32")
+        # built outside inference mode: the packs are ordinary tensors whatever mode the caller is in (and no version counter is read)
+        with torch.inference_mode(False), torch.no_grad():
+            pk = self._pk(for_llama=True)
+            dev = self.lm_head.weight.device
+
+            def q8(w):
+                return ops.quantize_fp8(w.detach().contiguous())
+
+            def cat(qs):
+                return ops.Fp8Weight(torch.cat([q.codes for q in qs]), torch.cat([q.scales for q in qs]))
+
+            llama = []
+            for l, d in zip(self.model.layers, pk["llama"]):
+                a, m = l.self_attn, l.mlp
+                # per-row scales: quantizing the q|k|v concatenation / the gate|up interleave row by row equals concatenating /
+                # interleaving the per-Linear codes and scales; after pack_weights(free_originals=True) only the packs are left
+                qkv = cat([q8(a.q_proj.weight), q8(a.k_proj.weight), q8(a.v_proj.weight)]) if a.q_proj.weight.numel() else q8(d["w_qkv"])
+                if m.gate_proj.weight.numel():
+                    g, u = q8(m.gate_proj.weight), q8(m.up_proj.weight)
+                    gu = ops.Fp8Weight(interleave_gate_up(g.codes, u.codes), interleave_gate_up(g.scales[:, None], u.scales[:, None]).view(-1))
+                else:
+                    gu = q8(d["w_gu"])
+                llama.append(dict(w_qkv=qkv, w_o=q8(d["w_o"]), w_gu=gu, w_down=q8(d["w_down"]), ln1=d["ln1"], ln2=d["ln2"]))
+            lm_head = q8(self.lm_head.weight)
+            # release the bf16 LLaMA weights and every copy derived from them (packs, tile-major copies, training-path buffers)
+            for d in pk["llama"]:
+                for k in ("w_qkv", "w_o", "w_gu", "w_down"):
+                    ops.unregister_tiled(d[k])
+            mods = [self.lm_head] + [mod for l in self.model.layers for mod in (l.self_attn.q_proj, l.self_attn.k_proj, l.self_attn.v_proj,
+                                                                                  l.self_attn.o_proj, l.mlp.gate_proj, l.mlp.up_proj, l.mlp.down_proj)]
+            for mod in mods:
+                ops.unregister_tiled(mod.weight)
+                mod.weight.data = torch.empty(0, device=dev, dtype=BF16)
+                mod.weight.requires_grad_(False)
+            new = {k: v for k, v in pk.items() if k not in ("llama", "_c_llama")}
+            new.update(llama=llama, lm_head=lm_head, freed=True, fp8=True)
+            self._packed = None
+            pk.clear()
+            self._packed = new
+            self._reset_alias_slots()
+            _clear_transposes()
+        self.weight_quantization = fmt
         return self
 
     # The version tuples are read on EVERY forward (a decode step too): walking the module tree for them cost 0.5 ms of host time per step
@@ -608,6 +708,8 @@ class UllavaCoreForCausalLM(nn.Module):
         (lora_alpha / r) * B(A(dropout(x))) to the projection as PEFT's Linear does; save_pretrained writes the adapter in PEFT's
         file layout and from_pretrained merges such files (checkpoint.merge_lora_adapter)."""
         import math
+        if self.weight_quantization is not None:
+            self._refuse_quantized("add_lora")
         targets = tuple(target_modules)
         if not targets or any(t not in ("q_proj", "k_proj", "v_proj") for t in targets):
             raise NotImplementedError("LoRA targets on this path: q_proj, k_proj, v_proj (the reference's configuration: q_proj, v_proj)")
@@ -902,15 +1004,19 @@ class UllavaCoreForCausalLM(nn.Module):
         all_h = []
         I = cfg.intermediate_size
         coarse = None
+        w8 = pk.get("fp8", False)            # quantize_weights(): the Linear weights are ops.Fp8Weight (ops.linear & co. dispatch on them)
         if ops.coarse_ok() and pk["llama"]:
             if fuse_append and I % 8 == 0:
                 coarse = "decode"
-            elif fuse_rope and cache is None and T > 16 and 16 < S <= 1024 and I % 64 == 0:
-                coarse = "prefill"
+            elif fuse_rope and cache is None and T > 16 and 16 < S <= 1024 and I % 64 == 0 and not w8:
+                coarse = "prefill"           # (an fp8 model's prefill takes the per-op path: dequantize + GEMM per Linear)
         if coarse is not None:
             # one C call for the whole layer stack (csrc/layers.hip): the same launches as the loop below, bit-identical results
             stack = pk.get("_c_llama")
-            if stack is None:
+            if stack is None and w8:
+                stack = pk["_c_llama"] = ops.LayerStack(_lib.LlamaLayerW8, [dict(ln1=w["ln1"], ln2=w["ln2"], qkv=w["w_qkv"], o=w["w_o"], gu=w["w_gu"],
+                                                                                  down=w["w_down"]) for w in pk["llama"]])
+            elif stack is None:
                 stack = pk["_c_llama"] = ops.LayerStack(_lib.LlamaLayer, [dict(ln1=w["ln1"], ln2=w["ln2"], qkv=(w["w_qkv"], None), o=(w["w_o"], None),
                                                                                 gu=(w["w_gu"], None), down=(w["w_down"], None)) for w in pk["llama"]])
             L = len(pk["llama"])
@@ -920,7 +1026,7 @@ class UllavaCoreForCausalLM(nn.Module):
             else:
                 outs = [torch.empty(T, D, device=dev, dtype=x.dtype)] * L
             if coarse == "decode":
-                ops.llama_decode_layers(stack, x, outs, rope_cs[0], rope_cs[1], key_mask, cache.c_ptrs()[0], cache.c_ptrs()[1], B, S, H, hd, I, cache.smax,
+                (ops.llama_decode_layers_w8 if w8 else ops.llama_decode_layers)(stack, x, outs, rope_cs[0], rope_cs[1], key_mask, cache.c_ptrs()[0], cache.c_ptrs()[1], B, S, H, hd, I, cache.smax,
                                         past, cfg.rms_norm_eps)
             else:
                 ops.llama_prefill_layers(stack, x, outs, rope_cs[0], rope_cs[1], key_mask, B, S, H, hd, I, cfg.rms_norm_eps)
@@ -985,6 +1091,8 @@ class UllavaCoreForCausalLM(nn.Module):
         """reference :279-355 (same argument list)."""
         if output_attentions:
             raise NotImplementedError("attention probabilities never leave LDS on this path")
+        if self.weight_quantization is not None and self._training_graph():
+            self._refuse_quantized("building a training graph (gradients enabled with trainable parameters; use torch.no_grad())")
         cache = None
         if past_key_values is not None or use_cache:
             if past_key_values is not None and not isinstance(past_key_values, KVCache):
@@ -1010,7 +1118,7 @@ class UllavaCoreForCausalLM(nn.Module):
             loss = A.shifted_cross_entropy(logits, labels) if labels is not None else None
         else:
             last, all_h = self._llama(inputs_embeds, attention_mask, position_ids, output_hidden_states, cache)
-            logits = ops.linear(last, self.lm_head.weight)
+            logits = ops.linear(last, self._packed["lm_head"] if self.weight_quantization is not None else self.lm_head.weight)
             loss = ops.shifted_cross_entropy(logits, labels) if labels is not None else None
         if not return_dict:
             # reference :346-348: (loss,) + (logits,) + LlamaModel outputs[1:] = past_key_values / hidden_states when requested

@@ -63,7 +63,18 @@ class UllavaForCausalLM(nn.Module):
         from .checkpoint import ullava_from_pretrained
         return ullava_from_pretrained(cls, pretrained_model_name_or_path, torch_dtype, device, **kwargs)
 
+    @property
+    def weight_quantization(self):
+        return self.llm.weight_quantization
+
+    def quantize_weights(self, fmt: str = "fp8_e4m3"):
+        """FP8 weight-only inference for the language model (UllavaCoreForCausalLM.quantize_weights); SAM and the heads keep their dtype."""
+        self.llm.quantize_weights(fmt)
+        return self
+
     def save_pretrained(self, save_directory, **kwargs):
+        if self.llm.weight_quantization is not None:
+            self.llm._refuse_quantized("save_pretrained")
         from .checkpoint import save_pretrained
         return save_pretrained(self, save_directory, **kwargs)
 
@@ -90,6 +101,8 @@ class UllavaForCausalLM(nn.Module):
         return self.llm.device
 
     def _apply(self, fn, *args, **kwargs):
+        if self.llm.weight_quantization is not None:
+            self.llm._refuse_cast(fn)                       # before any submodule is converted
         out = super()._apply(fn, *args, **kwargs)           # (the core model invalidates its own packs in its _apply)
         self._sam.invalidate()
         self._side = None

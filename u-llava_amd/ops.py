@@ -130,6 +130,132 @@ def _tiled_of(w: torch.Tensor):
     return e[1]
 
 
+def unregister_tiled(w: torch.Tensor) -> None:
+    """Drop the tile-major copy of `w` now (a weight whose storage is being released while the tensor object lives on)."""
+    e = _TILED.get(w.data_ptr())
+    if e is not None and e[0]() is w:
+        del _TILED[w.data_ptr()]
+
+
+# ---- FP8 (e4m3) weight-only storage (UllavaCoreForCausalLM.quantize_weights) ----------------------------------------------------------
+class Fp8Weight:
+    """A Linear weight [N, K] as e4m3fn codes (uint8 [N, K]) plus one fp32 power-of-two scale per row: dequant = float(code) * scale, exactly
+    a bf16 value.  `linear` / `linear_qkv_rope` / `linear_qkv_rope_append` take it in place of a bf16 weight and compute exactly what they
+    compute on the dequantized bf16 weight (the fp8 forms of the GEMV / skinny kernels at decode shapes; dequantize + the bf16 GEMM at
+    prefill shapes).  Immutable once built."""
+    __slots__ = ("codes", "scales")
+
+    def __init__(self, codes: torch.Tensor, scales: torch.Tensor):
+        if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or scales.dtype != F32 or scales.shape != (codes.shape[0],):
+            raise RuntimeError("u-llava_amd.Fp8Weight: codes uint8 [N, K] (rows contiguous), scales fp32 [N]")
+        self.codes, self.scales = codes, scales
+
+    @property
+    def shape(self):
+        return self.codes.shape
+
+    @property
+    def device(self):
+        return self.codes.device
+
+    def nbytes(self) -> int:
+        return self.codes.numel() + 4 * self.scales.numel()
+
+
+def quantize_fp8(w: torch.Tensor) -> Fp8Weight:
+    """Per-row e4m3 quantization of a bf16 weight [N, K] on the GPU (ull_quantize_rows_fp8_bf16): the row's scale is 2^s with s the smallest
+    integer such that amax|w| * 2^-s <= 448 (0 for an all-zero row); codes = e4m3fn(w * 2^-s), round to nearest even -- bit-identical to
+    torch's CPU cast `(w.float() * 2**-s).to(torch.float8_e4m3fn)`."""
+    _chk(w, "w", BF16)
+    if w.dim() != 2:
+        raise RuntimeError("u-llava_amd.quantize_fp8: w must be 2-D")
+    N, K = w.shape
+    codes = torch.empty(N, K, device=w.device, dtype=torch.uint8)
+    scales = torch.empty(N, device=w.device, dtype=F32)
+    _lib.call("ull_quantize_rows_fp8_bf16", _p(w), w.stride(0), N, K, _p(codes), _p(scales), _stream())
+    return Fp8Weight(codes, scales)
+
+
+def dequantize_fp8(q: Fp8Weight, tiled: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dequant(q) as bf16: [N, K] row-major, or (tiled) the ULL_EPI_W_TILED layout `tile_major` produces."""
+    N, K = q.shape
+    rows = -(-N // 256) * 256 if tiled else N
+    if out is None:
+        out = torch.empty(rows * K, device=q.device, dtype=BF16)
+    elif out.dtype != BF16 or out.numel() < rows * K or not out.is_contiguous():
+        raise RuntimeError("u-llava_amd.dequantize_fp8: `out` must be a contiguous bf16 buffer of at least the result's size")
+    _lib.call("ull_dequantize_rows_fp8_bf16", _p(q.codes), q.codes.stride(0), _p(q.scales), N, K, _p(out), int(tiled), _stream())
+    return out[:rows * K].view(rows // 256, K // 64, 256, 64) if tiled else out[:N * K].view(N, K)
+
+
+_W8_SCRATCH = {}     # (device, stream) -> the bf16 buffer prefill-shape fp8 Linears dequantize into (reused in stream order)
+
+
+def _w8_scratch(device: torch.device, stream_id: int, numel: int) -> torch.Tensor:
+    key = (device.index, stream_id)
+    buf = _W8_SCRATCH.get(key)
+    if buf is None or buf.numel() < numel:
+        with torch.cuda.device(device):
+            buf = _W8_SCRATCH[key] = torch.empty(numel, device=device, dtype=BF16)
+    return buf
+
+
+def _w8_dequant_for_gemm(q: Fp8Weight, M: int):
+    """(row-major view, tile-major view or None) of dequant(q) in the stream's scratch, laid out as the bf16 GEMM would read the
+    weight at this M: tile-major where a bf16 weight has its tile-major copy and the 256 x 256 path takes it (register_tiled / `big`)."""
+    N, K = q.shape
+    tiled = M >= 1024 and N >= 512 and K >= 128 and K % 64 == 0
+    buf = _w8_scratch(q.device, _stream(), (-(-N // 256) * 256 if tiled else N) * K)
+    wd = dequantize_fp8(q, tiled=tiled, out=buf)
+    if tiled:
+        return buf[:N * K].view(N, K), wd          # (the row-major view only carries the shape: the GEMM reads the tile-major copy)
+    return wd, None
+
+
+def _linear_w8(x, q: Fp8Weight, bias, act, residual, swiglu, out, out_f32, rms_w, rms_eps, tune, bias_after_rounding):
+    """`linear` on an fp8 weight: the same dispatch as for a bf16 weight of the same shape, each kernel in its fp8 form."""
+    if x.dtype != BF16:
+        raise RuntimeError(f"u-llava_amd.linear: fp8 weights need bf16 activations, got {x.dtype}")
+    _chk(x, "x")
+    M, ldx = _rows(x)
+    N, K = q.shape
+    lead = tuple(x.shape[:-1])
+    if x.shape[-1] != K:
+        raise RuntimeError(f"u-llava_amd.linear: K mismatch {x.shape[-1]} vs {K}")
+    ldq = q.codes.stride(0)
+    skinny = 3 <= M <= 16 and K % 32 == 0 and N * K >= (1 << 22) and ldq % 8 == 0 and tune == 0
+    decode = skinny or (M <= 4 and K % 8 == 0)
+    if not decode:
+        w, wt = _w8_dequant_for_gemm(q, M)
+        return linear(x, w, bias, act, residual, swiglu, out, out_f32, rms_w, rms_eps, tune, bias_after_rounding, _wt=wt)
+    if rms_w is not None and (skinny or not (M <= 4 and K % 8 == 0 and M * K <= 16384)):
+        x = rmsnorm(x, rms_w, rms_eps)
+        rms_w = None
+        M, ldx = _rows(x)
+    n_out = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty(*lead, n_out, device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
+    flags = ACTS[act] | (EPI_BIAS if bias is not None else 0) | (EPI_RESID if residual is not None else 0) | \
+        (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0) | (EPI_BIAS_ROUNDED if bias_after_rounding else 0)
+    if bias is not None:
+        _chk(bias, "bias", x.dtype)
+    ldr = 0
+    if residual is not None:
+        _chk(residual, "residual", x.dtype)
+        ldr = _rows(residual)[1]
+    if skinny:
+        _lib.call("ull_gemm_skinny_w8_bf16", _p(x), ldx, _p(q.codes), ldq, _p(q.scales), _p(out), _rows(out)[1], _p(bias), _p(residual), ldr, M, N, K,
+                  flags, _stream())
+    elif rms_w is not None:
+        _chk(rms_w, "rms_w", x.dtype)
+        _lib.call("ull_gemv_rmsnorm_w8_bf16", _p(x), ldx, _p(rms_w), float(rms_eps), _p(q.codes), ldq, _p(q.scales), _p(out), _rows(out)[1], _p(bias),
+                  _p(residual), ldr, M, N, K, flags, _stream())
+    else:
+        _lib.call("ull_gemv_w8_bf16", _p(x), ldx, _p(q.codes), ldq, _p(q.scales), _p(out), _rows(out)[1], _p(bias), _p(residual), ldr, M, N, K, flags,
+                  _stream())
+    return out
+
+
 # ---- stream-K workspace: one fp32 scratch buffer per (device, stream) ---------------------------------------------------
 # ull_gemm_bf16 splits a partial last round of 256x256 tiles along K into fp32 slabs in a CALLER-owned workspace.  Each HIP
 # stream gets its own buffer here, so GEMMs running concurrently on two streams (RES forward / evaluate: SAM encoder beside
@@ -190,11 +316,15 @@ class streamk_policy:
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act: Optional[str] = None,
            residual: Optional[torch.Tensor] = None, swiglu: bool = False, out: Optional[torch.Tensor] = None,
            out_f32: bool = False, rms_w: Optional[torch.Tensor] = None, rms_eps: float = 0.0, tune: int = 0,
-           bias_after_rounding: bool = False) -> torch.Tensor:
+           bias_after_rounding: bool = False, _wt: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = epilogue(x @ w.T).  x [..., K]; w [N, K] (nn.Linear layout).  swiglu: w is the 16-row interleaved gate/up pack.
     rms_w/rms_eps: apply LlamaRMSNorm to x first (fused into the GEMV prologue at decode shapes, a separate kernel otherwise).
     tune: ULL_GEMM_TUNE_* bits (tools/ only).  bias_after_rounding: y = round(round(x @ w.T) + bias) -- what at::linear computes
-    for a NON-contiguous 3-D input (matmul + add_ instead of the fused addmm)."""
+    for a NON-contiguous 3-D input (matmul + add_ instead of the fused addmm).
+    w may be an `Fp8Weight` (bf16 x only): the same result as on its dequantized bf16 weight, bit for bit.  (_wt: internal, the
+    tile-major weight of that path's 256 x 256 GEMM.)"""
+    if isinstance(w, Fp8Weight):
+        return _linear_w8(x, w, bias, act, residual, swiglu, out, out_f32, rms_w, rms_eps, tune, bias_after_rounding)
     _chk(x, "x"); _chk(w, "w", x.dtype)
     M, ldx = _rows(x)
     N, K = w.shape
@@ -280,7 +410,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         _, ldr = _rows(residual)
     _, ldc = _rows(out)
     big = M >= 1024 and N >= 512 and K >= 128
-    wt = _tiled_of(w) if big else None
+    wt = (_tiled_of(w) if _wt is None else _wt) if big else None
     st = _stream()
     ws_ptr, ws_bytes = None, 0
     min_k = _SK_MIN_K[0]
@@ -317,9 +447,13 @@ GEMM_TUNE_WAVES8, GEMM_TUNE_WAVES4 = 1 << 21, 1 << 22     # ULL_GEMM_TUNE_*: for
 
 
 def linear_qkv_rope(x: torch.Tensor, w: torch.Tensor, rope_cos: torch.Tensor, rope_sin: torch.Tensor, rope_cols: int, head_dim: int,
-                    out: Optional[torch.Tensor] = None, tune: int = 0) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, tune: int = 0, _wt: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused q|k|v projection + RoPE on the first `rope_cols` output columns (q and k heads), head_dim 128, K % 64 == 0, M > 4.
-    Bit-identical to linear() followed by rope_inplace()."""
+    Bit-identical to linear() followed by rope_inplace().  w may be an `Fp8Weight` (dequantized into a scratch first)."""
+    if isinstance(w, Fp8Weight):
+        if x.dtype != BF16:
+            raise RuntimeError(f"u-llava_amd.linear_qkv_rope: fp8 weights need bf16 activations, got {x.dtype}")
+        w, _wt = _w8_dequant_for_gemm(w, _rows(x)[0])
     _chk(x, "x"); _chk(w, "w", x.dtype); _chk(rope_cos, "rope_cos", x.dtype); _chk(rope_sin, "rope_sin", x.dtype)
     M, ldx = _rows(x)
     N, K = w.shape
@@ -329,7 +463,7 @@ def linear_qkv_rope(x: torch.Tensor, w: torch.Tensor, rope_cos: torch.Tensor, ro
         out = torch.empty(*x.shape[:-1], N, device=x.device, dtype=x.dtype)
     _, ldc = _rows(out)
     big = M >= 1024 and N >= 512 and K >= 128
-    wt = _tiled_of(w) if big else None
+    wt = (_tiled_of(w) if _wt is None else _wt) if big else None
     st = _stream()
     ws_ptr, ws_bytes = None, 0
     min_k = _SK_MIN_K[0]
@@ -486,17 +620,27 @@ def linear_qkv_rope_append(x: torch.Tensor, w_qkv: torch.Tensor, rope_cos: torch
                            rms_eps: float = 0.0) -> torch.Tensor:
     """decode step (B * S <= 4 tokens): q | k | v projection of x (optionally RMS-normalised first) with RoPE and the KV-cache append in the
     GEMV's epilogue.  Returns the rotated queries [B * S, H * hd]; the rotated keys / the values land in the caches.  Same bits as
-    `linear(x, w_qkv, rms_w=...)` followed by `rope_append`."""
-    _chk(x, "x"); _chk(w_qkv, "w_qkv", x.dtype); _chk(rope_cos, "rope_cos", x.dtype); _chk(rope_sin, "rope_sin", x.dtype)
+    `linear(x, w_qkv, rms_w=...)` followed by `rope_append`.  w_qkv may be an `Fp8Weight` (bf16 only)."""
+    w8 = isinstance(w_qkv, Fp8Weight)
+    if w8:
+        if x.dtype != BF16:
+            raise RuntimeError(f"u-llava_amd.linear_qkv_rope_append: fp8 weights need bf16 activations, got {x.dtype}")
+    else:
+        _chk(w_qkv, "w_qkv", x.dtype)
+    _chk(x, "x"); _chk(rope_cos, "rope_cos", x.dtype); _chk(rope_sin, "rope_sin", x.dtype)
     _chk(k_cache, "k_cache", x.dtype); _chk(vt_cache, "vt_cache", x.dtype)
     T, K = x.shape
     if T != B * S or T > 4 or w_qkv.shape != (3 * H * hd, K) or rope_cos.shape != (T, hd // 2) or rope_sin.shape != (T, hd // 2):
         raise RuntimeError("u-llava_amd.linear_qkv_rope_append: shapes (at most 4 tokens; w [3 * H * hd, K]; cos / sin [tokens, hd / 2])")
-    if x.stride(1) != 1 or w_qkv.stride(1) != 1 or not (rope_cos.is_contiguous() and rope_sin.is_contiguous()):
+    if x.stride(1) != 1 or (not w8 and w_qkv.stride(1) != 1) or not (rope_cos.is_contiguous() and rope_sin.is_contiguous()):
         raise RuntimeError("u-llava_amd.linear_qkv_rope_append: rows must be contiguous")
     if rms_w is not None:
         _chk(rms_w, "rms_w", x.dtype)
     q = torch.empty(T, H * hd, device=x.device, dtype=x.dtype)
+    if w8:
+        _lib.call("ull_gemv_qkv_rope_append_w8_bf16", _p(x), x.stride(0), _p(rms_w), float(rms_eps), _p(w_qkv.codes), w_qkv.codes.stride(0),
+                  _p(w_qkv.scales), _p(q), q.stride(0), _p(rope_cos), _p(rope_sin), _p(k_cache), _p(vt_cache), B, S, H, hd, K, smax, past, _stream())
+        return q
     _lib.call("ull_gemv_qkv_rope_append_" + _SFX[x.dtype], _p(x), x.stride(0), _p(rms_w), float(rms_eps), _p(w_qkv), w_qkv.stride(0), _p(q),
               q.stride(0), _p(rope_cos), _p(rope_sin), _p(k_cache), _p(vt_cache), B, S, H, hd, K, smax, past, _stream())
     return q
@@ -1092,8 +1236,8 @@ def coarse_ok() -> bool:
 
 
 class LayerStack:
-    """`kind`: _lib.LlamaLayer / ClipLayer / SamBlock; `layers`: one dict per layer, field name -> tensor (pointer fields) or
-    (weight, bias-or-None) (ull_linear fields) or int (plain fields)."""
+    """`kind`: _lib.LlamaLayer / LlamaLayerW8 / ClipLayer / SamBlock; `layers`: one dict per layer, field name -> tensor (pointer fields) or
+    (weight, bias-or-None) (ull_linear fields) or Fp8Weight (ull_linear_w8 fields) or int (plain fields)."""
 
     def __init__(self, kind, layers):
         self.kind, self.layers = kind, layers
@@ -1115,7 +1259,10 @@ class LayerStack:
             s = self.arr[i]
             for n, t in self.kind._fields_:
                 v = d[n]
-                if t is _lib.Linear:
+                if t is _lib.LinearW8:
+                    # an Fp8Weight: immutable, so nothing of it enters the fingerprint (and no version counter is read)
+                    setattr(s, n, _lib.LinearW8(v.codes.data_ptr(), v.scales.data_ptr(), v.shape[0], v.shape[1], v.codes.stride(0)))
+                elif t is _lib.Linear:
                     w, b = v
                     if w.dim() != 2 or w.stride(1) != 1:
                         raise RuntimeError("u-llava_amd: coarse entries need row-major 2-D weights")
@@ -1171,6 +1318,21 @@ def llama_decode_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos, 
     act = scratch[3 * T * D + T * max(D, I):3 * T * D + T * max(D, I) + T * I]
     _lib.call("ull_llama_decode_layers_" + _SFX[dt], stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid), _p(xn), _p(q), _p(att),
               _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k_ptrs, vt_ptrs, B, S, H, hd, I, smax, past, float(eps), _zeros(dev).data_ptr(), _stream())
+
+
+def llama_decode_layers_w8(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos, rope_sin, key_mask, k_ptrs, vt_ptrs, B: int, S: int, H: int,
+                           hd: int, I: int, smax: int, past: int, eps: float):
+    """llama_decode_layers on a stack of _lib.LlamaLayerW8 (fp8 weights, bf16 activations): ull_llama_decode_layers_w8_bf16."""
+    _chk(x_in, "x_in", BF16)
+    T, D = x_in.shape
+    dev = x_in.device
+    scratch = torch.empty(T * (4 * D + 2 * max(D, I)), device=dev, dtype=BF16)
+    x_mid, q, att = scratch[:T * D], scratch[T * D:2 * T * D], scratch[2 * T * D:3 * T * D]
+    xn = scratch[3 * T * D:3 * T * D + T * max(D, I)]
+    act = scratch[3 * T * D + T * max(D, I):3 * T * D + T * max(D, I) + T * I]
+    _lib.call("ull_llama_decode_layers_w8_bf16", stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid), _p(xn), _p(q), _p(att),
+              _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k_ptrs, vt_ptrs, B, S, H, hd, I, smax, past, float(eps), _zeros(dev).data_ptr(),
+              _stream())
 
 
 def clip_layers(stack: LayerStack, n_layers: int, h: torch.Tensor, n_img: int, S: int, H: int, hd: int, I: int, eps: float):
