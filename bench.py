@@ -1,21 +1,29 @@
 #!/usr/bin/env python
-"""bench.py -- images/sec of the u-LLaVA multimodal forward on MI355X through the HIP path, with the roofline of the dominant
-kernel and a CPU-oracle baseline.
+"""bench.py -- images/sec of the u-LLaVA multimodal forward on MI355X through the HIP path; with --full also the other BASELINE.json
+configurations, the roofline of the dominant kernel and a CPU-oracle baseline.
 
-  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and nothing else: it builds the workload's model and inputs, runs W warm-up and K timed
+steps, checks that the last step's outputs are finite, writes them if --dump-outputs is given and prints the result line.  --full adds
+everything else this script measures, as described below: the RES, C2 and C5 sub-records of a c4 run, the host-enqueue probe steps of
+every timed workload, the roofline / patchify probes and the CPU-oracle baseline with its parity check.  --no-res, --no-extra,
+--no-roofline and --no-cpu-baseline leave parts out of a --full run.
 
 --dump-outputs DIR: after the timed steps of each workload the run times, rank 0 writes what the last timed step returned (logits; for RES
 also the masks and boxes) to DIR/<workload>.<key>.npy as float32 (float64 for float64 / integer outputs), 60 MiB in all; an output larger
-than its share is written as a seeded stratified sample of its flattened elements (DIR/manifest.json: shapes, sample sizes, seed).  Inputs
-and weights are seeded, so two builds run with the same arguments can be compared output for output.
+than its share is written as a seeded stratified sample of its flattened elements (DIR/manifest.json: shapes, sample sizes, seed).  A
+plain run writes the same files as a --full run: given --dump-outputs, a plain c4 run also runs the RES, C2 and C5 steps, for their
+outputs alone (its line does not report them).  Inputs and weights are seeded, so two builds run with the same arguments can be compared
+output for output.
 
 N > 1: this script launches N ranks itself (re-exec under `torch.distributed.run`, one rank per GPU, RCCL over xGMI) unless it
 is already running inside such a launch (WORLD_SIZE set by the driver's own `python -m torch.distributed.run ... bench.py`).
 
 A "step" = one forward of the per-GPU batch.  Headline workload = BASELINE.json config C4 (336x336 synthetic images, 64-token
-prompts, S = 643, per-GPU batch 32, weak scaling); the same JSON line carries a `res` sub-record = config C3 (full RES forward:
+prompts, S = 643, per-GPU batch 32, weak scaling); with --full the same JSON line carries a `res` sub-record = config C3 (full RES forward:
 + SAM ViT-H encoder at 1024x1024, 3 [SEG]/[LOC] per image, MaskDecoder, postprocess; batch 8) timed with the same protocol, so
-both halves of BASELINE.json's metric ("ViT-L-336 + LLaMA-7B + SAM RES forward") are measured in the driver's run, and `extra.c2` /
+both halves of BASELINE.json's metric ("ViT-L-336 + LLaMA-7B + SAM RES forward") are measured in one run, and `extra.c2` /
 `extra.c5` = BASELINE.json configs[1] (VQA, batch 16, ragged prompts) and configs[4] (8-frame video clips, 8 per GPU) at their own sizes
 (`config.also_timed` repeats the three in brief).  Inputs and random-init weights are resident in HBM before the timed region.
 Every timed region is bracketed by barriers; the process group is destroyed after the last one and rank 0's single-rank probes
@@ -654,10 +662,11 @@ def dump_outputs(out, directory, prefix, budget):
     return manifest
 
 
-def timed_steps(step, steps, warmup, dist, batch, device, keep=None):
+def timed_steps(step, steps, warmup, dist, batch, device, keep=None, host_probe=False):
     """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides; MAX elapsed over ranks and
     SUM of images over ranks through the path's only collective (u-llava_amd.dist.global_rate).  keep(outputs of the last timed step) runs
-    after the timed region and before the host-enqueue probe steps, which may reuse the buffers those outputs live in."""
+    after the timed region and before the host-enqueue probe steps (host_probe, --full only), which may reuse the buffers those outputs
+    live in."""
     D = importlib.import_module("u-llava_amd.dist")
     sync = torch.cuda.synchronize if device.type == "cuda" else (lambda: None)
     for _ in range(warmup):
@@ -680,7 +689,7 @@ def timed_steps(step, steps, warmup, dist, batch, device, keep=None):
     if keep is not None:
         keep(last)
     host_ms = None
-    if device.type == "cuda":
+    if host_probe and device.type == "cuda":
         # host time to ENQUEUE one step (idle GPU, no synchronize inside): what a rank's Python thread costs per step -- eight of them share a
         # host at N = 8.  `coarse` = the shipped path (one C call per layer stack, csrc/layers.hip), `per_op` = one ctypes call per launch.
         ops = importlib.import_module("u-llava_amd.ops")
@@ -801,10 +810,12 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"],
                     help="fp16 / fp32 = the reference's --dtype options (side checks; default bf16 like inference_ullava.py:165).  fp32 is the plain-kernel "
                          "correctness build (csrc/f32.hip, ~1/50 of the bf16 speed): use it with --batch 1 or 2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-res", action="store_true", help="skip the C3 RES sub-record of the default (c4) run")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C2 / C5 sub-records of the default (c4) run")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, run the C3 / C2 / C5 sub-records of a c4 run, the host-enqueue "
+                    "probe steps, the roofline / patchify probes and the CPU-oracle baseline with its parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU-oracle baseline of a --full run")
+    ap.add_argument("--no-roofline", action="store_true", help="skip the roofline / patchify probes of a --full run")
+    ap.add_argument("--no-res", action="store_true", help="skip the C3 RES sub-record of a --full c4 run")
+    ap.add_argument("--no-extra", action="store_true", help="skip the C2 / C5 sub-records of a --full c4 run")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: CPU ranks (only with --stub)")
     ap.add_argument("--stub", action="store_true", help="replace the model step by a fixed host-side delay (tests the N-rank protocol without a GPU)")
     ap.add_argument("--init-pg", action="store_true", help="initialise the process group (RCCL) even at --gpus 1, so that the barrier and the "
@@ -864,8 +875,9 @@ def main():
         # what the collective layer itself reports: a SCALE record must show that RCCL saw N ranks, not what the launcher was asked for
         pg = {"backend": dist.get_backend(), "rccl_world_size": dist.get_world_size(), "rank": dist.get_rank()}
 
-    # --dump-outputs: rank 0 keeps the outputs of the last timed step of every workload this run times, each within an equal share
-    timed = [a.workload] + (["res"] + ([] if a.no_extra else ["c2", "c5"]) if a.workload == "c4" and not a.no_res and not a.stub else [])
+    # the workloads a --full run times.  --dump-outputs: rank 0 keeps the outputs of the last timed step of each of them, each within an
+    # equal share, whether or not --full is given (a plain run then runs the steps of the others for their outputs alone)
+    timed_full = [a.workload] + (["res"] + ([] if a.no_extra else ["c2", "c5"]) if a.workload == "c4" and not a.no_res and not a.stub else [])
     manifest = {}
 
     def keeper(name):
@@ -873,7 +885,7 @@ def main():
             return None
 
         def keep(out):
-            manifest[name] = dump_outputs(out, a.dump_outputs, name, DUMP_BUDGET // len(timed))
+            manifest[name] = dump_outputs(out, a.dump_outputs, name, DUMP_BUDGET // len(timed_full))
             with open(os.path.join(a.dump_outputs, "manifest.json"), "w") as f:
                 json.dump({"argv": sys.argv[1:], "outputs": manifest}, f, indent=1)
         return keep
@@ -895,13 +907,16 @@ def main():
         value, total_images, elapsed, spread = timed_steps(step, a.steps, a.warmup, dist, batch, dev, keep=keeper(a.workload))
         close_pg()
         if rank == 0:
-            import torch.distributed as dist_chk
-            probes = {"order": "after destroy_process_group", "process_group_alive": bool(dist_chk.is_initialized())}
-            time.sleep(0.02)                                     # stands for the roofline / patchify / cpu_baseline probes
+            probes = None
+            if a.full:
+                import torch.distributed as dist_chk
+                probes = {"order": "after destroy_process_group", "process_group_alive": bool(dist_chk.is_initialized())}
+                time.sleep(0.02)                                 # stands for the roofline / patchify / cpu_baseline probes
             print(json.dumps({"metric": METRIC, "value": round(value, 3), "unit": "images/sec (whole job)", "n_gpus": world, "steps": a.steps,
                               "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True,
                               "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "stub", "total_images": total_images,
-                              "cpu_affinity": affinity, "process_group": pg, "per_rank_ms_per_step": spread, "probes": probes,
+                              "cpu_affinity": affinity, "process_group": pg, "per_rank_ms_per_step": spread,
+                              **({"probes": probes} if probes is not None else {}),
                               "config": {"workload": "stub step (host-side delay), " + desc, "per_gpu_batch": batch,
                                          "global_batch": batch * world, "parallelism": f"dp{world}"}}), flush=True)
         return
@@ -916,19 +931,22 @@ def main():
 
     with (torch.enable_grad() if a.workload == "train" else torch.no_grad()):
         step, batch, S, cfg, desc, flops_img, model = workload_step(a.workload, dev, rank, a.batch, a.train_config)
-        value, total_images, elapsed, spread = timed_steps(step, a.steps, a.warmup, dist, batch, dev, keep=keeper(a.workload))
+        value, total_images, elapsed, spread = timed_steps(step, a.steps, a.warmup, dist, batch, dev, keep=keeper(a.workload), host_probe=a.full)
         image_size, prompt = WORKLOADS[a.workload][:2]
         res_rec = None
         extra = {}
-        if a.workload == "c4" and not a.no_res:
-            # second half of BASELINE.json's metric: the full RES forward (C3), same timing protocol, same process
+        if a.workload == "c4" and not a.no_res and (a.full or a.dump_outputs is not None):
+            # second half of BASELINE.json's metric: the full RES forward (C3), same timing protocol, same process.  A plain run given
+            # --dump-outputs runs these steps for their outputs alone: its line reports nothing about them
             del step, model
             torch.cuda.empty_cache()
             rstep, rbatch, rS, rcfg, rdesc, rflops, rmodel = workload_step("res", dev, rank)
             rsteps = max(3, min(a.steps, 10))
-            rvalue, rimgs, relapsed, rspread = timed_steps(rstep, rsteps, max(1, min(a.warmup, 2)), dist, rbatch, dev, keep=keeper("res"))
-            res_rec = sub_record(rvalue, rsteps, relapsed, rspread, rbatch, rS, rdesc, rflops,
-                                 sam_input="1024x1024 (valid 768x1024 -> 480x640 masks)", prompts_per_image=3)
+            rvalue, rimgs, relapsed, rspread = timed_steps(rstep, rsteps, max(1, min(a.warmup, 2)), dist, rbatch, dev, keep=keeper("res"),
+                                                           host_probe=a.full)
+            if a.full:
+                res_rec = sub_record(rvalue, rsteps, relapsed, rspread, rbatch, rS, rdesc, rflops,
+                                     sam_input="1024x1024 (valid 768x1024 -> 480x640 masks)", prompts_per_image=3)
             if not a.no_extra:
                 # the other two BASELINE.json configurations, timed at their own sizes on the RES model's language model (the very
                 # ViT-L/14-224 + LLaMA-7B of C2 / C5; SAM stays idle): C2 = configs[1] (VQA, batch 16, ragged prompts), C5 = configs[4] (video, 8 clips / GPU)
@@ -936,15 +954,16 @@ def main():
                 for wname in ("c2", "c5"):
                     wstep, wbatch, wS, _, wdesc, wflops, _ = workload_step(wname, dev, rank, model=rmodel.llm)
                     wsteps = max(3, min(a.steps, 5))
-                    wvalue, _, welapsed, wspread = timed_steps(wstep, wsteps, 2, dist, wbatch, dev, keep=keeper(wname))
-                    extra[wname] = sub_record(wvalue, wsteps, welapsed, wspread, wbatch, wS, wdesc, wflops)
+                    wvalue, _, welapsed, wspread = timed_steps(wstep, wsteps, 2, dist, wbatch, dev, keep=keeper(wname), host_probe=a.full)
+                    if a.full:
+                        extra[wname] = sub_record(wvalue, wsteps, welapsed, wspread, wbatch, wS, wdesc, wflops)
                     del wstep
             del rmodel
             torch.cuda.empty_cache()
         close_pg()
         # ---- single-rank probes: after the process group is gone (see close_pg) -------------------------------------------------------
         roof = patch_rec = res_roof = None
-        if rank == 0 and not a.no_roofline and a.workload != "train":
+        if a.full and rank == 0 and not a.no_roofline and a.workload != "train":
             roof = gemm_roofline(cfg, batch * S, dev)
             if a.workload == "c4":
                 patch_rec = patchify_record(dev)
@@ -953,9 +972,10 @@ def main():
 
     if rank == 0:
         line = {"metric": METRIC, "value": round(value, 3), "unit": "images/sec (whole job, all GPUs)", "cpu_affinity": affinity,
-                "outputs_finite": True, "process_group": pg, "host_enqueue_ms_per_step": spread.pop("host_enqueue_ms", None),
+                "outputs_finite": True, "process_group": pg,
+                **({"host_enqueue_ms_per_step": spread.pop("host_enqueue_ms", None)} if a.full else {}),
                 "per_rank_ms_per_step": spread,
-                "probes": {"order": "after destroy_process_group", "ranks_running": 1},
+                **({"probes": {"order": "after destroy_process_group", "ranks_running": 1}} if a.full else {}),
                 "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 3),
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
                 "config": {"workload": desc, "per_gpu_batch": batch, "global_batch": batch * world, "seq_len": S, "image": image_size,
@@ -981,7 +1001,7 @@ def main():
             line["patchify"] = patch_rec
         if roof is not None:
             line["roofline"] = roof
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(dev)
         print(json.dumps(line), flush=True)
 

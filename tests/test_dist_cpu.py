@@ -101,6 +101,31 @@ def test_bench_dump_outputs_stub(tmp_path):
     assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
 
 
+def test_bench_plain_run_leaves_the_probes_to_full():
+    """A plain run prints the headline line without the single-rank probes; `--full` adds them, after the process group is gone, and
+    reports the same headline fields (stub step, CPU)."""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    recs = {}
+    for extra in ([], ["--full"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--stub", "--steps", "3", "--warmup", "1"] + extra,
+                           capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        recs[bool(extra)] = json.loads(lines[0])
+    plain, full = recs[False], recs[True]
+    assert "probes" not in plain
+    assert full["probes"] == {"order": "after destroy_process_group", "process_group_alive": False}
+    for rec in (plain, full):
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] >= 10.0 and rec["higher_is_better"] is True
+        assert rec["dtype"] == "bf16" and rec["unit"] == "images/sec (whole job)" and rec["total_images"] == 32 * 3
+    assert set(full) - set(plain) == {"probes"}
+
+
 def test_bench_dump_outputs_budget_and_sample(tmp_path):
     """dump_outputs: the arrays a caller receives (not the KV cache), float32 / float64 only, the total within the budget, large arrays as a
     seeded stratified sample that is the same on every call and that the manifest identifies."""
@@ -197,7 +222,7 @@ def test_bench_launch_and_aggregation_gloo_world8_stub():
         env.pop(k, None)
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--stub", "--steps", "2",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout

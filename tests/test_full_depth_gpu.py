@@ -696,7 +696,7 @@ def test_bench_runs_with_rccl_process_group_at_one_gpu():
     for k in ("MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--init-pg", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--no-res", "--no-cpu-baseline", "--no-roofline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--no-res", "--no-cpu-baseline", "--no-roofline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 1 and rec["outputs_finite"] is True
@@ -735,7 +735,7 @@ def test_bench_two_ranks_with_real_steps_on_one_gpu():
     for k in ("MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--workload", "c2",
-                        "--batch", "4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--no-pin"],
+                        "--batch", "4", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-roofline", "--no-pin"],
                        capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -13,6 +13,6 @@ python tools/rocpd_stats.py $(ls $O/p_res/*/*.db | head -1) $O/res_stats.md > /d
 python tools/pmc_csv.py $O/pmc_fetch gemm256 > $O/pmc_summary.txt
 python tools/pmc_csv.py $O/pmc_write gemm256 >> $O/pmc_summary.txt
 python tools/pmc_csv.py $O/pmc_mfma gemm256 >> $O/pmc_summary.txt
-python bench.py > $O/bench_c4.json 2>/dev/null
-python bench.py --workload res > $O/bench_res.json 2>/dev/null
+python bench.py --full > $O/bench_c4.json 2>/dev/null
+python bench.py --full --workload res > $O/bench_res.json 2>/dev/null
 ls $O/p_c4/*/ | head; cat $O/pmc_summary.txt; tail -c 600 $O/bench_c4.json

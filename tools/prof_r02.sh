@@ -17,5 +17,5 @@ python tools/rocpd_stats.py $(ls $O/p_c4/*/*.db | head -1) $O/c4_kernel_stats.md
 python tools/rocpd_stats.py $(ls $O/p_res/*/*.db | head -1) $O/res_kernel_stats.md > /dev/null
 for d in pmc_fetch pmc_write pmc_l2 pmc_busy pmc_mfma; do python tools/pmc_csv.py $O/$d gemm256; done > $O/gemm_pmc_summary.txt
 python tools/make_traffic_json.py $O > $O/gemm_traffic.json
-python bench.py --steps 10 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 10 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err
 head -12 $O/c4_kernel_stats.md; cat $O/gemm_traffic.json; tail -c 1500 $O/bench_default.json

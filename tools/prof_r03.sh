@@ -23,5 +23,5 @@ for d in pmc_fetch pmc_write pmc_l2 pmc_busy pmc_mfma pmc_ea pmc_eaw; do python 
 python tools/make_traffic_json.py $O > $O/gemm_traffic.json
 python tools/mall_probe.py > $O/mall_probe.txt 2>&1
 python tools/gemm_shapes.py > $O/gemm_shapes.txt 2>&1
-python bench.py --steps 10 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 10 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err
 head -14 $O/c4_kernel_stats.md; cat $O/gemm_traffic.json; cat $O/mall_probe.txt; tail -c 2500 $O/bench_default.json

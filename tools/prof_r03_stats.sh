@@ -13,5 +13,5 @@ python tools/rocpd_stats.py $(ls $O/p_res/*/*.db | head -1) $O/res_kernel_stats.
 python tools/rocpd_stats.py $(ls $O/p_dec/*/*.db | head -1) $O/decode_kernel_stats.md > /dev/null
 python tools/attn_prefill_bench.py > $O/attn_prefill.txt 2>&1
 for b in 1 2 4 8; do python tools/decode_bench.py --batch $b --new 33 2>&1 | tail -1; done > $O/decode_bench.txt
-python bench.py --steps 10 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 10 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err
 head -12 $O/c4_kernel_stats.md | cut -c1-130; head -12 $O/res_kernel_stats.md | cut -c1-130; cat $O/decode_bench.txt; tail -c 1800 $O/bench_default.json
