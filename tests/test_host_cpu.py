@@ -555,3 +555,58 @@ def test_layer_stack_structs_follow_the_weights():
     assert arr[0].o.w == layers[0]["o"][0].data_ptr() and arr[0].o.bias == layers[0]["o"][1].data_ptr()
     with pytest.raises(RuntimeError, match="row-major"):
         ops.LayerStack(L.LlamaLayer, [dict(layers[0], o=(lin(D, D).t(), None))])
+
+
+# (M, N, K, ldw, tune) -> (route, rms_first, big) of ops.linear on a 16-bit or fp8 weight (`_linear_route`, `_big`); expected values written from
+# the dispatch of the parent of the change that made them the one rule.
+_T8 = 1 << 21                                                      # ops.GEMM_TUNE_WAVES8
+LINEAR_ROUTES = [
+    # M at the GEMV (<= 4), skinny (3 ..= 16) and 256 x 256 (>= 1024) edges, against a LLaMA-sized weight
+    ((2, 4096, 4096, 4096, 0), ("gemv", False, False)),
+    ((3, 4096, 4096, 4096, 0), ("skinny", True, False)),
+    ((4, 4096, 4096, 4096, 0), ("skinny", True, False)),
+    ((5, 4096, 4096, 4096, 0), ("skinny", True, False)),
+    ((16, 4096, 4096, 4096, 0), ("skinny", True, False)),
+    ((17, 4096, 4096, 4096, 0), ("gemm", True, False)),
+    ((1023, 4096, 4096, 4096, 0), ("gemm", True, False)),
+    ((1024, 4096, 4096, 4096, 0), ("gemm", True, True)),
+    # N and K at the 256 x 256 edges
+    ((1024, 511, 4096, 4096, 0), ("gemm", True, False)),
+    ((1024, 512, 4096, 4096, 0), ("gemm", True, True)),
+    ((1024, 4096, 127, 127, 0), ("gemm", True, False)),
+    ((1024, 4096, 128, 128, 0), ("gemm", True, True)),
+    # N * K just below and at 1 << 22
+    ((4, 1023, 4096, 4096, 0), ("gemv", False, False)),
+    ((4, 1024, 4096, 4096, 0), ("skinny", True, False)),
+    ((5, 1023, 4096, 4096, 0), ("gemm", True, False)),
+    ((5, 1024, 4096, 4096, 0), ("skinny", True, False)),
+    # K % 32 (K % 8 == 0), K % 8, K % 64 (K % 32 == 0)
+    ((3, 8192, 4104, 4104, 0), ("gemv", False, False)),
+    ((5, 8192, 4104, 4104, 0), ("gemm", True, False)),
+    ((1, 4096, 4100, 4100, 0), ("gemm", True, False)),
+    ((3, 4096, 4100, 4100, 0), ("gemm", True, False)),
+    ((8, 4096, 4128, 4128, 0), ("skinny", True, False)),
+    ((1024, 4096, 4128, 4128, 0), ("gemm", True, True)),
+    # the weight's row pitch
+    ((3, 4096, 4096, 4100, 0), ("gemv", False, False)),
+    ((8, 4096, 4096, 4100, 0), ("gemm", True, False)),
+    ((8, 4096, 4096, 4104, 0), ("skinny", True, False)),
+    # a forced GEMM form (tools / tests): no skinny kernel; the GEMV does not read it
+    ((8, 4096, 4096, 4096, _T8), ("gemm", True, False)),
+    ((3, 4096, 4096, 4096, _T8), ("gemv", False, False)),
+    # the GEMV's fused RMSNorm: M * K <= 16384
+    ((1, 4096, 16384, 16384, 0), ("gemv", False, False)),
+    ((1, 4096, 16392, 16392, 0), ("gemv", True, False)),
+    ((4, 512, 4096, 4096, 0), ("gemv", False, False)),
+    ((4, 512, 4104, 4104, 0), ("gemv", True, False)),
+    ((2, 4096, 8192, 8192, 0), ("gemv", False, False)),
+    ((2, 4096, 8200, 8200, 0), ("gemv", True, False)),
+    ((1, 64, 16385, 16385, 0), ("gemm", True, False)),
+]
+
+
+@pytest.mark.parametrize("shape,want", LINEAR_ROUTES)
+def test_linear_route_table(shape, want):
+    ops = pkg("ops")
+    assert ops.GEMM_TUNE_WAVES8 == _T8
+    assert (*ops._linear_route(*shape), ops._big(*shape[:3])) == want

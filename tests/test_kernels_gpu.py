@@ -72,6 +72,18 @@ def test_gemv_decode_shapes(M):
     assert_close_bf16(y, F.silu(_mm_ref(x, wg)) * _mm_ref(x, wu), what="gemv swiglu")
 
 
+def test_gemv_refuses_epilogue_operands_of_another_dtype():
+    """The GEMV route checks bias and residual as every route does: one of another dtype than x is refused, not read as raw bytes."""
+    ops = pkg("ops")
+    M, K, N = 2, 1088, 520
+    x, w = _rand(M, K, seed=31).to(DEV), _rand(N, K, seed=32, scale=K ** -0.5).to(DEV)
+    assert ops._linear_route(M, N, K, w.stride(0), 0)[0] == "gemv"
+    with pytest.raises(RuntimeError, match="`bias` must be torch.bfloat16"):
+        ops.linear(x, w, _rand(N, seed=33).to(DEV, torch.float16))
+    with pytest.raises(RuntimeError, match="`residual` must be torch.bfloat16"):
+        ops.linear(x, w, residual=torch.zeros(M, N, device=DEV))
+
+
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M", [2, 4, 5, 8, 16])
 def test_skinny_gemm_batched_decode_shapes(M, dt):

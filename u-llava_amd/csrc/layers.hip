@@ -32,26 +32,85 @@ struct SK {                      // the caller's stream-K policy (ops.streamk_po
     int64_t min_k;               // < 0: never split
 };
 
-// ops.linear for M > 16, K % 64 == 0: the tiled GEMM; 256 x 256 kernel + tile-major weights + stream-K tail when the shape is "big".
-inline int lin(const void* x, int64_t ldx, const ull_linear* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
-               const SK& sk, void* stream) {
+// How the tiled GEMM runs a Linear at M rows (ops._big / ops._gemm_ws): a "big" shape takes the 256 x 256 kernel, the tile-major weight where
+// there is one, and the stream-K tail from K >= min_k on.
+struct Tiled {
+    const void* w;
+    int64_t ldw;
+    int flags;
+    void* ws;
+    int64_t wsb;
+};
+inline Tiled tiled(const ull_linear* L, int64_t M, const SK& sk) {
     const bool big = M >= 1024 && L->n >= 512 && L->k >= 128;
-    void* ws = nullptr;
-    int64_t wsb = 0;
-    if (big && sk.min_k >= 0 && L->k >= sk.min_k) { ws = sk.ws; wsb = sk.bytes; }
-    if (L->bias) flags |= ULL_EPI_BIAS;
-    if (R) flags |= ULL_EPI_RESID;
-    if (big && L->w_tiled)
-        return FN(ull_gemm_)(x, ldx, L->w_tiled, L->k, out, ldc, L->bias, R, ldr, M, L->n, L->k, flags | ULL_EPI_W_TILED, ws, wsb, stream);
-    return FN(ull_gemm_)(x, ldx, L->w, L->ldw, out, ldc, L->bias, R, ldr, M, L->n, L->k, flags, ws, wsb, stream);
+    Tiled t{L->w, L->ldw, 0, nullptr, 0};
+    if (big && L->w_tiled) { t.w = L->w_tiled; t.ldw = L->k; t.flags = ULL_EPI_W_TILED; }
+    if (big && sk.min_k >= 0 && L->k >= sk.min_k) { t.ws = sk.ws; t.wsb = sk.bytes; }
+    return t;
 }
 
-// ops.linear for M <= 4 (decode steps): the skinny MFMA GEMM from M = 3 on against LLaMA-sized weights, the weight-streaming GEMV otherwise;
-// a preceding LlamaRMSNorm is fused into the GEMV where its LDS staging allows it and is a launch of its own otherwise.
-inline int lin_decode(const void* x, int64_t ldx, const void* rms_w, float eps, void* xn_scratch, const ull_linear* L, void* out, int64_t ldc,
-                      const void* R, int64_t ldr, int64_t M, int flags, void* stream) {
-    const bool skinny = M >= 3 && L->k % 32 == 0 && L->n * L->k >= ((int64_t)1 << 22) && L->ldw % 8 == 0;
+// ops.linear for M > 16, K % 64 == 0: the tiled GEMM.
+inline int lin(const void* x, int64_t ldx, const ull_linear* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
+               const SK& sk, void* stream) {
+    const Tiled t = tiled(L, M, sk);
     if (L->bias) flags |= ULL_EPI_BIAS;
+    if (R) flags |= ULL_EPI_RESID;
+    return FN(ull_gemm_)(x, ldx, t.w, t.ldw, out, ldc, L->bias, R, ldr, M, L->n, L->k, flags | t.flags, t.ws, t.wsb, stream);
+}
+
+// The weight formats of a decode-shape Linear: a 16-bit ull_linear, or (bf16 build) an fp8 ull_linear_w8, which has no bias.  Each overload
+// passes the weight to the entry of its format.
+inline bool has_weight(const ull_linear* L) { return L->w; }
+inline const void* bias_of(const ull_linear* L) { return L->bias; }
+inline int64_t ldw_of(const ull_linear* L) { return L->ldw; }
+inline int gemm_skinny(const void* x, int64_t ldx, const ull_linear* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
+                       void* stream) {
+    return FN(ull_gemm_skinny_)(x, ldx, L->w, L->ldw, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+}
+inline int gemv(const void* x, int64_t ldx, const ull_linear* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags, void* stream) {
+    return FN(ull_gemv_)(x, ldx, L->w, L->ldw, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+}
+inline int gemv_rmsnorm(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear* L, void* out, int64_t ldc, const void* R,
+                        int64_t ldr, int64_t M, int flags, void* stream) {
+    return FN(ull_gemv_rmsnorm_)(x, ldx, rms_w, eps, L->w, L->ldw, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+}
+inline int gemv_qkv_rope_append(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear* L, void* q, int64_t ldq, const void* cs,
+                                const void* sn, void* kc, void* vtc, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
+                                void* stream) {
+    return FN(ull_gemv_qkv_rope_append_)(x, ldx, rms_w, eps, L->w, L->ldw, q, ldq, cs, sn, kc, vtc, B, S, H, hd, L->k, smax, past, stream);
+}
+
+#ifndef ULL_ELEM_F16
+inline bool has_weight(const ull_linear_w8* L) { return L->codes && L->scales; }
+inline const void* bias_of(const ull_linear_w8*) { return nullptr; }
+inline int64_t ldw_of(const ull_linear_w8* L) { return L->ld; }
+inline int gemm_skinny(const void* x, int64_t ldx, const ull_linear_w8* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
+                       void* stream) {
+    return ull_gemm_skinny_w8_bf16(x, ldx, L->codes, L->ld, L->scales, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+}
+inline int gemv(const void* x, int64_t ldx, const ull_linear_w8* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
+                void* stream) {
+    return ull_gemv_w8_bf16(x, ldx, L->codes, L->ld, L->scales, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+}
+inline int gemv_rmsnorm(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear_w8* L, void* out, int64_t ldc, const void* R,
+                        int64_t ldr, int64_t M, int flags, void* stream) {
+    return ull_gemv_rmsnorm_w8_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+}
+inline int gemv_qkv_rope_append(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear_w8* L, void* q, int64_t ldq, const void* cs,
+                                const void* sn, void* kc, void* vtc, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
+                                void* stream) {
+    return ull_gemv_qkv_rope_append_w8_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, q, ldq, cs, sn, kc, vtc, B, S, H, hd, L->k, smax, past,
+                                            stream);
+}
+#endif  // !ULL_ELEM_F16
+
+// ops.linear for M <= 4 (decode steps), ops._linear_route: the skinny MFMA GEMM from M = 3 on against LLaMA-sized weights, the weight-streaming
+// GEMV otherwise; a preceding LlamaRMSNorm is fused into the GEMV where its LDS staging allows it and is a launch of its own otherwise.
+template <class Lin>
+inline int lin_decode(const void* x, int64_t ldx, const void* rms_w, float eps, void* xn_scratch, const Lin* L, void* out, int64_t ldc,
+                      const void* R, int64_t ldr, int64_t M, int flags, void* stream) {
+    const bool skinny = M >= 3 && L->k % 32 == 0 && L->n * L->k >= ((int64_t)1 << 22) && ldw_of(L) % 8 == 0;
+    if (bias_of(L)) flags |= ULL_EPI_BIAS;
     if (R) flags |= ULL_EPI_RESID;
     if (rms_w && (skinny || !(L->k % 8 == 0 && M * L->k <= 16384))) {
         TRY(FN(ull_rmsnorm_)(x, ldx, rms_w, xn_scratch, L->k, M, L->k, eps, stream));
@@ -59,9 +118,9 @@ inline int lin_decode(const void* x, int64_t ldx, const void* rms_w, float eps, 
         ldx = L->k;
         rms_w = nullptr;
     }
-    if (skinny) return FN(ull_gemm_skinny_)(x, ldx, L->w, L->ldw, out, ldc, L->bias, R, ldr, M, L->n, L->k, flags, stream);
-    if (rms_w) return FN(ull_gemv_rmsnorm_)(x, ldx, rms_w, eps, L->w, L->ldw, out, ldc, L->bias, R, ldr, M, L->n, L->k, flags, stream);
-    return FN(ull_gemv_)(x, ldx, L->w, L->ldw, out, ldc, L->bias, R, ldr, M, L->n, L->k, flags, stream);
+    if (skinny) return gemm_skinny(x, ldx, L, out, ldc, R, ldr, M, flags, stream);
+    if (rms_w) return gemv_rmsnorm(x, ldx, rms_w, eps, L, out, ldc, R, ldr, M, flags, stream);
+    return gemv(x, ldx, L, out, ldc, R, ldr, M, flags, stream);
 }
 
 }  // namespace
@@ -83,14 +142,8 @@ extern "C" int FN(ull_llama_prefill_layers_)(const ull_llama_layer* layers, int6
             return ULL_ERR_ARG;
         TRY(FN(ull_rmsnorm_)(x, D, w.ln1, xn, D, T, D, eps, stream));                                   // input_layernorm
         {                                                                                               // q|k|v projection + RoPE epilogue
-            const bool big = T >= 1024 && w.qkv.n >= 512 && w.qkv.k >= 128;
-            void* wsp = nullptr;
-            int64_t wsb = 0;
-            if (big && sk.min_k >= 0 && D >= sk.min_k) { wsp = ws; wsb = ws_bytes; }
-            if (big && w.qkv.w_tiled)
-                TRY(FN(ull_gemm_qkv_rope_)(xn, D, w.qkv.w_tiled, D, qkv, 3 * D, T, 3 * D, D, rope_cos, rope_sin, 2 * D, hd, ULL_EPI_W_TILED, wsp, wsb, stream));
-            else
-                TRY(FN(ull_gemm_qkv_rope_)(xn, D, w.qkv.w, w.qkv.ldw, qkv, 3 * D, T, 3 * D, D, rope_cos, rope_sin, 2 * D, hd, 0, wsp, wsb, stream));
+            const Tiled t = tiled(&w.qkv, T, sk);
+            TRY(FN(ull_gemm_qkv_rope_)(xn, D, t.w, t.ldw, qkv, 3 * D, T, 3 * D, D, rope_cos, rope_sin, 2 * D, hd, t.flags, t.ws, t.wsb, stream));
         }
         // causal attention, V read as rows of the fused q|k|v buffer (vt_len = 0)
         TRY(FN(ull_attention_)(q, S * 3 * D, hd, 3 * D, q + D * 2, S * 3 * D, hd, 3 * D, q + 2 * D * 2, S * 3 * D, hd, 3 * D, 0, att, S * D, hd, D, key_mask,
@@ -104,21 +157,30 @@ extern "C" int FN(ull_llama_prefill_layers_)(const ull_llama_layer* layers, int6
     return ULL_OK;
 }
 
-extern "C" int FN(ull_llama_decode_layers_)(const ull_llama_layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid,
-                                            void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
-                                            const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H,
-                                            int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
+namespace {
+
+// The decode-step layer loop over either layer struct.  Every layer is checked before anything is enqueued.
+template <class Layer>
+int llama_decode_layers(const Layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn, void* q, void* att, void* act,
+                        const void* rope_cos, const void* rope_sin, const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B,
+                        int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
     if (!layers || !x_in || !x_out || !x_mid || !xn || !q || !att || !act || !rope_cos || !rope_sin || !k_cache || !vt_cache || !zeros || n_layers <= 0)
         return ULL_ERR_ARG;
     const int64_t D = H * hd, T = B * S;
-    if (T > 4 || T <= 0 || past <= 0 || (hd & 1) || D % 8 || T * D * 2 > 32768 || past + S > smax) return ULL_ERR_SHAPE;
+    if (T > 4 || T <= 0 || past <= 0 || (hd & 1) || D % 8 || I <= 0 || I % 8 || T * D * 2 > 32768 || past + S > smax) return ULL_ERR_SHAPE;
+    for (int64_t l = 0; l < n_layers; ++l) {
+        const Layer& w = layers[l];
+        if (w.qkv.n != 3 * D || w.qkv.k != D || w.o.n != D || w.o.k != D || w.gu.n != 2 * I || w.gu.k != D || w.down.n != D || w.down.k != I)
+            return ULL_ERR_SHAPE;
+        for (const auto* L : {&w.qkv, &w.o, &w.gu, &w.down})
+            if (!has_weight(L) || ldw_of(L) < L->k) return ULL_ERR_ARG;
+        if (!w.ln1 || !w.ln2 || !k_cache[l] || !vt_cache[l] || !x_out[l]) return ULL_ERR_ARG;
+    }
     const float scale = 1.0f / sqrtf((float)hd);
     const void* x = x_in;
     for (int64_t l = 0; l < n_layers; ++l) {
-        const ull_llama_layer& w = layers[l];
-        if (w.qkv.n != 3 * D || w.qkv.k != D || !k_cache[l] || !vt_cache[l] || !x_out[l]) return ULL_ERR_ARG;
-        TRY(FN(ull_gemv_qkv_rope_append_)(x, D, w.ln1, eps, w.qkv.w, w.qkv.ldw, q, D, rope_cos, rope_sin, k_cache[l], vt_cache[l], B, S, H, hd, D, smax,
-                                          past, stream));
+        const Layer& w = layers[l];
+        TRY(gemv_qkv_rope_append(x, D, w.ln1, eps, &w.qkv, q, D, rope_cos, rope_sin, k_cache[l], vt_cache[l], B, S, H, hd, smax, past, stream));
         TRY(FN(ull_attention_)(q, S * D, hd, D, k_cache[l], H * smax * hd, smax * hd, hd, vt_cache[l], H * hd * smax, hd * smax, smax, smax, att, S * D, hd, D,
                                key_mask, B, H, S, past + S, hd, 1, 1, scale, 1.0f, nullptr, nullptr, 0, 0, 0, zeros, stream));
         TRY(lin_decode(att, D, nullptr, 0.f, xn, &w.o, x_mid, D, x, D, T, 0, stream));
@@ -129,59 +191,23 @@ extern "C" int FN(ull_llama_decode_layers_)(const ull_llama_layer* layers, int64
     return ULL_OK;
 }
 
-#ifndef ULL_ELEM_F16
-namespace {
-
-// lin_decode on an fp8 weight: the same GEMV / skinny choice and RMSNorm placement, the fp8 forms of the entries
-inline int lin_decode_w8(const void* x, int64_t ldx, const void* rms_w, float eps, void* xn_scratch, const ull_linear_w8* L, void* out, int64_t ldc,
-                         const void* R, int64_t ldr, int64_t M, int flags, void* stream) {
-    const bool skinny = M >= 3 && L->k % 32 == 0 && L->n * L->k >= ((int64_t)1 << 22) && L->ld % 8 == 0;
-    if (R) flags |= ULL_EPI_RESID;
-    if (rms_w && (skinny || !(L->k % 8 == 0 && M * L->k <= 16384))) {
-        TRY(FN(ull_rmsnorm_)(x, ldx, rms_w, xn_scratch, L->k, M, L->k, eps, stream));
-        x = xn_scratch;
-        ldx = L->k;
-        rms_w = nullptr;
-    }
-    if (skinny) return ull_gemm_skinny_w8_bf16(x, ldx, L->codes, L->ld, L->scales, out, ldc, nullptr, R, ldr, M, L->n, L->k, flags, stream);
-    if (rms_w) return ull_gemv_rmsnorm_w8_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, out, ldc, nullptr, R, ldr, M, L->n, L->k, flags, stream);
-    return ull_gemv_w8_bf16(x, ldx, L->codes, L->ld, L->scales, out, ldc, nullptr, R, ldr, M, L->n, L->k, flags, stream);
-}
-
 }  // namespace
 
-// ull_llama_decode_layers_bf16 on fp8 weights: the same launches with the fp8 entries; every layer's shapes are checked before anything is
-// enqueued.
+extern "C" int FN(ull_llama_decode_layers_)(const ull_llama_layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid,
+                                            void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
+                                            const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H,
+                                            int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
+    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask, k_cache, vt_cache, B, S, H, hd, I,
+                               smax, past, eps, zeros, stream);
+}
+
+#ifndef ULL_ELEM_F16
 extern "C" int ull_llama_decode_layers_w8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid,
                                                void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
                                                const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H,
                                                int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
-    if (!layers || !x_in || !x_out || !x_mid || !xn || !q || !att || !act || !rope_cos || !rope_sin || !k_cache || !vt_cache || !zeros || n_layers <= 0)
-        return ULL_ERR_ARG;
-    const int64_t D = H * hd, T = B * S;
-    if (T > 4 || T <= 0 || past <= 0 || (hd & 1) || D % 8 || I <= 0 || I % 8 || T * D * 2 > 32768 || past + S > smax) return ULL_ERR_SHAPE;
-    for (int64_t l = 0; l < n_layers; ++l) {
-        const ull_llama_layer_w8& w = layers[l];
-        if (w.qkv.n != 3 * D || w.qkv.k != D || w.o.n != D || w.o.k != D || w.gu.n != 2 * I || w.gu.k != D || w.down.n != D || w.down.k != I)
-            return ULL_ERR_SHAPE;
-        for (const ull_linear_w8* L : {&w.qkv, &w.o, &w.gu, &w.down})
-            if (!L->codes || !L->scales || L->ld < L->k) return ULL_ERR_ARG;
-        if (!w.ln1 || !w.ln2 || !k_cache[l] || !vt_cache[l] || !x_out[l]) return ULL_ERR_ARG;
-    }
-    const float scale = 1.0f / sqrtf((float)hd);
-    const void* x = x_in;
-    for (int64_t l = 0; l < n_layers; ++l) {
-        const ull_llama_layer_w8& w = layers[l];
-        TRY(ull_gemv_qkv_rope_append_w8_bf16(x, D, w.ln1, eps, w.qkv.codes, w.qkv.ld, w.qkv.scales, q, D, rope_cos, rope_sin, k_cache[l], vt_cache[l], B, S,
-                                             H, hd, D, smax, past, stream));
-        TRY(FN(ull_attention_)(q, S * D, hd, D, k_cache[l], H * smax * hd, smax * hd, hd, vt_cache[l], H * hd * smax, hd * smax, smax, smax, att, S * D, hd, D,
-                               key_mask, B, H, S, past + S, hd, 1, 1, scale, 1.0f, nullptr, nullptr, 0, 0, 0, zeros, stream));
-        TRY(lin_decode_w8(att, D, nullptr, 0.f, xn, &w.o, x_mid, D, x, D, T, 0, stream));
-        TRY(lin_decode_w8(x_mid, D, w.ln2, eps, xn, &w.gu, act, I, nullptr, 0, T, ULL_EPI_SWIGLU, stream));
-        TRY(lin_decode_w8(act, I, nullptr, 0.f, xn, &w.down, x_out[l], D, x_mid, D, T, 0, stream));
-        x = x_out[l];
-    }
-    return ULL_OK;
+    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask, k_cache, vt_cache, B, S, H, hd, I,
+                               smax, past, eps, zeros, stream);
 }
 #endif  // !ULL_ELEM_F16
 

@@ -1026,7 +1026,7 @@ class UllavaCoreForCausalLM(nn.Module):
             else:
                 outs = [torch.empty(T, D, device=dev, dtype=x.dtype)] * L
             if coarse == "decode":
-                (ops.llama_decode_layers_w8 if w8 else ops.llama_decode_layers)(stack, x, outs, rope_cs[0], rope_cs[1], key_mask, cache.c_ptrs()[0], cache.c_ptrs()[1], B, S, H, hd, I, cache.smax,
+                ops.llama_decode_layers(stack, x, outs, rope_cs[0], rope_cs[1], key_mask, cache.c_ptrs()[0], cache.c_ptrs()[1], B, S, H, hd, I, cache.smax,
                                         past, cfg.rms_norm_eps)
             else:
                 ops.llama_prefill_layers(stack, x, outs, rope_cs[0], rope_cs[1], key_mask, B, S, H, hd, I, cfg.rms_norm_eps)

@@ -202,9 +202,9 @@ def _w8_scratch(device: torch.device, stream_id: int, numel: int) -> torch.Tenso
 
 def _w8_dequant_for_gemm(q: Fp8Weight, M: int):
     """(row-major view, tile-major view or None) of dequant(q) in the stream's scratch, laid out as the bf16 GEMM would read the
-    weight at this M: tile-major where a bf16 weight has its tile-major copy and the 256 x 256 path takes it (register_tiled / `big`)."""
+    weight at this M: tile-major where a bf16 weight has its tile-major copy (register_tiled: K % 64 == 0) and the 256 x 256 path takes it."""
     N, K = q.shape
-    tiled = M >= 1024 and N >= 512 and K >= 128 and K % 64 == 0
+    tiled = _big(M, N, K) and K % 64 == 0
     buf = _w8_scratch(q.device, _stream(), (-(-N // 256) * 256 if tiled else N) * K)
     wd = dequantize_fp8(q, tiled=tiled, out=buf)
     if tiled:
@@ -212,48 +212,12 @@ def _w8_dequant_for_gemm(q: Fp8Weight, M: int):
     return wd, None
 
 
-def _linear_w8(x, q: Fp8Weight, bias, act, residual, swiglu, out, out_f32, rms_w, rms_eps, tune, bias_after_rounding):
-    """`linear` on an fp8 weight: the same dispatch as for a bf16 weight of the same shape, each kernel in its fp8 form."""
-    if x.dtype != BF16:
-        raise RuntimeError(f"u-llava_amd.linear: fp8 weights need bf16 activations, got {x.dtype}")
-    _chk(x, "x")
-    M, ldx = _rows(x)
-    N, K = q.shape
-    lead = tuple(x.shape[:-1])
-    if x.shape[-1] != K:
-        raise RuntimeError(f"u-llava_amd.linear: K mismatch {x.shape[-1]} vs {K}")
-    ldq = q.codes.stride(0)
-    skinny = 3 <= M <= 16 and K % 32 == 0 and N * K >= (1 << 22) and ldq % 8 == 0 and tune == 0
-    decode = skinny or (M <= 4 and K % 8 == 0)
-    if not decode:
-        w, wt = _w8_dequant_for_gemm(q, M)
-        return linear(x, w, bias, act, residual, swiglu, out, out_f32, rms_w, rms_eps, tune, bias_after_rounding, _wt=wt)
-    if rms_w is not None and (skinny or not (M <= 4 and K % 8 == 0 and M * K <= 16384)):
-        x = rmsnorm(x, rms_w, rms_eps)
-        rms_w = None
-        M, ldx = _rows(x)
-    n_out = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty(*lead, n_out, device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
-    flags = ACTS[act] | (EPI_BIAS if bias is not None else 0) | (EPI_RESID if residual is not None else 0) | \
-        (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0) | (EPI_BIAS_ROUNDED if bias_after_rounding else 0)
-    if bias is not None:
-        _chk(bias, "bias", x.dtype)
-    ldr = 0
-    if residual is not None:
-        _chk(residual, "residual", x.dtype)
-        ldr = _rows(residual)[1]
-    if skinny:
-        _lib.call("ull_gemm_skinny_w8_bf16", _p(x), ldx, _p(q.codes), ldq, _p(q.scales), _p(out), _rows(out)[1], _p(bias), _p(residual), ldr, M, N, K,
-                  flags, _stream())
-    elif rms_w is not None:
-        _chk(rms_w, "rms_w", x.dtype)
-        _lib.call("ull_gemv_rmsnorm_w8_bf16", _p(x), ldx, _p(rms_w), float(rms_eps), _p(q.codes), ldq, _p(q.scales), _p(out), _rows(out)[1], _p(bias),
-                  _p(residual), ldr, M, N, K, flags, _stream())
-    else:
-        _lib.call("ull_gemv_w8_bf16", _p(x), ldx, _p(q.codes), ldq, _p(q.scales), _p(out), _rows(out)[1], _p(bias), _p(residual), ldr, M, N, K, flags,
-                  _stream())
-    return out
+def _weight_args(w):
+    """(entry suffix, weight arguments) of a decode-shape entry (skinny GEMM, GEMV, GEMV + RMSNorm, q|k|v + RoPE + cache append): a 16-bit
+    weight passes (pointer, row pitch), an Fp8Weight (codes, row pitch, scales) to the *_w8_bf16 form."""
+    if isinstance(w, Fp8Weight):
+        return "w8_bf16", (w.codes.data_ptr(), w.codes.stride(0), w.scales.data_ptr())
+    return _SFX[w.dtype], (w.data_ptr(), w.stride(0))
 
 
 # ---- stream-K workspace: one fp32 scratch buffer per (device, stream) ---------------------------------------------------
@@ -313,121 +277,122 @@ class streamk_policy:
         return False
 
 
+# ---- the Linear dispatch rule: every route of `linear` / `linear_qkv_rope` is decided here ------------------------------------------------
+def _linear_route(M: int, N: int, K: int, ldw: int, tune: int):
+    """(route, rms_first) of a 16-bit or fp8 Linear x [M, K] @ w.T, w [N, K] with row pitch ldw.
+    route "skinny": batched decode steps against LLaMA-sized weights put the weight stream on the matrix cores (the GEMV is FMA-bound from
+    M = 4 on and measured slower from M = 3 on (decode step at batch 3: 4.47 vs 4.24 ms; at batch 2 the GEMV wins, 4.00 vs 4.08); the tiled
+    GEMM's grid is a few dozen blocks at these M).  Small weights stay where they were.  "gemv": the weight-streaming GEMV at decode shapes
+    (no padding, no MFMA).  "gemm": the tiled GEMM.
+    rms_first: a requested RMSNorm is a launch of its own ahead of the Linear; the GEMV fuses it into its prologue while the M x K
+    activations fit its LDS staging.  csrc/layers.hip `lin_decode` mirrors this rule for the coarse decode entries."""
+    if 3 <= M <= 16 and K % 32 == 0 and N * K >= (1 << 22) and ldw % 8 == 0 and tune == 0:
+        return "skinny", True
+    if M <= 4 and K % 8 == 0:
+        return "gemv", M * K > 16384
+    return "gemm", True
+
+
+def _big(M: int, N: int, K: int) -> bool:
+    """The tiled GEMM takes its 256 x 256 kernel, the weight's tile-major copy and (K >= streamk_min_k) the stream-K tail
+    (csrc/layers.hip `tiled` mirrors this and _gemm_ws's stream-K choice)."""
+    return M >= 1024 and N >= 512 and K >= 128
+
+
+def _gemm_ws(device: torch.device, stream_id: int, big: bool, M: int, N: int, K: int, small_m: bool):
+    """(pointer, bytes) of the fp32 workspace a tiled GEMM splits K into, or (None, 0): the stream-K tail of a big GEMM, or -- small_m: the
+    kernel has the split, and small_m_split_k is on -- the split-K of a small-M one."""
+    min_k = _SK_MIN_K[0]
+    if min_k is None:
+        return None, 0
+    if big:
+        split = K >= min_k
+    else:
+        # opt-in latency mode (small_m_split_k): few 128x128 tiles, a long K and a weight of at least 8 MB (single-image prefill: o_proj /
+        # down_proj, CLIP's fc2): the kernel splits K over the idle CUs (376 -> 256 us per LLaMA layer at M = 323)
+        split = small_m and _SMALL_M_SPLIT_K[0] and K >= 1024 and M >= 128 and N * K >= (1 << 22) and -(-M // 128) * -(-N // 128) <= 256
+    if not split:
+        return None, 0
+    ws = _streamk_ws(device, stream_id)
+    return ws.data_ptr(), ws.numel()
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act: Optional[str] = None,
            residual: Optional[torch.Tensor] = None, swiglu: bool = False, out: Optional[torch.Tensor] = None,
            out_f32: bool = False, rms_w: Optional[torch.Tensor] = None, rms_eps: float = 0.0, tune: int = 0,
-           bias_after_rounding: bool = False, _wt: Optional[torch.Tensor] = None) -> torch.Tensor:
+           bias_after_rounding: bool = False) -> torch.Tensor:
     """y = epilogue(x @ w.T).  x [..., K]; w [N, K] (nn.Linear layout).  swiglu: w is the 16-row interleaved gate/up pack.
     rms_w/rms_eps: apply LlamaRMSNorm to x first (fused into the GEMV prologue at decode shapes, a separate kernel otherwise).
     tune: ULL_GEMM_TUNE_* bits (tools/ only).  bias_after_rounding: y = round(round(x @ w.T) + bias) -- what at::linear computes
     for a NON-contiguous 3-D input (matmul + add_ instead of the fused addmm).
-    w may be an `Fp8Weight` (bf16 x only): the same result as on its dequantized bf16 weight, bit for bit.  (_wt: internal, the
-    tile-major weight of that path's 256 x 256 GEMM.)"""
-    if isinstance(w, Fp8Weight):
-        return _linear_w8(x, w, bias, act, residual, swiglu, out, out_f32, rms_w, rms_eps, tune, bias_after_rounding)
-    _chk(x, "x"); _chk(w, "w", x.dtype)
+    w may be an `Fp8Weight` (bf16 x only): the same result as on its dequantized bf16 weight, bit for bit."""
+    w8 = isinstance(w, Fp8Weight)
+    if w8 and x.dtype != BF16:
+        raise RuntimeError(f"u-llava_amd.linear: fp8 weights need bf16 activations, got {x.dtype}")
+    _chk(x, "x")
+    if not w8:
+        _chk(w, "w", x.dtype)
     M, ldx = _rows(x)
     N, K = w.shape
-    lead = tuple(x.shape[:-1])
     if x.shape[-1] != K:
         raise RuntimeError(f"u-llava_amd.linear: K mismatch {x.shape[-1]} vs {K}")
+    wt = None
     if x.dtype == F32:
-        # fp32 build: one plain GEMM kernel for every shape (any M / N / K / strides), the preceding RMSNorm as its own launch
-        if rms_w is not None:
-            x = rmsnorm(x, rms_w, rms_eps)
-            M, ldx = _rows(x)
-        if w.stride(1) != 1:
-            w = w.contiguous()
-        n_out = N // 2 if swiglu else N
-        if out is None:
-            out = torch.empty(*lead, n_out, device=x.device, dtype=F32)
-        flags = ACTS[act] | (EPI_BIAS if bias is not None else 0) | (EPI_RESID if residual is not None else 0) | (EPI_SWIGLU if swiglu else 0)
-        if bias is not None:
-            _chk(bias, "bias", F32)
-        ldr = 0
-        if residual is not None:
-            _chk(residual, "residual", F32)
-            ldr = _rows(residual)[1]
-        _lib.call("ull_gemm_f32", _p(x), ldx, _p(w), w.stride(0), _p(out), _rows(out)[1], _p(bias), _p(residual), ldr, M, N, K, flags, None, 0, _stream())
-        return out
-    # batched decode steps against LLaMA-sized weights: the weight stream on the matrix cores (the GEMV is FMA-bound from M = 4 on and
-    # measured slower from M = 3 on (decode step at batch 3: 4.47 vs 4.24 ms; at batch 2 the GEMV wins, 4.00 vs 4.08); the tiled GEMM's grid
-    # is a few dozen blocks at these M).  Small weights stay where they were.
-    skinny = 3 <= M <= 16 and K % 32 == 0 and N * K >= (1 << 22) and w.stride(0) % 8 == 0 and w.stride(1) == 1 and tune == 0
-    if rms_w is not None and (skinny or not (M <= 4 and K % 8 == 0 and M * K <= 16384)):
+        # fp32 build: one plain GEMM kernel for every shape (any M / N / K / strides), the preceding RMSNorm as its own launch; its output
+        # is fp32 anyway and its epilogue rounds nothing
+        route, rms_first = "f32", True
+        out_f32 = bias_after_rounding = False
+    else:
+        route, rms_first = _linear_route(M, N, K, (w.codes if w8 else w).stride(0), tune)
+        if w8 and route == "gemm":
+            # prefill shapes: dequantize into the stream's scratch, then the bf16 flow on dequant(w)
+            w, wt = _w8_dequant_for_gemm(w, M)
+            route, rms_first = _linear_route(M, N, K, w.stride(0), tune)
+    if rms_w is not None and rms_first:
         x = rmsnorm(x, rms_w, rms_eps)
         rms_w = None
         M, ldx = _rows(x)
-    if skinny:
-        n_out = N // 2 if swiglu else N
-        if out is None:
-            out = torch.empty(*lead, n_out, device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
-        flags = ACTS[act] | (EPI_BIAS if bias is not None else 0) | (EPI_RESID if residual is not None else 0) | \
-            (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0) | (EPI_BIAS_ROUNDED if bias_after_rounding else 0)
-        if bias is not None:
-            _chk(bias, "bias", x.dtype)
-        ldr = 0
-        if residual is not None:
-            _chk(residual, "residual", x.dtype)
-            ldr = _rows(residual)[1]
-        _lib.call("ull_gemm_skinny_" + _SFX[x.dtype], _p(x), ldx, _p(w), w.stride(0), _p(out), _rows(out)[1], _p(bias), _p(residual), ldr, M, N, K,
-                  flags, _stream())
-        return out
-    if M <= 4 and K % 8 == 0:
-        # decode shape: weight-streaming GEMV (no padding, no MFMA)
-        n_out = N // 2 if swiglu else N
-        if out is None:
-            out = torch.empty(*lead, n_out, device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
-        flags = ACTS[act] | (EPI_BIAS if bias is not None else 0) | (EPI_RESID if residual is not None else 0) | \
-            (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0) | (EPI_BIAS_ROUNDED if bias_after_rounding else 0)
-        ldr = _rows(residual)[1] if residual is not None else 0
-        if rms_w is not None:
-            _chk(rms_w, "rms_w", x.dtype)
-            _lib.call("ull_gemv_rmsnorm_" + _SFX[x.dtype], _p(x), ldx, _p(rms_w), float(rms_eps), _p(w), w.stride(0), _p(out), _rows(out)[1], _p(bias),
-                      _p(residual), ldr, M, N, K, flags, _stream())
-        else:
-            _lib.call("ull_gemv_" + _SFX[x.dtype], _p(x), ldx, _p(w), w.stride(0), _p(out), _rows(out)[1], _p(bias), _p(residual), ldr, M, N, K, flags,
-                      _stream())
-        return out
-    if K % 64:
-        # The MFMA kernel consumes K in 64-wide DMA tiles.  Every real width on the path (1024, 1280, 4096, 5120,
-        # 11008, 256, 128, 2048, 64, patch K padded by im2col) is a multiple of 64; only the tiny test models are not.
-        # Zero-padding K is exact (adds 0*0 terms).
-        Kp = ((K + 63) // 64) * 64
-        x = torch.nn.functional.pad(x.reshape(M, K) if x.dim() != 2 else x, (0, Kp - K))
-        w = torch.nn.functional.pad(w, (0, Kp - K))
-        K, ldx = Kp, Kp
-    n_out = N // 2 if swiglu else N
     if out is None:
-        out = torch.empty(*lead, n_out, device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
-    flags = ACTS[act] | (EPI_BIAS if bias is not None else 0) | (EPI_RESID if residual is not None else 0) | \
-        (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0) | (EPI_BIAS_ROUNDED if bias_after_rounding else 0)
+        out = torch.empty(*x.shape[:-1], N // 2 if swiglu else N, device=x.device, dtype=F32 if out_f32 else x.dtype)
+    flags = ACTS[act] | (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0) | (EPI_BIAS_ROUNDED if bias_after_rounding else 0)
     if bias is not None:
         _chk(bias, "bias", x.dtype)
+        flags |= EPI_BIAS
     ldr = 0
     if residual is not None:
         _chk(residual, "residual", x.dtype)
-        _, ldr = _rows(residual)
-    _, ldc = _rows(out)
-    big = M >= 1024 and N >= 512 and K >= 128
-    wt = (_tiled_of(w) if _wt is None else _wt) if big else None
+        flags |= EPI_RESID
+        ldr = _rows(residual)[1]
+    ldc = _rows(out)[1]
     st = _stream()
-    ws_ptr, ws_bytes = None, 0
-    min_k = _SK_MIN_K[0]
-    if big and min_k is not None and K >= min_k:
-        ws = _streamk_ws(x.device, st)
-        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
-    elif _SMALL_M_SPLIT_K[0] and not big and min_k is not None and K >= 1024 and M >= 128 and N * K >= (1 << 22) and -(-M // 128) * -(-N // 128) <= 256:
-        # opt-in latency mode (small_m_split_k): few 128x128 tiles, a long K and a weight of at least 8 MB (single-image prefill: o_proj /
-        # down_proj, CLIP's fc2): the kernel splits K over the idle CUs (376 -> 256 us per LLaMA layer at M = 323)
-        ws = _streamk_ws(x.device, st)
-        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
-    if wt is not None:
-        _lib.call("ull_gemm_" + _SFX[x.dtype], _p(x), ldx, _p(wt), K, _p(out), ldc, _p(bias), _p(residual), ldr, M, N, K, flags | EPI_W_TILED | tune,
+    if route == "f32":
+        _lib.call("ull_gemm_f32", _p(x), ldx, _p(w), w.stride(0), _p(out), ldc, _p(bias), _p(residual), ldr, M, N, K, flags, None, 0, st)
+    elif route == "gemm":
+        if K % 64:
+            # The MFMA kernel consumes K in 64-wide DMA tiles.  Every real width on the path (1024, 1280, 4096, 5120,
+            # 11008, 256, 128, 2048, 64, patch K padded by im2col) is a multiple of 64; only the tiny test models are not.
+            # Zero-padding K is exact (adds 0*0 terms).
+            Kp = ((K + 63) // 64) * 64
+            x = torch.nn.functional.pad(x.reshape(M, K) if x.dim() != 2 else x, (0, Kp - K))
+            w = torch.nn.functional.pad(w, (0, Kp - K))
+            K, ldx = Kp, Kp
+        big = _big(M, N, K)
+        if big and wt is None:
+            wt = _tiled_of(w)
+        ws_ptr, ws_bytes = _gemm_ws(x.device, st, big, M, N, K, small_m=True)
+        wp, ldw, flags = (wt, K, flags | EPI_W_TILED) if wt is not None else (w, w.stride(0), flags)
+        _lib.call("ull_gemm_" + _SFX[x.dtype], _p(x), ldx, _p(wp), ldw, _p(out), ldc, _p(bias), _p(residual), ldr, M, N, K, flags | tune,
                   ws_ptr, ws_bytes, st)
     else:
-        _lib.call("ull_gemm_" + _SFX[x.dtype], _p(x), ldx, _p(w), w.stride(0), _p(out), ldc, _p(bias), _p(residual), ldr, M, N, K, flags | tune,
-                  ws_ptr, ws_bytes, st)
+        sfx, wargs = _weight_args(w)
+        if route == "skinny":
+            _lib.call("ull_gemm_skinny_" + sfx, _p(x), ldx, *wargs, _p(out), ldc, _p(bias), _p(residual), ldr, M, N, K, flags, st)
+        elif rms_w is not None:
+            _chk(rms_w, "rms_w", x.dtype)
+            _lib.call("ull_gemv_rmsnorm_" + sfx, _p(x), ldx, _p(rms_w), float(rms_eps), *wargs, _p(out), ldc, _p(bias), _p(residual), ldr, M, N, K,
+                      flags, st)
+        else:
+            _lib.call("ull_gemv_" + sfx, _p(x), ldx, *wargs, _p(out), ldc, _p(bias), _p(residual), ldr, M, N, K, flags, st)
     return out
 
 
@@ -447,13 +412,14 @@ GEMM_TUNE_WAVES8, GEMM_TUNE_WAVES4 = 1 << 21, 1 << 22     # ULL_GEMM_TUNE_*: for
 
 
 def linear_qkv_rope(x: torch.Tensor, w: torch.Tensor, rope_cos: torch.Tensor, rope_sin: torch.Tensor, rope_cols: int, head_dim: int,
-                    out: Optional[torch.Tensor] = None, tune: int = 0, _wt: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, tune: int = 0) -> torch.Tensor:
     """Fused q|k|v projection + RoPE on the first `rope_cols` output columns (q and k heads), head_dim 128, K % 64 == 0, M > 4.
     Bit-identical to linear() followed by rope_inplace().  w may be an `Fp8Weight` (dequantized into a scratch first)."""
+    wt = None
     if isinstance(w, Fp8Weight):
         if x.dtype != BF16:
             raise RuntimeError(f"u-llava_amd.linear_qkv_rope: fp8 weights need bf16 activations, got {x.dtype}")
-        w, _wt = _w8_dequant_for_gemm(w, _rows(x)[0])
+        w, wt = _w8_dequant_for_gemm(w, _rows(x)[0])
     _chk(x, "x"); _chk(w, "w", x.dtype); _chk(rope_cos, "rope_cos", x.dtype); _chk(rope_sin, "rope_sin", x.dtype)
     M, ldx = _rows(x)
     N, K = w.shape
@@ -462,20 +428,14 @@ def linear_qkv_rope(x: torch.Tensor, w: torch.Tensor, rope_cos: torch.Tensor, ro
     if out is None:
         out = torch.empty(*x.shape[:-1], N, device=x.device, dtype=x.dtype)
     _, ldc = _rows(out)
-    big = M >= 1024 and N >= 512 and K >= 128
-    wt = (_tiled_of(w) if _wt is None else _wt) if big else None
+    big = _big(M, N, K)
+    if big and wt is None:
+        wt = _tiled_of(w)
     st = _stream()
-    ws_ptr, ws_bytes = None, 0
-    min_k = _SK_MIN_K[0]
-    if big and min_k is not None and K >= min_k:
-        ws = _streamk_ws(x.device, st)
-        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
-    if wt is not None:
-        _lib.call("ull_gemm_qkv_rope_" + _SFX[x.dtype], _p(x), ldx, _p(wt), K, _p(out), ldc, M, N, K, _p(rope_cos), _p(rope_sin), rope_cols,
-                  head_dim, EPI_W_TILED | tune, ws_ptr, ws_bytes, st)
-    else:
-        _lib.call("ull_gemm_qkv_rope_" + _SFX[x.dtype], _p(x), ldx, _p(w), w.stride(0), _p(out), ldc, M, N, K, _p(rope_cos), _p(rope_sin),
-                  rope_cols, head_dim, tune, ws_ptr, ws_bytes, st)
+    ws_ptr, ws_bytes = _gemm_ws(x.device, st, big, M, N, K, small_m=False)
+    wp, ldw, flags = (wt, K, EPI_W_TILED) if wt is not None else (w, w.stride(0), 0)
+    _lib.call("ull_gemm_qkv_rope_" + _SFX[x.dtype], _p(x), ldx, _p(wp), ldw, _p(out), ldc, M, N, K, _p(rope_cos), _p(rope_sin), rope_cols, head_dim,
+              flags | tune, ws_ptr, ws_bytes, st)
     return out
 
 
@@ -621,28 +581,23 @@ def linear_qkv_rope_append(x: torch.Tensor, w_qkv: torch.Tensor, rope_cos: torch
     """decode step (B * S <= 4 tokens): q | k | v projection of x (optionally RMS-normalised first) with RoPE and the KV-cache append in the
     GEMV's epilogue.  Returns the rotated queries [B * S, H * hd]; the rotated keys / the values land in the caches.  Same bits as
     `linear(x, w_qkv, rms_w=...)` followed by `rope_append`.  w_qkv may be an `Fp8Weight` (bf16 only)."""
-    w8 = isinstance(w_qkv, Fp8Weight)
-    if w8:
-        if x.dtype != BF16:
-            raise RuntimeError(f"u-llava_amd.linear_qkv_rope_append: fp8 weights need bf16 activations, got {x.dtype}")
-    else:
+    if not isinstance(w_qkv, Fp8Weight):
         _chk(w_qkv, "w_qkv", x.dtype)
+    elif x.dtype != BF16:
+        raise RuntimeError(f"u-llava_amd.linear_qkv_rope_append: fp8 weights need bf16 activations, got {x.dtype}")
     _chk(x, "x"); _chk(rope_cos, "rope_cos", x.dtype); _chk(rope_sin, "rope_sin", x.dtype)
     _chk(k_cache, "k_cache", x.dtype); _chk(vt_cache, "vt_cache", x.dtype)
     T, K = x.shape
     if T != B * S or T > 4 or w_qkv.shape != (3 * H * hd, K) or rope_cos.shape != (T, hd // 2) or rope_sin.shape != (T, hd // 2):
         raise RuntimeError("u-llava_amd.linear_qkv_rope_append: shapes (at most 4 tokens; w [3 * H * hd, K]; cos / sin [tokens, hd / 2])")
-    if x.stride(1) != 1 or (not w8 and w_qkv.stride(1) != 1) or not (rope_cos.is_contiguous() and rope_sin.is_contiguous()):
+    if not (rope_cos.is_contiguous() and rope_sin.is_contiguous()):
         raise RuntimeError("u-llava_amd.linear_qkv_rope_append: rows must be contiguous")
     if rms_w is not None:
         _chk(rms_w, "rms_w", x.dtype)
     q = torch.empty(T, H * hd, device=x.device, dtype=x.dtype)
-    if w8:
-        _lib.call("ull_gemv_qkv_rope_append_w8_bf16", _p(x), x.stride(0), _p(rms_w), float(rms_eps), _p(w_qkv.codes), w_qkv.codes.stride(0),
-                  _p(w_qkv.scales), _p(q), q.stride(0), _p(rope_cos), _p(rope_sin), _p(k_cache), _p(vt_cache), B, S, H, hd, K, smax, past, _stream())
-        return q
-    _lib.call("ull_gemv_qkv_rope_append_" + _SFX[x.dtype], _p(x), x.stride(0), _p(rms_w), float(rms_eps), _p(w_qkv), w_qkv.stride(0), _p(q),
-              q.stride(0), _p(rope_cos), _p(rope_sin), _p(k_cache), _p(vt_cache), B, S, H, hd, K, smax, past, _stream())
+    sfx, wargs = _weight_args(w_qkv)
+    _lib.call("ull_gemv_qkv_rope_append_" + sfx, _p(x), x.stride(0), _p(rms_w), float(rms_eps), *wargs, _p(q), q.stride(0), _p(rope_cos), _p(rope_sin),
+              _p(k_cache), _p(vt_cache), B, S, H, hd, K, smax, past, _stream())
     return q
 
 
@@ -1213,7 +1168,7 @@ def sumsq(g: torch.Tensor, out: torch.Tensor) -> None:
 # The per-op wrappers above cost a ctypes round trip + Python marshalling per LAUNCH (~15 us); a C4 step has ~400 launches, a decode step ~160.
 # A LayerStack holds the ctypes array of per-layer structs (weight / bias / norm pointers) and refreshes it when a pointer it recorded has
 # moved (a re-made tile-major copy after an optimizer step, a re-pack).  Results are bit-identical to the per-op path: same entries, same
-# dispatch rules (layers.hip `lin` / `lin_decode` mirror `linear` above).
+# dispatch rules (layers.hip `lin_decode` mirrors `_linear_route`, `tiled` mirrors `_big` and the stream-K tail of `_gemm_ws`).
 COARSE = [True]     # `with ops.per_op_layers():` = the per-op path (tests A/B the two)
 
 
@@ -1308,31 +1263,19 @@ def llama_prefill_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos,
 
 def llama_decode_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos, rope_sin, key_mask, k_ptrs, vt_ptrs, B: int, S: int, H: int, hd: int,
                         I: int, smax: int, past: int, eps: float):
-    """One generation step through all layers (T = B*S <= 4).  k_ptrs / vt_ptrs: ctypes void* arrays of the per-layer caches."""
-    _chk(x_in, "x_in")
+    """One generation step through all layers (T = B*S <= 4).  k_ptrs / vt_ptrs: ctypes void* arrays of the per-layer caches.  A stack of
+    _lib.LlamaLayerW8 (fp8 weights, bf16 activations) goes to ull_llama_decode_layers_w8_bf16."""
+    w8 = stack.kind is _lib.LlamaLayerW8
+    _chk(x_in, "x_in", BF16 if w8 else None)
     T, D = x_in.shape
     dev, dt = x_in.device, x_in.dtype
     scratch = torch.empty(T * (4 * D + 2 * max(D, I)), device=dev, dtype=dt)
     x_mid, q, att = scratch[:T * D], scratch[T * D:2 * T * D], scratch[2 * T * D:3 * T * D]
     xn = scratch[3 * T * D:3 * T * D + T * max(D, I)]
     act = scratch[3 * T * D + T * max(D, I):3 * T * D + T * max(D, I) + T * I]
-    _lib.call("ull_llama_decode_layers_" + _SFX[dt], stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid), _p(xn), _p(q), _p(att),
-              _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k_ptrs, vt_ptrs, B, S, H, hd, I, smax, past, float(eps), _zeros(dev).data_ptr(), _stream())
-
-
-def llama_decode_layers_w8(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos, rope_sin, key_mask, k_ptrs, vt_ptrs, B: int, S: int, H: int,
-                           hd: int, I: int, smax: int, past: int, eps: float):
-    """llama_decode_layers on a stack of _lib.LlamaLayerW8 (fp8 weights, bf16 activations): ull_llama_decode_layers_w8_bf16."""
-    _chk(x_in, "x_in", BF16)
-    T, D = x_in.shape
-    dev = x_in.device
-    scratch = torch.empty(T * (4 * D + 2 * max(D, I)), device=dev, dtype=BF16)
-    x_mid, q, att = scratch[:T * D], scratch[T * D:2 * T * D], scratch[2 * T * D:3 * T * D]
-    xn = scratch[3 * T * D:3 * T * D + T * max(D, I)]
-    act = scratch[3 * T * D + T * max(D, I):3 * T * D + T * max(D, I) + T * I]
-    _lib.call("ull_llama_decode_layers_w8_bf16", stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid), _p(xn), _p(q), _p(att),
-              _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k_ptrs, vt_ptrs, B, S, H, hd, I, smax, past, float(eps), _zeros(dev).data_ptr(),
-              _stream())
+    _lib.call("ull_llama_decode_layers_" + ("w8_bf16" if w8 else _SFX[dt]), stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid),
+              _p(xn), _p(q), _p(att), _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k_ptrs, vt_ptrs, B, S, H, hd, I, smax, past, float(eps),
+              _zeros(dev).data_ptr(), _stream())
 
 
 def clip_layers(stack: LayerStack, n_layers: int, h: torch.Tensor, n_img: int, S: int, H: int, hd: int, I: int, eps: float):
