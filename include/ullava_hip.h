@@ -129,6 +129,29 @@ int ull_gemv_qkv_rope_append_w8_bf16(const void* X, int64_t ldx, const void* nor
 int ull_gemm_skinny_w8_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc, const void* bias,
                             const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
 
+/* ---- FP8 (e4m3) KV cache (bf16 build only) ------------------------------------------------------------------------------------------
+ * KVCache(kv_dtype="fp8_e4m3") keeps, per layer, K codes [B, H, smax, hd] and V^T codes [B, H, hd, smax] (the key-permuted slot order of
+ * ull_transpose_v) plus one fp32 scale 2^s per (batch, head, position) for the K row (k_scale [B, H, smax], by key) and one for the V column
+ * (vt_scale [B, H, smax], by V^T slot), with the rule of ull_quantize_rows_fp8_bf16.  dequant = float(code) * 2^s is a bf16 value; every
+ * entry below reads / writes exactly what the bf16 path computes on the dequantized cache (hf LlamaAttention.forward's past_key_value
+ * concatenation, models/ullava_core.py:357-395, on the dequantized keys and values). */
+/* Decode attention over the cache (scale_mode 1, causal): keys < past = Sk - Sq from the codes, the Sq new keys from the bf16 staging window
+ * k_stage [B, H, 128, hd] / vt_stage [B, H, hd, 128] at row / slot k - w0 (w0 = past rounded down to 64: the decode appenders called on the
+ * staging buffers with smax = 128 and past - w0); then stores the new keys' codes and scales.  1 <= Sq <= 16, 2 <= ceil(Sk / 64) <= 64.
+ * Same bits as ull_attention_bf16 on the dequantized cache with the new keys appended. */
+int ull_attention_kv8_bf16(const void* Q, int64_t q_bs, int64_t q_hs, int64_t q_ss, const void* k_stage, const void* vt_stage, const void* k8,
+                           const void* vt8, const void* k_scale, const void* vt_scale, int64_t smax, void* O, int64_t o_bs, int64_t o_hs, int64_t o_ss,
+                           const void* key_mask, int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t hd, float scale, const void* zeros, void* stream);
+/* Quantize positions p0 .. p0 + n - 1 from bf16 sources at positions src_p0 + s: K rows (k_bs, k_hs, k_ss); V rows (v_bs, v_hs, v_ss) or,
+ * with v_image = 1, a V^T image in the permuted slot order (d stride v_ss).  Codes bit-identical to torch's CPU cast. */
+int ull_kv8_quantize_bf16(const void* K, int64_t k_bs, int64_t k_hs, int64_t k_ss, const void* V, int64_t v_bs, int64_t v_hs, int64_t v_ss, int v_image,
+                          int64_t src_p0, void* k8, void* vt8, void* k_scale, void* vt_scale, int64_t B, int64_t H, int64_t hd, int64_t smax, int64_t p0,
+                          int64_t n, void* stream);
+/* Dequantize positions [0, n): K_out [B, H, k_pitch, hd] and V^T Vt_out [B, H, hd, vt_pitch] (slots up to round_up(n, 64), keys >= n zero);
+ * either output may be null. */
+int ull_kv8_dequantize_bf16(const void* k8, const void* vt8, const void* k_scale, const void* vt_scale, int64_t B, int64_t H, int64_t hd, int64_t smax,
+                            int64_t n, void* K_out, int64_t k_pitch, void* Vt_out, int64_t vt_pitch, void* stream);
+
 /* y = w * bf16(x * rsqrt(mean(x^2) + eps)).  hf: LlamaRMSNorm.forward. */
 int ull_rmsnorm_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int64_t rows, int64_t D, float eps, void* stream);
 
@@ -511,6 +534,20 @@ int ull_llama_decode_layers_w8_bf16(const ull_llama_layer_w8* layers, int64_t n_
                                     void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
                                     void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax,
                                     int64_t past, float eps, const void* zeros, void* stream);
+/* ull_llama_decode_layers_bf16 / ull_llama_decode_layers_w8_bf16 on an fp8 KV cache (see ull_attention_kv8_bf16): per layer the q|k|v GEMV appends
+ * the step's keys to the shared bf16 staging window (k_stage [B, H, 128, hd], vt_stage [B, H, hd, 128]; pitch 128, first new key at past mod 64)
+ * and ull_attention_kv8_bf16 reads the layer's codes / scales (k8, vt8, k_scale, vt_scale: per-layer pointer arrays, cache pitch smax) plus
+ * the window, then quantizes the new keys into the layer's cache -- the same launches as the bf16-cache entry.  Every layer is checked before
+ * anything is enqueued, as above; in addition S <= 16 and 64 < past + S <= 4096 (the shapes ull_attention_kv8_bf16 takes; ULL_ERR_ARG). */
+int ull_llama_decode_layers_kv8_bf16(const ull_llama_layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
+                                     void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask, void* const* k8,
+                                     void* const* vt8, void* const* k_scale, void* const* vt_scale, void* k_stage, void* vt_stage, int64_t B, int64_t S,
+                                     int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream);
+int ull_llama_decode_layers_w8_kv8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
+                                        void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
+                                        void* const* k8, void* const* vt8, void* const* k_scale, void* const* vt_scale, void* k_stage, void* vt_stage,
+                                        int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros,
+                                        void* stream);
 
 /* hf CLIPEncoder.forward's layer loop (modeling_clip.py:353-384; models/ullava_core.py:146-158 reads hidden_states[-2], so the caller passes
  * the first 23 layers): h [T = n_img * S, D] is updated in place; h_mid [T, D], y [T, D], qkv [T, 3D], att [T, D], f [T, I] scratch.

@@ -135,9 +135,15 @@ SIGNATURES.update({
     "ull_gemv_rmsnorm_w8_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
     "ull_gemv_qkv_rope_append_w8_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64,
                                          _i64, _i64, _ptr],
+    "ull_attention_kv8_bf16": [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64,
+                               _i64, _f32, _ptr, _ptr],
+    "ull_kv8_quantize_bf16": [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr],
+    "ull_kv8_dequantize_bf16": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr],
     "ull_gemm_skinny_w8_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
     "ull_llama_decode_layers_w8_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
                                         _i64, _i64, _i64, _f32, _ptr, _ptr],
+    "ull_llama_decode_layers_kv8_bf16": [_ptr, _i64] + [_ptr] * 16 + [_i64] * 7 + [_f32, _ptr, _ptr],
+    "ull_llama_decode_layers_w8_kv8_bf16": [_ptr, _i64] + [_ptr] * 16 + [_i64] * 7 + [_f32, _ptr, _ptr],
 })
 
 # fp16-only entry points (no bf16 twin): the fp32 neck of an fp16 SAM encoder (image_encoder.py:117-124)

@@ -70,15 +70,7 @@ ULL_DEV uint2 w_load8(const uint8_t* p) {
     return make_uint2(v.x, v.y);
 }
 
-// 8 e4m3fn codes (element j in byte j) -> 8 floats float(q_j) * s.  The conversion is exact and s is a power of two, so the product is
-// exact too (and representable in bf16: 4 significant bits).
-ULL_DEV void unpack8_w8(const uint2& v, float s, float* f) {
-    typedef float f2_t __attribute__((ext_vector_type(2)));
-    const f2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, true);
-    const f2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, true);
-    f[0] = a[0] * s; f[1] = a[1] * s; f[2] = b[0] * s; f[3] = b[1] * s;
-    f[4] = c[0] * s; f[5] = c[1] * s; f[6] = d[0] * s; f[7] = d[1] * s;
-}
+// (unpack8_w8, fp8_scale_exp: ull_common.h)
 
 constexpr int XS_MAX_BYTES = 32 * 1024;     // X (optionally RMS-normalised) is staged in LDS when M * K * 2 fits in this
 
@@ -512,14 +504,7 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const elem_t* __
         for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
     }
     amax = wave_max(amax);
-    int s = 0;
-    if (amax > 0.f) {
-        int e;
-        frexpf(amax, &e);                                  // amax in [2^(e-1), 2^e): s is e - 9 or e - 8, settled exactly below
-        s = e - 9;
-        while (amax > ldexpf(448.f, s)) ++s;
-        while (amax <= ldexpf(448.f, s - 1)) --s;
-    }
+    const int s = fp8_scale_exp(amax);
     if (lane == 0) scales[row] = ldexpf(1.f, s);
     uint8_t* q = codes + (long)row * K;
     for (int c = lane; c < nchunk; c += 64) {

@@ -159,30 +159,66 @@ extern "C" int FN(ull_llama_prefill_layers_)(const ull_llama_layer* layers, int6
 
 namespace {
 
-// The decode-step layer loop over either layer struct.  Every layer is checked before anything is enqueued.
-template <class Layer>
+// The KV-cache formats of a decode step.  BfCache: the model-dtype K / V^T buffers per layer, appended to in place.  Kv8Cache (bf16 build):
+// the fp8 cache (csrc/kv8.hip) -- per-layer codes and scales plus ONE bf16 staging window shared by the layers: the appender writes the
+// step's keys into the window (pitch 128, first new key at past mod 64), ull_attention_kv8 reads the cached keys from the codes and the new
+// ones from the window, then quantizes the new keys into the layer's cache.  The same launches per layer in both formats.
+struct BfCache {
+    void* const* k; void* const* vt;
+};
+inline bool cache_layer_ok(const BfCache& c, int64_t l) { return c.k[l] && c.vt[l]; }
+inline bool cache_shape_ok(const BfCache& c, int64_t, int64_t) { return c.k && c.vt; }
+template <class Lin>
+inline int append_and_attend(const BfCache& c, int64_t l, const void* x, int64_t D, const void* ln1, float eps, const Lin* qkv, void* q, const void* cs,
+                             const void* sn, void* att, const void* key_mask, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
+                             float scale, const void* zeros, void* stream) {
+    TRY(gemv_qkv_rope_append(x, D, ln1, eps, qkv, q, D, cs, sn, c.k[l], c.vt[l], B, S, H, hd, smax, past, stream));
+    return FN(ull_attention_)(q, S * D, hd, D, c.k[l], H * smax * hd, smax * hd, hd, c.vt[l], H * hd * smax, hd * smax, smax, smax, att, S * D, hd, D,
+                              key_mask, B, H, S, past + S, hd, 1, 1, scale, 1.0f, nullptr, nullptr, 0, 0, 0, zeros, stream);
+}
+
+#ifndef ULL_ELEM_F16
+struct Kv8Cache {
+    void* const* k8; void* const* vt8; void* const* ks; void* const* vs;
+    void* k_stage; void* vt_stage;
+};
+inline bool cache_layer_ok(const Kv8Cache& c, int64_t l) { return c.k8[l] && c.vt8[l] && c.ks[l] && c.vs[l]; }
+// the shapes ull_attention_kv8 takes (the model routes other calls through the dequantized per-op path)
+inline bool cache_shape_ok(const Kv8Cache& c, int64_t S, int64_t past) {
+    return c.k8 && c.vt8 && c.ks && c.vs && c.k_stage && c.vt_stage && S <= 16 && past + S > 64 && past + S <= 4096;
+}
+template <class Lin>
+inline int append_and_attend(const Kv8Cache& c, int64_t l, const void* x, int64_t D, const void* ln1, float eps, const Lin* qkv, void* q, const void* cs,
+                             const void* sn, void* att, const void* key_mask, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
+                             float scale, const void* zeros, void* stream) {
+    TRY(gemv_qkv_rope_append(x, D, ln1, eps, qkv, q, D, cs, sn, c.k_stage, c.vt_stage, B, S, H, hd, 128, past & 63, stream));
+    return ull_attention_kv8_bf16(q, S * D, hd, D, c.k_stage, c.vt_stage, c.k8[l], c.vt8[l], c.ks[l], c.vs[l], smax, att, S * D, hd, D, key_mask, B, H, S,
+                                  past + S, hd, scale, zeros, stream);
+}
+#endif  // !ULL_ELEM_F16
+
+// The decode-step layer loop over either layer struct and either cache format.  Every layer is checked before anything is enqueued.
+template <class Layer, class Cache>
 int llama_decode_layers(const Layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn, void* q, void* att, void* act,
-                        const void* rope_cos, const void* rope_sin, const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B,
-                        int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
-    if (!layers || !x_in || !x_out || !x_mid || !xn || !q || !att || !act || !rope_cos || !rope_sin || !k_cache || !vt_cache || !zeros || n_layers <= 0)
-        return ULL_ERR_ARG;
+                        const void* rope_cos, const void* rope_sin, const void* key_mask, const Cache& cache, int64_t B, int64_t S, int64_t H,
+                        int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
+    if (!layers || !x_in || !x_out || !x_mid || !xn || !q || !att || !act || !rope_cos || !rope_sin || !zeros || n_layers <= 0) return ULL_ERR_ARG;
     const int64_t D = H * hd, T = B * S;
     if (T > 4 || T <= 0 || past <= 0 || (hd & 1) || D % 8 || I <= 0 || I % 8 || T * D * 2 > 32768 || past + S > smax) return ULL_ERR_SHAPE;
+    if (!cache_shape_ok(cache, S, past)) return ULL_ERR_ARG;
     for (int64_t l = 0; l < n_layers; ++l) {
         const Layer& w = layers[l];
         if (w.qkv.n != 3 * D || w.qkv.k != D || w.o.n != D || w.o.k != D || w.gu.n != 2 * I || w.gu.k != D || w.down.n != D || w.down.k != I)
             return ULL_ERR_SHAPE;
         for (const auto* L : {&w.qkv, &w.o, &w.gu, &w.down})
             if (!has_weight(L) || ldw_of(L) < L->k) return ULL_ERR_ARG;
-        if (!w.ln1 || !w.ln2 || !k_cache[l] || !vt_cache[l] || !x_out[l]) return ULL_ERR_ARG;
+        if (!w.ln1 || !w.ln2 || !cache_layer_ok(cache, l) || !x_out[l]) return ULL_ERR_ARG;
     }
     const float scale = 1.0f / sqrtf((float)hd);
     const void* x = x_in;
     for (int64_t l = 0; l < n_layers; ++l) {
         const Layer& w = layers[l];
-        TRY(gemv_qkv_rope_append(x, D, w.ln1, eps, &w.qkv, q, D, rope_cos, rope_sin, k_cache[l], vt_cache[l], B, S, H, hd, smax, past, stream));
-        TRY(FN(ull_attention_)(q, S * D, hd, D, k_cache[l], H * smax * hd, smax * hd, hd, vt_cache[l], H * hd * smax, hd * smax, smax, smax, att, S * D, hd, D,
-                               key_mask, B, H, S, past + S, hd, 1, 1, scale, 1.0f, nullptr, nullptr, 0, 0, 0, zeros, stream));
+        TRY(append_and_attend(cache, l, x, D, w.ln1, eps, &w.qkv, q, rope_cos, rope_sin, att, key_mask, B, S, H, hd, smax, past, scale, zeros, stream));
         TRY(lin_decode(att, D, nullptr, 0.f, xn, &w.o, x_mid, D, x, D, T, 0, stream));
         TRY(lin_decode(x_mid, D, w.ln2, eps, xn, &w.gu, act, I, nullptr, 0, T, ULL_EPI_SWIGLU, stream));
         TRY(lin_decode(act, I, nullptr, 0.f, xn, &w.down, x_out[l], D, x_mid, D, T, 0, stream));
@@ -197,8 +233,8 @@ extern "C" int FN(ull_llama_decode_layers_)(const ull_llama_layer* layers, int64
                                             void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
                                             const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H,
                                             int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
-    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask, k_cache, vt_cache, B, S, H, hd, I,
-                               smax, past, eps, zeros, stream);
+    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask, BfCache{k_cache, vt_cache}, B, S, H,
+                               hd, I, smax, past, eps, zeros, stream);
 }
 
 #ifndef ULL_ELEM_F16
@@ -206,8 +242,26 @@ extern "C" int ull_llama_decode_layers_w8_bf16(const ull_llama_layer_w8* layers,
                                                void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
                                                const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H,
                                                int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
-    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask, k_cache, vt_cache, B, S, H, hd, I,
-                               smax, past, eps, zeros, stream);
+    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask, BfCache{k_cache, vt_cache}, B, S, H,
+                               hd, I, smax, past, eps, zeros, stream);
+}
+
+extern "C" int ull_llama_decode_layers_kv8_bf16(const ull_llama_layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid,
+                                                void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
+                                                const void* key_mask, void* const* k8, void* const* vt8, void* const* k_scale, void* const* vt_scale,
+                                                void* k_stage, void* vt_stage, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax,
+                                                int64_t past, float eps, const void* zeros, void* stream) {
+    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask,
+                               Kv8Cache{k8, vt8, k_scale, vt_scale, k_stage, vt_stage}, B, S, H, hd, I, smax, past, eps, zeros, stream);
+}
+
+extern "C" int ull_llama_decode_layers_w8_kv8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out,
+                                                   void* x_mid, void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
+                                                   const void* key_mask, void* const* k8, void* const* vt8, void* const* k_scale,
+                                                   void* const* vt_scale, void* k_stage, void* vt_stage, int64_t B, int64_t S, int64_t H, int64_t hd,
+                                                   int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
+    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask,
+                               Kv8Cache{k8, vt8, k_scale, vt_scale, k_stage, vt_stage}, B, S, H, hd, I, smax, past, eps, zeros, stream);
 }
 #endif  // !ULL_ELEM_F16
 

@@ -119,6 +119,31 @@ ULL_DEV float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// ---- FP8 (e4m3fn) with one power-of-two scale per vector: fp8 weights (gemv.hip) and the fp8 KV cache (kv8.hip) ----------
+// The scale of a vector is 2^s, s the smallest integer with amax * 2^-s <= 448 (an all-zero vector: s = 0); its codes are
+// e4m3fn(x * 2^-s) rounded to nearest even, bit-identical to torch's CPU cast.  dequant = float(code) * 2^s has at most 4 significant
+// bits: a bf16 value.
+ULL_DEV int fp8_scale_exp(float amax) {
+    int s = 0;
+    if (amax > 0.f) {
+        int e;
+        frexpf(amax, &e);                                  // amax in [2^(e-1), 2^e): s is e - 9 or e - 8, settled exactly below
+        s = e - 9;
+        while (amax > ldexpf(448.f, s)) ++s;
+        while (amax <= ldexpf(448.f, s - 1)) --s;
+    }
+    return s;
+}
+// 8 e4m3fn codes (element j in byte j) -> 8 floats float(q_j) * s.  The conversion is exact and s is a power of two, so the product is
+// exact too (and representable in bf16: 4 significant bits).
+ULL_DEV void unpack8_w8(const uint2& v, float s, float* f) {
+    typedef float f2_t __attribute__((ext_vector_type(2)));
+    const f2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, true);
+    const f2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, true);
+    f[0] = a[0] * s; f[1] = a[1] * s; f[2] = b[0] * s; f[3] = b[1] * s;
+    f[4] = c[0] * s; f[5] = c[1] * s; f[6] = d[0] * s; f[7] = d[1] * s;
+}
+
 // reduce across the `w` lanes (power of two <= 64) that share the same (lane / w)
 ULL_DEV float group_sum(float v, int w) {
     for (int o = w >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -177,35 +177,115 @@ class GenerateOutput(dict):
     __getattr__ = dict.__getitem__
 
 
+KV_CACHE_DTYPES = ("fp8_e4m3",)
+
+
+def _check_kv_dtype(kv_dtype, dtype):
+    """the cache formats there are: None (the model dtype) or "fp8_e4m3" (bf16 models only)."""
+    if kv_dtype is None:
+        return
+    if not isinstance(kv_dtype, str) or kv_dtype not in KV_CACHE_DTYPES:
+        raise ValueError(f"unknown KV cache dtype {kv_dtype!r} (supported: None, {', '.join(repr(d) for d in KV_CACHE_DTYPES)})")
+    if dtype != BF16:
+        raise NotImplementedError(f"an fp8 KV cache needs a bf16 model, not {dtype}: the dequantized values of a position with a small amax "
+                                  "can fall below the fp16 range, and the fp32 build has no fp8 kernels")
+
+
 class KVCache:
     """Per-layer K [B,H,Smax,hd] (post-RoPE) and V^T [B,H,hd,Smax] in the attention kernel's key-permuted layout, plus the
     last-layer hidden states of every position seen so far (what `evaluate()` reads for [SEG]/[LOC] rows).  Truthy once a
     prefill has been stored, like a non-empty HF past_key_values tuple."""
 
-    def __init__(self, n_layers, B, H, hd, smax, device, dtype=BF16):
+    kv_dtype = None                        # "fp8_e4m3": see below
+
+    def __init__(self, n_layers, B, H, hd, smax, device, dtype=BF16, kv_dtype=None):
+        """kv_dtype="fp8_e4m3" (bf16 models only): the cache holds e4m3fn codes in the same two layouts (k8 [B,H,Smax,hd], vt8 [B,H,hd,Smax])
+        plus one fp32 power-of-two scale per (batch, head, position) for the K row (k_scale, by key) and the V column (vt_scale, by V^T slot),
+        with the fp8-weight rule (DESIGN f2).  Attention reads the K / V of its own forward call at full bf16 precision and the earlier
+        positions dequantized; the new positions are quantized into the cache.  So the model equals, bit for bit, the same model with a bf16
+        cache holding the dequantized positions (`dequantized()`).  A decode step's new keys pass through a bf16 staging window (k_stage /
+        vt_stage: 128 positions, one window shared by all layers) on their way into the cache."""
+        _check_kv_dtype(kv_dtype, dtype)
         self.smax = ((smax + 63) // 64) * 64
-        self.k = [torch.empty(B, H, self.smax, hd, device=device, dtype=dtype) for _ in range(n_layers)]
-        self.vt = [torch.zeros(B, H, hd, self.smax, device=device, dtype=dtype) for _ in range(n_layers)]
         self.length = 0
         self.last_hidden = []
+        if kv_dtype is None:
+            self.k = [torch.empty(B, H, self.smax, hd, device=device, dtype=dtype) for _ in range(n_layers)]
+            self.vt = [torch.zeros(B, H, hd, self.smax, device=device, dtype=dtype) for _ in range(n_layers)]
+            return
+        self.kv_dtype = kv_dtype
+        self.k = self.vt = None
+        u8, f32 = torch.uint8, torch.float32
+        self.k8 = [torch.zeros(B, H, self.smax, hd, device=device, dtype=u8) for _ in range(n_layers)]
+        self.vt8 = [torch.zeros(B, H, hd, self.smax, device=device, dtype=u8) for _ in range(n_layers)]
+        self.k_scale = [torch.zeros(B, H, self.smax, device=device, dtype=f32) for _ in range(n_layers)]
+        self.vt_scale = [torch.zeros(B, H, self.smax, device=device, dtype=f32) for _ in range(n_layers)]
+        self.k_stage = torch.zeros(B, H, 128, hd, device=device, dtype=dtype)
+        self.vt_stage = torch.zeros(B, H, hd, 128, device=device, dtype=dtype)
+        self._kv8_ptrs = None              # (data_ptr key, ctypes arrays) of c_ptrs()
+
+    def kv8_layer(self, li):
+        """(k8, vt8, k_scale, vt_scale) of layer li of an fp8 cache."""
+        return self.k8[li], self.vt8[li], self.k_scale[li], self.vt_scale[li]
+
+    def bf16_scratch(self):
+        """(fp8 cache) a bf16 K [B,H,Smax,hd] / V^T [B,H,hd,Smax] pair (V^T zero-filled) for the calls the fp8 decode attention does not take
+        (<= 64 keys, > 16 new tokens): each layer is dequantized into it, runs the bf16 path, and its new positions are quantized back.
+        Made per forward call and shared by its layers; the cache itself keeps no bf16 buffer but the staging window."""
+        B, H, smax, hd = self.k8[0].shape
+        dev = self.k8[0].device
+        return torch.empty(B, H, smax, hd, device=dev, dtype=BF16), torch.zeros(B, H, hd, smax, device=dev, dtype=BF16)
+
+    def nbytes(self) -> int:
+        """bytes of every device buffer the cache keeps (fp8: codes, scales and the staging window; bf16: K and V^T)."""
+        ts = (self.k + self.vt) if self.kv_dtype is None else (self.k8 + self.vt8 + self.k_scale + self.vt_scale + [self.k_stage, self.vt_stage])
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def dequantized(self) -> "KVCache":
+        """The bf16 twin of an fp8 cache: a bf16 KVCache whose positions < length hold dequant(codes) = float(code) * 2^s (same length,
+        same last_hidden).  A bf16 cache returns itself."""
+        if self.kv_dtype is None:
+            return self
+        B, H, smax, hd = self.k8[0].shape
+        c = KVCache(len(self), B, H, hd, smax, self.k8[0].device, BF16)
+        if self.length:
+            for li in range(len(self)):
+                ops.dequantize_kv(*self.kv8_layer(li), self.length, k_out=c.k[li], vt_out=c.vt[li])
+        c.length = self.length
+        c.last_hidden = list(self.last_hidden)
+        return c
 
     def __bool__(self):
         return self.length > 0
 
     def c_ptrs(self):
-        """(void* array of the K buffers, void* array of the V^T buffers) for the coarse decode entry; built once per cache."""
+        """(void* array of the K buffers, void* array of the V^T buffers) for the coarse decode entry; built once per cache.
+        fp8 cache: (k8, vt8, k_scale, vt_scale void* arrays, k_stage, vt_stage) for the *_kv8 entries, rebuilt whenever a list entry has
+        been rebound since (the arrays hold raw pointers)."""
+        if self.kv_dtype is not None:
+            import ctypes
+            lists = (self.k8, self.vt8, self.k_scale, self.vt_scale)
+            key = tuple(t.data_ptr() for l in lists for t in l)
+            if self._kv8_ptrs is None or self._kv8_ptrs[0] != key:
+                arrs = tuple((ctypes.c_void_p * len(l))(*[t.data_ptr() for t in l]) for l in lists)
+                self._kv8_ptrs = (key, arrs + (self.k_stage, self.vt_stage))
+            return self._kv8_ptrs[1]
         if getattr(self, "_c_ptrs", None) is None:
             import ctypes
             self._c_ptrs = ((ctypes.c_void_p * len(self.k))(*[t.data_ptr() for t in self.k]), (ctypes.c_void_p * len(self.vt))(*[t.data_ptr() for t in self.vt]))
         return self._c_ptrs
 
     def __len__(self):
-        return len(self.k)
+        return len(self.k) if self.kv_dtype is None else len(self.k8)
 
     def to_legacy_cache(self):
         """The HF view of this cache (what `outputs.past_key_values` is in the reference under transformers 4.29.1, models/ullava_core.py:349-355):
         a tuple of per-layer (key, value) pairs, each [B, H, length, hd] with post-RoPE keys.  Pure data movement (a slice of the K buffer;
-        the key-permuted V^T image gathered back into natural key order and transposed); `KVCache.from_hf` is the inverse."""
+        the key-permuted V^T image gathered back into natural key order and transposed); `KVCache.from_hf` is the inverse.  An fp8 cache
+        hands out its dequantized positions: it builds its bf16 twin (`dequantized()`, every layer at once) first, a transient allocation of
+        about twice the fp8 cache's size; `__getitem__` dequantizes one layer only."""
+        if self.kv_dtype is not None:
+            return self.dequantized().to_legacy_cache()
         n = self.length
         idx = ops.vt_unpermute_index(self.smax).to(self.k[0].device)[:n]
         return tuple((k[:, :, :n].contiguous(), vt[..., idx].transpose(-1, -2).contiguous()) for k, vt in zip(self.k, self.vt))
@@ -215,18 +295,26 @@ class KVCache:
 
     def __getitem__(self, i):
         """layer i's (key, value) pair -- so that code written against a tuple of pairs (`past_key_values[0][0].shape[2]`, the idiom of
-        4.29-era callers) reads this object too."""
+        4.29-era callers) reads this object too.  An fp8 cache dequantizes the layer."""
+        if self.kv_dtype is not None:
+            B, H, smax, hd = self.k8[i].shape
+            k = torch.empty(B, H, max(self.length, 1), hd, device=self.k8[i].device, dtype=BF16)
+            vt = torch.zeros(B, H, hd, smax, device=self.k8[i].device, dtype=BF16)
+            if self.length:
+                ops.dequantize_kv(*self.kv8_layer(i), self.length, k_out=k, vt_out=vt)
+            idx = ops.vt_unpermute_index(smax).to(vt.device)[:self.length]
+            return k[:, :, :self.length], vt[..., idx].transpose(-1, -2)
         n = self.length
         idx = ops.vt_unpermute_index(self.smax).to(self.k[i].device)[:n]
         return self.k[i][:, :, :n], self.vt[i][..., idx].transpose(-1, -2)
 
     @classmethod
-    def from_hf(cls, past, headroom: int = 512):
+    def from_hf(cls, past, headroom: int = 512, kv_dtype=None):
         """A caller-supplied HF `past_key_values` -> KVCache (reference models/ullava_core.py:279-292 takes `past_key_values:
         Optional[List[torch.FloatTensor]]`): the legacy tuple of per-layer (key, value) pairs, each [B, H, S, hd] with post-RoPE keys, or a
         transformers Cache object exposing `key_cache` / `value_cache` lists (or `.layers[i].keys / .values`).  Keys are copied into the
         K buffers, values go through `ull_transpose_v` into the permuted V^T layout; `last_hidden` starts empty (hidden states of the
-        cached positions are not part of an HF cache)."""
+        cached positions are not part of an HF cache).  kv_dtype="fp8_e4m3": the keys and values are quantized into an fp8 cache."""
         if hasattr(past, "key_cache") and hasattr(past, "value_cache"):
             pairs = list(zip(past.key_cache, past.value_cache))
         elif hasattr(past, "layers"):
@@ -239,10 +327,14 @@ class KVCache:
         if k0.dim() != 4:
             raise ValueError("past_key_values entries must be [batch, heads, seq, head_dim] tensors")
         B, H, S, hd = k0.shape
-        c = cls(len(pairs), B, H, hd, S + headroom, k0.device, k0.dtype)
+        c = cls(len(pairs), B, H, hd, S + headroom, k0.device, k0.dtype, kv_dtype=kv_dtype)
         for li, (k, v) in enumerate(pairs):
             if k.shape != (B, H, S, hd) or v.shape != (B, H, S, hd):
                 raise ValueError("past_key_values layers disagree in shape")
+            if kv_dtype is not None:
+                k, v = k.contiguous(), v.contiguous()
+                ops.quantize_kv(k, k.stride()[:3], v, v.stride()[:3], *c.kv8_layer(li), 0, S)
+                continue
             c.k[li][:, :, :S].copy_(k)
             vr = v.permute(0, 2, 1, 3).contiguous()                              # [B, S, H, hd]: heads contiguous per token (data movement)
             ops.transpose_v(vr, S * H * hd, H * hd, B, S, H, hd, pitch=c.smax, out=c.vt[li])
@@ -1005,8 +1097,15 @@ class UllavaCoreForCausalLM(nn.Module):
         I = cfg.intermediate_size
         coarse = None
         w8 = pk.get("fp8", False)            # quantize_weights(): the Linear weights are ops.Fp8Weight (ops.linear & co. dispatch on them)
+        kv8 = cache is not None and cache.kv_dtype is not None
+        if kv8 and x.dtype != BF16:
+            _check_kv_dtype(cache.kv_dtype, x.dtype)
+        # fp8 cache, past > 0: up to 16 new tokens against more than 64 keys take the fp8 decode attention (the appenders write the
+        # staging window); other calls dequantize each layer into a bf16 scratch, run the bf16 path on it and quantize the new positions back
+        kv8_fewq = kv8 and past > 0 and S <= 16 and 64 < past + S <= 4096
+        kv8_scr = []                          # (the per-call bf16 scratch of the other fp8-cache calls, made on first use)
         if ops.coarse_ok() and pk["llama"]:
-            if fuse_append and I % 8 == 0:
+            if fuse_append and I % 8 == 0 and (kv8_fewq or not kv8):
                 coarse = "decode"
             elif fuse_rope and cache is None and T > 16 and 16 < S <= 1024 and I % 64 == 0 and not w8:
                 coarse = "prefill"           # (an fp8 model's prefill takes the per-op path: dequantize + GEMM per Linear)
@@ -1025,7 +1124,10 @@ class UllavaCoreForCausalLM(nn.Module):
                 all_h = [x.view(B, S, D)] + [o.view(B, S, D) for o in outs[:-1]]
             else:
                 outs = [torch.empty(T, D, device=dev, dtype=x.dtype)] * L
-            if coarse == "decode":
+            if coarse == "decode" and kv8:
+                ops.llama_decode_layers(stack, x, outs, rope_cs[0], rope_cs[1], key_mask, None, None, B, S, H, hd, I, cache.smax, past, cfg.rms_norm_eps,
+                                        kv8=cache.c_ptrs())
+            elif coarse == "decode":
                 ops.llama_decode_layers(stack, x, outs, rope_cs[0], rope_cs[1], key_mask, cache.c_ptrs()[0], cache.c_ptrs()[1], B, S, H, hd, I, cache.smax,
                                         past, cfg.rms_norm_eps)
             else:
@@ -1035,13 +1137,19 @@ class UllavaCoreForCausalLM(nn.Module):
             if output_hidden_states:
                 all_h.append(x.view(B, S, D))
             decode = cache is not None and past > 0
+            if kv8 and decode:
+                kc, vtc, smax_, past_ = self._kv8_decode_buffers(cache, li, past, kv8_fewq, kv8_scr)
+            elif decode:
+                kc, vtc, smax_, past_ = cache.k[li], cache.vt[li], cache.smax, past
             if fuse_append:
-                kc, vtc = cache.k[li], cache.vt[li]
-                q = ops.linear_qkv_rope_append(x, w["w_qkv"], rope_cs[0], rope_cs[1], B, S, H, hd, kc, vtc, cache.smax, past, rms_w=w["ln1"],
+                q = ops.linear_qkv_rope_append(x, w["w_qkv"], rope_cs[0], rope_cs[1], B, S, H, hd, kc, vtc, smax_, past_, rms_w=w["ln1"],
                                                rms_eps=cfg.rms_norm_eps)
                 att = torch.empty(T, D, device=dev, dtype=x.dtype)
-                ops.attention(q, kc, vtc, att, B, H, S, past + S, hd, (S * D, hd, D), (H * cache.smax * hd, cache.smax * hd, hd), (S * D, hd, D),
-                              key_mask, causal=True, scale_mode=1, scale=hd ** -0.5)
+                if kv8:
+                    self._kv8_attention(q, (S * D, hd, D), cache, li, att, B, H, S, past, hd, key_mask, kv8_fewq, kv8_scr)
+                else:
+                    ops.attention(q, kc, vtc, att, B, H, S, past + S, hd, (S * D, hd, D), (H * cache.smax * hd, cache.smax * hd, hd),
+                                  (S * D, hd, D), key_mask, causal=True, scale_mode=1, scale=hd ** -0.5)
                 x = ops.linear(att, w["w_o"], residual=x)
                 a = ops.linear(x, w["w_gu"], swiglu=True, rms_w=w["ln2"], rms_eps=cfg.rms_norm_eps)
                 x = ops.linear(a, w["w_down"], residual=x)
@@ -1053,10 +1161,12 @@ class UllavaCoreForCausalLM(nn.Module):
             att = torch.empty(T, D, device=dev, dtype=x.dtype)
             if decode:
                 # generation step: RoPE + cache append in one launch, then the split-key attention over the cache
-                kc, vtc = cache.k[li], cache.vt[li]
-                ops.rope_append(qkv, 3 * D, pos, inv_freq, B, S, H, hd, kc, vtc, cache.smax, past)
-                ops.attention(qkv, kc, vtc, att, B, H, S, past + S, hd, (S * 3 * D, hd, 3 * D), (H * cache.smax * hd, cache.smax * hd, hd),
-                              (S * D, hd, D), key_mask, causal=True, scale_mode=1, scale=hd ** -0.5)
+                ops.rope_append(qkv, 3 * D, pos, inv_freq, B, S, H, hd, kc, vtc, smax_, past_)
+                if kv8:
+                    self._kv8_attention(qkv, (S * 3 * D, hd, 3 * D), cache, li, att, B, H, S, past, hd, key_mask, kv8_fewq, kv8_scr)
+                else:
+                    ops.attention(qkv, kc, vtc, att, B, H, S, past + S, hd, (S * 3 * D, hd, 3 * D), (H * cache.smax * hd, cache.smax * hd, hd),
+                                  (S * D, hd, D), key_mask, causal=True, scale_mode=1, scale=hd ** -0.5)
             else:
                 if not fuse_rope:
                     ops.rope_inplace(qkv, 3 * D, pos, inv_freq, T, 2 * H, hd)
@@ -1064,6 +1174,12 @@ class UllavaCoreForCausalLM(nn.Module):
                 if cache is None:                                # V goes in as rows of the fused q|k|v buffer: no V^T pass
                     ops.attention(qkv, qkv[:, D:], qkv[:, 2 * D:], att, B, H, S, S, hd, st, st, (S * D, hd, D), key_mask, causal=True,
                                   scale_mode=1, scale=hd ** -0.5, v_strides=st)
+                elif kv8:                                        # prefill into an fp8 cache: the bf16-cache prefill on a transient V^T, then
+                    vt = torch.empty(B, H, hd, cache.smax, device=dev, dtype=x.dtype)      # the K rows and V rows quantized into the cache
+                    ops.transpose_v(qkv[:, 2 * D:], S * 3 * D, 3 * D, B, S, H, hd, pitch=cache.smax, out=vt)
+                    ops.attention(qkv, qkv[:, D:], vt, att, B, H, S, S, hd, st, st, (S * D, hd, D), key_mask, causal=True, scale_mode=1,
+                                  scale=hd ** -0.5)
+                    ops.quantize_kv(qkv[:, D:], st, qkv[:, 2 * D:], st, *cache.kv8_layer(li), 0, S)
                 else:                                            # prefill that also fills the cache (K rows, V^T image)
                     kc, vt = cache.k[li], cache.vt[li]
                     kc[:, :, :S].copy_(qkv.view(B, S, 3, H, hd)[:, :, 1].permute(0, 2, 1, 3))
@@ -1081,6 +1197,33 @@ class UllavaCoreForCausalLM(nn.Module):
         if output_hidden_states:
             all_h.append(last)
         return last, (tuple(all_h) if output_hidden_states else None)
+
+    @staticmethod
+    def _kv8_decode_buffers(cache: KVCache, li: int, past: int, fewq: bool, scr: list):
+        """(K, V^T, pitch, position of the first new key) the decode appenders of layer li write into, on an fp8 cache: the staging window
+        (first new key at past mod 64) where the fp8 decode attention takes the call (fewq), else the call's bf16 scratch (scr, made on first
+        use) with positions < past dequantized."""
+        if fewq:
+            return cache.k_stage, cache.vt_stage, 128, past & 63
+        if not scr:
+            scr.append(cache.bf16_scratch())
+        kc, vtc = scr[0]
+        ops.dequantize_kv(*cache.kv8_layer(li), past, k_out=kc, vt_out=vtc)
+        return kc, vtc, cache.smax, past
+
+    @staticmethod
+    def _kv8_attention(q, q_strides, cache: KVCache, li: int, att, B: int, H: int, S: int, past: int, hd: int, key_mask, fewq: bool, scr: list):
+        """the decode attention of layer li over an fp8 cache, after _kv8_decode_buffers' appenders; the new positions end in the cache."""
+        if fewq:
+            ops.attention_kv8(q, q_strides, cache.k_stage, cache.vt_stage, *cache.kv8_layer(li), att, (S * H * hd, hd, H * hd), B, H, S, past + S,
+                              hd, key_mask, hd ** -0.5)
+            return
+        kc, vtc = scr[0]
+        smax = cache.smax
+        ops.attention(q, kc, vtc, att, B, H, S, past + S, hd, q_strides, (H * smax * hd, smax * hd, hd), (S * H * hd, hd, H * hd), key_mask,
+                      causal=True, scale_mode=1, scale=hd ** -0.5)
+        ops.quantize_kv(kc, (H * smax * hd, smax * hd, hd), vtc, (H * hd * smax, hd * smax, smax), *cache.kv8_layer(li), past, S, src_p0=past,
+                        v_image=True)
 
     def forward(self, input_ids: torch.LongTensor = None, attention_mask: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.LongTensor] = None, past_key_values: Optional[List[torch.FloatTensor]] = None,
@@ -1109,7 +1252,8 @@ class UllavaCoreForCausalLM(nn.Module):
             B_, S_ = inputs_embeds.shape[:2]
             cache = KVCache(self.config.num_hidden_layers, B_, self.config.num_attention_heads,
                             self.config.hidden_size // self.config.num_attention_heads,
-                            max(S_ + getattr(self, "_cache_headroom", 512), 64), inputs_embeds.device, inputs_embeds.dtype)
+                            max(S_ + getattr(self, "_cache_headroom", 512), 64), inputs_embeds.device, inputs_embeds.dtype,
+                            kv_dtype=getattr(self, "_new_cache_kv_dtype", None))
         if self._training_graph():
             if cache is not None:
                 raise NotImplementedError("use_cache / past_key_values are inference features (the training scripts set use_cache=False)")
@@ -1146,7 +1290,7 @@ class UllavaCoreForCausalLM(nn.Module):
     def generate(self, input_ids=None, images=None, videos=None, attention_mask=None, max_new_tokens=32, do_sample=False,
                  temperature=1.0, top_p=None, top_k=50, num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, eos_token_id=None,
                  pad_token_id=None, output_hidden_states=False, return_dict_in_generate=False, use_cache=None,
-                 keep_last_step_only=False, **kwargs):
+                 keep_last_step_only=False, kv_cache_dtype=None, **kwargs):
         """Token-by-token decoding with HF GenerationMixin's greedy / sampling semantics (the reference inherits `generate`):
         every step goes through `prepare_inputs_for_generation` (position_ids = cumsum(attention_mask) - 1, so left-padded batches
         get the reference's RoPE positions); `eos_token_id` defaults to `config.eos_token_id` (int or list); rows that have emitted
@@ -1155,7 +1299,9 @@ class UllavaCoreForCausalLM(nn.Module):
         use_cache=False reproduces the reference checkpoints' behaviour (config.use_cache=False: every step re-runs the multimodal
         prefill); use_cache=True prefills once and then streams the weights once per token through the GEMV kernels
         with a KV cache.  Greedy (`do_sample=False`) is deterministic; sampling draws from torch's RNG on
-        softmax(logits / temperature) with optional nucleus filtering."""
+        softmax(logits / temperature) with optional nucleus filtering.
+        kv_cache_dtype="fp8_e4m3" (bf16 models, use_cache=True) keeps the KV cache as e4m3 codes with per-position scales (KVCache);
+        the result equals the same run with a bf16 cache holding the dequantized positions, bit for bit."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not used by the reference callers (num_beams=1)")
         if kwargs:
@@ -1167,6 +1313,10 @@ class UllavaCoreForCausalLM(nn.Module):
         if ngram < 0:
             raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer, but is {no_repeat_ngram_size}")
         use_cache = self.config.use_cache if use_cache is None else use_cache
+        if kv_cache_dtype is not None:
+            _check_kv_dtype(kv_cache_dtype, self.dtype)
+            if not use_cache:
+                raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r} needs use_cache=True: without a KV cache there is nothing to quantize")
         seq = input_ids
         B = seq.shape[0]
         eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
@@ -1212,7 +1362,14 @@ class UllavaCoreForCausalLM(nn.Module):
                 # KV-cached decoding: prefill once, then one token per step; vision runs once
                 if step > 0:
                     inputs["images"] = inputs["videos"] = None
-                out = self.forward(**inputs)
+                if step == 0 and kv_cache_dtype is not None:
+                    self._new_cache_kv_dtype = kv_cache_dtype        # the cache forward() creates for the prefill
+                    try:
+                        out = self.forward(**inputs)
+                    finally:
+                        self._new_cache_kv_dtype = None
+                else:
+                    out = self.forward(**inputs)
                 cache = out.past_key_values
             else:
                 # the reference's released checkpoints run with use_cache=False: every step re-runs the multimodal prefill

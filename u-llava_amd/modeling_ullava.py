@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaConfig
-from .modeling_core import BF16, Linear, UllavaCoreForCausalLM, _Holder
+from .modeling_core import BF16, Linear, UllavaCoreForCausalLM, _Holder, _check_kv_dtype
 from .sam import SamEngine, build_sam_holder
 
 
@@ -269,8 +269,11 @@ class UllavaForCausalLM(nn.Module):
 
     @torch.no_grad()
     def evaluate(self, images_sam, images, input_ids, raw_size_list, resize_list, max_new_tokens=32, temperature=0.2, top_p=None,
-                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None):
-        """reference ullava.py:335-434 -> (output_ids, pred_masks, pred_boxes)."""
+                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None):
+        """reference ullava.py:335-434 -> (output_ids, pred_masks, pred_boxes).  kv_cache_dtype="fp8_e4m3": generate with an fp8 KV cache
+        (which implies use_cache=True; see UllavaCoreForCausalLM.generate)."""
+        if kv_cache_dtype is not None:
+            _check_kv_dtype(kv_cache_dtype, self.llm.dtype)
         main = torch.cuda.current_stream()                          # SAM image encoder on the second stream, under the generation loop
         side = self._side_stream()
         side.wait_stream(main)
@@ -279,7 +282,8 @@ class UllavaForCausalLM(nn.Module):
         outputs = self.llm.generate(input_ids=input_ids, images=images, max_new_tokens=max_new_tokens, num_beams=num_beams, top_p=top_p,
                                     do_sample=True if temperature > 0 else False, temperature=temperature, output_hidden_states=True,
                                     return_dict_in_generate=True, no_repeat_ngram_size=no_repeat_ngram_size,
-                                    stopping_criteria=stopping_criteria, keep_last_step_only=True)
+                                    stopping_criteria=stopping_criteria, keep_last_step_only=True,
+                                    **({} if kv_cache_dtype is None else dict(use_cache=True, kv_cache_dtype=kv_cache_dtype)))
         output_ids = outputs.sequences
         last = outputs.hidden_states[-1][-1]                          # last step, last layer: [B, L-1, D]
         seg_token_mask = output_ids[:, 1:] == self.config.seg_token_idx

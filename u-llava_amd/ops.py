@@ -537,6 +537,48 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Ten
     return out
 
 
+def quantize_kv(k: torch.Tensor, k_strides, v: torch.Tensor, v_strides, k8: torch.Tensor, vt8: torch.Tensor, k_scale: torch.Tensor,
+                vt_scale: torch.Tensor, p0: int, n: int, src_p0: int = 0, v_image: bool = False) -> None:
+    """Positions p0 .. p0 + n - 1 of one layer's fp8 KV cache (codes k8 [B, H, smax, hd] / vt8 [B, H, hd, smax], scales [B, H, smax]) from
+    bf16 K rows (k_strides = batch, head, position) and V rows (v_strides likewise) or, with v_image, a V^T image in the permuted slot order
+    (v_strides = batch, head, d); source position src_p0 + s.  Codes and scales follow the fp8-weight rule (bit-identical to torch's cast)."""
+    _chk(k, "k", BF16); _chk(v, "v", BF16)
+    B, H, smax, hd = k8.shape
+    _lib.call("ull_kv8_quantize_bf16", _p(k), *k_strides, _p(v), *v_strides, int(v_image), src_p0, _p(k8), _p(vt8), _p(k_scale), _p(vt_scale),
+              B, H, hd, smax, p0, n, _stream())
+
+
+def dequantize_kv(k8: torch.Tensor, vt8: torch.Tensor, k_scale: torch.Tensor, vt_scale: torch.Tensor, n: int, k_out: Optional[torch.Tensor] = None,
+                  vt_out: Optional[torch.Tensor] = None) -> None:
+    """Positions [0, n) of one layer's fp8 KV cache as bf16: k_out [B, H, P, hd] rows 0 .. n - 1, vt_out [B, H, hd, P'] (permuted V^T, slots up
+    to round_up(n, 64), keys >= n zero).  Exactly the operands attention_kv8 reads."""
+    B, H, smax, hd = k8.shape
+    for t, nm, shp in ((k_out, "k_out", (B, H, None, hd)), (vt_out, "vt_out", (B, H, hd, None))):
+        if t is not None:
+            _chk(t, nm, BF16)
+            if t.dim() != 4 or not t.is_contiguous() or any(a is not None and a != b for a, b in zip(shp, t.shape)):
+                raise RuntimeError(f"u-llava_amd.dequantize_kv: {nm} must be a contiguous bf16 tensor of shape {shp}")
+    _lib.call("ull_kv8_dequantize_bf16", _p(k8), _p(vt8), _p(k_scale), _p(vt_scale), B, H, hd, smax, n, _p(k_out),
+              k_out.shape[2] if k_out is not None else 0, _p(vt_out), vt_out.shape[3] if vt_out is not None else 0, _stream())
+
+
+def attention_kv8(q: torch.Tensor, q_strides, k_stage: torch.Tensor, vt_stage: torch.Tensor, k8: torch.Tensor, vt8: torch.Tensor,
+                  k_scale: torch.Tensor, vt_scale: torch.Tensor, out: torch.Tensor, o_strides, B: int, H: int, Sq: int, Sk: int, hd: int,
+                  key_mask: Optional[torch.Tensor], scale: float) -> torch.Tensor:
+    """The LLaMA decode call of `attention` (causal, scale_mode 1) over an fp8 cache: keys < Sk - Sq from the codes, the Sq new keys from
+    the staging window (k_stage [B, H, 128, hd], vt_stage [B, H, hd, 128], key k at row / slot k - w0, w0 = (Sk - Sq) rounded down to 64,
+    where rope_append / linear_qkv_rope_append put them with smax = 128 and past - w0).  Stores the new keys' codes and scales.  Same bits
+    as `attention` on the dequantized cache.  Sq <= 16 and 64 < Sk <= 4096."""
+    _chk(q, "q", BF16); _chk(out, "out", BF16); _chk(k_stage, "k_stage", BF16); _chk(vt_stage, "vt_stage", BF16)
+    if key_mask is not None:
+        _chk(key_mask, "key_mask", torch.int32)
+    if k_stage.shape != (B, H, 128, hd) or vt_stage.shape != (B, H, hd, 128) or k8.shape[:2] != (B, H) or k8.shape[3] != hd:
+        raise RuntimeError("u-llava_amd.attention_kv8: staging / cache shapes")
+    _lib.call("ull_attention_kv8_bf16", _p(q), *q_strides, _p(k_stage), _p(vt_stage), _p(k8), _p(vt8), _p(k_scale), _p(vt_scale), k8.shape[2],
+              _p(out), *o_strides, _p(key_mask), B, H, Sq, Sk, hd, float(scale), _zeros(q.device).data_ptr(), _stream())
+    return out
+
+
 def dropout_apply(x: torch.Tensor, keep: torch.Tensor, p: float) -> torch.Tensor:
     """y = keep ? x / (1 - p) : 0 (keep: uint8, same number of elements)."""
     _chk(x, "x"); _chk(keep, "keep", torch.uint8)
@@ -1262,17 +1304,24 @@ def llama_prefill_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos,
 
 
 def llama_decode_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos, rope_sin, key_mask, k_ptrs, vt_ptrs, B: int, S: int, H: int, hd: int,
-                        I: int, smax: int, past: int, eps: float):
+                        I: int, smax: int, past: int, eps: float, kv8=None):
     """One generation step through all layers (T = B*S <= 4).  k_ptrs / vt_ptrs: ctypes void* arrays of the per-layer caches.  A stack of
-    _lib.LlamaLayerW8 (fp8 weights, bf16 activations) goes to ull_llama_decode_layers_w8_bf16."""
+    _lib.LlamaLayerW8 (fp8 weights, bf16 activations) goes to ull_llama_decode_layers_w8_bf16.  kv8 = (k8, vt8, k_scale, vt_scale pointer
+    arrays, k_stage, vt_stage) of an fp8 cache (KVCache.c_ptrs): the *_kv8_bf16 entries, k_ptrs / vt_ptrs unused."""
     w8 = stack.kind is _lib.LlamaLayerW8
-    _chk(x_in, "x_in", BF16 if w8 else None)
+    _chk(x_in, "x_in", BF16 if (w8 or kv8 is not None) else None)
     T, D = x_in.shape
     dev, dt = x_in.device, x_in.dtype
     scratch = torch.empty(T * (4 * D + 2 * max(D, I)), device=dev, dtype=dt)
     x_mid, q, att = scratch[:T * D], scratch[T * D:2 * T * D], scratch[2 * T * D:3 * T * D]
     xn = scratch[3 * T * D:3 * T * D + T * max(D, I)]
     act = scratch[3 * T * D + T * max(D, I):3 * T * D + T * max(D, I) + T * I]
+    if kv8 is not None:
+        k8, vt8, ks, vs, k_stage, vt_stage = kv8
+        _lib.call("ull_llama_decode_layers_" + ("w8_kv8_bf16" if w8 else "kv8_bf16"), stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out),
+                  _p(x_mid), _p(xn), _p(q), _p(att), _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k8, vt8, ks, vs, _p(k_stage), _p(vt_stage),
+                  B, S, H, hd, I, smax, past, float(eps), _zeros(dev).data_ptr(), _stream())
+        return
     _lib.call("ull_llama_decode_layers_" + ("w8_bf16" if w8 else _SFX[dt]), stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid),
               _p(xn), _p(q), _p(att), _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k_ptrs, vt_ptrs, B, S, H, hd, I, smax, past, float(eps),
               _zeros(dev).data_ptr(), _stream())
