@@ -219,6 +219,18 @@ int ull_mm_spans(const void* ids, int64_t B, int64_t S, int64_t img_start, int64
 int ull_greedy_step_bf16(const void* logits, int64_t row_stride, int64_t B, int64_t V, void* unfinished, const void* eos, int64_t n_eos,
                          int64_t pad, int has_pad, void* seq, int64_t seq_ld, int64_t pos, void* alive, void* stream);
 
+/* One SAMPLED decoding step of HF `generate` for the whole batch, the sampling counterpart of ull_greedy_step_* (compiled once; logits_dtype
+ * is ULL_DT_F32 0 / BF16 1 / F16 2).  Per row, in fp32: s = float(logit) / temperature (IEEE division); top_k > 0: keep s >= the k-th
+ * largest s (k clipped to V, ties with it stay); top_p < 1: among the survivors in ascending order drop those whose cumulative softmax is
+ * <= 1 - top_p (the largest stays; equal scores are ordered the same way on every run); token = argmax over the kept i of
+ * exp(s_i - max) / noise[b*V + i] (lowest index on exact ties), which is torch.multinomial(probs, 1) when noise is the caller's
+ * torch.empty(B, V).exponential_() (fp32, contiguous).  unfinished / eos / pad / seq / pos / alive: as ull_greedy_step_*.
+ * temperature > 0 (ULL_ERR_ARG otherwise).  The row is staged in LDS: V > ULL_SAMPLE_MAX_V is ULL_ERR_SHAPE. */
+#define ULL_SAMPLE_MAX_V 36608
+int ull_sample_step(const void* logits, int logits_dtype, int64_t row_stride, int64_t B, int64_t V, const void* noise, float temperature,
+                    int64_t top_k, float top_p, void* unfinished, const void* eos, int64_t n_eos, int64_t pad, int has_pad, void* seq,
+                    int64_t seq_ld, int64_t pos, void* alive, void* stream);
+
 /* models/ullava_core.py:191,243-245,266-268: token-embedding lookup with the projected visual tokens spliced in after
  * the first start token (the torch.cat of the reference, done as one gather).  Image i's n_img_tok feature rows start
  * at row i*img_pitch + img_off of img_feat (pitch = patches + 1, off = 1 skips the CLS row without a copy).

@@ -395,6 +395,13 @@ def sampling_probs(logits: torch.Tensor, temperature: float, top_k: Optional[int
     return torch.softmax(scores, dim=-1)
 
 
+def check_sampler(sampler) -> bool:
+    """generate()'s `sampler`: None / "host" = torch's sampling path, "device" = ops.sample_step in the fused loop (True)."""
+    if sampler not in (None, "host", "device"):
+        raise ValueError(f'unknown sampler {sampler!r} (None / "host": the torch path; "device": one HIP launch per token)')
+    return sampler == "device"
+
+
 # ----------------------------------------------------------------------------------------------------------
 class UllavaCoreForCausalLM(nn.Module):
     config_class = UllavaCoreConfig
@@ -1290,7 +1297,7 @@ class UllavaCoreForCausalLM(nn.Module):
     def generate(self, input_ids=None, images=None, videos=None, attention_mask=None, max_new_tokens=32, do_sample=False,
                  temperature=1.0, top_p=None, top_k=50, num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, eos_token_id=None,
                  pad_token_id=None, output_hidden_states=False, return_dict_in_generate=False, use_cache=None,
-                 keep_last_step_only=False, kv_cache_dtype=None, **kwargs):
+                 keep_last_step_only=False, kv_cache_dtype=None, sampler=None, **kwargs):
         """Token-by-token decoding with HF GenerationMixin's greedy / sampling semantics (the reference inherits `generate`):
         every step goes through `prepare_inputs_for_generation` (position_ids = cumsum(attention_mask) - 1, so left-padded batches
         get the reference's RoPE positions); `eos_token_id` defaults to `config.eos_token_id` (int or list); rows that have emitted
@@ -1301,7 +1308,12 @@ class UllavaCoreForCausalLM(nn.Module):
         with a KV cache.  Greedy (`do_sample=False`) is deterministic; sampling draws from torch's RNG on
         softmax(logits / temperature) with optional nucleus filtering.
         kv_cache_dtype="fp8_e4m3" (bf16 models, use_cache=True) keeps the KV cache as e4m3 codes with per-position scales (KVCache);
-        the result equals the same run with a bf16 cache holding the dequantized positions, bit for bit."""
+        the result equals the same run with a bf16 cache holding the dequantized positions, bit for bit.
+        sampler="device" (opt-in; None and "host" are the torch path above) draws each sampled token in one launch (ops.sample_step: the
+        same distribution, the same torch noise, so a seeded run draws the host path's tokens) inside the device-resident loop greedy
+        decoding uses.  That loop looks at the host every 8 steps, so it may run up to 7 steps past the point where every row had
+        finished: the returned ids are trimmed and equal, but the global generator has advanced further than on the host path.
+        It does not combine with `no_repeat_ngram_size` (host-side list work)."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not used by the reference callers (num_beams=1)")
         if kwargs:
@@ -1312,6 +1324,14 @@ class UllavaCoreForCausalLM(nn.Module):
         ngram = int(no_repeat_ngram_size) if no_repeat_ngram_size else 0
         if ngram < 0:
             raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer, but is {no_repeat_ngram_size}")
+        sampling = bool(do_sample and temperature and temperature > 0)
+        device_sampler = check_sampler(sampler)
+        if device_sampler and ngram:
+            raise ValueError('sampler="device" does not combine with `no_repeat_ngram_size`: the n-gram ban is host-side list work '
+                             '(use sampler=None)')
+        if device_sampler and sampling and self.config.vocab_size > ops.SAMPLE_MAX_V:
+            raise ValueError(f'sampler="device" stages a row of logits in LDS: vocab_size {self.config.vocab_size} is above its limit of '
+                             f"{ops.SAMPLE_MAX_V} (use sampler=None)")
         use_cache = self.config.use_cache if use_cache is None else use_cache
         if kv_cache_dtype is not None:
             _check_kv_dtype(kv_cache_dtype, self.dtype)
@@ -1333,13 +1353,15 @@ class UllavaCoreForCausalLM(nn.Module):
         # are the same (position_ids = cumsum(ones) - 1 = arange; every key attended) and the attention kernels skip their per-key
         # mask loads, which sit on the latency chain of every decode step.
         no_pad = attention_mask is None or bool(attention_mask.ne(0).all())
-        sampling = bool(do_sample and temperature and temperature > 0)
         crit = [] if stopping_criteria is None else (list(stopping_criteria) if isinstance(stopping_criteria, (list, tuple)) else [stopping_criteria])
         # Greedy decoding keeps the whole step on the device: the tokens land in a pre-sized [B, L0 + max_new_tokens] buffer, the
         # argmax / pad-fill / EOS bookkeeping is ONE kernel (ops.greedy_step), and the host looks at the "rows still unfinished"
         # counters only every CHECK steps (every step when a stopping criterion needs the ids on the host anyway).  Steps that run past
         # the point where every row had finished only produce pad tokens; the result is trimmed to what a per-step check returns.
-        fused = not sampling and ngram == 0 and seq.is_cuda
+        # sampler="device": the same loop with ops.sample_step in place of ops.greedy_step.
+        if device_sampler and sampling and not seq.is_cuda:
+            raise RuntimeError('sampler="device" needs GPU tensors (no CPU path exists)')
+        fused = (not sampling or device_sampler) and ngram == 0 and seq.is_cuda
         L0 = seq.shape[1]
         CHECK = 1 if crit else 8
         if fused:
@@ -1380,7 +1402,13 @@ class UllavaCoreForCausalLM(nn.Module):
                     else:
                         steps_hidden.append(out.hidden_states)
             if fused:
-                ops.greedy_step(out.logits[:, -1], live, eos_ids, pad, buf, L0 + step, alive[step:step + 1])
+                if sampling:
+                    last = out.logits[:, -1]
+                    # torch's noise, drawn as torch.multinomial draws it: the generator moves as it does on the host path
+                    noise = torch.empty(last.shape, dtype=torch.float32, device=last.device).exponential_()
+                    ops.sample_step(last, noise, temperature, top_k, top_p, live, eos_ids, pad, buf, L0 + step, alive[step:step + 1])
+                else:
+                    ops.greedy_step(out.logits[:, -1], live, eos_ids, pad, buf, L0 + step, alive[step:step + 1])
                 n_done = step + 1
                 if crit:
                     if any(bool(torch.as_tensor(c(buf[:, :L0 + n_done], None)).all()) for c in crit):

@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaConfig
-from .modeling_core import BF16, Linear, UllavaCoreForCausalLM, _Holder, _check_kv_dtype
+from .modeling_core import BF16, Linear, UllavaCoreForCausalLM, _Holder, _check_kv_dtype, check_sampler
 from .sam import SamEngine, build_sam_holder
 
 
@@ -269,11 +269,14 @@ class UllavaForCausalLM(nn.Module):
 
     @torch.no_grad()
     def evaluate(self, images_sam, images, input_ids, raw_size_list, resize_list, max_new_tokens=32, temperature=0.2, top_p=None,
-                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None):
+                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None, sampler=None):
         """reference ullava.py:335-434 -> (output_ids, pred_masks, pred_boxes).  kv_cache_dtype="fp8_e4m3": generate with an fp8 KV cache
-        (which implies use_cache=True; see UllavaCoreForCausalLM.generate)."""
+        (which implies use_cache=True; see UllavaCoreForCausalLM.generate).  sampler="device": draw the tokens with the on-device sampler
+        (same ids under the same seed; see generate)."""
         if kv_cache_dtype is not None:
             _check_kv_dtype(kv_cache_dtype, self.llm.dtype)
+        if check_sampler(sampler) and no_repeat_ngram_size:
+            raise ValueError('sampler="device" does not combine with `no_repeat_ngram_size` (use sampler=None)')
         main = torch.cuda.current_stream()                          # SAM image encoder on the second stream, under the generation loop
         side = self._side_stream()
         side.wait_stream(main)
@@ -282,7 +285,7 @@ class UllavaForCausalLM(nn.Module):
         outputs = self.llm.generate(input_ids=input_ids, images=images, max_new_tokens=max_new_tokens, num_beams=num_beams, top_p=top_p,
                                     do_sample=True if temperature > 0 else False, temperature=temperature, output_hidden_states=True,
                                     return_dict_in_generate=True, no_repeat_ngram_size=no_repeat_ngram_size,
-                                    stopping_criteria=stopping_criteria, keep_last_step_only=True,
+                                    stopping_criteria=stopping_criteria, keep_last_step_only=True, sampler=sampler,
                                     **({} if kv_cache_dtype is None else dict(use_cache=True, kv_cache_dtype=kv_cache_dtype)))
         output_ids = outputs.sequences
         last = outputs.hidden_states[-1][-1]                          # last step, last layer: [B, L-1, D]

@@ -733,6 +733,33 @@ def greedy_step(logits_last: torch.Tensor, unfinished: torch.Tensor, eos_ids: Op
               int(pad) if pad is not None else 0, int(pad is not None), _p(seq), seq.stride(0), int(pos), _p(alive), _stream())
 
 
+SAMPLE_MAX_V = 36608        # ULL_SAMPLE_MAX_V: the longest row sample_step stages in LDS
+
+
+def sample_step(logits_last: torch.Tensor, noise: torch.Tensor, temperature: float, top_k: Optional[int], top_p: Optional[float],
+                unfinished: torch.Tensor, eos_ids: Optional[torch.Tensor], pad: Optional[int], seq: torch.Tensor, pos: int,
+                alive: torch.Tensor) -> None:
+    """One sampled step in one launch (see ull_sample_step): the token of every row is drawn from HF's distribution (`sampling_probs`:
+    temperature, top_k, top_p) with the caller's noise, fp32 [B, V] filled by `torch.empty(B, V).exponential_()` -- what
+    torch.multinomial(probs, 1) draws and divides by -- and the bookkeeping is greedy_step's.  top_k None / 0 and top_p None / >= 1 are off."""
+    _chk(logits_last, "logits"); _chk(unfinished, "unfinished", torch.int32); _chk(seq, "seq", torch.int64); _chk(alive, "alive", torch.int32)
+    _chk(noise, "noise", torch.float32)
+    B, V = logits_last.shape
+    if seq.stride(1) != 1 or not unfinished.is_contiguous() or logits_last.stride(1) != 1:
+        raise RuntimeError("u-llava_amd.sample_step: logits rows / seq rows / unfinished must be contiguous")
+    if tuple(noise.shape) != (B, V) or not noise.is_contiguous():
+        raise RuntimeError(f"u-llava_amd.sample_step: noise must be a contiguous fp32 [{B}, {V}] tensor, got {tuple(noise.shape)}")
+    if not temperature > 0:
+        raise ValueError(f"u-llava_amd.sample_step: temperature must be positive, got {temperature}")
+    n_eos = 0
+    if eos_ids is not None:
+        _chk(eos_ids, "eos_ids", torch.int64)
+        n_eos = eos_ids.numel()
+    _lib.call("ull_sample_step", _p(logits_last), DT_CODE[logits_last.dtype], logits_last.stride(0), B, V, _p(noise), float(temperature),
+              int(top_k) if top_k is not None and top_k > 0 else 0, float(top_p) if top_p is not None and top_p < 1.0 else 1.0, _p(unfinished),
+              _p(eos_ids), n_eos, int(pad) if pad is not None else 0, int(pad is not None), _p(seq), seq.stride(0), int(pos), _p(alive), _stream())
+
+
 def video_pool(f: torch.Tensor, B: int, T: int, N: int, tok_pitch: Optional[int] = None, tok_off: int = 0) -> torch.Tensor:
     """f [B*T, tok_pitch, D]; patches are tokens tok_off..tok_off+N of every frame."""
     _chk(f, "f")
