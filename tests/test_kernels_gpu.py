@@ -356,8 +356,9 @@ def test_attention_takes_v_as_rows(B, H, S, hd, causal, masked, dt):
 
 @pytest.mark.parametrize("Sq,Sk,left_pad", [(1, 70, 0), (1, 700, 13), (3, 1024, 0), (2, 2000, 100), (16, 4096, 0)])
 def test_attention_decode_step_shapes(Sq, Sk, left_pad):
-    """<= 16 new queries against a longer key cache (KV-cached generation incl. left-padded prompts; few-query split-key kernel up to
-    4096 keys): causal offset Sk - Sq, key mask, K / V^T read by cache strides."""
+    """<= 16 new queries against a longer key cache (KV-cached generation incl. left-padded prompts): causal offset Sk - Sq, key mask,
+    K / V^T read by cache strides.  Five points of the few-query split-key kernel (70 .. 4096 keys, random inputs); its edges -- one tile,
+    the 16 / 17-tile switch, more than 64 tiles, 16 against 17 queries -- are in test_attention_cached_gpu.py."""
     ops = pkg("ops")
     B, H, hd = 2, 4, 128
     D = H * hd
