@@ -129,6 +129,47 @@ int ull_gemv_qkv_rope_append_w8_bf16(const void* X, int64_t ldx, const void* nor
 int ull_gemm_skinny_w8_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc, const void* bias,
                             const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
 
+/* ---- MXFP4 weight-only decode (bf16 build only: no *_f16 twins) ---------------------------------------------------------------------
+ * UllavaCoreForCausalLM.quantize_weights("mxfp4") stores every LLaMA Linear and lm_head in the OCP microscaling format MXFP4 (bf16 models
+ * only; K % 32 == 0):
+ *   scale     one per row and per block of 32 consecutive K elements: 2^s, s the smallest integer with amax|block| * 2^-s <= 6 (an all-zero
+ *             block: s = 0), clamped to [-125, 126] so that every non-zero dequantized value is a normal float; stored as the E8M0 byte s + 127
+ *             (at s = 126 the codes of 4 and 6 would be 2^128 and above, so a block whose amax exceeds 3.5 * 2^126 -- within 14 % of the bf16
+ *             maximum -- saturates at the code of 3: every dequantized value the quantizer produces is finite);
+ *   element   e2m1(w * 2^-s): 0, 0.5, 1, 1.5, 2, 3, 4, 6 as codes 0 .. 7, rounded to nearest with ties to the even code (0.25 -> 0, 0.75 -> 1,
+ *             1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), sign in bit 3 (the sign of w: -0 only where w was -0 or rounded to it);
+ *   standard layout   codes [N, K / 2] bytes, element 2i in the low nibble of byte i (torch.float4_e2m1fn_x2), scales [N, K / 32] bytes;
+ *   resident layout   what the decode entries read: the standard layout with the bytes of each row permuted.  With a CHUNK = 8 consecutive
+ *             elements (4 code bytes) and a SUPERBLOCK = 256 chunks (2048 elements): inside whole superblock b, chunk b * 256 + g * 64 + l
+ *             (g < 4, l < 64) sits at code byte b * 1024 + l * 16 + g * 4, and the scale of block b * 64 + g * 16 + j (j < 16) at scale byte
+ *             b * 64 + j * 4 + g -- the four chunks of a GEMV lane are one 16-byte load, their scales one 4-byte load.  Chunks and blocks
+ *             after the last whole superblock keep the standard order.  Row pitches: codes a multiple of 16 bytes, scales a multiple of 4.
+ * dequant = e2m1 * 2^s has two significant bits, so it is exactly a bf16 value, and every decode entry below computes exactly what the bf16
+ * entry it replaces computes on the dequantized weight (same FMA / MFMA operands in the same order): bit-identical outputs, 4.25 bits per
+ * weight. */
+/* Quantize W [N, K] (bf16, row pitch ldw elements) into codes (row pitch ldq bytes) + scales (row pitch lds bytes); resident = 0: standard
+ * layout, 1: resident layout. */
+int ull_quantize_rows_mxfp4_bf16(const void* W, int64_t ldw, int64_t N, int64_t K, void* codes, int64_t ldq, void* scales, int64_t lds, int resident,
+                                 void* stream);
+/* dequant(codes) into bf16: tiled = 0: row-major [N, K]; tiled = 1: the ULL_EPI_W_TILED layout of ull_gemm_bf16 (K % 64 == 0, ceil(N / 256) * 256
+ * rows, padding rows zero).  Replaces the bf16 weight (or its tile-major copy) of a prefill-shape ull_gemm_bf16 / ull_gemm_qkv_rope_bf16 call. */
+int ull_dequantize_rows_mxfp4_bf16(const void* codes, int64_t ldq, const void* scales, int64_t lds, int64_t N, int64_t K, void* out, int tiled,
+                                   int resident, void* stream);
+/* Replaces ull_gemv_bf16 on an mxfp4 weight (resident layout, here and below). */
+int ull_gemv_w4_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C, int64_t ldc, const void* bias,
+                     const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+/* Replaces ull_gemv_rmsnorm_bf16 on an mxfp4 weight. */
+int ull_gemv_rmsnorm_w4_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales, int64_t lds,
+                             void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
+                             void* stream);
+/* Replaces ull_gemv_qkv_rope_append_bf16 on an mxfp4 q|k|v weight. */
+int ull_gemv_qkv_rope_append_w4_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales,
+                                     int64_t lds, void* Q_out, int64_t ldq_out, const void* cos_tab, const void* sin_tab, void* k_cache,
+                                     void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax, int64_t past, void* stream);
+/* Replaces ull_gemm_skinny_bf16 on an mxfp4 weight. */
+int ull_gemm_skinny_w4_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C, int64_t ldc,
+                            const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+
 /* ---- FP8 (e4m3) KV cache (bf16 build only) ------------------------------------------------------------------------------------------
  * KVCache(kv_dtype="fp8_e4m3") keeps, per layer, K codes [B, H, smax, hd] and V^T codes [B, H, hd, smax] (the key-permuted slot order of
  * ull_transpose_v) plus one fp32 scale 2^s per (batch, head, position) for the K row (k_scale [B, H, smax], by key) and one for the V column
@@ -546,6 +587,22 @@ int ull_llama_decode_layers_w8_bf16(const ull_llama_layer_w8* layers, int64_t n_
                                     void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
                                     void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax,
                                     int64_t past, float eps, const void* zeros, void* stream);
+/* The same on a model quantized to mxfp4 weights (resident layout; the *_w4_bf16 entries).  Same checks before the first launch, plus the row
+ * pitches (ld >= k / 2, a multiple of 16; lds >= k / 32, a multiple of 4; k % 32 == 0: ULL_ERR_ARG). */
+typedef struct ull_linear_w4 {
+    const void* codes;   /* [n, k / 2] bytes, row pitch ld */
+    const void* scales;  /* [n, k / 32] E8M0 bytes, row pitch lds */
+    int64_t n, k, ld, lds;
+} ull_linear_w4;
+typedef struct ull_llama_layer_w4 {
+    const void* ln1;
+    const void* ln2;
+    ull_linear_w4 qkv, o, gu, down;
+} ull_llama_layer_w4;
+int ull_llama_decode_layers_w4_bf16(const ull_llama_layer_w4* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
+                                    void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
+                                    void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax,
+                                    int64_t past, float eps, const void* zeros, void* stream);
 /* ull_llama_decode_layers_bf16 / ull_llama_decode_layers_w8_bf16 on an fp8 KV cache (see ull_attention_kv8_bf16): per layer the q|k|v GEMV appends
  * the step's keys to the shared bf16 staging window (k_stage [B, H, 128, hd], vt_stage [B, H, hd, 128]; pitch 128, first new key at past mod 64)
  * and ull_attention_kv8_bf16 reads the layer's codes / scales (k8, vt8, k_scale, vt_scale: per-layer pointer arrays, cache pitch smax) plus
@@ -556,6 +613,11 @@ int ull_llama_decode_layers_kv8_bf16(const ull_llama_layer* layers, int64_t n_la
                                      void* const* vt8, void* const* k_scale, void* const* vt_scale, void* k_stage, void* vt_stage, int64_t B, int64_t S,
                                      int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream);
 int ull_llama_decode_layers_w8_kv8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
+                                        void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
+                                        void* const* k8, void* const* vt8, void* const* k_scale, void* const* vt_scale, void* k_stage, void* vt_stage,
+                                        int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros,
+                                        void* stream);
+int ull_llama_decode_layers_w4_kv8_bf16(const ull_llama_layer_w4* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
                                         void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
                                         void* const* k8, void* const* vt8, void* const* k_scale, void* const* vt_scale, void* k_stage, void* vt_stage,
                                         int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros,

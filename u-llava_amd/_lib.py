@@ -30,6 +30,14 @@ class LlamaLayerW8(ctypes.Structure):
     _fields_ = [("ln1", _ptr), ("ln2", _ptr), ("qkv", LinearW8), ("o", LinearW8), ("gu", LinearW8), ("down", LinearW8)]
 
 
+class LinearW4(ctypes.Structure):
+    _fields_ = [("codes", _ptr), ("scales", _ptr), ("n", _i64), ("k", _i64), ("ld", _i64), ("lds", _i64)]
+
+
+class LlamaLayerW4(ctypes.Structure):
+    _fields_ = [("ln1", _ptr), ("ln2", _ptr), ("qkv", LinearW4), ("o", LinearW4), ("gu", LinearW4), ("down", LinearW4)]
+
+
 class ClipLayer(ctypes.Structure):
     _fields_ = [("ln1_w", _ptr), ("ln1_b", _ptr), ("ln2_w", _ptr), ("ln2_b", _ptr), ("qkv", Linear), ("out", Linear), ("fc1", Linear), ("fc2", Linear)]
 
@@ -145,6 +153,20 @@ SIGNATURES.update({
                                         _i64, _i64, _i64, _f32, _ptr, _ptr],
     "ull_llama_decode_layers_kv8_bf16": [_ptr, _i64] + [_ptr] * 16 + [_i64] * 7 + [_f32, _ptr, _ptr],
     "ull_llama_decode_layers_w8_kv8_bf16": [_ptr, _i64] + [_ptr] * 16 + [_i64] * 7 + [_f32, _ptr, _ptr],
+})
+
+# mxfp4 weight-only decode: bf16-only entry points (no fp16 twin)
+SIGNATURES.update({
+    "ull_quantize_rows_mxfp4_bf16": [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _i32, _ptr],
+    "ull_dequantize_rows_mxfp4_bf16": [_ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i32, _i32, _ptr],
+    "ull_gemv_w4_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
+    "ull_gemv_rmsnorm_w4_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
+    "ull_gemv_qkv_rope_append_w4_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
+                                         _i64, _i64, _i64, _ptr],
+    "ull_gemm_skinny_w4_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
+    "ull_llama_decode_layers_w4_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
+                                        _i64, _i64, _i64, _f32, _ptr, _ptr],
+    "ull_llama_decode_layers_w4_kv8_bf16": [_ptr, _i64] + [_ptr] * 16 + [_i64] * 7 + [_f32, _ptr, _ptr],
 })
 
 # fp16-only entry points (no bf16 twin): the fp32 neck of an fp16 SAM encoder (image_encoder.py:117-124)

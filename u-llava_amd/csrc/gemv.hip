@@ -47,7 +47,10 @@ ULL_DEV uint4 w_load16(const elem_t* p) {
 // values of the dequantized weight -- and feeds them to the same FMAs / MFMAs in the same order, so the result equals the 16-bit
 // kernel's on dequant(W) bit for bit.  The format is a template parameter: for WF_ELEM the pointer type below is the plain weight pointer,
 // so the existing instantiations keep their arguments and code.
-constexpr int WF_ELEM = 0, WF_FP8 = 1;
+// WF_MXFP4 (bf16 build only): e2m1 code rows with one E8M0 scale per 32 elements, in the resident layout of ull_common.h (mx_code_pos): a lane's four
+// chunks of a superblock arrive in one 16-byte load, their four scale bytes in one 4-byte load, and v_cvt_scalef32_pk_f32_fp4 turns each chunk
+// into the 8 floats e2m1 * 2^s -- again exactly the bf16 values of the dequantized weight, multiplied in the order of the 16-bit kernel.
+constexpr int WF_ELEM = 0, WF_FP8 = 1, WF_MXFP4 = 2;
 
 struct W8Rows {
     const uint8_t* codes;                    // [N][ldw] e4m3fn bytes
@@ -64,13 +67,41 @@ template <> struct WFmt<WF_FP8> {
     ULL_DEV static const uint8_t* rows(const W8Rows& W) { return W.codes; }
 };
 
+struct W4Rows {
+    const uint8_t* codes;                    // [N][ldw] bytes: two e2m1 codes each, resident layout
+    const uint8_t* scales;                   // [N][lds] E8M0 bytes, resident layout
+    long lds;
+};
+template <> struct WFmt<WF_MXFP4> {
+    typedef W4Rows ptr_t;
+    typedef uint8_t w_t;
+    ULL_DEV static const uint8_t* rows(const W4Rows& W) { return W.codes; }
+};
+
 typedef uint32_t gv_u32x2_t __attribute__((ext_vector_type(2)));
 ULL_DEV uint2 w_load8(const uint8_t* p) {
     const gv_u32x2_t v = __builtin_nontemporal_load((const gv_u32x2_t*)p);
     return make_uint2(v.x, v.y);
 }
 
-// (unpack8_w8, fp8_scale_exp: ull_common.h)
+// (unpack8_w8, fp8_scale_exp, unpack8_w4, mx_code_pos, mx_scale_pos: ull_common.h)
+
+// One weight chunk (8 elements) of a GEMV lane against the M activation rows: the FMAs of gemv_kernel's 16-bit loop, in its order.
+template <int M>
+ULL_DEV void gemv_fma_chunk(const float* wv, const float* uv, bool swiglu, const elem_t* __restrict__ X, long ldx, const elem_t* xs, int K, int staged,
+                            int c, float* a0, float* a1) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        float xv[8];
+        if (staged) unpack8(*(const uint4*)(xs + (long)m * K + c * 8), xv);
+        else unpack8(*(const uint4*)(X + (long)m * ldx + c * 8), xv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            a0[m] += wv[j] * xv[j];
+            if (swiglu) a1[m] += uv[j] * xv[j];
+        }
+    }
+}
 
 constexpr int XS_MAX_BYTES = 32 * 1024;     // X (optionally RMS-normalised) is staged in LDS when M * K * 2 fits in this
 
@@ -160,40 +191,82 @@ __global__ __launch_bounds__(256) void gemv_kernel(const elem_t* __restrict__ X,
         float a0[M], a1[M];
 #pragma unroll
         for (int m = 0; m < M; ++m) a0[m] = a1[m] = 0.f;
-        for (int c0 = lane; c0 < nchunk; c0 += 64 * U) {
-            typename std::conditional<WF == WF_FP8, uint2, uint4>::type wq[U], uq[U];
+        if constexpr (WF == WF_MXFP4) {
+            // whole superblocks: U 16-byte loads per lane in flight, each the lane's chunks b * 256 + g * 64 + lane, g = 0 .. 3 -- ascending K,
+            // the order in which the 16-bit kernel's lane meets them; then the standard-order chunks after the last whole superblock
+            const uint8_t* sc0 = W.scales + (long)row0 * W.lds;
+            const uint8_t* sc1 = sc0 + (long)row1_off * W.lds;
+            const int nsb = nchunk >> 8;
+            for (int b0 = 0; b0 < nsb; b0 += U) {
+                uint4 wq[U], uq[U];
+                uint32_t ws[U], us[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int c = c0 + 64 * u;
-                if constexpr (WF == WF_FP8) {
-                    wq[u] = c < nchunk ? w_load8(w0 + c * 8) : make_uint2(0, 0);
-                    if (swiglu) uq[u] = c < nchunk ? w_load8(w1 + c * 8) : make_uint2(0, 0);
-                } else {
-                    wq[u] = c < nchunk ? w_load16(w0 + c * 8) : make_uint4(0, 0, 0, 0);
-                    if (swiglu) uq[u] = c < nchunk ? w_load16(w1 + c * 8) : make_uint4(0, 0, 0, 0);
+                for (int u = 0; u < U; ++u) {
+                    const int b = min(b0 + u, nsb - 1);                       // past the end: a repeated, unused superblock
+                    wq[u] = w_load16((const elem_t*)(w0 + (long)b * 1024 + lane * 16));
+                    ws[u] = *(const uint32_t*)(sc0 + b * 64 + (lane >> 2) * 4);
+                    if (swiglu) {
+                        uq[u] = w_load16((const elem_t*)(w1 + (long)b * 1024 + lane * 16));
+                        us[u] = *(const uint32_t*)(sc1 + b * 64 + (lane >> 2) * 4);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (b0 + u < nsb) {
+                        const uint32_t* wc = (const uint32_t*)&wq[u];
+                        const uint32_t* uc = (const uint32_t*)&uq[u];
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            float wv[8], uv[8];
+                            unpack8_w4(wc[g], mx_scale_f32(ws[u] >> (8 * g)), wv);
+                            if (swiglu) unpack8_w4(uc[g], mx_scale_f32(us[u] >> (8 * g)), uv);
+                            gemv_fma_chunk<M>(wv, uv, swiglu, X, ldx, xs, K, staged, (b0 + u) * 256 + g * 64 + lane, a0, a1);
+                        }
+                    }
                 }
             }
+            for (int c = nsb * 256 + lane; c < nchunk; c += 64) {
+                float wv[8], uv[8];
+                unpack8_w4(*(const uint32_t*)(w0 + (long)c * 4), mx_scale_f32(sc0[c >> 2]), wv);
+                if (swiglu) unpack8_w4(*(const uint32_t*)(w1 + (long)c * 4), mx_scale_f32(sc1[c >> 2]), uv);
+                gemv_fma_chunk<M>(wv, uv, swiglu, X, ldx, xs, K, staged, c, a0, a1);
+            }
+        } else {
+            for (int c0 = lane; c0 < nchunk; c0 += 64 * U) {
+                typename std::conditional<WF == WF_FP8, uint2, uint4>::type wq[U], uq[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int c = c0 + 64 * u;
-                if (c < nchunk) {
-                    float wv[8], uv[8];
+                for (int u = 0; u < U; ++u) {
+                    const int c = c0 + 64 * u;
                     if constexpr (WF == WF_FP8) {
-                        unpack8_w8(wq[u], s0, wv);
-                        if (swiglu) unpack8_w8(uq[u], s1, uv);
+                        wq[u] = c < nchunk ? w_load8(w0 + c * 8) : make_uint2(0, 0);
+                        if (swiglu) uq[u] = c < nchunk ? w_load8(w1 + c * 8) : make_uint2(0, 0);
                     } else {
-                        unpack8(wq[u], wv);
-                        if (swiglu) unpack8(uq[u], uv);
+                        wq[u] = c < nchunk ? w_load16(w0 + c * 8) : make_uint4(0, 0, 0, 0);
+                        if (swiglu) uq[u] = c < nchunk ? w_load16(w1 + c * 8) : make_uint4(0, 0, 0, 0);
                     }
+                }
 #pragma unroll
-                    for (int m = 0; m < M; ++m) {
-                        float xv[8];
-                        if (staged) unpack8(*(const uint4*)(xs + (long)m * K + c * 8), xv);
-                        else unpack8(*(const uint4*)(X + (long)m * ldx + c * 8), xv);
+                for (int u = 0; u < U; ++u) {
+                    const int c = c0 + 64 * u;
+                    if (c < nchunk) {
+                        float wv[8], uv[8];
+                        if constexpr (WF == WF_FP8) {
+                            unpack8_w8(wq[u], s0, wv);
+                            if (swiglu) unpack8_w8(uq[u], s1, uv);
+                        } else {
+                            unpack8(wq[u], wv);
+                            if (swiglu) unpack8(uq[u], uv);
+                        }
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            a0[m] += wv[j] * xv[j];
-                            if (swiglu) a1[m] += uv[j] * xv[j];
+                        for (int m = 0; m < M; ++m) {
+                            float xv[8];
+                            if (staged) unpack8(*(const uint4*)(xs + (long)m * K + c * 8), xv);
+                            else unpack8(*(const uint4*)(X + (long)m * ldx + c * 8), xv);
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) {
+                                a0[m] += wv[j] * xv[j];
+                                if (swiglu) a1[m] += uv[j] * xv[j];
+                            }
                         }
                     }
                 }
@@ -254,6 +327,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(const elem_t* __restrict__ X,
 // weight fragments straight from HBM (8 in flight per lane), X fragments from L2 (M x K x 2 bytes, shared by every block), partial
 // sums through LDS, then the GEMV's epilogue (same flags, same rounding points).  MFMA work is 16 / M times the useful flops and
 // still far below the stream's time.  WF_FP8: 8 code bytes per lane and fragment, turned into the exact bf16 fragment of dequant(W).
+// WF_MXFP4: 4 code bytes and the block's scale byte per lane and fragment (a 32-wide k-step is one scale block), at their resident positions;
+// v_cvt_scalef32_pk_bf16_fp4 yields the bf16 fragment of dequant(W) directly.
 template <bool SW, int WF = WF_ELEM>
 __global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restrict__ X, long ldx, typename WFmt<WF>::ptr_t W, long ldw, void* C,
                                                           long ldc, const elem_t* __restrict__ bias, const elem_t* __restrict__ R, long ldr, int M,
@@ -263,7 +338,7 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restri
     const int o0 = blockIdx.x * 16;                              // first output feature of the block
     // weight row of A-operand row fr: plain: o0 + fr; SwiGLU pack: gate rows (o0/16)*32 + fr, up rows 16 below
     const int wr0 = SW ? (o0 >> 4) * 32 + fr : min(o0 + fr, N - 1);
-    const typename WFmt<WF>::w_t* w0 = WFmt<WF>::rows(W) + (long)wr0 * ldw + fg * 8;
+    const typename WFmt<WF>::w_t* w0 = WFmt<WF>::rows(W) + (long)wr0 * ldw + (WF == WF_MXFP4 ? 0 : fg * 8);   // (mxfp4: see mx_code_pos below)
     const typename WFmt<WF>::w_t* w1 = w0 + 16 * ldw;
     float s0 = 1.f, s1 = 1.f;                                    // (WF_FP8) the scales of rows wr0 and wr0 + 16
     if constexpr (WF == WF_FP8) {
@@ -272,16 +347,31 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restri
     }
     const elem_t* xr = X + (long)min(fr, M - 1) * ldx + fg * 8;  // rows >= M repeat the last row: those accumulator columns are not stored
     const int nks = K >> 5;                                      // 32-wide k-steps
+    const uint8_t *sc0 = nullptr, *sc1 = nullptr;                // (WF_MXFP4) the scale rows of wr0 and wr0 + 16
+    if constexpr (WF == WF_MXFP4) {
+        sc0 = W.scales + (long)wr0 * W.lds;
+        sc1 = sc0 + 16 * W.lds;
+    }
+    const int nsb = K >> 11;                                     // (WF_MXFP4) whole superblocks of the resident layout
     const int ks0 = (int)((long)nks * wave / 8), ks1 = (int)((long)nks * (wave + 1) / 8);
     f32x4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
     constexpr int U = SW ? 4 : 8;              // (SwiGLU streams two weight rows per fragment: 8 would cost the second block per CU its registers)
     for (int k0 = ks0; k0 < ks1; k0 += U) {
-        typename std::conditional<WF == WF_FP8, uint2, uint4>::type wq[U], uq[U];
+        typename std::conditional<WF == WF_FP8, uint2, typename std::conditional<WF == WF_MXFP4, uint32_t, uint4>::type>::type wq[U], uq[U];
+        uint32_t wsc[U], usc[U];                                 // (WF_MXFP4) the k-steps' scale bytes
         uint4 xq[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int ks = min(k0 + u, ks1 - 1);                 // past the end: a repeated, unused fragment
-            if constexpr (WF == WF_FP8) {
+            if constexpr (WF == WF_MXFP4) {
+                const long cp = mx_code_pos(ks * 4 + fg, nsb), sp = mx_scale_pos(ks, nsb);
+                wq[u] = *(const uint32_t*)(w0 + cp);
+                wsc[u] = sc0[sp];
+                if constexpr (SW) {
+                    uq[u] = *(const uint32_t*)(w1 + cp);
+                    usc[u] = sc1[sp];
+                }
+            } else if constexpr (WF == WF_FP8) {
                 wq[u] = *(const uint2*)(w0 + ks * 32);
                 if constexpr (SW) uq[u] = *(const uint2*)(w1 + ks * 32);
             } else {
@@ -293,7 +383,10 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restri
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (k0 + u < ks1) {
-                if constexpr (WF == WF_FP8) {
+                if constexpr (WF == WF_MXFP4) {
+                    a0 = mfma16(unpack8_w4_bf16(wq[u], mx_scale_f32(wsc[u])), xq[u], a0);
+                    if constexpr (SW) a1 = mfma16(unpack8_w4_bf16(uq[u], mx_scale_f32(usc[u])), xq[u], a1);
+                } else if constexpr (WF == WF_FP8) {
                     float f[8];
                     unpack8_w8(wq[u], s0, f);
                     a0 = mfma16(pack8(f), xq[u], a0);
@@ -352,17 +445,48 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restri
     }
 }
 
+// Launch shape of the mxfp4 GEMV: W4_U 16-byte weight loads per lane in flight, W4_BLOCKS the grid cap where every block pays the X staging.
+// The constants are the sweep's choice (profiles/mxfp4_decode.txt, batch-1 decode ms per step: U = 1 / 2 / 4 at 1536 blocks 2.58 / 2.50 / 2.92;
+// U = 2 at 1024 / 1536 / 2048 / 3072 / 4096 blocks 2.55 / 2.50 / 2.59 / 2.66 / 2.66).  A build with -DULL_W4_TUNE (make CXXFLAGS+=-DULL_W4_TUNE; tools/
+// only, not part of the ABI in include/ullava_hip.h) adds U = 1, 2, 4 instantiations and a process-wide run-time switch,
+// ull_gemv_w4_tune_bf16(u, blocks), which tools/mxfp4_decode_bench.py --sweep drives.
+constexpr int W4_U = 2, W4_BLOCKS = 1536;
+#if defined(ULL_W4_TUNE) && !defined(ULL_ELEM_F16)
+struct W4Tune { int u, blocks; };
+W4Tune g_w4_tune = {W4_U, W4_BLOCKS};
+#endif
+
+// the row pitches an mxfp4 weight needs: whole rows, 16-byte aligned code rows, 4-byte aligned scale rows
+inline bool w4_pitch_ok(int64_t K, int64_t ldw, int64_t lds) { return !(K & 31) && ldw >= K / 2 && !(ldw & 15) && lds >= K / 32 && !(lds & 3); }
+
 // scales != nullptr: W holds e4m3 codes (row pitch ldw bytes) with one fp32 scale per row (WF_FP8, bf16 build only).
+// mx_scales != nullptr: W holds mxfp4 codes (row pitch ldw bytes), mx_scales the E8M0 bytes (row pitch mx_ld), resident layout (WF_MXFP4, bf16 build only).
 int launch_skinny(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr,
-                  int64_t M, int64_t N, int64_t K, int flags, void* stream, const float* scales = nullptr) {
+                  int64_t M, int64_t N, int64_t K, int flags, void* stream, const float* scales = nullptr, const void* mx_scales = nullptr,
+                  int64_t mx_ld = 0) {
     if (!X || !W || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
     if (M > 16 || (K & 31) || (ldx & 7) || (ldw & 7)) return ULL_ERR_SHAPE;
+    if (mx_scales && !w4_pitch_ok(K, ldw, mx_ld)) return ULL_ERR_SHAPE;
     if ((flags & EPI_BIAS) && !bias) return ULL_ERR_ARG;
     if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
     if ((flags & EPI_SWIGLU) && ((N & 31) || (flags & (EPI_BIAS | EPI_ACT_MASK)))) return ULL_ERR_SHAPE;
     const int n_out = (int)((flags & EPI_SWIGLU) ? N / 2 : N);
     const unsigned blocks = (unsigned)((n_out + 15) / 16);
     hipStream_t st = (hipStream_t)stream;
+    if (mx_scales) {
+#ifdef ULL_ELEM_F16
+        return ULL_ERR_ARG;
+#else
+        const W4Rows w4{(const uint8_t*)W, (const uint8_t*)mx_scales, (long)mx_ld};
+        if (flags & EPI_SWIGLU)
+            hipLaunchKernelGGL((skinny_gemm_kernel<true, WF_MXFP4>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, w4, ldw, C, ldc,
+                               (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
+        else
+            hipLaunchKernelGGL((skinny_gemm_kernel<false, WF_MXFP4>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, w4, ldw, C, ldc,
+                               (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
+        return ull_check_launch();
+#endif
+    }
     if (scales) {
 #ifdef ULL_ELEM_F16
         return ULL_ERR_ARG;
@@ -386,14 +510,15 @@ int launch_skinny(const void* X, int64_t ldx, const void* W, int64_t ldw, void* 
     return ull_check_launch();
 }
 
-// scales != nullptr: W holds e4m3 codes, as in launch_skinny.
+// scales != nullptr: W holds e4m3 codes; mx_scales != nullptr: mxfp4 codes, as in launch_skinny.
 int launch_gemv(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr,
                 int64_t M, int64_t N, int64_t K, int flags, const void* norm_w, float eps, void* stream, const RopeAppend* rope = nullptr,
-                const float* scales = nullptr) {
+                const float* scales = nullptr, const void* mx_scales = nullptr, int64_t mx_ld = 0) {
     if (!X || !W || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
     if ((flags & EPI_ROPE_APPEND) && (!rope || flags != EPI_ROPE_APPEND || (N & 1))) return ULL_ERR_ARG;   // (not part of the public flags)
     const RopeAppend ra = rope ? *rope : RopeAppend{};
     if (M > MAXM || (K & 7) || (ldx & 7) || (ldw & 7)) return ULL_ERR_SHAPE;
+    if (mx_scales && !w4_pitch_ok(K, ldw, mx_ld)) return ULL_ERR_SHAPE;
     if ((flags & EPI_BIAS) && !bias) return ULL_ERR_ARG;
     if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
     if ((flags & EPI_SWIGLU) && ((N & 31) || (flags & (EPI_BIAS | EPI_ACT_MASK)))) return ULL_ERR_SHAPE;
@@ -406,6 +531,44 @@ int launch_gemv(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C,
     if (staged && blocks > 1024) blocks = 1024;
     if (blocks > 8192) blocks = 8192;
     hipStream_t st = (hipStream_t)stream;
+    if (mx_scales) {
+#ifdef ULL_ELEM_F16
+        return ULL_ERR_ARG;
+#else
+        // A quarter of the bytes per row: a K = 4096 row is two 16-byte loads per lane (launch shape: W4_U, W4_BLOCKS above).
+        const W4Rows w4{(const uint8_t*)W, (const uint8_t*)mx_scales, (long)mx_ld};
+        int blocks4 = (n_out + 3) / 4;
+#ifdef ULL_W4_TUNE
+        const int cap4 = g_w4_tune.blocks;
+#else
+        const int cap4 = W4_BLOCKS;
+#endif
+        if (staged && blocks4 > cap4) blocks4 = cap4;
+        if (blocks4 > 8192) blocks4 = 8192;
+#define ULL_GV4(MM, UU)                                                                                                                   \
+    hipLaunchKernelGGL((gemv_kernel<MM, UU, WF_MXFP4>), dim3(blocks4), dim3(256), lds, st, (const elem_t*)X, ldx, w4, ldw, C, ldc,   \
+                       (const elem_t*)bias, (const elem_t*)R, ldr, (int)N, (int)K, flags, n_out, (const elem_t*)norm_w, eps, staged, ra)
+#ifdef ULL_W4_TUNE
+#define ULL_GV4_U(MM)                          \
+    switch (g_w4_tune.u) {                     \
+        case 1: ULL_GV4(MM, 1); break;         \
+        case 4: ULL_GV4(MM, 4); break;         \
+        default: ULL_GV4(MM, 2); break;        \
+    }
+#else
+#define ULL_GV4_U(MM) ULL_GV4(MM, W4_U)
+#endif
+        switch ((int)M) {
+            case 1: ULL_GV4_U(1); break;
+            case 2: ULL_GV4_U(2); break;
+            case 3: ULL_GV4_U(3); break;
+            default: ULL_GV4_U(4); break;
+        }
+#undef ULL_GV4_U
+#undef ULL_GV4
+        return ull_check_launch();
+#endif
+    }
     if (scales) {
 #ifdef ULL_ELEM_F16
         return ULL_ERR_ARG;
@@ -597,4 +760,137 @@ extern "C" int ULL_FN(ull_gemm_skinny_w8_)(const void* X, int64_t ldx, const voi
     if (!scales) return ULL_ERR_ARG;
     return launch_skinny(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, stream, (const float*)scales);
 }
+#endif  // !ULL_ELEM_F16
+
+// ---- MXFP4 weight-only decode: bf16 build only -------------------------------------------------------------------------------------
+// A weight W [N, K], K % 32 == 0, is stored as e2m1 codes (two per byte, element 2i in the low nibble: [N, K / 2] bytes) plus one E8M0 scale
+// byte s + 127 per row and block of 32 consecutive K elements ([N, K / 32]); s is the smallest integer with amax|block| * 2^-s <= 6 (all-zero
+// block: s = 0) clamped to [-125, 126], a code is e2m1(w * 2^-s) rounded to nearest, ties to the even code, sign in bit 3 (ull_common.h).
+// dequant = e2m1 * 2^s is exactly a bf16 value, so the mxfp4 kernels above compute exactly what the 16-bit kernels compute on dequant(W).
+// `resident` selects the byte order within a row: 0 the standard layout just described, 1 the resident layout the decode kernels read
+// (mx_code_pos / mx_scale_pos: a permutation of the standard layout's bytes within the row).
+#ifndef ULL_ELEM_F16
+namespace {
+
+// one row per wave; a lane owns chunks of 8 elements, four neighbouring lanes one scale block
+__global__ __launch_bounds__(256) void quantize_rows_mxfp4_kernel(const elem_t* __restrict__ W, long ldw, int N, int K, uint8_t* __restrict__ codes,
+                                                                  long ldq, uint8_t* __restrict__ scales, long lds, int resident) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const elem_t* w = W + (long)row * ldw;
+    const int nchunk = K >> 3, nsb = resident ? nchunk >> 8 : 0;
+    uint8_t* q = codes + (long)row * ldq;
+    uint8_t* sc = scales + (long)row * lds;
+    for (int c0 = 0; c0 < nchunk; c0 += 64) {                    // (nchunk % 4 == 0: the four lanes of a block are in or out together)
+        const int c = c0 + lane;
+        float v[8];
+        if (c < nchunk) unpack8(*(const uint4*)(w + c * 8), v);
+        else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = 0.f;
+        }
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+        amax = group_max(amax, 4);
+        const int s = mxfp4_scale_exp(amax);
+        if (c < nchunk) {
+            uint32_t code = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) code |= mxfp4_code(ldexpf(v[j], -s), s == 126 ? 5u : 7u) << (4 * j);     // exact, or below a quarter of the smallest step
+            *(uint32_t*)(q + mx_code_pos(c, nsb)) = code;
+            if ((lane & 3) == 0) sc[mx_scale_pos(c >> 2, nsb)] = (uint8_t)(s + 127);
+        }
+    }
+}
+
+// codes -> dequant(W) in bf16, row-major [N, K] or (tiled) the ULL_EPI_W_TILED layout of ull_gemm_bf16 with the padding rows zeroed.
+// One thread per 8 elements.
+__global__ __launch_bounds__(256) void dequantize_rows_mxfp4_kernel(const uint8_t* __restrict__ codes, long ldq, const uint8_t* __restrict__ scales,
+                                                                    long lds, int N, int K, elem_t* __restrict__ out, int tiled, int resident,
+                                                                    long total) {
+    const int g8 = K >> 3, nsb = resident ? g8 >> 8 : 0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int n = (int)(i / g8), c = (int)(i - (long)n * g8), k = c * 8;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (n < N)
+            v = unpack8_w4_bf16(*(const uint32_t*)(codes + (long)n * ldq + mx_code_pos(c, nsb)),
+                                mx_scale_f32(scales[(long)n * lds + mx_scale_pos(c >> 2, nsb)]));
+        const long o = tiled ? (((long)(n >> 8) * (K >> 6) + (k >> 6)) * 256 + (n & 255)) * 64 + (k & 63) : (long)n * K + k;
+        *(uint4*)(out + o) = v;
+    }
+}
+
+}  // namespace
+
+// MXFP4 quantization (see above) of a bf16 weight W [N, K] (row pitch ldw elements): codes [N, K / 2] bytes (row pitch ldq), scales
+// [N, K / 32] bytes (row pitch lds).  K % 32 == 0.
+extern "C" int ULL_FN(ull_quantize_rows_mxfp4_)(const void* W, int64_t ldw, int64_t N, int64_t K, void* codes, int64_t ldq, void* scales, int64_t lds,
+                                                int resident, void* stream) {
+    if (!W || !codes || !scales || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if ((K & 31) || (ldw & 7) || ldw < K || (ldq & 3) || ldq < K / 2 || lds < K / 32 || N > (1 << 28)) return ULL_ERR_SHAPE;
+    hipLaunchKernelGGL(quantize_rows_mxfp4_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const elem_t*)W, (long)ldw,
+                       (int)N, (int)K, (uint8_t*)codes, (long)ldq, (uint8_t*)scales, (long)lds, resident ? 1 : 0);
+    return ull_check_launch();
+}
+
+// dequant(codes) into a bf16 buffer: tiled = 0: row-major [N, K]; tiled = 1: ull_gemm_bf16's ULL_EPI_W_TILED layout (K % 64 == 0; out holds
+// ceil(N / 256) * 256 * K elements).  The prefill path of an mxfp4 weight: this, then the unchanged 16-bit GEMM.
+extern "C" int ULL_FN(ull_dequantize_rows_mxfp4_)(const void* codes, int64_t ldq, const void* scales, int64_t lds, int64_t N, int64_t K, void* out,
+                                                  int tiled, int resident, void* stream) {
+    if (!codes || !scales || !out || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if ((K & 31) || (ldq & 3) || ldq < K / 2 || lds < K / 32 || (tiled && (K & 63))) return ULL_ERR_SHAPE;
+    const long rows = tiled ? (N + 255) / 256 * 256 : N;
+    const long total = rows * (K >> 3);
+    const long blocks = std::min<long>((total + 255) / 256, 16384);
+    hipLaunchKernelGGL(dequantize_rows_mxfp4_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)codes, (long)ldq,
+                       (const uint8_t*)scales, (long)lds, (int)N, (int)K, (elem_t*)out, tiled, resident ? 1 : 0, total);
+    return ull_check_launch();
+}
+
+// ull_gemv_bf16 / ull_gemv_rmsnorm_bf16 / ull_gemv_qkv_rope_append_bf16 / ull_gemm_skinny_bf16 on an mxfp4 weight in the resident layout: Q = codes
+// (row pitch ldq bytes, a multiple of 16), scales = E8M0 bytes (row pitch lds, a multiple of 4).  Same contract and bits as the bf16 entry on
+// dequant(Q); K % 32 == 0.
+extern "C" int ULL_FN(ull_gemv_w4_)(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C, int64_t ldc,
+                                    const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
+    if (!scales) return ULL_ERR_ARG;
+    return launch_gemv(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, nullptr, 0.f, stream, nullptr, nullptr, scales, lds);
+}
+
+extern "C" int ULL_FN(ull_gemv_rmsnorm_w4_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales,
+                                            int64_t lds, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N,
+                                            int64_t K, int flags, void* stream) {
+    if (!norm_w || !scales) return ULL_ERR_ARG;
+    return launch_gemv(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, norm_w, eps, stream, nullptr, nullptr, scales, lds);
+}
+
+extern "C" int ULL_FN(ull_gemv_qkv_rope_append_w4_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq,
+                                                    const void* scales, int64_t lds, void* Q_out, int64_t ldq_out, const void* cos_tab,
+                                                    const void* sin_tab, void* k_cache, void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd,
+                                                    int64_t K, int64_t smax, int64_t past, void* stream) {
+    if (!scales || !cos_tab || !sin_tab || !k_cache || !vt_cache || B <= 0 || S <= 0 || H <= 0) return ULL_ERR_ARG;
+    if (hd <= 0 || (hd & 1) || past < 0 || past + S > smax || ldq_out < H * hd) return ULL_ERR_SHAPE;
+    RopeAppend ra;
+    ra.cs = (const elem_t*)cos_tab; ra.sn = (const elem_t*)sin_tab; ra.kc = (elem_t*)k_cache; ra.vtc = (elem_t*)vt_cache;
+    ra.S = (int)S; ra.H = (int)H; ra.hd = (int)hd; ra.smax = (int)smax; ra.past = (int)past;
+    return launch_gemv(X, ldx, Q, ldq, Q_out, ldq_out, nullptr, nullptr, 0, B * S, 3 * H * hd, K, EPI_ROPE_APPEND, norm_w, norm_w ? eps : 0.f, stream,
+                       &ra, nullptr, scales, lds);
+}
+
+extern "C" int ULL_FN(ull_gemm_skinny_w4_)(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C,
+                                           int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
+                                           void* stream) {
+    if (!scales) return ULL_ERR_ARG;
+    return launch_skinny(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, stream, nullptr, scales, lds);
+}
+
+#ifdef ULL_W4_TUNE
+// (ULL_W4_TUNE builds only) the launch shape of the mxfp4 GEMV for the sweep of tools/mxfp4_decode_bench.py: u = 1, 2 or 4, blocks = 256 .. 8192.
+extern "C" int ull_gemv_w4_tune_bf16(int u, int blocks) {
+    if ((u != 1 && u != 2 && u != 4) || blocks < 256 || blocks > 8192) return ULL_ERR_ARG;
+    g_w4_tune = W4Tune{u, blocks};
+    return ULL_OK;
+}
+#endif
 #endif  // !ULL_ELEM_F16

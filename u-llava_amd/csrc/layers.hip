@@ -58,9 +58,11 @@ inline int lin(const void* x, int64_t ldx, const ull_linear* L, void* out, int64
     return FN(ull_gemm_)(x, ldx, t.w, t.ldw, out, ldc, L->bias, R, ldr, M, L->n, L->k, flags | t.flags, t.ws, t.wsb, stream);
 }
 
-// The weight formats of a decode-shape Linear: a 16-bit ull_linear, or (bf16 build) an fp8 ull_linear_w8, which has no bias.  Each overload
-// passes the weight to the entry of its format.
+// The weight formats of a decode-shape Linear: a 16-bit ull_linear, or (bf16 build) an fp8 ull_linear_w8 or an mxfp4 ull_linear_w4, which have
+// no bias.  Each overload passes the weight to the entry of its format.  ldw_of: the row pitch the routing rule (ops._linear_route) sees;
+// pitch_ok: the rows are whole.
 inline bool has_weight(const ull_linear* L) { return L->w; }
+inline bool pitch_ok(const ull_linear* L) { return L->ldw >= L->k; }
 inline const void* bias_of(const ull_linear* L) { return L->bias; }
 inline int64_t ldw_of(const ull_linear* L) { return L->ldw; }
 inline int gemm_skinny(const void* x, int64_t ldx, const ull_linear* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
@@ -82,6 +84,7 @@ inline int gemv_qkv_rope_append(const void* x, int64_t ldx, const void* rms_w, f
 
 #ifndef ULL_ELEM_F16
 inline bool has_weight(const ull_linear_w8* L) { return L->codes && L->scales; }
+inline bool pitch_ok(const ull_linear_w8* L) { return L->ld >= L->k; }
 inline const void* bias_of(const ull_linear_w8*) { return nullptr; }
 inline int64_t ldw_of(const ull_linear_w8* L) { return L->ld; }
 inline int gemm_skinny(const void* x, int64_t ldx, const ull_linear_w8* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
@@ -101,6 +104,29 @@ inline int gemv_qkv_rope_append(const void* x, int64_t ldx, const void* rms_w, f
                                 void* stream) {
     return ull_gemv_qkv_rope_append_w8_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, q, ldq, cs, sn, kc, vtc, B, S, H, hd, L->k, smax, past,
                                             stream);
+}
+
+inline bool has_weight(const ull_linear_w4* L) { return L->codes && L->scales; }
+inline bool pitch_ok(const ull_linear_w4* L) { return L->k % 32 == 0 && L->ld >= L->k / 2 && L->ld % 16 == 0 && L->lds >= L->k / 32 && L->lds % 4 == 0; }
+inline const void* bias_of(const ull_linear_w4*) { return nullptr; }
+inline int64_t ldw_of(const ull_linear_w4* L) { return L->k; }        // (ops.linear passes K for an Mxfp4Weight: its rows are always whole)
+inline int gemm_skinny(const void* x, int64_t ldx, const ull_linear_w4* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
+                       void* stream) {
+    return ull_gemm_skinny_w4_bf16(x, ldx, L->codes, L->ld, L->scales, L->lds, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+}
+inline int gemv(const void* x, int64_t ldx, const ull_linear_w4* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
+                void* stream) {
+    return ull_gemv_w4_bf16(x, ldx, L->codes, L->ld, L->scales, L->lds, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+}
+inline int gemv_rmsnorm(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear_w4* L, void* out, int64_t ldc, const void* R,
+                        int64_t ldr, int64_t M, int flags, void* stream) {
+    return ull_gemv_rmsnorm_w4_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, L->lds, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+}
+inline int gemv_qkv_rope_append(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear_w4* L, void* q, int64_t ldq, const void* cs,
+                                const void* sn, void* kc, void* vtc, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
+                                void* stream) {
+    return ull_gemv_qkv_rope_append_w4_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, L->lds, q, ldq, cs, sn, kc, vtc, B, S, H, hd, L->k, smax,
+                                            past, stream);
 }
 #endif  // !ULL_ELEM_F16
 
@@ -211,7 +237,7 @@ int llama_decode_layers(const Layer* layers, int64_t n_layers, const void* x_in,
         if (w.qkv.n != 3 * D || w.qkv.k != D || w.o.n != D || w.o.k != D || w.gu.n != 2 * I || w.gu.k != D || w.down.n != D || w.down.k != I)
             return ULL_ERR_SHAPE;
         for (const auto* L : {&w.qkv, &w.o, &w.gu, &w.down})
-            if (!has_weight(L) || ldw_of(L) < L->k) return ULL_ERR_ARG;
+            if (!has_weight(L) || !pitch_ok(L)) return ULL_ERR_ARG;
         if (!w.ln1 || !w.ln2 || !cache_layer_ok(cache, l) || !x_out[l]) return ULL_ERR_ARG;
     }
     const float scale = 1.0f / sqrtf((float)hd);
@@ -256,6 +282,23 @@ extern "C" int ull_llama_decode_layers_kv8_bf16(const ull_llama_layer* layers, i
 }
 
 extern "C" int ull_llama_decode_layers_w8_kv8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out,
+                                                   void* x_mid, void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
+                                                   const void* key_mask, void* const* k8, void* const* vt8, void* const* k_scale,
+                                                   void* const* vt_scale, void* k_stage, void* vt_stage, int64_t B, int64_t S, int64_t H, int64_t hd,
+                                                   int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
+    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask,
+                               Kv8Cache{k8, vt8, k_scale, vt_scale, k_stage, vt_stage}, B, S, H, hd, I, smax, past, eps, zeros, stream);
+}
+
+extern "C" int ull_llama_decode_layers_w4_bf16(const ull_llama_layer_w4* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid,
+                                               void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
+                                               const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H,
+                                               int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
+    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask, BfCache{k_cache, vt_cache}, B, S, H,
+                               hd, I, smax, past, eps, zeros, stream);
+}
+
+extern "C" int ull_llama_decode_layers_w4_kv8_bf16(const ull_llama_layer_w4* layers, int64_t n_layers, const void* x_in, void* const* x_out,
                                                    void* x_mid, void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
                                                    const void* key_mask, void* const* k8, void* const* vt8, void* const* k_scale,
                                                    void* const* vt_scale, void* k_stage, void* vt_stage, int64_t B, int64_t S, int64_t H, int64_t hd,

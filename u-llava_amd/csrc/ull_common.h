@@ -144,6 +144,66 @@ ULL_DEV void unpack8_w8(const uint2& v, float s, float* f) {
     f[4] = c[0] * s; f[5] = c[1] * s; f[6] = d[0] * s; f[7] = d[1] * s;
 }
 
+// ---- MXFP4 (OCP microscaling: e2m1 elements, one E8M0 scale per 32 elements along K): mxfp4 weights (gemv.hip) ----------------------
+// The scale of a block is 2^s, s the smallest integer with amax * 2^-s <= 6 (an all-zero block: s = 0), clamped to [-125, 126] so that every
+// non-zero dequantized value is a normal float; it is stored as the E8M0 byte s + 127.  An element is e2m1(w * 2^-s) -- 0, 0.5, 1, 1.5, 2, 3,
+// 4, 6 as codes 0 .. 7, sign in bit 3 -- rounded to nearest with ties to the even code.  dequant = e2m1 * 2^s has 2 significant bits: a bf16
+// value.  At s = 126 the codes of 4 and 6 would dequantize to 2^128 and above, which no float holds; a block that large (amax above 3.5 * 2^126,
+// within 14 % of the bf16 maximum) saturates at the code of 3 instead, so that every dequantized value is finite.
+ULL_DEV int mxfp4_scale_exp(float amax) {
+    int s = 0;
+    if (amax > 0.f) {
+        int e;
+        frexpf(amax, &e);                                  // amax in [2^(e-1), 2^e): s is e - 3 or e - 2, settled exactly below
+        s = e - 3;
+        while (s < 126 && amax > ldexpf(6.f, s)) ++s;
+        while (s > -125 && amax <= ldexpf(6.f, s - 1)) --s;
+        s = min(max(s, -125), 126);
+    }
+    return s;
+}
+// the e2m1 code of v (|v| <= 6 after scaling; larger magnitudes saturate at 6): the midpoints between neighbours, ties to the even code;
+// max_mag: the largest magnitude code allowed (7, or 5 at s = 126)
+ULL_DEV uint32_t mxfp4_code(float v, uint32_t max_mag) {
+    const float a = fabsf(v);
+    uint32_t m = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) + (uint32_t)(a > 2.5f) +
+                       (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.f);
+    m = min(m, max_mag);
+    return m | ((__float_as_uint(v) >> 31) << 3);
+}
+// The RESIDENT layout of an mxfp4 row (ops.Mxfp4Weight): a permutation of the standard layout's bytes within the row.  In units of CHUNKS
+// (8 consecutive K elements = 4 code bytes, element 2i in the low nibble of byte i) a GEMV lane owns the chunks lane, lane + 64, lane + 128,
+// ...; a SUPERBLOCK is 256 chunks (2048 elements, 1024 bytes), and inside a whole superblock b the four chunks b * 256 + g * 64 + lane
+// (g = 0 .. 3) of a lane sit adjacent at byte b * 1024 + lane * 16 + g * 4: one 16-byte load.  The scale bytes are grouped the same way: the
+// four blocks of 32 elements those chunks belong to, b * 64 + g * 16 + lane / 4, sit at scale byte b * 64 + (lane / 4) * 4 + g: one 4-byte
+// load.  The chunks / blocks after the last whole superblock (nsb = K / 2048 of them) keep the standard order.
+ULL_DEV long mx_code_pos(int c, int nsb) {                 // byte offset in the row of chunk c's 4 code bytes
+    if (c >= nsb * 256) return (long)c * 4;
+    return (long)(c >> 8) * 1024 + (c & 63) * 16 + ((c >> 6) & 3) * 4;
+}
+ULL_DEV long mx_scale_pos(int blk, int nsb) {              // byte offset in the row of the E8M0 byte of 32-element block blk
+    if (blk >= nsb * 64) return blk;
+    return (long)(blk >> 6) * 64 + (blk & 15) * 4 + ((blk >> 4) & 3);
+}
+ULL_DEV float mx_scale_f32(uint32_t e8m0) { return __uint_as_float((e8m0 & 255u) << 23); }   // 2^(e - 127), e in [2, 253]: a normal float
+// 8 e2m1 codes (element j in nibble j of v) -> the 8 floats e2m1_j * s, s a power of two: v_cvt_scalef32_pk_f32_fp4 per byte, exact.
+ULL_DEV void unpack8_w4(uint32_t v, float s, float* f) {
+    typedef float f2_t __attribute__((ext_vector_type(2)));
+    const f2_t a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(v, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(v, s, 1);
+    const f2_t c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(v, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(v, s, 3);
+    f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
+    f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
+}
+// the same 8 values as packed bf16 (element j in half-word j): v_cvt_scalef32_pk_bf16_fp4 per byte -- an MFMA fragment as it stands
+ULL_DEV uint4 unpack8_w4_bf16(uint32_t v, float s) {
+    typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
+    const bf2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, s, 1);
+    const bf2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, s, 3);
+    uint4 r;
+    __builtin_memcpy(&r.x, &a, 4); __builtin_memcpy(&r.y, &b, 4); __builtin_memcpy(&r.z, &c, 4); __builtin_memcpy(&r.w, &d, 4);
+    return r;
+}
+
 // reduce across the `w` lanes (power of two <= 64) that share the same (lane / w)
 ULL_DEV float group_sum(float v, int w) {
     for (int o = w >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -405,7 +405,7 @@ def check_sampler(sampler) -> bool:
 # ----------------------------------------------------------------------------------------------------------
 class UllavaCoreForCausalLM(nn.Module):
     config_class = UllavaCoreConfig
-    weight_quantization = None             # "fp8_e4m3" after quantize_weights()
+    weight_quantization = None             # "fp8_e4m3" / "mxfp4" after quantize_weights()
 
     def __init__(self, config: UllavaCoreConfig, device=None, dtype=BF16):
         super().__init__()
@@ -467,11 +467,12 @@ class UllavaCoreForCausalLM(nn.Module):
         return self.model.embed_tokens
 
     def _refuse_quantized(self, what: str):
+        kind = "mxfp4" if self.weight_quantization == "mxfp4" else "fp8"
         raise NotImplementedError(f"{what} is not supported on a model quantized with quantize_weights('{self.weight_quantization}'): its LLaMA "
-                                  "Linear weights exist only as fp8 codes and scales (inference only; load the bf16 model for this)")
+                                  f"Linear weights exist only as {kind} codes and scales (inference only; load the bf16 model for this)")
 
     def _refuse_cast(self, fn):
-        """_apply on a quantized model: the fp8 packs are the only copy of the LLaMA weights, so a cast or a move has nothing to rebuild
+        """_apply on a quantized model: the fp8 / mxfp4 packs are the only copy of the LLaMA weights, so a cast or a move has nothing to rebuild
         them from; a no-op (.to(the same device)) is allowed."""
         probe = torch.empty(0, device=self.device, dtype=self.dtype)
         moved = fn(probe)
@@ -607,32 +608,45 @@ class UllavaCoreForCausalLM(nn.Module):
         the GEMV / skinny kernels); prefill shapes dequantize each weight into a bf16 scratch and run the bf16 GEMM.  The bf16 LLaMA
         weights and their tile-major copies are released: the fp8 packs become the only copy (like pack_weights(free_originals=True)),
         so the model can no longer train, take LoRA adapters, be saved, exported through state_dict() or cast.  bf16 models only;
-        call merge_lora() first when adapters are attached."""
-        if fmt != "fp8_e4m3":
-            raise ValueError(f"quantize_weights: unknown format {fmt!r} (supported: 'fp8_e4m3')")
+        call merge_lora() first when adapters are attached.
+
+        fmt="mxfp4": the OCP microscaling format instead (ops.quantize_mxfp4, DESIGN f7): e2m1 codes with one E8M0 power-of-two scale per row
+        and block of 32 consecutive K elements, 4.25 bits per weight.  dequant = e2m1 * 2^s is a bf16 value too, so the same twin rule holds
+        bit for bit, through the mxfp4 forms of the same kernels; everything said above about the fp8 model applies.  Weight-only
+        round-to-nearest without calibration: the weights lose far more precision than with fp8 (profiles/mxfp4_decode.txt).  A model
+        quantized to one format cannot be re-quantized to the other."""
+        if fmt not in ("fp8_e4m3", "mxfp4"):
+            raise ValueError(f"quantize_weights: unknown format {fmt!r} (supported: 'fp8_e4m3', 'mxfp4')")
+        mx = fmt == "mxfp4"
         if self.weight_quantization is not None:
             if self.weight_quantization == fmt:
                 return self
             self._refuse_quantized(f"quantize_weights({fmt!r})")
         if self.dtype != BF16:
-            raise NotImplementedError(f"quantize_weights('fp8_e4m3') covers bf16 models only (this one is {self.dtype}): for fp16 the dequantized "
-                                      "weights are not always representable, and fp32 has no fp8 kernels")
+            raise NotImplementedError(f"quantize_weights('{fmt}') covers bf16 models only (this one is {self.dtype}): for fp16 the dequantized "
+                                      f"weights are not always representable, and fp32 has no {'mxfp4' if mx else 'fp8'} kernels")
         if getattr(self, "_lora", None) is not None:
             raise NotImplementedError("quantize_weights: LoRA adapters are attached -- call merge_lora() first")
+        cfg = self.config
+        bad_k = cfg.hidden_size % 32 or cfg.intermediate_size % 32
+        if mx and bad_k:                     # (mxfp4 refuses before any device work: one scale per 32 elements of K)
+            raise NotImplementedError("quantize_weights('mxfp4'): hidden_size and intermediate_size (the K of every LLaMA Linear) must be multiples "
+                                      f"of 32 (got {cfg.hidden_size} and {cfg.intermediate_size})")
         if not self.lm_head.weight.is_cuda:
             raise RuntimeError("quantize_weights: move the model to the GPU first (the quantization runs there)")
-        cfg = self.config
-        if cfg.hidden_size % 32 or cfg.intermediate_size % 32:
+        if bad_k:                            # (fp8: the order and the message it has always had)
             raise NotImplementedError("quantize_weights: hidden_size and intermediate_size must be multiples of 32")
         # built outside inference mode: the packs are ordinary tensors whatever mode the caller is in (and no version counter is read)
         with torch.inference_mode(False), torch.no_grad():
             pk = self._pk(for_llama=True)
             dev = self.lm_head.weight.device
 
-            def q8(w):
-                return ops.quantize_fp8(w.detach().contiguous())
+            def quant(w):
+                return (ops.quantize_mxfp4 if mx else ops.quantize_fp8)(w.detach().contiguous())
 
             def cat(qs):
+                if mx:                       # (the resident layout permutes bytes within a row only: rows concatenate as they are)
+                    return ops.Mxfp4Weight(torch.cat([q.codes for q in qs]), torch.cat([q.scales for q in qs]), qs[0].K)
                 return ops.Fp8Weight(torch.cat([q.codes for q in qs]), torch.cat([q.scales for q in qs]))
 
             llama = []
@@ -640,14 +654,17 @@ class UllavaCoreForCausalLM(nn.Module):
                 a, m = l.self_attn, l.mlp
                 # per-row scales: quantizing the q|k|v concatenation / the gate|up interleave row by row equals concatenating /
                 # interleaving the per-Linear codes and scales; after pack_weights(free_originals=True) only the packs are left
-                qkv = cat([q8(a.q_proj.weight), q8(a.k_proj.weight), q8(a.v_proj.weight)]) if a.q_proj.weight.numel() else q8(d["w_qkv"])
+                qkv = cat([quant(a.q_proj.weight), quant(a.k_proj.weight), quant(a.v_proj.weight)]) if a.q_proj.weight.numel() else quant(d["w_qkv"])
                 if m.gate_proj.weight.numel():
-                    g, u = q8(m.gate_proj.weight), q8(m.up_proj.weight)
-                    gu = ops.Fp8Weight(interleave_gate_up(g.codes, u.codes), interleave_gate_up(g.scales[:, None], u.scales[:, None]).view(-1))
+                    g, u = quant(m.gate_proj.weight), quant(m.up_proj.weight)
+                    if mx:
+                        gu = ops.Mxfp4Weight(interleave_gate_up(g.codes, u.codes), interleave_gate_up(g.scales, u.scales), g.K)
+                    else:
+                        gu = ops.Fp8Weight(interleave_gate_up(g.codes, u.codes), interleave_gate_up(g.scales[:, None], u.scales[:, None]).view(-1))
                 else:
-                    gu = q8(d["w_gu"])
-                llama.append(dict(w_qkv=qkv, w_o=q8(d["w_o"]), w_gu=gu, w_down=q8(d["w_down"]), ln1=d["ln1"], ln2=d["ln2"]))
-            lm_head = q8(self.lm_head.weight)
+                    gu = quant(d["w_gu"])
+                llama.append(dict(w_qkv=qkv, w_o=quant(d["w_o"]), w_gu=gu, w_down=quant(d["w_down"]), ln1=d["ln1"], ln2=d["ln2"]))
+            lm_head = quant(self.lm_head.weight)
             # release the bf16 LLaMA weights and every copy derived from them (packs, tile-major copies, training-path buffers)
             for d in pk["llama"]:
                 for k in ("w_qkv", "w_o", "w_gu", "w_down"):
@@ -659,7 +676,7 @@ class UllavaCoreForCausalLM(nn.Module):
                 mod.weight.data = torch.empty(0, device=dev, dtype=BF16)
                 mod.weight.requires_grad_(False)
             new = {k: v for k, v in pk.items() if k not in ("llama", "_c_llama")}
-            new.update(llama=llama, lm_head=lm_head, freed=True, fp8=True)
+            new.update(llama=llama, lm_head=lm_head, freed=True, fp8=not mx, mxfp4=mx)
             self._packed = None
             pk.clear()
             self._packed = new
@@ -1103,7 +1120,8 @@ class UllavaCoreForCausalLM(nn.Module):
         all_h = []
         I = cfg.intermediate_size
         coarse = None
-        w8 = pk.get("fp8", False)            # quantize_weights(): the Linear weights are ops.Fp8Weight (ops.linear & co. dispatch on them)
+        w4 = pk.get("mxfp4", False)          # quantize_weights(): the Linear weights are ops.Fp8Weight / ops.Mxfp4Weight (ops.linear & co.
+        wq = pk.get("fp8", False) or w4      # dispatch on them)
         kv8 = cache is not None and cache.kv_dtype is not None
         if kv8 and x.dtype != BF16:
             _check_kv_dtype(cache.kv_dtype, x.dtype)
@@ -1114,14 +1132,15 @@ class UllavaCoreForCausalLM(nn.Module):
         if ops.coarse_ok() and pk["llama"]:
             if fuse_append and I % 8 == 0 and (kv8_fewq or not kv8):
                 coarse = "decode"
-            elif fuse_rope and cache is None and T > 16 and 16 < S <= 1024 and I % 64 == 0 and not w8:
-                coarse = "prefill"           # (an fp8 model's prefill takes the per-op path: dequantize + GEMM per Linear)
+            elif fuse_rope and cache is None and T > 16 and 16 < S <= 1024 and I % 64 == 0 and not wq:
+                coarse = "prefill"           # (a quantized model's prefill takes the per-op path: dequantize + GEMM per Linear)
         if coarse is not None:
             # one C call for the whole layer stack (csrc/layers.hip): the same launches as the loop below, bit-identical results
             stack = pk.get("_c_llama")
-            if stack is None and w8:
-                stack = pk["_c_llama"] = ops.LayerStack(_lib.LlamaLayerW8, [dict(ln1=w["ln1"], ln2=w["ln2"], qkv=w["w_qkv"], o=w["w_o"], gu=w["w_gu"],
-                                                                                  down=w["w_down"]) for w in pk["llama"]])
+            if stack is None and wq:
+                kind = _lib.LlamaLayerW4 if w4 else _lib.LlamaLayerW8
+                stack = pk["_c_llama"] = ops.LayerStack(kind, [dict(ln1=w["ln1"], ln2=w["ln2"], qkv=w["w_qkv"], o=w["w_o"], gu=w["w_gu"],
+                                                                    down=w["w_down"]) for w in pk["llama"]])
             elif stack is None:
                 stack = pk["_c_llama"] = ops.LayerStack(_lib.LlamaLayer, [dict(ln1=w["ln1"], ln2=w["ln2"], qkv=(w["w_qkv"], None), o=(w["w_o"], None),
                                                                                 gu=(w["w_gu"], None), down=(w["w_down"], None)) for w in pk["llama"]])

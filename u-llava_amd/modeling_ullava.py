@@ -68,7 +68,8 @@ class UllavaForCausalLM(nn.Module):
         return self.llm.weight_quantization
 
     def quantize_weights(self, fmt: str = "fp8_e4m3"):
-        """FP8 weight-only inference for the language model (UllavaCoreForCausalLM.quantize_weights); SAM and the heads keep their dtype."""
+        """FP8 ("fp8_e4m3") or MXFP4 ("mxfp4") weight-only inference for the language model (UllavaCoreForCausalLM.quantize_weights); SAM and
+        the heads keep their dtype."""
         self.llm.quantize_weights(fmt)
         return self
 

@@ -188,33 +188,151 @@ def dequantize_fp8(q: Fp8Weight, tiled: bool = False, out: Optional[torch.Tensor
     return out[:rows * K].view(rows // 256, K // 64, 256, 64) if tiled else out[:N * K].view(N, K)
 
 
-_W8_SCRATCH = {}     # (device, stream) -> the bf16 buffer prefill-shape fp8 Linears dequantize into (reused in stream order)
+# ---- MXFP4 weight-only storage (UllavaCoreForCausalLM.quantize_weights("mxfp4")) -------------------------------------------------------
+_MX_PERM = {}        # (K, device) -> (code byte index, scale byte index): resident position of every standard-layout byte of a row
 
 
-def _w8_scratch(device: torch.device, stream_id: int, numel: int) -> torch.Tensor:
+def _mx_perm(K: int, device):
+    """Index tensors of the resident layout (include/ullava_hip.h): resident[:, idx] = standard.  A chunk is 8 elements (4 code bytes), a
+    superblock 256 chunks; inside whole superblock b chunk b * 256 + g * 64 + l sits at byte b * 1024 + l * 16 + g * 4, and the scale of block
+    b * 64 + g * 16 + j at byte b * 64 + j * 4 + g; the rest of the row keeps the standard order."""
+    key = (K, str(device))
+    e = _MX_PERM.get(key)
+    if e is None:
+        nsb = K // 2048
+        c = torch.arange(K // 8, device=device)
+        cpos = torch.where(c < nsb * 256, (c >> 8) * 1024 + (c & 63) * 16 + ((c >> 6) & 3) * 4, c * 4)
+        cidx = (cpos[:, None] + torch.arange(4, device=device)).reshape(-1)
+        b = torch.arange(K // 32, device=device)
+        sidx = torch.where(b < nsb * 64, (b >> 6) * 64 + (b & 15) * 4 + ((b >> 4) & 3), b)
+        e = _MX_PERM[key] = (cidx, sidx)
+    return e
+
+
+class Mxfp4Weight:
+    """A Linear weight [N, K] (K % 32 == 0) in the OCP microscaling format MXFP4: e2m1 codes, two per byte, plus one E8M0 scale byte per row
+    and block of 32 consecutive K elements; dequant = e2m1 * 2^(scale - 127), exactly a bf16 value.  The object holds the RESIDENT layout
+    the decode kernels read (codes uint8 [N, K / 2], scales uint8 [N, K / 32 rounded up to a multiple of 4]): the standard layout
+    (`to_standard()`: codes [N, K / 2] with element 2i in the low nibble -- torch.float4_e2m1fn_x2 -- and scales [N, K / 32]) with the bytes
+    of each row permuted, see include/ullava_hip.h.  `linear` / `linear_qkv_rope` / `linear_qkv_rope_append` take it in place of a bf16
+    weight and compute exactly what they compute on the dequantized bf16 weight.  Immutable once built."""
+    __slots__ = ("codes", "scales", "K")
+
+    def __init__(self, codes: torch.Tensor, scales: torch.Tensor, K: int):
+        if (codes.dtype != torch.uint8 or codes.dim() != 2 or K % 32 or codes.shape[1] != K // 2 or not codes.is_contiguous() or
+                scales.dtype != torch.uint8 or scales.shape != (codes.shape[0], self.scale_pitch(K)) or not scales.is_contiguous()):
+            raise RuntimeError("u-llava_amd.Mxfp4Weight: codes uint8 [N, K / 2], scales uint8 [N, K / 32 rounded up to 4], contiguous, K % 32 == 0")
+        self.codes, self.scales, self.K = codes, scales, K
+
+    @staticmethod
+    def scale_pitch(K: int) -> int:
+        return -(-(K // 32) // 4) * 4
+
+    @property
+    def shape(self):
+        return torch.Size((self.codes.shape[0], self.K))
+
+    @property
+    def device(self):
+        return self.codes.device
+
+    def nbytes(self) -> int:
+        return self.codes.numel() + self.scales.numel()
+
+    def to_standard(self):
+        """(codes uint8 [N, K / 2], scales uint8 [N, K / 32]) in the standard layout."""
+        cidx, sidx = _mx_perm(self.K, self.device)
+        return self.codes[:, cidx], self.scales[:, sidx]
+
+    @classmethod
+    def from_standard(cls, codes: torch.Tensor, scales: torch.Tensor) -> "Mxfp4Weight":
+        if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2:
+            raise RuntimeError("u-llava_amd.Mxfp4Weight.from_standard: codes uint8 [N, K / 2], scales uint8 [N, K / 32]")
+        N, K = codes.shape[0], codes.shape[1] * 2
+        if K % 32 or scales.shape != (N, K // 32):
+            raise RuntimeError("u-llava_amd.Mxfp4Weight.from_standard: codes uint8 [N, K / 2], scales uint8 [N, K / 32], K % 32 == 0")
+        cidx, sidx = _mx_perm(K, codes.device)
+        rc = torch.empty_like(codes, memory_format=torch.contiguous_format)
+        rc[:, cidx] = codes
+        rs = torch.zeros(N, cls.scale_pitch(K), device=scales.device, dtype=torch.uint8)
+        rs[:, sidx] = scales
+        return cls(rc, rs, K)
+
+
+def quantize_mxfp4(w: torch.Tensor) -> Mxfp4Weight:
+    """MXFP4 quantization of a bf16 weight [N, K], K % 32 == 0, on the GPU (ull_quantize_rows_mxfp4_bf16): per row and block of 32 K elements
+    the scale is 2^s with s the smallest integer such that amax * 2^-s <= 6 (0 for an all-zero block), clamped to [-125, 126]; an element is
+    e2m1(w * 2^-s) rounded to nearest, ties to the even code (at s = 126 saturating at the code of 3: 4 * 2^126 is no float).  Weight-only round-to-nearest, no calibration."""
+    if w.dim() != 2:
+        raise RuntimeError("u-llava_amd.quantize_mxfp4: w must be 2-D")
+    N, K = w.shape
+    if K % 32:
+        raise NotImplementedError(f"u-llava_amd.quantize_mxfp4: K must be a multiple of 32 (one scale per 32 elements), got {K}")
+    _chk(w, "w", BF16)
+    codes = torch.empty(N, K // 2, device=w.device, dtype=torch.uint8)
+    lds = Mxfp4Weight.scale_pitch(K)
+    scales = (torch.empty if lds == K // 32 else torch.zeros)(N, lds, device=w.device, dtype=torch.uint8)
+    _lib.call("ull_quantize_rows_mxfp4_bf16", _p(w), w.stride(0), N, K, _p(codes), K // 2, _p(scales), lds, 1, _stream())
+    return Mxfp4Weight(codes, scales, K)
+
+
+def dequantize_mxfp4(q: Mxfp4Weight, tiled: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dequant(q) as bf16: [N, K] row-major, or (tiled) the ULL_EPI_W_TILED layout `tile_major` produces."""
+    N, K = q.shape
+    rows = -(-N // 256) * 256 if tiled else N
+    if out is None:
+        out = torch.empty(rows * K, device=q.device, dtype=BF16)
+    elif out.dtype != BF16 or out.numel() < rows * K or not out.is_contiguous():
+        raise RuntimeError("u-llava_amd.dequantize_mxfp4: `out` must be a contiguous bf16 buffer of at least the result's size")
+    _lib.call("ull_dequantize_rows_mxfp4_bf16", _p(q.codes), q.codes.stride(0), _p(q.scales), q.scales.stride(0), N, K, _p(out), int(tiled), 1,
+              _stream())
+    return out[:rows * K].view(rows // 256, K // 64, 256, 64) if tiled else out[:N * K].view(N, K)
+
+
+QuantWeight = (Fp8Weight, Mxfp4Weight)      # the quantized weight types the Linear dispatch rule takes beside a 16-bit tensor
+
+_WQ_SCRATCH = {}     # (device, stream) -> the bf16 buffer prefill-shape fp8 / mxfp4 Linears dequantize into (reused in stream order)
+
+
+def _wq_scratch(device: torch.device, stream_id: int, numel: int) -> torch.Tensor:
     key = (device.index, stream_id)
-    buf = _W8_SCRATCH.get(key)
+    buf = _WQ_SCRATCH.get(key)
     if buf is None or buf.numel() < numel:
         with torch.cuda.device(device):
-            buf = _W8_SCRATCH[key] = torch.empty(numel, device=device, dtype=BF16)
+            buf = _WQ_SCRATCH[key] = torch.empty(numel, device=device, dtype=BF16)
     return buf
 
 
-def _w8_dequant_for_gemm(q: Fp8Weight, M: int):
+def _wq_dequant_for_gemm(q, M: int):
     """(row-major view, tile-major view or None) of dequant(q) in the stream's scratch, laid out as the bf16 GEMM would read the
     weight at this M: tile-major where a bf16 weight has its tile-major copy (register_tiled: K % 64 == 0) and the 256 x 256 path takes it."""
     N, K = q.shape
     tiled = _big(M, N, K) and K % 64 == 0
-    buf = _w8_scratch(q.device, _stream(), (-(-N // 256) * 256 if tiled else N) * K)
-    wd = dequantize_fp8(q, tiled=tiled, out=buf)
+    buf = _wq_scratch(q.device, _stream(), (-(-N // 256) * 256 if tiled else N) * K)
+    wd = (dequantize_mxfp4 if isinstance(q, Mxfp4Weight) else dequantize_fp8)(q, tiled=tiled, out=buf)
     if tiled:
         return buf[:N * K].view(N, K), wd          # (the row-major view only carries the shape: the GEMM reads the tile-major copy)
     return wd, None
 
 
+def _fmt_name(w) -> str:
+    return "mxfp4" if isinstance(w, Mxfp4Weight) else "fp8"
+
+
+def _route_pitch(w) -> int:
+    """the row pitch `_linear_route` sees: elements for a 16-bit weight, code bytes (= elements) for an Fp8Weight, K for an Mxfp4Weight
+    (its rows are always whole)."""
+    if isinstance(w, Mxfp4Weight):
+        return w.K
+    return (w.codes if isinstance(w, Fp8Weight) else w).stride(0)
+
+
 def _weight_args(w):
     """(entry suffix, weight arguments) of a decode-shape entry (skinny GEMM, GEMV, GEMV + RMSNorm, q|k|v + RoPE + cache append): a 16-bit
-    weight passes (pointer, row pitch), an Fp8Weight (codes, row pitch, scales) to the *_w8_bf16 form."""
+    weight passes (pointer, row pitch), an Fp8Weight (codes, row pitch, scales) to the *_w8_bf16 form, an Mxfp4Weight (codes, row pitch,
+    scales, row pitch) to the *_w4_bf16 form."""
+    if isinstance(w, Mxfp4Weight):
+        return "w4_bf16", (w.codes.data_ptr(), w.codes.stride(0), w.scales.data_ptr(), w.scales.stride(0))
     if isinstance(w, Fp8Weight):
         return "w8_bf16", (w.codes.data_ptr(), w.codes.stride(0), w.scales.data_ptr())
     return _SFX[w.dtype], (w.data_ptr(), w.stride(0))
@@ -325,12 +443,12 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     rms_w/rms_eps: apply LlamaRMSNorm to x first (fused into the GEMV prologue at decode shapes, a separate kernel otherwise).
     tune: ULL_GEMM_TUNE_* bits (tools/ only).  bias_after_rounding: y = round(round(x @ w.T) + bias) -- what at::linear computes
     for a NON-contiguous 3-D input (matmul + add_ instead of the fused addmm).
-    w may be an `Fp8Weight` (bf16 x only): the same result as on its dequantized bf16 weight, bit for bit."""
-    w8 = isinstance(w, Fp8Weight)
-    if w8 and x.dtype != BF16:
-        raise RuntimeError(f"u-llava_amd.linear: fp8 weights need bf16 activations, got {x.dtype}")
+    w may be an `Fp8Weight` or an `Mxfp4Weight` (bf16 x only): the same result as on its dequantized bf16 weight, bit for bit."""
+    wq = isinstance(w, QuantWeight)
+    if wq and x.dtype != BF16:
+        raise RuntimeError(f"u-llava_amd.linear: {_fmt_name(w)} weights need bf16 activations, got {x.dtype}")
     _chk(x, "x")
-    if not w8:
+    if not wq:
         _chk(w, "w", x.dtype)
     M, ldx = _rows(x)
     N, K = w.shape
@@ -343,10 +461,10 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         route, rms_first = "f32", True
         out_f32 = bias_after_rounding = False
     else:
-        route, rms_first = _linear_route(M, N, K, (w.codes if w8 else w).stride(0), tune)
-        if w8 and route == "gemm":
+        route, rms_first = _linear_route(M, N, K, _route_pitch(w), tune)
+        if wq and route == "gemm":
             # prefill shapes: dequantize into the stream's scratch, then the bf16 flow on dequant(w)
-            w, wt = _w8_dequant_for_gemm(w, M)
+            w, wt = _wq_dequant_for_gemm(w, M)
             route, rms_first = _linear_route(M, N, K, w.stride(0), tune)
     if rms_w is not None and rms_first:
         x = rmsnorm(x, rms_w, rms_eps)
@@ -414,12 +532,12 @@ GEMM_TUNE_WAVES8, GEMM_TUNE_WAVES4 = 1 << 21, 1 << 22     # ULL_GEMM_TUNE_*: for
 def linear_qkv_rope(x: torch.Tensor, w: torch.Tensor, rope_cos: torch.Tensor, rope_sin: torch.Tensor, rope_cols: int, head_dim: int,
                     out: Optional[torch.Tensor] = None, tune: int = 0) -> torch.Tensor:
     """Fused q|k|v projection + RoPE on the first `rope_cols` output columns (q and k heads), head_dim 128, K % 64 == 0, M > 4.
-    Bit-identical to linear() followed by rope_inplace().  w may be an `Fp8Weight` (dequantized into a scratch first)."""
+    Bit-identical to linear() followed by rope_inplace().  w may be an `Fp8Weight` / `Mxfp4Weight` (dequantized into a scratch first)."""
     wt = None
-    if isinstance(w, Fp8Weight):
+    if isinstance(w, QuantWeight):
         if x.dtype != BF16:
-            raise RuntimeError(f"u-llava_amd.linear_qkv_rope: fp8 weights need bf16 activations, got {x.dtype}")
-        w, wt = _w8_dequant_for_gemm(w, _rows(x)[0])
+            raise RuntimeError(f"u-llava_amd.linear_qkv_rope: {_fmt_name(w)} weights need bf16 activations, got {x.dtype}")
+        w, wt = _wq_dequant_for_gemm(w, _rows(x)[0])
     _chk(x, "x"); _chk(w, "w", x.dtype); _chk(rope_cos, "rope_cos", x.dtype); _chk(rope_sin, "rope_sin", x.dtype)
     M, ldx = _rows(x)
     N, K = w.shape
@@ -622,11 +740,11 @@ def linear_qkv_rope_append(x: torch.Tensor, w_qkv: torch.Tensor, rope_cos: torch
                            rms_eps: float = 0.0) -> torch.Tensor:
     """decode step (B * S <= 4 tokens): q | k | v projection of x (optionally RMS-normalised first) with RoPE and the KV-cache append in the
     GEMV's epilogue.  Returns the rotated queries [B * S, H * hd]; the rotated keys / the values land in the caches.  Same bits as
-    `linear(x, w_qkv, rms_w=...)` followed by `rope_append`.  w_qkv may be an `Fp8Weight` (bf16 only)."""
-    if not isinstance(w_qkv, Fp8Weight):
+    `linear(x, w_qkv, rms_w=...)` followed by `rope_append`.  w_qkv may be an `Fp8Weight` / `Mxfp4Weight` (bf16 only)."""
+    if not isinstance(w_qkv, QuantWeight):
         _chk(w_qkv, "w_qkv", x.dtype)
     elif x.dtype != BF16:
-        raise RuntimeError(f"u-llava_amd.linear_qkv_rope_append: fp8 weights need bf16 activations, got {x.dtype}")
+        raise RuntimeError(f"u-llava_amd.linear_qkv_rope_append: {_fmt_name(w_qkv)} weights need bf16 activations, got {x.dtype}")
     _chk(x, "x"); _chk(rope_cos, "rope_cos", x.dtype); _chk(rope_sin, "rope_sin", x.dtype)
     _chk(k_cache, "k_cache", x.dtype); _chk(vt_cache, "vt_cache", x.dtype)
     T, K = x.shape
@@ -1260,8 +1378,9 @@ def coarse_ok() -> bool:
 
 
 class LayerStack:
-    """`kind`: _lib.LlamaLayer / LlamaLayerW8 / ClipLayer / SamBlock; `layers`: one dict per layer, field name -> tensor (pointer fields) or
-    (weight, bias-or-None) (ull_linear fields) or Fp8Weight (ull_linear_w8 fields) or int (plain fields)."""
+    """`kind`: _lib.LlamaLayer / LlamaLayerW8 / LlamaLayerW4 / ClipLayer / SamBlock; `layers`: one dict per layer, field name -> tensor (pointer
+    fields) or (weight, bias-or-None) (ull_linear fields) or Fp8Weight (ull_linear_w8 fields) or Mxfp4Weight (ull_linear_w4 fields) or int
+    (plain fields)."""
 
     def __init__(self, kind, layers):
         self.kind, self.layers = kind, layers
@@ -1283,7 +1402,10 @@ class LayerStack:
             s = self.arr[i]
             for n, t in self.kind._fields_:
                 v = d[n]
-                if t is _lib.LinearW8:
+                if t is _lib.LinearW4:
+                    # an Mxfp4Weight: immutable like an Fp8Weight
+                    setattr(s, n, _lib.LinearW4(v.codes.data_ptr(), v.scales.data_ptr(), v.shape[0], v.shape[1], v.codes.stride(0), v.scales.stride(0)))
+                elif t is _lib.LinearW8:
                     # an Fp8Weight: immutable, so nothing of it enters the fingerprint (and no version counter is read)
                     setattr(s, n, _lib.LinearW8(v.codes.data_ptr(), v.scales.data_ptr(), v.shape[0], v.shape[1], v.codes.stride(0)))
                 elif t is _lib.Linear:
@@ -1333,10 +1455,11 @@ def llama_prefill_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos,
 def llama_decode_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos, rope_sin, key_mask, k_ptrs, vt_ptrs, B: int, S: int, H: int, hd: int,
                         I: int, smax: int, past: int, eps: float, kv8=None):
     """One generation step through all layers (T = B*S <= 4).  k_ptrs / vt_ptrs: ctypes void* arrays of the per-layer caches.  A stack of
-    _lib.LlamaLayerW8 (fp8 weights, bf16 activations) goes to ull_llama_decode_layers_w8_bf16.  kv8 = (k8, vt8, k_scale, vt_scale pointer
+    _lib.LlamaLayerW8 (fp8 weights, bf16 activations) goes to ull_llama_decode_layers_w8_bf16, one of _lib.LlamaLayerW4 (mxfp4 weights) to
+    ull_llama_decode_layers_w4_bf16.  kv8 = (k8, vt8, k_scale, vt_scale pointer
     arrays, k_stage, vt_stage) of an fp8 cache (KVCache.c_ptrs): the *_kv8_bf16 entries, k_ptrs / vt_ptrs unused."""
-    w8 = stack.kind is _lib.LlamaLayerW8
-    _chk(x_in, "x_in", BF16 if (w8 or kv8 is not None) else None)
+    wq = {_lib.LlamaLayerW8: "w8_", _lib.LlamaLayerW4: "w4_"}.get(stack.kind)       # the quantized-weight forms of the entry
+    _chk(x_in, "x_in", BF16 if (wq or kv8 is not None) else None)
     T, D = x_in.shape
     dev, dt = x_in.device, x_in.dtype
     scratch = torch.empty(T * (4 * D + 2 * max(D, I)), device=dev, dtype=dt)
@@ -1345,11 +1468,11 @@ def llama_decode_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos, 
     act = scratch[3 * T * D + T * max(D, I):3 * T * D + T * max(D, I) + T * I]
     if kv8 is not None:
         k8, vt8, ks, vs, k_stage, vt_stage = kv8
-        _lib.call("ull_llama_decode_layers_" + ("w8_kv8_bf16" if w8 else "kv8_bf16"), stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out),
+        _lib.call("ull_llama_decode_layers_" + (wq or "") + "kv8_bf16", stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out),
                   _p(x_mid), _p(xn), _p(q), _p(att), _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k8, vt8, ks, vs, _p(k_stage), _p(vt_stage),
                   B, S, H, hd, I, smax, past, float(eps), _zeros(dev).data_ptr(), _stream())
         return
-    _lib.call("ull_llama_decode_layers_" + ("w8_bf16" if w8 else _SFX[dt]), stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid),
+    _lib.call("ull_llama_decode_layers_" + (wq + "bf16" if wq else _SFX[dt]), stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid),
               _p(xn), _p(q), _p(att), _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k_ptrs, vt_ptrs, B, S, H, hd, I, smax, past, float(eps),
               _zeros(dev).data_ptr(), _stream())
 
