@@ -63,6 +63,8 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
+        if x.dtype == torch.float32 and (ctx.relu or (ctx.has_bias and ctx.needs_input_grad[2])):
+            raise RuntimeError("u-llava_amd: the fp32 Linear backward computes dX and dW only (csrc/f32.hip has no bias sum and no ReLU mask)")
         dy = dy.contiguous()
         g = ops.relu_mask(y, dy) if ctx.relu else dy                                   # selection (HIP kernel)
         g2, x2 = g.reshape(-1, g.shape[-1]), x.reshape(-1, x.shape[-1])

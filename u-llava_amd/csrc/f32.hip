@@ -7,7 +7,9 @@
 // host layer (u-llava_amd/ops.py) dispatches by tensor dtype alone.  Pure data movement (embedding splice, row gather, window partition)
 // has no fp32 entry: the host hands the 16-bit kernels the same bytes as rows of twice as many 16-bit elements.
 // Not covered (the host never routes fp32 tensors there): the fused / tiled fast paths (ull_gemm_qkv_rope, ull_patchify, ull_sam_window_attention,
-// the fused mask-decoder kernels, the coarse layer-stack entries), rel_mode 2 of the attention, and the backward kernels.
+// the fused mask-decoder kernels, the coarse layer-stack entries), rel_mode 2 of the attention, and the backward kernels -- except
+// ull_transpose2d_f32, which with ull_gemm_f32 makes the backward of a plain fp32 Linear (autograd_ops._Linear: dX and dW; no fp32 bias
+// sum or ReLU mask).
 #include "ull_common.h"
 
 #define ULL_EPI_BIAS 1
@@ -504,6 +506,22 @@ __global__ __launch_bounds__(256) void shifted_ce_f32_kernel(const float* __rest
     }
 }
 
+// y[c][r] = x[r][c]: 64 x 64 tiles through the LDS, any R / C / row pitches (the transposed operands of an fp32 Linear backward:
+// dX = dY W and dW = dY^T X are ull_gemm_f32 on W^T, dY^T and X^T)
+__global__ __launch_bounds__(256) void transpose2d_f32_kernel(const float* __restrict__ x, long ldx, float* __restrict__ y, long ldy, int R, int C) {
+    __shared__ float t[64][65];                             // [c][r]
+    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
+        const int r = i >> 6, c = i & 63;
+        if (r0 + r < R && c0 + c < C) t[c][r] = x[(long)(r0 + r) * ldx + c0 + c];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
+        const int c = i >> 6, r = i & 63;
+        if (r0 + r < R && c0 + c < C) y[(long)(c0 + c) * ldy + r0 + r] = t[c][r];
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -549,6 +567,14 @@ extern "C" int ull_transpose_v_f32(const void* v, int64_t v_bs, int64_t v_ss, vo
     const long total = B * H * hd * pitch;
     hipLaunchKernelGGL(transpose_v_f32_kernel, dim3(grid_for(total)), dim3(256), 0, ST, (const float*)v, (long)v_bs, (long)v_ss, (float*)vt, (int)S, (int)H,
                        (int)hd, (int)pitch, total);
+    return ull_check_launch();
+}
+
+extern "C" int ull_transpose2d_f32(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t R, int64_t C, void* stream) {
+    if (!x || !y || R <= 0 || C <= 0 || ldx < C || ldy < R) return ULL_ERR_ARG;
+    if (R > 65535 * 64 || C > (1 << 30)) return ULL_ERR_SHAPE;          // grid y = ceil(R / 64) <= 65535
+    hipLaunchKernelGGL(transpose2d_f32_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)((R + 63) / 64)), dim3(256), 0, ST, (const float*)x, (long)ldx,
+                       (float*)y, (long)ldy, (int)R, (int)C);
     return ull_check_launch();
 }
 

@@ -80,9 +80,12 @@ def _rows(t: torch.Tensor):
         return 1, t.shape[0]
     if t.dim() == 2:
         return t.shape[0], t.stride(0)
-    if not t.is_contiguous():
-        raise RuntimeError("u-llava_amd: >2-D operands must be contiguous")
-    return t.numel() // t.shape[-1], t.shape[-1]
+    if t.is_contiguous():
+        return t.numel() // t.shape[-1], t.shape[-1]
+    # a [..., :D] view of a wider buffer (a [B, S, D] slice of packed rows): the leading dims still fold onto ONE row stride
+    if t.stride(-1) != 1 or any(t.stride(i) != t.shape[i + 1] * t.stride(i + 1) for i in range(t.dim() - 2)):
+        raise RuntimeError("u-llava_amd: >2-D operands must be contiguous, or rows of one common pitch")
+    return t.numel() // t.shape[-1], t.stride(-2)
 
 
 EPI_W_TILED = 64
