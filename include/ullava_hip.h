@@ -80,6 +80,12 @@ int ull_rope_table_bf16(const void* positions, const void* inv_freq, int64_t tok
 /* Bytes of stream-K workspace that cover every shape ull_gemm_bf16 may split (256 slabs of 256 x 256 fp32 = 64 MiB). */
 int64_t ull_gemm_streamk_ws_bytes(void);
 
+/* Weight formats of the decode-shape Linear entries (*_wq_bf16) and of ull_linear: the model's 16-bit elements, or one of the two weight-only
+ * quantized formats described below (bf16 build only). */
+#define ULL_WF_ELEM 0
+#define ULL_WF_FP8 1
+#define ULL_WF_MXFP4 2
+
 /* The same Linear for decode steps (M <= 4 rows, K % 8 == 0): a pure weight stream, one wave per output feature, no LDS/MFMA.
  * Same flags, layouts and rounding points as ull_gemm_bf16.  Reached from generate() after the prefill
  * (models/ullava_core.py:357-395 keeps only the last token once a KV cache exists). */
@@ -109,25 +115,13 @@ int ull_gemv_qkv_rope_append_bf16(const void* X, int64_t ldx, const void* norm_w
  * UllavaCoreForCausalLM.quantize_weights("fp8_e4m3") stores every LLaMA Linear and lm_head as e4m3fn codes [N, K] (row pitch ldq bytes) plus
  * one fp32 scale 2^s per row: s is the smallest integer with amax|w_row| * 2^-s <= 448 (all-zero row: s = 0), q = e4m3fn(w * 2^-s) rounded to
  * nearest even.  dequant(q) = float(q) * 2^s is exactly a bf16 value, and every entry below computes exactly what the bf16 entry it replaces
- * computes on the dequantized weight (same FMA / MFMA operands in the same order): bit-identical outputs, half the weight bytes. */
+ * computes on the dequantized weight (same FMA / MFMA operands in the same order): bit-identical outputs, half the weight bytes.  The decode
+ * entries are the *_wq_bf16 ones after the mxfp4 section. */
 /* Quantize W [N, K] (bf16, row pitch ldw) into codes [N, K] (pitch K bytes) + scales [N]; matches torch's CPU cast bit for bit.  K % 8 == 0. */
 int ull_quantize_rows_fp8_bf16(const void* W, int64_t ldw, int64_t N, int64_t K, void* codes, void* scales, void* stream);
 /* dequant(codes) into bf16: tiled = 0: row-major [N, K]; tiled = 1: the ULL_EPI_W_TILED layout of ull_gemm_bf16 (K % 64 == 0, ceil(N / 256) * 256
  * rows, padding rows zero).  Replaces the bf16 weight (or its tile-major copy) of a prefill-shape ull_gemm_bf16 / ull_gemm_qkv_rope_bf16 call. */
 int ull_dequantize_rows_fp8_bf16(const void* codes, int64_t ldq, const void* scales, int64_t N, int64_t K, void* out, int tiled, void* stream);
-/* Replaces ull_gemv_bf16 on an fp8 weight. */
-int ull_gemv_w8_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc, const void* bias, const void* R,
-                     int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
-/* Replaces ull_gemv_rmsnorm_bf16 on an fp8 weight. */
-int ull_gemv_rmsnorm_w8_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales, void* C,
-                             int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
-/* Replaces ull_gemv_qkv_rope_append_bf16 on an fp8 q|k|v weight. */
-int ull_gemv_qkv_rope_append_w8_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales,
-                                     void* Q_out, int64_t ldq_out, const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int64_t B,
-                                     int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax, int64_t past, void* stream);
-/* Replaces ull_gemm_skinny_bf16 on an fp8 weight. */
-int ull_gemm_skinny_w8_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc, const void* bias,
-                            const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
 
 /* ---- MXFP4 weight-only decode (bf16 build only: no *_f16 twins) ---------------------------------------------------------------------
  * UllavaCoreForCausalLM.quantize_weights("mxfp4") stores every LLaMA Linear and lm_head in the OCP microscaling format MXFP4 (bf16 models
@@ -155,20 +149,23 @@ int ull_quantize_rows_mxfp4_bf16(const void* W, int64_t ldw, int64_t N, int64_t 
  * rows, padding rows zero).  Replaces the bf16 weight (or its tile-major copy) of a prefill-shape ull_gemm_bf16 / ull_gemm_qkv_rope_bf16 call. */
 int ull_dequantize_rows_mxfp4_bf16(const void* codes, int64_t ldq, const void* scales, int64_t lds, int64_t N, int64_t K, void* out, int tiled,
                                    int resident, void* stream);
-/* Replaces ull_gemv_bf16 on an mxfp4 weight (resident layout, here and below). */
-int ull_gemv_w4_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C, int64_t ldc, const void* bias,
-                     const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
-/* Replaces ull_gemv_rmsnorm_bf16 on an mxfp4 weight. */
-int ull_gemv_rmsnorm_w4_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales, int64_t lds,
-                             void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
-                             void* stream);
-/* Replaces ull_gemv_qkv_rope_append_bf16 on an mxfp4 q|k|v weight. */
-int ull_gemv_qkv_rope_append_w4_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales,
-                                     int64_t lds, void* Q_out, int64_t ldq_out, const void* cos_tab, const void* sin_tab, void* k_cache,
-                                     void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax, int64_t past, void* stream);
-/* Replaces ull_gemm_skinny_bf16 on an mxfp4 weight. */
-int ull_gemm_skinny_w4_bf16(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C, int64_t ldc,
+
+/* ---- Decode-shape Linear on a quantized weight (bf16 build only: no *_f16 twins) -----------------------------------------------------
+ * The weight format is an argument: ULL_WF_FP8 (Q = e4m3 codes, row pitch ldq bytes; scales = fp32 [N]; lds ignored) or ULL_WF_MXFP4 (Q = codes
+ * in the resident layout, ldq a multiple of 16; scales = E8M0 bytes, row pitch lds, a multiple of 4; K % 32 == 0 -- ULL_ERR_SHAPE otherwise).
+ * ULL_WF_ELEM reads Q as the bf16 weight of the plain entry (scales / lds ignored); any other wfmt, or null scales: ULL_ERR_ARG.  Each entry
+ * has the contract of the bf16 entry named in it, with (W, ldw) replaced by (wfmt, Q, ldq, scales, lds), and its bits on dequant(Q). */
+int ull_gemv_wq_bf16(const void* X, int64_t ldx, int wfmt, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C, int64_t ldc,
+                     const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+int ull_gemm_skinny_wq_bf16(const void* X, int64_t ldx, int wfmt, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C, int64_t ldc,
                             const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+int ull_gemv_rmsnorm_wq_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, int wfmt, const void* Q, int64_t ldq, const void* scales,
+                             int64_t lds, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K,
+                             int flags, void* stream);
+int ull_gemv_qkv_rope_append_wq_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, int wfmt, const void* Q, int64_t ldq,
+                                     const void* scales, int64_t lds, void* Q_out, int64_t ldq_out, const void* cos_tab, const void* sin_tab,
+                                     void* k_cache, void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax, int64_t past,
+                                     void* stream);
 
 /* ---- FP8 (e4m3) KV cache (bf16 build only) ------------------------------------------------------------------------------------------
  * KVCache(kv_dtype="fp8_e4m3") keeps, per layer, K codes [B, H, smax, hd] and V^T codes [B, H, hd, smax] (the key-permuted slot order of
@@ -531,6 +528,9 @@ typedef struct ull_linear {
     const void* w_tiled; /* its ULL_EPI_W_TILED copy for the 256 x 256 kernel, or NULL */
     const void* bias;    /* [n] or NULL */
     int64_t n, k, ldw;
+    int format;          /* ULL_WF_*.  A quantized weight (decode-layers entries of the bf16 build only; ULL_ERR_ARG elsewhere): w = codes, ldw = code */
+    const void* scales;  /* row pitch in bytes, scales / lds as for the *_wq_bf16 entries, w_tiled = bias = NULL */
+    int64_t lds;
 } ull_linear;
 typedef struct ull_llama_layer { /* hf LlamaDecoderLayer: input_layernorm, q|k|v (one [3D, D] matrix), o_proj, post_attention_layernorm, gate|up */
     const void* ln1;             /* (interleaved in 16-row groups, ULL_EPI_SWIGLU), down_proj */
@@ -564,46 +564,17 @@ int ull_llama_prefill_layers_bf16(const ull_llama_layer* layers, int64_t n_layer
 /* The same loop for generation steps (T = B * S <= 4 new tokens on a filled KV cache; models/ullava_core.py:357-395): per layer
  * ull_gemv_qkv_rope_append_bf16 -> split-key attention over the cache -> o_proj -> RMSNorm + gate|up + SwiGLU -> down_proj, the GEMV / skinny-GEMM
  * choice per Linear as in the per-op path.  k_cache[l] [B, H, smax, hd], vt_cache[l] [B, H, hd, smax] (permuted, see ull_transpose_v_bf16);
- * q [T, D], att [T, D], xn [T, max(D, I)], act [T, I], x_mid [T, D] scratch; rope tables [T, hd / 2] of the step's positions. */
+ * q [T, D], att [T, D], xn [T, max(D, I)], act [T, I], x_mid [T, D] scratch; rope tables [T, hd / 2] of the step's positions.
+ * Every layer is checked before anything is enqueued: qkv [3D, D], o [D, D], gu [2I, D], down [D, I], I % 8 == 0 (ULL_ERR_SHAPE otherwise); null
+ * pointers, an unknown format, a quantized Linear without scales or (mxfp4) off its pitch rules, any quantized Linear in the f16 build:
+ * ULL_ERR_ARG.  The Linears of a layer may be quantized (the same launches through the *_wq_bf16 entries); a quantized model's prefill takes the
+ * per-op path (ull_dequantize_rows_*_bf16 + ull_gemm_bf16). */
 int ull_llama_decode_layers_bf16(const ull_llama_layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
                                  void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
                                  void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax,
                                  int64_t past, float eps, const void* zeros, void* stream);
 
-/* Replaces ull_llama_decode_layers_bf16 on a model quantized to fp8 weights (the same launches through the *_w8_bf16 entries).  Every layer is
- * checked before anything is enqueued: qkv [3D, D], o [D, D], gu [2I, D], down [D, I], I % 8 == 0 (ULL_ERR_SHAPE otherwise; null pointers:
- * ULL_ERR_ARG).  An fp8 model's prefill takes the per-op path (ull_dequantize_rows_fp8_bf16 + ull_gemm_bf16). */
-typedef struct ull_linear_w8 {
-    const void* codes;   /* [n, k] e4m3fn, row pitch ld bytes */
-    const void* scales;  /* [n] fp32 powers of two */
-    int64_t n, k, ld;
-} ull_linear_w8;
-typedef struct ull_llama_layer_w8 {
-    const void* ln1;
-    const void* ln2;
-    ull_linear_w8 qkv, o, gu, down;
-} ull_llama_layer_w8;
-int ull_llama_decode_layers_w8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
-                                    void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
-                                    void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax,
-                                    int64_t past, float eps, const void* zeros, void* stream);
-/* The same on a model quantized to mxfp4 weights (resident layout; the *_w4_bf16 entries).  Same checks before the first launch, plus the row
- * pitches (ld >= k / 2, a multiple of 16; lds >= k / 32, a multiple of 4; k % 32 == 0: ULL_ERR_ARG). */
-typedef struct ull_linear_w4 {
-    const void* codes;   /* [n, k / 2] bytes, row pitch ld */
-    const void* scales;  /* [n, k / 32] E8M0 bytes, row pitch lds */
-    int64_t n, k, ld, lds;
-} ull_linear_w4;
-typedef struct ull_llama_layer_w4 {
-    const void* ln1;
-    const void* ln2;
-    ull_linear_w4 qkv, o, gu, down;
-} ull_llama_layer_w4;
-int ull_llama_decode_layers_w4_bf16(const ull_llama_layer_w4* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
-                                    void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
-                                    void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax,
-                                    int64_t past, float eps, const void* zeros, void* stream);
-/* ull_llama_decode_layers_bf16 / ull_llama_decode_layers_w8_bf16 on an fp8 KV cache (see ull_attention_kv8_bf16): per layer the q|k|v GEMV appends
+/* ull_llama_decode_layers_bf16 on an fp8 KV cache (see ull_attention_kv8_bf16): per layer the q|k|v GEMV appends
  * the step's keys to the shared bf16 staging window (k_stage [B, H, 128, hd], vt_stage [B, H, hd, 128]; pitch 128, first new key at past mod 64)
  * and ull_attention_kv8_bf16 reads the layer's codes / scales (k8, vt8, k_scale, vt_scale: per-layer pointer arrays, cache pitch smax) plus
  * the window, then quantizes the new keys into the layer's cache -- the same launches as the bf16-cache entry.  Every layer is checked before
@@ -612,16 +583,6 @@ int ull_llama_decode_layers_kv8_bf16(const ull_llama_layer* layers, int64_t n_la
                                      void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask, void* const* k8,
                                      void* const* vt8, void* const* k_scale, void* const* vt_scale, void* k_stage, void* vt_stage, int64_t B, int64_t S,
                                      int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream);
-int ull_llama_decode_layers_w8_kv8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
-                                        void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
-                                        void* const* k8, void* const* vt8, void* const* k_scale, void* const* vt_scale, void* k_stage, void* vt_stage,
-                                        int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros,
-                                        void* stream);
-int ull_llama_decode_layers_w4_kv8_bf16(const ull_llama_layer_w4* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn,
-                                        void* q, void* att, void* act, const void* rope_cos, const void* rope_sin, const void* key_mask,
-                                        void* const* k8, void* const* vt8, void* const* k_scale, void* const* vt_scale, void* k_stage, void* vt_stage,
-                                        int64_t B, int64_t S, int64_t H, int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros,
-                                        void* stream);
 
 /* hf CLIPEncoder.forward's layer loop (modeling_clip.py:353-384; models/ullava_core.py:146-158 reads hidden_states[-2], so the caller passes
  * the first 23 layers): h [T = n_img * S, D] is updated in place; h_mid [T, D], y [T, D], qkv [T, 3D], att [T, D], f [T, I] scratch.

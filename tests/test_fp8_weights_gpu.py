@@ -364,22 +364,22 @@ def test_quantized_model_refuses_training_lora_save_and_cast(tmp_path):
         assert torch.equal(fp8(input_ids=ids, attention_mask=mask, images=images).logits, twin(input_ids=ids, attention_mask=mask, images=images).logits)
 
 
-@pytest.mark.parametrize("entry", ["ull_llama_decode_layers_w8_bf16", "ull_llama_decode_layers_bf16"])
-def test_coarse_decode_entry_validates_shapes_without_launching(entry):
-    """Both coarse decode entries (fp8 and bf16 weights) check every layer before the first launch: an inconsistent layer or intermediate
+@pytest.mark.parametrize("fmt", ["fp8", "bf16"])
+def test_coarse_decode_entry_validates_shapes_without_launching(fmt):
+    """The coarse decode entry checks every layer (fp8 and bf16 weights) before the first launch: an inconsistent layer or intermediate
     size is refused with the output untouched."""
     L, ops = pkg("_lib"), pkg("ops")
-    w8 = entry == "ull_llama_decode_layers_w8_bf16"
+    w8 = fmt == "fp8"
     H, hd, I, T = 4, 16, 128, 1
     D = H * hd
     ws = {n: _weight(r, c, i) for i, (n, r, c) in enumerate((("qkv", 3 * D, D), ("o", D, D), ("gu", 2 * I, D), ("down", D, I)))}
     q = {n: ops.quantize_fp8(w) for n, w in ws.items()} if w8 else ws
-    Layer = L.LlamaLayerW8 if w8 else L.LlamaLayer
+    Layer = L.LlamaLayer
     ln = torch.ones(D, device=DEV, dtype=BF)
 
     def lin(w, n=None):
         if w8:
-            return L.LinearW8(w.codes.data_ptr(), w.scales.data_ptr(), n or w.shape[0], w.shape[1], w.codes.stride(0))
+            return L.Linear(w.codes.data_ptr(), None, None, n or w.shape[0], w.shape[1], w.codes.stride(0), L.WF_FP8, w.scales.data_ptr(), 0)
         return L.Linear(w.data_ptr(), None, None, n or w.shape[0], w.shape[1], w.stride(0))
 
     def call(layer, I_):
@@ -392,7 +392,7 @@ def test_coarse_decode_entry_validates_shapes_without_launching(entry):
         arr = (Layer * 1)(layer)
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         ptrs = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
-        fn = getattr(L.load(), entry)
+        fn = L.load().ull_llama_decode_layers_bf16
         rc = fn(arr, 1, p(x), ptrs(out), p(x_mid), p(xn), p(qb), p(att), p(act), p(cs), p(cs), None, ptrs(kc), ptrs(vt),
                 1, 1, H, hd, I_, 64, 5, 1e-6, ops._zeros(DEV).data_ptr(), ops._stream())
         torch.cuda.synchronize()

@@ -1,5 +1,6 @@
 """CPU: host logic that needs no GPU -- the C-ABI library loads and exports every declared symbol, configs mirror the
 reference, weight packing layouts, state-dict key names."""
+import ctypes
 import os
 import re
 
@@ -610,3 +611,102 @@ def test_linear_route_table(shape, want):
     ops = pkg("ops")
     assert ops.GEMM_TUNE_WAVES8 == _T8
     assert (*ops._linear_route(*shape), ops._big(*shape[:3])) == want
+
+
+# ---- the weight format travels with the weight (ULL_WF_*): refusals, all of which return before any launch --------------------------------
+_ADDR = 0x10000                 # a non-null address that is never dereferenced: every call below returns from its argument checks
+ERR_ARG, ERR_SHAPE = -1, -2
+WQ_ENTRIES = ("ull_gemv_wq_bf16", "ull_gemm_skinny_wq_bf16", "ull_gemv_rmsnorm_wq_bf16", "ull_gemv_qkv_rope_append_wq_bf16")
+
+
+def _wq_call(entry, wfmt, ldq, scales, lds, K=64):
+    """rc of a *_wq_bf16 entry on a [96, K] weight at `_ADDR` (q|k|v of 2 heads of 16)."""
+    lib = pkg("_lib").load()
+    w = (wfmt, _ADDR, ldq, scales, lds)
+    if entry == "ull_gemv_qkv_rope_append_wq_bf16":
+        return lib.ull_gemv_qkv_rope_append_wq_bf16(_ADDR, K, None, 0.0, *w, _ADDR, 32, _ADDR, _ADDR, _ADDR, _ADDR, 1, 1, 2, 16, K, 64, 5, None)
+    tail = (_ADDR, 96, None, None, 0, 3 if "skinny" in entry else 1, 96, K, 0, None)
+    if entry == "ull_gemv_rmsnorm_wq_bf16":
+        return lib.ull_gemv_rmsnorm_wq_bf16(_ADDR, K, _ADDR, 1e-6, *w, *tail)
+    return getattr(lib, entry)(_ADDR, K, *w, *tail)
+
+
+@pytest.mark.parametrize("entry", WQ_ENTRIES)
+def test_wq_entries_refuse_bad_weight_descriptors(entry):
+    L = pkg("_lib")
+    assert _wq_call(entry, 7, 64, _ADDR, 4) == ERR_ARG, "an unknown format"
+    assert _wq_call(entry, -1, 64, _ADDR, 4) == ERR_ARG, "an unknown format"
+    assert _wq_call(entry, L.WF_FP8, 64, None, 0) == ERR_ARG, "fp8 without scales"
+    assert _wq_call(entry, L.WF_MXFP4, 32, None, 4) == ERR_ARG, "mxfp4 without scales"
+    assert _wq_call(entry, L.WF_MXFP4, 40, _ADDR, 4) == ERR_SHAPE, "an mxfp4 code pitch that is no multiple of 16"
+    assert _wq_call(entry, L.WF_MXFP4, 32, _ADDR, 6) == ERR_SHAPE, "an mxfp4 scale pitch that is no multiple of 4"
+    assert _wq_call(entry, L.WF_MXFP4, 16, _ADDR, 4) == ERR_SHAPE, "an mxfp4 code pitch below K / 2"
+
+
+def _lin(n, k, fmt=0, scales=None, ldw=None, lds=0, bias=None):
+    L = pkg("_lib")
+    return L.Linear(_ADDR, None, bias, n, k, k if ldw is None else ldw, fmt, scales, lds)
+
+
+def _quantized_lin(n, k, fmt):
+    """A well-formed fp8 / mxfp4 ull_linear [n, k]."""
+    L = pkg("_lib")
+    return _lin(n, k, fmt, _ADDR, *((k, 0) if fmt == L.WF_FP8 else (k // 2, -(-(k // 32) // 4) * 4)))
+
+
+def _decode_layers_rc(entry, qkv):
+    """rc of a decode-layers entry on ONE layer (H = 4, hd = 16, I = 128, one new token on 5 cached ones) whose q|k|v Linear is `qkv`."""
+    L = pkg("_lib")
+    D, I = 64, 128
+    arr = (L.LlamaLayer * 1)(L.LlamaLayer(_ADDR, _ADDR, qkv, _lin(D, D), _lin(2 * I, D), _lin(D, I)))
+    ptrs = lambda: (ctypes.c_void_p * 1)(_ADDR)
+    return getattr(L.load(), entry)(arr, 1, _ADDR, ptrs(), _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, None, ptrs(), ptrs(), 1, 1, 4, 16, I, 64, 5,
+                                    1e-6, _ADDR, None)
+
+
+def test_decode_layers_refuse_bad_weight_descriptors():
+    L = pkg("_lib")
+    D = 64
+    assert _decode_layers_rc("ull_llama_decode_layers_bf16", _lin(3 * D, D, 7, _ADDR)) == ERR_ARG, "an unknown format"
+    assert _decode_layers_rc("ull_llama_decode_layers_bf16", _lin(3 * D, D, L.WF_FP8, None)) == ERR_ARG, "fp8 without scales"
+    assert _decode_layers_rc("ull_llama_decode_layers_bf16", _lin(3 * D, D, L.WF_MXFP4, None, D // 2, 4)) == ERR_ARG, "mxfp4 without scales"
+    for fmt in (L.WF_FP8, L.WF_MXFP4):
+        assert _decode_layers_rc("ull_llama_decode_layers_f16", _quantized_lin(3 * D, D, fmt)) == ERR_ARG, "the f16 build has no quantized kernels"
+
+
+@pytest.mark.parametrize("fmt", ["fp8", "mxfp4"])
+def test_prefill_clip_and_sam_stacks_refuse_quantized_linears(fmt):
+    """The 16-bit GEMM stacks take ULL_WF_ELEM Linears only: a quantized one is refused in the layer's check, before its first launch."""
+    L = pkg("_lib")
+    lib, wf = L.load(), {"fp8": L.WF_FP8, "mxfp4": L.WF_MXFP4}[fmt]
+    ptrs = (ctypes.c_void_p * 1)(_ADDR)
+    D, I = 128, 128                                                   # LLaMA prefill: one head of 128, 32 tokens
+    llama = (L.LlamaLayer * 1)(L.LlamaLayer(_ADDR, _ADDR, _lin(3 * D, D), _lin(D, D), _quantized_lin(2 * I, D, wf), _lin(D, I)))
+    assert lib.ull_llama_prefill_layers_bf16(llama, 1, _ADDR, ptrs, _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, None, 1, 32, 1, 128, I, 1e-6, None, 0,
+                                             -1, _ADDR, None) == ERR_ARG
+    D, I = 64, 64                                                     # CLIP: one head of 64, 32 tokens
+    clip = (L.ClipLayer * 1)(L.ClipLayer(_ADDR, _ADDR, _ADDR, _ADDR, _quantized_lin(3 * D, D, wf), _lin(D, D), _lin(I, D), _lin(D, I)))
+    assert lib.ull_clip_layers_bf16(clip, 1, _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, 1, 32, 1, 64, I, 1e-5, None, 0, -1, _ADDR, None) == ERR_ARG
+    C, I = 320, 64                                                    # SAM: four heads of 80 on the 64 x 64 grid
+    sam = (L.SamBlock * 1)(L.SamBlock(_ADDR, _ADDR, _ADDR, _ADDR, _lin(3 * C, C, bias=_ADDR), _lin(C, C), _lin(I, C), _quantized_lin(C, I, wf),
+                                      _ADDR, _ADDR, 14))
+    assert lib.ull_sam_blocks_bf16(sam, 1, _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, _ADDR, 1, 64, 4, 80, I, 1e-6, None, 0, -1, _ADDR, None) == ERR_ARG
+
+
+def test_layer_stack_fills_a_linear_from_every_weight_form():
+    """ops.LayerStack takes a (weight, bias) pair, a bare 16-bit weight or a quantized weight for an ull_linear field; only 16-bit weights enter
+    its fingerprint."""
+    ops, L = pkg("ops"), pkg("_lib")
+    w, b = torch.zeros(8, 64, dtype=torch.bfloat16), torch.zeros(8, dtype=torch.bfloat16)
+    q8 = ops.Fp8Weight(torch.zeros(8, 64, dtype=torch.uint8), torch.ones(8))
+    q4 = ops.Mxfp4Weight(torch.zeros(8, 32, dtype=torch.uint8), torch.zeros(8, 4, dtype=torch.uint8), 64)
+    ln = torch.ones(64, dtype=torch.bfloat16)
+    st = ops.LayerStack(L.LlamaLayer, [dict(ln1=ln, ln2=ln, qkv=(w, b), o=w, gu=q8, down=q4)])
+    a = st.arr[0]
+    assert (a.qkv.format, a.qkv.w, a.qkv.bias, a.qkv.scales) == (L.WF_ELEM, w.data_ptr(), b.data_ptr(), None)
+    assert (a.o.format, a.o.w, a.o.bias, a.o.ldw) == (L.WF_ELEM, w.data_ptr(), None, 64)
+    assert (a.gu.format, a.gu.w, a.gu.scales, a.gu.n, a.gu.k, a.gu.ldw) == (L.WF_FP8, q8.codes.data_ptr(), q8.scales.data_ptr(), 8, 64, 64)
+    assert (a.down.format, a.down.w, a.down.scales, a.down.n, a.down.k, a.down.ldw, a.down.lds) == (L.WF_MXFP4, q4.codes.data_ptr(),
+                                                                                                   q4.scales.data_ptr(), 8, 64, 32, 4)
+    assert a.gu.bias is None and a.gu.w_tiled is None and a.down.bias is None and a.down.w_tiled is None
+    assert st.quantized and st._fingerprint() == [w.data_ptr(), w._version] * 2

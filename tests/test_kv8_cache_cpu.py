@@ -10,8 +10,7 @@ from helpers import pkg
 from test_fp8_weights_cpu import _tiny_core
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KV8_ENTRIES = ("ull_attention_kv8_bf16", "ull_kv8_quantize_bf16", "ull_kv8_dequantize_bf16", "ull_llama_decode_layers_kv8_bf16",
-               "ull_llama_decode_layers_w8_kv8_bf16")
+KV8_ENTRIES = ("ull_attention_kv8_bf16", "ull_kv8_quantize_bf16", "ull_kv8_dequantize_bf16", "ull_llama_decode_layers_kv8_bf16")
 
 
 def test_kv8_entries_declared_bound_and_exported():

@@ -363,22 +363,23 @@ def test_coarse_kv8_decode_equals_per_op(fp8_weights, monkeypatch):
     assert calls.count(True) == 2 * 4, calls             # steps 2 .. 5 (65 .. 68 keys) of the coarse runs at both batch sizes
 
 
-@pytest.mark.parametrize("entry", ["ull_llama_decode_layers_kv8_bf16", "ull_llama_decode_layers_w8_kv8_bf16"])
-def test_coarse_kv8_decode_entry_validates_without_launching(entry):
-    """Both fp8-cache decode entries check every layer, the cache pointers and the shapes ull_attention_kv8 takes before the first launch."""
+@pytest.mark.parametrize("fmt", ["bf16", "fp8"])
+def test_coarse_kv8_decode_entry_validates_without_launching(fmt):
+    """The fp8-cache decode entry checks every layer (bf16 and fp8 weights), the cache pointers and the shapes ull_attention_kv8 takes before
+    the first launch."""
     import ctypes
     L, ops = pkg("_lib"), pkg("ops")
-    w8 = "w8" in entry
+    w8 = fmt == "fp8"
     H, hd, I, T = 4, 16, 128, 1
     D = H * hd
     ws = {n: _rand(r, c, sc=0.02, seed=i) for i, (n, r, c) in enumerate((("qkv", 3 * D, D), ("o", D, D), ("gu", 2 * I, D), ("down", D, I)))}
     q = {n: ops.quantize_fp8(w) for n, w in ws.items()} if w8 else ws
-    Layer = L.LlamaLayerW8 if w8 else L.LlamaLayer
+    Layer = L.LlamaLayer
     ln = torch.ones(D, device=DEV, dtype=BF)
 
     def lin(w, n=None):
         if w8:
-            return L.LinearW8(w.codes.data_ptr(), w.scales.data_ptr(), n or w.shape[0], w.shape[1], w.codes.stride(0))
+            return L.Linear(w.codes.data_ptr(), None, None, n or w.shape[0], w.shape[1], w.codes.stride(0), L.WF_FP8, w.scales.data_ptr(), 0)
         return L.Linear(w.data_ptr(), None, None, n or w.shape[0], w.shape[1], w.stride(0))
 
     def call(layer, I_=I, past=70, stage=True, k8_null=False):
@@ -390,7 +391,7 @@ def test_coarse_kv8_decode_entry_validates_without_launching(entry):
         arr = (Layer * 1)(layer)
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         ptrs = lambda t: (ctypes.c_void_p * 1)(None if t is None else t.data_ptr())
-        fn = getattr(L.load(), entry)
+        fn = L.load().ull_llama_decode_layers_kv8_bf16
         rc = fn(arr, 1, p(x), ptrs(out), p(x_mid), p(xn), p(qb), p(att), p(act), p(cs), p(cs), None, ptrs(None if k8_null else c.k8[0]),
                 ptrs(c.vt8[0]), ptrs(c.k_scale[0]), ptrs(c.vt_scale[0]), p(c.k_stage) if stage else None, p(c.vt_stage), 1, 1, H, hd, I_, 128, past,
                 1e-6, ops._zeros(DEV).data_ptr(), ops._stream())

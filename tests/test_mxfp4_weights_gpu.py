@@ -463,7 +463,7 @@ def test_requantizing_same_format_is_noop_other_format_raises():
 
 @pytest.mark.parametrize("kv8", [False, True])
 def test_coarse_decode_entries_validate_shapes_without_launching(kv8):
-    """ull_llama_decode_layers_w4_bf16 / _w4_kv8_bf16 check every layer before the first launch: an inconsistent layer, an odd intermediate
+    """ull_llama_decode_layers_bf16 / _kv8_bf16 check every layer of an mxfp4 model before the first launch: an inconsistent layer, an odd intermediate
     size or a bad pitch is refused with ULL_ERR_ARG / ULL_ERR_SHAPE and the output untouched."""
     L, ops = pkg("_lib"), pkg("ops")
     H, hd, I, T = 4, 16, 128, 1
@@ -474,14 +474,15 @@ def test_coarse_decode_entries_validate_shapes_without_launching(kv8):
     ln = torch.ones(D, device=DEV, dtype=BF)
 
     def lin(w, n=None, ld=None):
-        return L.LinearW4(w.codes.data_ptr(), w.scales.data_ptr(), n or w.shape[0], w.shape[1], ld or w.codes.stride(0), w.scales.stride(0))
+        return L.Linear(w.codes.data_ptr(), None, None, n or w.shape[0], w.shape[1], ld or w.codes.stride(0), L.WF_MXFP4, w.scales.data_ptr(),
+                        w.scales.stride(0))
 
     def call(layer, I_):
         x = torch.zeros(T, D, device=DEV, dtype=BF)
         out = torch.full((T, D), 7.0, device=DEV, dtype=BF)
         x_mid, xn, qb, att, act = (torch.zeros(T, n, device=DEV, dtype=BF) for n in (D, max(D, I), D, D, I))
         cs = torch.ones(T, hd // 2, device=DEV, dtype=BF)
-        arr = (L.LlamaLayerW4 * 1)(layer)
+        arr = (L.LlamaLayer * 1)(layer)
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         ptrs = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
         if kv8:
@@ -491,30 +492,30 @@ def test_coarse_decode_entries_validate_shapes_without_launching(kv8):
             vs = torch.ones(1, H, smax, device=DEV, dtype=torch.float32)
             kst = torch.zeros(1, H, 128, hd, device=DEV, dtype=BF)
             vst = torch.zeros(1, H, hd, 128, device=DEV, dtype=BF)
-            rc = L.load().ull_llama_decode_layers_w4_kv8_bf16(arr, 1, p(x), ptrs(out), p(x_mid), p(xn), p(qb), p(att), p(act), p(cs), p(cs), None,
-                                                              ptrs(k8), ptrs(vt8), ptrs(ks), ptrs(vs), p(kst), p(vst), 1, 1, H, hd, I_, smax, past,
-                                                              1e-6, ops._zeros(DEV).data_ptr(), ops._stream())
+            rc = L.load().ull_llama_decode_layers_kv8_bf16(arr, 1, p(x), ptrs(out), p(x_mid), p(xn), p(qb), p(att), p(act), p(cs), p(cs), None,
+                                                           ptrs(k8), ptrs(vt8), ptrs(ks), ptrs(vs), p(kst), p(vst), 1, 1, H, hd, I_, smax, past,
+                                                           1e-6, ops._zeros(DEV).data_ptr(), ops._stream())
         else:
             kc = torch.zeros(1, H, smax, hd, device=DEV, dtype=BF)
             vt = torch.zeros(1, H, hd, smax, device=DEV, dtype=BF)
-            rc = L.load().ull_llama_decode_layers_w4_bf16(arr, 1, p(x), ptrs(out), p(x_mid), p(xn), p(qb), p(att), p(act), p(cs), p(cs), None,
-                                                          ptrs(kc), ptrs(vt), 1, 1, H, hd, I_, smax, past, 1e-6, ops._zeros(DEV).data_ptr(),
-                                                          ops._stream())
+            rc = L.load().ull_llama_decode_layers_bf16(arr, 1, p(x), ptrs(out), p(x_mid), p(xn), p(qb), p(att), p(act), p(cs), p(cs), None,
+                                                       ptrs(kc), ptrs(vt), 1, 1, H, hd, I_, smax, past, 1e-6, ops._zeros(DEV).data_ptr(),
+                                                       ops._stream())
         torch.cuda.synchronize()
         return rc, out
 
-    good = L.LlamaLayerW4(ln.data_ptr(), ln.data_ptr(), lin(q["qkv"]), lin(q["o"]), lin(q["gu"]), lin(q["down"]))
+    good = L.LlamaLayer(ln.data_ptr(), ln.data_ptr(), lin(q["qkv"]), lin(q["o"]), lin(q["gu"]), lin(q["down"]))
     rc, out = call(good, I)
     assert rc == 0 and not bool((out == 7.0).all())
-    bad_gu = L.LlamaLayerW4(ln.data_ptr(), ln.data_ptr(), lin(q["qkv"]), lin(q["o"]), lin(q["gu"], n=2 * I - 32), lin(q["down"]))
+    bad_gu = L.LlamaLayer(ln.data_ptr(), ln.data_ptr(), lin(q["qkv"]), lin(q["o"]), lin(q["gu"], n=2 * I - 32), lin(q["down"]))
     rc, out = call(bad_gu, I)
     assert rc in (-1, -2) and bool((out == 7.0).all()), "inconsistent gu.n must be refused before any launch"
     rc, out = call(good, I - 3)
     assert rc in (-1, -2) and bool((out == 7.0).all()), "an odd intermediate size must be refused before any launch"
-    bad_ld = L.LlamaLayerW4(ln.data_ptr(), ln.data_ptr(), lin(q["qkv"]), lin(q["o"]), lin(q["gu"]), lin(q["down"], ld=I // 2 - 16))
+    bad_ld = L.LlamaLayer(ln.data_ptr(), ln.data_ptr(), lin(q["qkv"]), lin(q["o"]), lin(q["gu"]), lin(q["down"], ld=I // 2 - 16))
     rc, out = call(bad_ld, I)
     assert rc == -1 and bool((out == 7.0).all()), "a code row pitch below K / 2 is ULL_ERR_ARG, before any launch"
-    null_sc = L.LlamaLayerW4(ln.data_ptr(), ln.data_ptr(), lin(q["qkv"]), L.LinearW4(q["o"].codes.data_ptr(), None, D, D, D // 2, 4), lin(q["gu"]),
-                             lin(q["down"]))
+    null_sc = L.LlamaLayer(ln.data_ptr(), ln.data_ptr(), lin(q["qkv"]), L.Linear(q["o"].codes.data_ptr(), None, None, D, D, D // 2, L.WF_MXFP4, None, 4),
+                           lin(q["gu"]), lin(q["down"]))
     rc, out = call(null_sc, I)
     assert rc == -1 and bool((out == 7.0).all()), "a null scale pointer is ULL_ERR_ARG, before any launch"

@@ -5,7 +5,8 @@ quantize_weights("fp8_e4m3") and times the same steps, then rebuilds the model f
 them again.  Prints per batch and format: prefill + first token, ms per decode step (median and the spread of --reps runs), the effective
 weight stream rate, torch.cuda.memory_allocated; and the relative Frobenius error of both formats' dequantized weights (computed on the
 device).  --sweep adds the launch-shape sweep of the mxfp4 GEMV at batch 1; it needs a library built with the tuning switch
-(`make -C u-llava_amd/csrc clean all CXXFLAGS+=-DULL_W4_TUNE`, or ULL_LIB_PATH pointing at such a build), which the shipped build leaves out.
+(`make -C u-llava_amd/csrc clean`, then `make -C u-llava_amd/csrc HIPCC="/opt/rocm/bin/hipcc -DULL_W4_TUNE"`, or ULL_LIB_PATH pointing at
+such a build), which the shipped build leaves out.
 
     python tools/mxfp4_decode_bench.py [--new 33] [--reps 3] [--sweep]
     python tools/mxfp4_decode_bench.py --prefill-only        # an mxfp4 model's prefill + 1 token, twice: the run to put under a kernel trace

@@ -13,29 +13,16 @@ LIB_PATH = os.environ.get("ULL_LIB_PATH", os.path.join(_HERE, "csrc", "libullava
 _i64, _i32, _f32, _ptr = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
 
+WF_ELEM, WF_FP8, WF_MXFP4 = 0, 1, 2      # ULL_WF_*: the weight format of a Linear / of a *_wq_bf16 entry
+
+
 # the structs of include/ullava_hip.h's coarse entries (one call = a whole stack of layers)
 class Linear(ctypes.Structure):
-    _fields_ = [("w", _ptr), ("w_tiled", _ptr), ("bias", _ptr), ("n", _i64), ("k", _i64), ("ldw", _i64)]
+    _fields_ = [("w", _ptr), ("w_tiled", _ptr), ("bias", _ptr), ("n", _i64), ("k", _i64), ("ldw", _i64), ("format", _i32), ("scales", _ptr), ("lds", _i64)]
 
 
 class LlamaLayer(ctypes.Structure):
     _fields_ = [("ln1", _ptr), ("ln2", _ptr), ("qkv", Linear), ("o", Linear), ("gu", Linear), ("down", Linear)]
-
-
-class LinearW8(ctypes.Structure):
-    _fields_ = [("codes", _ptr), ("scales", _ptr), ("n", _i64), ("k", _i64), ("ld", _i64)]
-
-
-class LlamaLayerW8(ctypes.Structure):
-    _fields_ = [("ln1", _ptr), ("ln2", _ptr), ("qkv", LinearW8), ("o", LinearW8), ("gu", LinearW8), ("down", LinearW8)]
-
-
-class LinearW4(ctypes.Structure):
-    _fields_ = [("codes", _ptr), ("scales", _ptr), ("n", _i64), ("k", _i64), ("ld", _i64), ("lds", _i64)]
-
-
-class LlamaLayerW4(ctypes.Structure):
-    _fields_ = [("ln1", _ptr), ("ln2", _ptr), ("qkv", LinearW4), ("o", LinearW4), ("gu", LinearW4), ("down", LinearW4)]
 
 
 class ClipLayer(ctypes.Structure):
@@ -136,37 +123,26 @@ SIGNATURES.update({name[:-4] + "f16": args for name, args in list(SIGNATURES.ite
 F32_TWINS = ['ull_gemm', 'ull_attention', 'ull_transpose_v', 'ull_transpose2d', 'ull_rmsnorm', 'ull_layernorm', 'ull_clip_embed_ln', 'ull_layernorm2d_cl', 'ull_rope_inplace', 'ull_rope_append', 'ull_im2col', 'ull_im2col3x3', 'ull_video_pool', 'ull_add_rows', 'ull_window_unpartition_add', 'ull_sam_relpos', 'ull_interp_rows_linear', 'ull_mask_matmul', 'ull_greedy_step', 'ull_shifted_cross_entropy']
 SIGNATURES.update({name + "_f32": SIGNATURES[name + "_bf16"] for name in F32_TWINS})
 
-# fp8 (e4m3) weight-only decode: bf16-only entry points (no fp16 twin)
+# fp8 (e4m3) weights and KV cache: bf16-only entry points (no fp16 twin)
 SIGNATURES.update({
     "ull_quantize_rows_fp8_bf16": [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr],
     "ull_dequantize_rows_fp8_bf16": [_ptr, _i64, _ptr, _i64, _i64, _ptr, _i32, _ptr],
-    "ull_gemv_w8_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_gemv_rmsnorm_w8_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_gemv_qkv_rope_append_w8_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64,
-                                         _i64, _i64, _ptr],
     "ull_attention_kv8_bf16": [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64,
                                _i64, _f32, _ptr, _ptr],
     "ull_kv8_quantize_bf16": [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr],
     "ull_kv8_dequantize_bf16": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr],
-    "ull_gemm_skinny_w8_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_llama_decode_layers_w8_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
-                                        _i64, _i64, _i64, _f32, _ptr, _ptr],
     "ull_llama_decode_layers_kv8_bf16": [_ptr, _i64] + [_ptr] * 16 + [_i64] * 7 + [_f32, _ptr, _ptr],
-    "ull_llama_decode_layers_w8_kv8_bf16": [_ptr, _i64] + [_ptr] * 16 + [_i64] * 7 + [_f32, _ptr, _ptr],
 })
 
-# mxfp4 weight-only decode: bf16-only entry points (no fp16 twin)
+# mxfp4 weights, and the decode-shape Linear entries on a quantized weight (wfmt, Q, ldq, scales, lds): bf16-only entry points (no fp16 twin)
 SIGNATURES.update({
     "ull_quantize_rows_mxfp4_bf16": [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _i32, _ptr],
     "ull_dequantize_rows_mxfp4_bf16": [_ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i32, _i32, _ptr],
-    "ull_gemv_w4_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_gemv_rmsnorm_w4_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_gemv_qkv_rope_append_w4_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
+    "ull_gemv_wq_bf16": [_ptr, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
+    "ull_gemm_skinny_wq_bf16": [_ptr, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
+    "ull_gemv_rmsnorm_wq_bf16": [_ptr, _i64, _ptr, _f32, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
+    "ull_gemv_qkv_rope_append_wq_bf16": [_ptr, _i64, _ptr, _f32, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
                                          _i64, _i64, _i64, _ptr],
-    "ull_gemm_skinny_w4_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_llama_decode_layers_w4_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
-                                        _i64, _i64, _i64, _f32, _ptr, _ptr],
-    "ull_llama_decode_layers_w4_kv8_bf16": [_ptr, _i64] + [_ptr] * 16 + [_i64] * 7 + [_f32, _ptr, _ptr],
 })
 
 # fp16-only entry points (no bf16 twin): the fp32 neck of an fp16 SAM encoder (image_encoder.py:117-124)

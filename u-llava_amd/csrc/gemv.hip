@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "ull_common.h"
+#include "../../include/ullava_hip.h"
 
 namespace {
 
@@ -50,7 +51,7 @@ ULL_DEV uint4 w_load16(const elem_t* p) {
 // WF_MXFP4 (bf16 build only): e2m1 code rows with one E8M0 scale per 32 elements, in the resident layout of ull_common.h (mx_code_pos): a lane's four
 // chunks of a superblock arrive in one 16-byte load, their four scale bytes in one 4-byte load, and v_cvt_scalef32_pk_f32_fp4 turns each chunk
 // into the 8 floats e2m1 * 2^s -- again exactly the bf16 values of the dequantized weight, multiplied in the order of the 16-bit kernel.
-constexpr int WF_ELEM = 0, WF_FP8 = 1, WF_MXFP4 = 2;
+constexpr int WF_ELEM = ULL_WF_ELEM, WF_FP8 = ULL_WF_FP8, WF_MXFP4 = ULL_WF_MXFP4;
 
 struct W8Rows {
     const uint8_t* codes;                    // [N][ldw] e4m3fn bytes
@@ -445,166 +446,160 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const elem_t* __restri
     }
 }
 
-// Launch shape of the mxfp4 GEMV: W4_U 16-byte weight loads per lane in flight, W4_BLOCKS the grid cap where every block pays the X staging.
-// The constants are the sweep's choice (profiles/mxfp4_decode.txt, batch-1 decode ms per step: U = 1 / 2 / 4 at 1536 blocks 2.58 / 2.50 / 2.92;
-// U = 2 at 1024 / 1536 / 2048 / 3072 / 4096 blocks 2.55 / 2.50 / 2.59 / 2.66 / 2.66).  A build with -DULL_W4_TUNE (make CXXFLAGS+=-DULL_W4_TUNE; tools/
-// only, not part of the ABI in include/ullava_hip.h) adds U = 1, 2, 4 instantiations and a process-wide run-time switch,
-// ull_gemv_w4_tune_bf16(u, blocks), which tools/mxfp4_decode_bench.py --sweep drives.
-constexpr int W4_U = 2, W4_BLOCKS = 1536;
-#if defined(ULL_W4_TUNE) && !defined(ULL_ELEM_F16)
-struct W4Tune { int u, blocks; };
-W4Tune g_w4_tune = {W4_U, W4_BLOCKS};
-#endif
+// ---- host side: one weight descriptor, one launcher per kernel family ---------------------------------------------------------------
+// A decode-shape weight as the entries hand it to the launchers: its format, the rows the kernel streams (16-bit elements, or code bytes) with
+// their pitch, and for a quantized format the scales (WF_FP8: fp32 [N], lds unused; WF_MXFP4: E8M0 bytes, row pitch lds; both bf16 build only).
+struct Weight {
+    int fmt;
+    const void* rows; int64_t ld;
+    const void* scales; int64_t lds;
+};
 
+// the kernel argument of a weight in format WF (WFmt<WF>::ptr_t)
+template <int WF> inline auto kernel_weight(const Weight& w) {
+    if constexpr (WF == WF_FP8) return W8Rows{(const uint8_t*)w.rows, (const float*)w.scales};
+    else if constexpr (WF == WF_MXFP4) return W4Rows{(const uint8_t*)w.rows, (const uint8_t*)w.scales, (long)w.lds};
+    else return (const elem_t*)w.rows;
+}
+
+// a format this build has kernels for, with the pointers it needs
+inline bool weight_ok(const Weight& w) {
+#ifndef ULL_ELEM_F16
+    if (w.fmt == WF_FP8 || w.fmt == WF_MXFP4) return w.rows && w.scales;
+#endif
+    return w.fmt == WF_ELEM && w.rows;
+}
 // the row pitches an mxfp4 weight needs: whole rows, 16-byte aligned code rows, 4-byte aligned scale rows
 inline bool w4_pitch_ok(int64_t K, int64_t ldw, int64_t lds) { return !(K & 31) && ldw >= K / 2 && !(ldw & 15) && lds >= K / 32 && !(lds & 3); }
 
-// scales != nullptr: W holds e4m3 codes (row pitch ldw bytes) with one fp32 scale per row (WF_FP8, bf16 build only).
-// mx_scales != nullptr: W holds mxfp4 codes (row pitch ldw bytes), mx_scales the E8M0 bytes (row pitch mx_ld), resident layout (WF_MXFP4, bf16 build only).
-int launch_skinny(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr,
-                  int64_t M, int64_t N, int64_t K, int flags, void* stream, const float* scales = nullptr, const void* mx_scales = nullptr,
-                  int64_t mx_ld = 0) {
-    if (!X || !W || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
-    if (M > 16 || (K & 31) || (ldx & 7) || (ldw & 7)) return ULL_ERR_SHAPE;
-    if (mx_scales && !w4_pitch_ok(K, ldw, mx_ld)) return ULL_ERR_SHAPE;
+// Launch shape of the GEMV per format: U[M - 1] weight loads per lane in flight, BLOCKS the grid cap where every block pays the X staging.
+template <int WF> struct GemvShape {                 // 16-bit rows: 16-byte loads; ~2 blocks per CU, several output rows per wave
+    static constexpr int U[MAXM] = {8, 4, 4, 4}, BLOCKS = 1024;
+};
+// Half the bytes per row make a row's latency, not the stream, the limit: more waves in flight (a 1536-block grid where the 16-bit form has
+// 1024) and fewer registers per wave (4 loads per lane in flight at M = 1) -- measured on the LLaMA-7B decode step (tools/fp8_decode_bench.py,
+// batch 1): U = 16 / 1024 blocks 3.06 ms, U = 8 / 2048 blocks 2.66, U = 4 / 2048 2.56, U = 4 / 1536 2.46, U = 4 / 1280 2.45, U = 4 / 1024 2.51,
+// U = 2 / 2048 2.60 (bf16: 3.37).
+template <> struct GemvShape<WF_FP8> {
+    static constexpr int U[MAXM] = {4, 8, 8, 8}, BLOCKS = 1536;
+};
+// A quarter of the bytes per row: a K = 4096 row is two 16-byte loads per lane.  The constants are the sweep's choice (profiles/mxfp4_decode.txt,
+// batch-1 decode ms per step: U = 1 / 2 / 4 at 1536 blocks 2.58 / 2.50 / 2.92; U = 2 at 1024 / 1536 / 2048 / 3072 / 4096 blocks 2.55 / 2.50 / 2.59 /
+// 2.66 / 2.66).  A build with -DULL_W4_TUNE (make HIPCC="/opt/rocm/bin/hipcc -DULL_W4_TUNE"; tools/ only, not part of the ABI in
+// include/ullava_hip.h) adds U = 1, 2, 4 instantiations and a process-wide run-time switch, ull_gemv_w4_tune_bf16(u, blocks), which
+// tools/mxfp4_decode_bench.py --sweep drives.
+constexpr int W4_U = 2, W4_BLOCKS = 1536;
+template <> struct GemvShape<WF_MXFP4> {
+    static constexpr int U[MAXM] = {W4_U, W4_U, W4_U, W4_U}, BLOCKS = W4_BLOCKS;
+};
+#ifdef ULL_W4_TUNE
+struct W4Tune { int u, blocks; };
+W4Tune g_w4_tune = {W4_U, W4_BLOCKS};
+#endif
+template <int V> using Int = std::integral_constant<int, V>;
+
+template <int WF>
+int launch_skinny_as(const void* X, int64_t ldx, const Weight& w, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M,
+                     int64_t N, int64_t K, int flags, int n_out, hipStream_t st) {
+    const auto wk = kernel_weight<WF>(w);
+    const unsigned blocks = (unsigned)((n_out + 15) / 16);
+    if (flags & EPI_SWIGLU)
+        hipLaunchKernelGGL((skinny_gemm_kernel<true, WF>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, wk, w.ld, C, ldc, (const elem_t*)bias,
+                           (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
+    else
+        hipLaunchKernelGGL((skinny_gemm_kernel<false, WF>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, wk, w.ld, C, ldc, (const elem_t*)bias,
+                           (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
+    return ull_check_launch();
+}
+
+int launch_skinny(const void* X, int64_t ldx, const Weight& w, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N,
+                  int64_t K, int flags, void* stream) {
+    if (!X || !weight_ok(w) || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if (M > 16 || (K & 31) || (ldx & 7) || (w.ld & 7)) return ULL_ERR_SHAPE;
+    if (w.fmt == WF_MXFP4 && !w4_pitch_ok(K, w.ld, w.lds)) return ULL_ERR_SHAPE;
     if ((flags & EPI_BIAS) && !bias) return ULL_ERR_ARG;
     if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
     if ((flags & EPI_SWIGLU) && ((N & 31) || (flags & (EPI_BIAS | EPI_ACT_MASK)))) return ULL_ERR_SHAPE;
     const int n_out = (int)((flags & EPI_SWIGLU) ? N / 2 : N);
-    const unsigned blocks = (unsigned)((n_out + 15) / 16);
     hipStream_t st = (hipStream_t)stream;
-    if (mx_scales) {
-#ifdef ULL_ELEM_F16
-        return ULL_ERR_ARG;
-#else
-        const W4Rows w4{(const uint8_t*)W, (const uint8_t*)mx_scales, (long)mx_ld};
-        if (flags & EPI_SWIGLU)
-            hipLaunchKernelGGL((skinny_gemm_kernel<true, WF_MXFP4>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, w4, ldw, C, ldc,
-                               (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
-        else
-            hipLaunchKernelGGL((skinny_gemm_kernel<false, WF_MXFP4>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, w4, ldw, C, ldc,
-                               (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
-        return ull_check_launch();
+    switch (w.fmt) {
+#ifndef ULL_ELEM_F16
+        case WF_FP8: return launch_skinny_as<WF_FP8>(X, ldx, w, C, ldc, bias, R, ldr, M, N, K, flags, n_out, st);
+        case WF_MXFP4: return launch_skinny_as<WF_MXFP4>(X, ldx, w, C, ldc, bias, R, ldr, M, N, K, flags, n_out, st);
 #endif
+        default: return launch_skinny_as<WF_ELEM>(X, ldx, w, C, ldc, bias, R, ldr, M, N, K, flags, n_out, st);
     }
-    if (scales) {
-#ifdef ULL_ELEM_F16
-        return ULL_ERR_ARG;
-#else
-        const W8Rows w8{(const uint8_t*)W, scales};
-        if (flags & EPI_SWIGLU)
-            hipLaunchKernelGGL((skinny_gemm_kernel<true, WF_FP8>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, w8, ldw, C, ldc,
-                               (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
-        else
-            hipLaunchKernelGGL((skinny_gemm_kernel<false, WF_FP8>), dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, w8, ldw, C, ldc,
-                               (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
-        return ull_check_launch();
+}
+
+template <int WF>
+int launch_gemv_as(const void* X, int64_t ldx, const Weight& w, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N,
+                   int64_t K, int flags, int n_out, const void* norm_w, float eps, int staged, const RopeAppend& ra, hipStream_t st) {
+    typedef GemvShape<WF> Shape;
+    const auto wk = kernel_weight<WF>(w);
+    const int lds = staged ? (int)(M * K * 2) : 0;
+    int cap = Shape::BLOCKS;
+#ifdef ULL_W4_TUNE
+    if constexpr (WF == WF_MXFP4) cap = g_w4_tune.blocks;
 #endif
+    int blocks = (n_out + 3) / 4;
+    if (staged && blocks > cap) blocks = cap;
+    if (blocks > 8192) blocks = 8192;
+    const auto go = [&](auto m, auto u) {
+        hipLaunchKernelGGL((gemv_kernel<decltype(m)::value, decltype(u)::value, WF>), dim3(blocks), dim3(256), lds, st, (const elem_t*)X, ldx, wk, w.ld, C,
+                           ldc, (const elem_t*)bias, (const elem_t*)R, ldr, (int)N, (int)K, flags, n_out, (const elem_t*)norm_w, eps, staged, ra);
+    };
+    const auto go_m = [&](auto m) {
+#ifdef ULL_W4_TUNE
+        if constexpr (WF == WF_MXFP4) {
+            if (g_w4_tune.u == 1) return go(m, Int<1>{});
+            if (g_w4_tune.u == 4) return go(m, Int<4>{});
+            return go(m, Int<2>{});
+        } else
+#endif
+            return go(m, Int<Shape::U[decltype(m)::value - 1]>{});
+    };
+    switch ((int)M) {
+        case 1: go_m(Int<1>{}); break;
+        case 2: go_m(Int<2>{}); break;
+        case 3: go_m(Int<3>{}); break;
+        default: go_m(Int<4>{}); break;
     }
-    if (flags & EPI_SWIGLU)
-        hipLaunchKernelGGL(skinny_gemm_kernel<true>, dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, (const elem_t*)W, ldw, C, ldc,
-                           (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
-    else
-        hipLaunchKernelGGL(skinny_gemm_kernel<false>, dim3(blocks), dim3(512), 0, st, (const elem_t*)X, ldx, (const elem_t*)W, ldw, C, ldc,
-                           (const elem_t*)bias, (const elem_t*)R, ldr, (int)M, (int)N, (int)K, flags, n_out);
     return ull_check_launch();
 }
 
-// scales != nullptr: W holds e4m3 codes; mx_scales != nullptr: mxfp4 codes, as in launch_skinny.
-int launch_gemv(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr,
-                int64_t M, int64_t N, int64_t K, int flags, const void* norm_w, float eps, void* stream, const RopeAppend* rope = nullptr,
-                const float* scales = nullptr, const void* mx_scales = nullptr, int64_t mx_ld = 0) {
-    if (!X || !W || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
+int launch_gemv(const void* X, int64_t ldx, const Weight& w, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N,
+                int64_t K, int flags, const void* norm_w, float eps, void* stream, const RopeAppend* rope = nullptr) {
+    if (!X || !weight_ok(w) || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
     if ((flags & EPI_ROPE_APPEND) && (!rope || flags != EPI_ROPE_APPEND || (N & 1))) return ULL_ERR_ARG;   // (not part of the public flags)
     const RopeAppend ra = rope ? *rope : RopeAppend{};
-    if (M > MAXM || (K & 7) || (ldx & 7) || (ldw & 7)) return ULL_ERR_SHAPE;
-    if (mx_scales && !w4_pitch_ok(K, ldw, mx_ld)) return ULL_ERR_SHAPE;
+    if (M > MAXM || (K & 7) || (ldx & 7) || (w.ld & 7)) return ULL_ERR_SHAPE;
+    if (w.fmt == WF_MXFP4 && !w4_pitch_ok(K, w.ld, w.lds)) return ULL_ERR_SHAPE;
     if ((flags & EPI_BIAS) && !bias) return ULL_ERR_ARG;
     if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
     if ((flags & EPI_SWIGLU) && ((N & 31) || (flags & (EPI_BIAS | EPI_ACT_MASK)))) return ULL_ERR_SHAPE;
     const int staged = M * K * 2 <= XS_MAX_BYTES;
     if (norm_w && !staged) return ULL_ERR_SHAPE;
-    const int lds = staged ? (int)(M * K * 2) : 0;
     const int n_out = (int)((flags & (EPI_SWIGLU | EPI_ROPE_APPEND)) ? N / 2 : N);
-    // every block pays the X staging once, so give a block several output rows per wave: ~2 blocks per CU
-    int blocks = (n_out + 3) / 4;
-    if (staged && blocks > 1024) blocks = 1024;
-    if (blocks > 8192) blocks = 8192;
     hipStream_t st = (hipStream_t)stream;
-    if (mx_scales) {
-#ifdef ULL_ELEM_F16
-        return ULL_ERR_ARG;
-#else
-        // A quarter of the bytes per row: a K = 4096 row is two 16-byte loads per lane (launch shape: W4_U, W4_BLOCKS above).
-        const W4Rows w4{(const uint8_t*)W, (const uint8_t*)mx_scales, (long)mx_ld};
-        int blocks4 = (n_out + 3) / 4;
-#ifdef ULL_W4_TUNE
-        const int cap4 = g_w4_tune.blocks;
-#else
-        const int cap4 = W4_BLOCKS;
+    switch (w.fmt) {
+#ifndef ULL_ELEM_F16
+        case WF_FP8: return launch_gemv_as<WF_FP8>(X, ldx, w, C, ldc, bias, R, ldr, M, N, K, flags, n_out, norm_w, eps, staged, ra, st);
+        case WF_MXFP4: return launch_gemv_as<WF_MXFP4>(X, ldx, w, C, ldc, bias, R, ldr, M, N, K, flags, n_out, norm_w, eps, staged, ra, st);
 #endif
-        if (staged && blocks4 > cap4) blocks4 = cap4;
-        if (blocks4 > 8192) blocks4 = 8192;
-#define ULL_GV4(MM, UU)                                                                                                                   \
-    hipLaunchKernelGGL((gemv_kernel<MM, UU, WF_MXFP4>), dim3(blocks4), dim3(256), lds, st, (const elem_t*)X, ldx, w4, ldw, C, ldc,   \
-                       (const elem_t*)bias, (const elem_t*)R, ldr, (int)N, (int)K, flags, n_out, (const elem_t*)norm_w, eps, staged, ra)
-#ifdef ULL_W4_TUNE
-#define ULL_GV4_U(MM)                          \
-    switch (g_w4_tune.u) {                     \
-        case 1: ULL_GV4(MM, 1); break;         \
-        case 4: ULL_GV4(MM, 4); break;         \
-        default: ULL_GV4(MM, 2); break;        \
+        default: return launch_gemv_as<WF_ELEM>(X, ldx, w, C, ldc, bias, R, ldr, M, N, K, flags, n_out, norm_w, eps, staged, ra, st);
     }
-#else
-#define ULL_GV4_U(MM) ULL_GV4(MM, W4_U)
-#endif
-        switch ((int)M) {
-            case 1: ULL_GV4_U(1); break;
-            case 2: ULL_GV4_U(2); break;
-            case 3: ULL_GV4_U(3); break;
-            default: ULL_GV4_U(4); break;
-        }
-#undef ULL_GV4_U
-#undef ULL_GV4
-        return ull_check_launch();
-#endif
-    }
-    if (scales) {
-#ifdef ULL_ELEM_F16
-        return ULL_ERR_ARG;
-#else
-        // Half the bytes per row make a row's latency, not the stream, the limit: more waves in flight (a 1536-block grid where the
-        // 16-bit form has 1024) and fewer registers per wave (4 loads per lane in flight at M = 1) -- measured on the LLaMA-7B decode step
-        // (tools/fp8_decode_bench.py, batch 1): U = 16 / 1024 blocks 3.06 ms, U = 8 / 2048 blocks 2.66, U = 4 / 2048 2.56, U = 4 / 1536
-        // 2.46, U = 4 / 1280 2.45, U = 4 / 1024 2.51, U = 2 / 2048 2.60 (bf16: 3.37).
-        const W8Rows w8{(const uint8_t*)W, scales};
-        int blocks8 = (n_out + 3) / 4;
-        if (staged && blocks8 > 1536) blocks8 = 1536;
-        if (blocks8 > 8192) blocks8 = 8192;
-#define ULL_GV8(MM, UU)                                                                                                                   \
-    hipLaunchKernelGGL((gemv_kernel<MM, UU, WF_FP8>), dim3(blocks8), dim3(256), lds, st, (const elem_t*)X, ldx, w8, ldw, C, ldc,           \
-                       (const elem_t*)bias, (const elem_t*)R, ldr, (int)N, (int)K, flags, n_out, (const elem_t*)norm_w, eps, staged, ra)
-        switch ((int)M) {
-            case 1: ULL_GV8(1, 4); break;
-            case 2: ULL_GV8(2, 8); break;
-            case 3: ULL_GV8(3, 8); break;
-            default: ULL_GV8(4, 8); break;
-        }
-#undef ULL_GV8
-        return ull_check_launch();
-#endif
-    }
-#define ULL_GV(MM, UU)                                                                                                                    \
-    hipLaunchKernelGGL((gemv_kernel<MM, UU>), dim3(blocks), dim3(256), lds, st, (const elem_t*)X, ldx, (const elem_t*)W, ldw, C, ldc,     \
-                       (const elem_t*)bias, (const elem_t*)R, ldr, (int)N, (int)K, flags, n_out, (const elem_t*)norm_w, eps, staged, ra)
-    switch ((int)M) {
-        case 1: ULL_GV(1, 8); break;
-        case 2: ULL_GV(2, 4); break;
-        case 3: ULL_GV(3, 4); break;
-        default: ULL_GV(4, 4); break;
-    }
-#undef ULL_GV
-    return ull_check_launch();
+}
+
+// The q | k | v projection with RoPE and the cache append (see RopeAppend) on a weight of any format: the checks of its arguments, then the GEMV.
+int launch_qkv_rope_append(const void* X, int64_t ldx, const void* norm_w, float eps, const Weight& w, void* Q_out, int64_t ldq, const void* cos_tab,
+                           const void* sin_tab, void* k_cache, void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax,
+                           int64_t past, void* stream) {
+    if (!cos_tab || !sin_tab || !k_cache || !vt_cache || B <= 0 || S <= 0 || H <= 0) return ULL_ERR_ARG;
+    if (hd <= 0 || (hd & 1) || past < 0 || past + S > smax || ldq < H * hd) return ULL_ERR_SHAPE;
+    RopeAppend ra;
+    ra.cs = (const elem_t*)cos_tab; ra.sn = (const elem_t*)sin_tab; ra.kc = (elem_t*)k_cache; ra.vtc = (elem_t*)vt_cache;
+    ra.S = (int)S; ra.H = (int)H; ra.hd = (int)hd; ra.smax = (int)smax; ra.past = (int)past;
+    return launch_gemv(X, ldx, w, Q_out, ldq, nullptr, nullptr, 0, B * S, 3 * H * hd, K, EPI_ROPE_APPEND, norm_w, norm_w ? eps : 0.f, stream, &ra);
 }
 
 }  // namespace
@@ -612,7 +607,7 @@ int launch_gemv(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C,
 // Same contract as ull_gemm_bf16 (flags, layouts) for M <= 4; K % 8 == 0.
 extern "C" int ULL_FN(ull_gemv_)(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* R,
                              int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
-    return launch_gemv(X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, nullptr, 0.f, stream);
+    return launch_gemv(X, ldx, Weight{WF_ELEM, W, ldw}, C, ldc, bias, R, ldr, M, N, K, flags, nullptr, 0.f, stream);
 }
 
 // The same with the preceding LlamaRMSNorm fused in: C = epilogue(rmsnorm(X; norm_w, eps) * W^T).  M * K <= 16384.
@@ -620,7 +615,7 @@ extern "C" int ULL_FN(ull_gemv_rmsnorm_)(const void* X, int64_t ldx, const void*
                                      int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
                                      void* stream) {
     if (!norm_w) return ULL_ERR_ARG;
-    return launch_gemv(X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, norm_w, eps, stream);
+    return launch_gemv(X, ldx, Weight{WF_ELEM, W, ldw}, C, ldc, bias, R, ldr, M, N, K, flags, norm_w, eps, stream);
 }
 
 // Decode-step q | k | v projection with RoPE and the KV-cache append in its epilogue (see RopeAppend): W = [3 * H * hd, K] (q | k | v rows),
@@ -629,20 +624,45 @@ extern "C" int ULL_FN(ull_gemv_rmsnorm_)(const void* X, int64_t ldx, const void*
 extern "C" int ULL_FN(ull_gemv_qkv_rope_append_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* W, int64_t ldw, void* Q_out,
                                              int64_t ldq, const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int64_t B,
                                              int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax, int64_t past, void* stream) {
-    if (!cos_tab || !sin_tab || !k_cache || !vt_cache || B <= 0 || S <= 0 || H <= 0) return ULL_ERR_ARG;
-    if (hd <= 0 || (hd & 1) || past < 0 || past + S > smax || ldq < H * hd) return ULL_ERR_SHAPE;
-    RopeAppend ra;
-    ra.cs = (const elem_t*)cos_tab; ra.sn = (const elem_t*)sin_tab; ra.kc = (elem_t*)k_cache; ra.vtc = (elem_t*)vt_cache;
-    ra.S = (int)S; ra.H = (int)H; ra.hd = (int)hd; ra.smax = (int)smax; ra.past = (int)past;
-    return launch_gemv(X, ldx, W, ldw, Q_out, ldq, nullptr, nullptr, 0, B * S, 3 * H * hd, K, EPI_ROPE_APPEND, norm_w, norm_w ? eps : 0.f, stream,
-                       &ra);
+    return launch_qkv_rope_append(X, ldx, norm_w, eps, Weight{WF_ELEM, W, ldw}, Q_out, ldq, cos_tab, sin_tab, k_cache, vt_cache, B, S, H, hd, K, smax, past,
+                                  stream);
 }
 
 // The same contract for 2 <= M <= 16 on the matrix cores (batched decode steps); K % 32 == 0.
 extern "C" int ULL_FN(ull_gemm_skinny_)(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* R,
                                     int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
-    return launch_skinny(X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, stream);
+    return launch_skinny(X, ldx, Weight{WF_ELEM, W, ldw}, C, ldc, bias, R, ldr, M, N, K, flags, stream);
 }
+
+#ifndef ULL_ELEM_F16
+// The four entries above on a weight of format wfmt (ULL_WF_*): Q = its rows (row pitch ldq: 16-bit elements, or code bytes), scales / lds as the
+// format has them (the two sections below).  Same contract and bits as the bf16 entry on dequant(Q).  bf16 build only.
+extern "C" int ull_gemv_wq_bf16(const void* X, int64_t ldx, int wfmt, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C, int64_t ldc,
+                                const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
+    return launch_gemv(X, ldx, Weight{wfmt, Q, ldq, scales, lds}, C, ldc, bias, R, ldr, M, N, K, flags, nullptr, 0.f, stream);
+}
+
+extern "C" int ull_gemv_rmsnorm_wq_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, int wfmt, const void* Q, int64_t ldq,
+                                        const void* scales, int64_t lds, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M,
+                                        int64_t N, int64_t K, int flags, void* stream) {
+    if (!norm_w) return ULL_ERR_ARG;
+    return launch_gemv(X, ldx, Weight{wfmt, Q, ldq, scales, lds}, C, ldc, bias, R, ldr, M, N, K, flags, norm_w, eps, stream);
+}
+
+extern "C" int ull_gemv_qkv_rope_append_wq_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, int wfmt, const void* Q, int64_t ldq,
+                                                const void* scales, int64_t lds, void* Q_out, int64_t ldq_out, const void* cos_tab,
+                                                const void* sin_tab, void* k_cache, void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd,
+                                                int64_t K, int64_t smax, int64_t past, void* stream) {
+    return launch_qkv_rope_append(X, ldx, norm_w, eps, Weight{wfmt, Q, ldq, scales, lds}, Q_out, ldq_out, cos_tab, sin_tab, k_cache, vt_cache, B, S, H, hd,
+                                  K, smax, past, stream);
+}
+
+extern "C" int ull_gemm_skinny_wq_bf16(const void* X, int64_t ldx, int wfmt, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C,
+                                       int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
+                                       void* stream) {
+    return launch_skinny(X, ldx, Weight{wfmt, Q, ldq, scales, lds}, C, ldc, bias, R, ldr, M, N, K, flags, stream);
+}
+#endif  // !ULL_ELEM_F16
 
 // ---- FP8 (e4m3) weight-only decode: bf16 build only ------------------------------------------------------------------------------
 // A weight W [N, K] is stored as e4m3fn codes q [N, K] plus one fp32 scale 2^s per row, s the smallest integer with amax|w| * 2^-s <= 448
@@ -727,39 +747,6 @@ extern "C" int ULL_FN(ull_dequantize_rows_fp8_)(const void* codes, int64_t ldq, 
     return ull_check_launch();
 }
 
-// ull_gemv_bf16 / ull_gemv_rmsnorm_bf16 / ull_gemv_qkv_rope_append_bf16 / ull_gemm_skinny_bf16 on an fp8 weight: Q = e4m3 codes (row pitch
-// ldq bytes), scales [N] fp32.  Same contract and bits as the bf16 entry on dequant(Q).
-extern "C" int ULL_FN(ull_gemv_w8_)(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc, const void* bias,
-                                const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
-    if (!scales) return ULL_ERR_ARG;
-    return launch_gemv(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, nullptr, 0.f, stream, nullptr, (const float*)scales);
-}
-
-extern "C" int ULL_FN(ull_gemv_rmsnorm_w8_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales,
-                                        void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
-                                        void* stream) {
-    if (!norm_w || !scales) return ULL_ERR_ARG;
-    return launch_gemv(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, norm_w, eps, stream, nullptr, (const float*)scales);
-}
-
-extern "C" int ULL_FN(ull_gemv_qkv_rope_append_w8_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq,
-                                                const void* scales, void* Q_out, int64_t ldq_out, const void* cos_tab, const void* sin_tab,
-                                                void* k_cache, void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax,
-                                                int64_t past, void* stream) {
-    if (!scales || !cos_tab || !sin_tab || !k_cache || !vt_cache || B <= 0 || S <= 0 || H <= 0) return ULL_ERR_ARG;
-    if (hd <= 0 || (hd & 1) || past < 0 || past + S > smax || ldq_out < H * hd) return ULL_ERR_SHAPE;
-    RopeAppend ra;
-    ra.cs = (const elem_t*)cos_tab; ra.sn = (const elem_t*)sin_tab; ra.kc = (elem_t*)k_cache; ra.vtc = (elem_t*)vt_cache;
-    ra.S = (int)S; ra.H = (int)H; ra.hd = (int)hd; ra.smax = (int)smax; ra.past = (int)past;
-    return launch_gemv(X, ldx, Q, ldq, Q_out, ldq_out, nullptr, nullptr, 0, B * S, 3 * H * hd, K, EPI_ROPE_APPEND, norm_w, norm_w ? eps : 0.f, stream,
-                       &ra, (const float*)scales);
-}
-
-extern "C" int ULL_FN(ull_gemm_skinny_w8_)(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, void* C, int64_t ldc,
-                                       const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
-    if (!scales) return ULL_ERR_ARG;
-    return launch_skinny(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, stream, (const float*)scales);
-}
 #endif  // !ULL_ELEM_F16
 
 // ---- MXFP4 weight-only decode: bf16 build only -------------------------------------------------------------------------------------
@@ -847,42 +834,6 @@ extern "C" int ULL_FN(ull_dequantize_rows_mxfp4_)(const void* codes, int64_t ldq
     hipLaunchKernelGGL(dequantize_rows_mxfp4_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)codes, (long)ldq,
                        (const uint8_t*)scales, (long)lds, (int)N, (int)K, (elem_t*)out, tiled, resident ? 1 : 0, total);
     return ull_check_launch();
-}
-
-// ull_gemv_bf16 / ull_gemv_rmsnorm_bf16 / ull_gemv_qkv_rope_append_bf16 / ull_gemm_skinny_bf16 on an mxfp4 weight in the resident layout: Q = codes
-// (row pitch ldq bytes, a multiple of 16), scales = E8M0 bytes (row pitch lds, a multiple of 4).  Same contract and bits as the bf16 entry on
-// dequant(Q); K % 32 == 0.
-extern "C" int ULL_FN(ull_gemv_w4_)(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C, int64_t ldc,
-                                    const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
-    if (!scales) return ULL_ERR_ARG;
-    return launch_gemv(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, nullptr, 0.f, stream, nullptr, nullptr, scales, lds);
-}
-
-extern "C" int ULL_FN(ull_gemv_rmsnorm_w4_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq, const void* scales,
-                                            int64_t lds, void* C, int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N,
-                                            int64_t K, int flags, void* stream) {
-    if (!norm_w || !scales) return ULL_ERR_ARG;
-    return launch_gemv(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, norm_w, eps, stream, nullptr, nullptr, scales, lds);
-}
-
-extern "C" int ULL_FN(ull_gemv_qkv_rope_append_w4_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* Q, int64_t ldq,
-                                                    const void* scales, int64_t lds, void* Q_out, int64_t ldq_out, const void* cos_tab,
-                                                    const void* sin_tab, void* k_cache, void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd,
-                                                    int64_t K, int64_t smax, int64_t past, void* stream) {
-    if (!scales || !cos_tab || !sin_tab || !k_cache || !vt_cache || B <= 0 || S <= 0 || H <= 0) return ULL_ERR_ARG;
-    if (hd <= 0 || (hd & 1) || past < 0 || past + S > smax || ldq_out < H * hd) return ULL_ERR_SHAPE;
-    RopeAppend ra;
-    ra.cs = (const elem_t*)cos_tab; ra.sn = (const elem_t*)sin_tab; ra.kc = (elem_t*)k_cache; ra.vtc = (elem_t*)vt_cache;
-    ra.S = (int)S; ra.H = (int)H; ra.hd = (int)hd; ra.smax = (int)smax; ra.past = (int)past;
-    return launch_gemv(X, ldx, Q, ldq, Q_out, ldq_out, nullptr, nullptr, 0, B * S, 3 * H * hd, K, EPI_ROPE_APPEND, norm_w, norm_w ? eps : 0.f, stream,
-                       &ra, nullptr, scales, lds);
-}
-
-extern "C" int ULL_FN(ull_gemm_skinny_w4_)(const void* X, int64_t ldx, const void* Q, int64_t ldq, const void* scales, int64_t lds, void* C,
-                                           int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
-                                           void* stream) {
-    if (!scales) return ULL_ERR_ARG;
-    return launch_skinny(X, ldx, Q, ldq, C, ldc, bias, R, ldr, M, N, K, flags, stream, nullptr, scales, lds);
 }
 
 #ifdef ULL_W4_TUNE

@@ -58,82 +58,61 @@ inline int lin(const void* x, int64_t ldx, const ull_linear* L, void* out, int64
     return FN(ull_gemm_)(x, ldx, t.w, t.ldw, out, ldc, L->bias, R, ldr, M, L->n, L->k, flags | t.flags, t.ws, t.wsb, stream);
 }
 
-// The weight formats of a decode-shape Linear: a 16-bit ull_linear, or (bf16 build) an fp8 ull_linear_w8 or an mxfp4 ull_linear_w4, which have
-// no bias.  Each overload passes the weight to the entry of its format.  ldw_of: the row pitch the routing rule (ops._linear_route) sees;
-// pitch_ok: the rows are whole.
-inline bool has_weight(const ull_linear* L) { return L->w; }
-inline bool pitch_ok(const ull_linear* L) { return L->ldw >= L->k; }
-inline const void* bias_of(const ull_linear* L) { return L->bias; }
-inline int64_t ldw_of(const ull_linear* L) { return L->ldw; }
+// A decode-shape Linear in any weight format (ull_linear.format): a quantized one (bf16 build only) has no bias and goes to the *_wq_bf16 form of
+// the entry, which takes the format as an argument.  format_ok: a format this build's entries take; has_weight: its pointers are there;
+// pitch_ok: the rows are whole; ldw_of: the row pitch the routing rule (ops._linear_route) sees.
+inline bool quantized(const ull_linear* L) { return L->format != ULL_WF_ELEM; }
+inline bool format_ok(const ull_linear* L) {
+#ifndef ULL_ELEM_F16
+    if (L->format == ULL_WF_FP8 || L->format == ULL_WF_MXFP4) return true;
+#endif
+    return !quantized(L);
+}
+inline bool has_weight(const ull_linear* L) { return L->w && (!quantized(L) || L->scales); }
+inline bool pitch_ok(const ull_linear* L) {
+    if (L->format == ULL_WF_MXFP4) return L->k % 32 == 0 && L->ldw >= L->k / 2 && L->ldw % 16 == 0 && L->lds >= L->k / 32 && L->lds % 4 == 0;
+    return L->ldw >= L->k;
+}
+inline const void* bias_of(const ull_linear* L) { return quantized(L) ? nullptr : L->bias; }
+// (ops.linear passes K for an Mxfp4Weight: its rows are always whole)
+inline int64_t ldw_of(const ull_linear* L) { return L->format == ULL_WF_MXFP4 ? L->k : L->ldw; }
 inline int gemm_skinny(const void* x, int64_t ldx, const ull_linear* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
                        void* stream) {
+#ifndef ULL_ELEM_F16
+    if (quantized(L))
+        return ull_gemm_skinny_wq_bf16(x, ldx, L->format, L->w, L->ldw, L->scales, L->lds, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+#endif
     return FN(ull_gemm_skinny_)(x, ldx, L->w, L->ldw, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
 }
 inline int gemv(const void* x, int64_t ldx, const ull_linear* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags, void* stream) {
+#ifndef ULL_ELEM_F16
+    if (quantized(L)) return ull_gemv_wq_bf16(x, ldx, L->format, L->w, L->ldw, L->scales, L->lds, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
+#endif
     return FN(ull_gemv_)(x, ldx, L->w, L->ldw, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
 }
 inline int gemv_rmsnorm(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear* L, void* out, int64_t ldc, const void* R,
                         int64_t ldr, int64_t M, int flags, void* stream) {
+#ifndef ULL_ELEM_F16
+    if (quantized(L))
+        return ull_gemv_rmsnorm_wq_bf16(x, ldx, rms_w, eps, L->format, L->w, L->ldw, L->scales, L->lds, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags,
+                                        stream);
+#endif
     return FN(ull_gemv_rmsnorm_)(x, ldx, rms_w, eps, L->w, L->ldw, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
 }
 inline int gemv_qkv_rope_append(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear* L, void* q, int64_t ldq, const void* cs,
                                 const void* sn, void* kc, void* vtc, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
                                 void* stream) {
+#ifndef ULL_ELEM_F16
+    if (quantized(L))
+        return ull_gemv_qkv_rope_append_wq_bf16(x, ldx, rms_w, eps, L->format, L->w, L->ldw, L->scales, L->lds, q, ldq, cs, sn, kc, vtc, B, S, H, hd, L->k,
+                                                smax, past, stream);
+#endif
     return FN(ull_gemv_qkv_rope_append_)(x, ldx, rms_w, eps, L->w, L->ldw, q, ldq, cs, sn, kc, vtc, B, S, H, hd, L->k, smax, past, stream);
 }
 
-#ifndef ULL_ELEM_F16
-inline bool has_weight(const ull_linear_w8* L) { return L->codes && L->scales; }
-inline bool pitch_ok(const ull_linear_w8* L) { return L->ld >= L->k; }
-inline const void* bias_of(const ull_linear_w8*) { return nullptr; }
-inline int64_t ldw_of(const ull_linear_w8* L) { return L->ld; }
-inline int gemm_skinny(const void* x, int64_t ldx, const ull_linear_w8* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
-                       void* stream) {
-    return ull_gemm_skinny_w8_bf16(x, ldx, L->codes, L->ld, L->scales, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
-}
-inline int gemv(const void* x, int64_t ldx, const ull_linear_w8* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
-                void* stream) {
-    return ull_gemv_w8_bf16(x, ldx, L->codes, L->ld, L->scales, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
-}
-inline int gemv_rmsnorm(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear_w8* L, void* out, int64_t ldc, const void* R,
-                        int64_t ldr, int64_t M, int flags, void* stream) {
-    return ull_gemv_rmsnorm_w8_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
-}
-inline int gemv_qkv_rope_append(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear_w8* L, void* q, int64_t ldq, const void* cs,
-                                const void* sn, void* kc, void* vtc, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
-                                void* stream) {
-    return ull_gemv_qkv_rope_append_w8_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, q, ldq, cs, sn, kc, vtc, B, S, H, hd, L->k, smax, past,
-                                            stream);
-}
-
-inline bool has_weight(const ull_linear_w4* L) { return L->codes && L->scales; }
-inline bool pitch_ok(const ull_linear_w4* L) { return L->k % 32 == 0 && L->ld >= L->k / 2 && L->ld % 16 == 0 && L->lds >= L->k / 32 && L->lds % 4 == 0; }
-inline const void* bias_of(const ull_linear_w4*) { return nullptr; }
-inline int64_t ldw_of(const ull_linear_w4* L) { return L->k; }        // (ops.linear passes K for an Mxfp4Weight: its rows are always whole)
-inline int gemm_skinny(const void* x, int64_t ldx, const ull_linear_w4* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
-                       void* stream) {
-    return ull_gemm_skinny_w4_bf16(x, ldx, L->codes, L->ld, L->scales, L->lds, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
-}
-inline int gemv(const void* x, int64_t ldx, const ull_linear_w4* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
-                void* stream) {
-    return ull_gemv_w4_bf16(x, ldx, L->codes, L->ld, L->scales, L->lds, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
-}
-inline int gemv_rmsnorm(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear_w4* L, void* out, int64_t ldc, const void* R,
-                        int64_t ldr, int64_t M, int flags, void* stream) {
-    return ull_gemv_rmsnorm_w4_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, L->lds, out, ldc, bias_of(L), R, ldr, M, L->n, L->k, flags, stream);
-}
-inline int gemv_qkv_rope_append(const void* x, int64_t ldx, const void* rms_w, float eps, const ull_linear_w4* L, void* q, int64_t ldq, const void* cs,
-                                const void* sn, void* kc, void* vtc, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
-                                void* stream) {
-    return ull_gemv_qkv_rope_append_w4_bf16(x, ldx, rms_w, eps, L->codes, L->ld, L->scales, L->lds, q, ldq, cs, sn, kc, vtc, B, S, H, hd, L->k, smax,
-                                            past, stream);
-}
-#endif  // !ULL_ELEM_F16
-
 // ops.linear for M <= 4 (decode steps), ops._linear_route: the skinny MFMA GEMM from M = 3 on against LLaMA-sized weights, the weight-streaming
 // GEMV otherwise; a preceding LlamaRMSNorm is fused into the GEMV where its LDS staging allows it and is a launch of its own otherwise.
-template <class Lin>
-inline int lin_decode(const void* x, int64_t ldx, const void* rms_w, float eps, void* xn_scratch, const Lin* L, void* out, int64_t ldc,
+inline int lin_decode(const void* x, int64_t ldx, const void* rms_w, float eps, void* xn_scratch, const ull_linear* L, void* out, int64_t ldc,
                       const void* R, int64_t ldr, int64_t M, int flags, void* stream) {
     const bool skinny = M >= 3 && L->k % 32 == 0 && L->n * L->k >= ((int64_t)1 << 22) && ldw_of(L) % 8 == 0;
     if (bias_of(L)) flags |= ULL_EPI_BIAS;
@@ -164,7 +143,8 @@ extern "C" int FN(ull_llama_prefill_layers_)(const ull_llama_layer* layers, int6
     const void* x = x_in;
     for (int64_t l = 0; l < n_layers; ++l) {
         const ull_llama_layer& w = layers[l];
-        if (w.qkv.n != 3 * D || w.qkv.k != D || w.o.n != D || w.o.k != D || w.gu.n != 2 * I || w.gu.k != D || w.down.n != D || w.down.k != I || !x_out[l])
+        if (w.qkv.n != 3 * D || w.qkv.k != D || w.o.n != D || w.o.k != D || w.gu.n != 2 * I || w.gu.k != D || w.down.n != D || w.down.k != I || !x_out[l] ||
+            quantized(&w.qkv) || quantized(&w.o) || quantized(&w.gu) || quantized(&w.down))       // (a quantized model's prefill: the per-op path)
             return ULL_ERR_ARG;
         TRY(FN(ull_rmsnorm_)(x, D, w.ln1, xn, D, T, D, eps, stream));                                   // input_layernorm
         {                                                                                               // q|k|v projection + RoPE epilogue
@@ -194,8 +174,7 @@ struct BfCache {
 };
 inline bool cache_layer_ok(const BfCache& c, int64_t l) { return c.k[l] && c.vt[l]; }
 inline bool cache_shape_ok(const BfCache& c, int64_t, int64_t) { return c.k && c.vt; }
-template <class Lin>
-inline int append_and_attend(const BfCache& c, int64_t l, const void* x, int64_t D, const void* ln1, float eps, const Lin* qkv, void* q, const void* cs,
+inline int append_and_attend(const BfCache& c, int64_t l, const void* x, int64_t D, const void* ln1, float eps, const ull_linear* qkv, void* q, const void* cs,
                              const void* sn, void* att, const void* key_mask, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
                              float scale, const void* zeros, void* stream) {
     TRY(gemv_qkv_rope_append(x, D, ln1, eps, qkv, q, D, cs, sn, c.k[l], c.vt[l], B, S, H, hd, smax, past, stream));
@@ -213,8 +192,7 @@ inline bool cache_layer_ok(const Kv8Cache& c, int64_t l) { return c.k8[l] && c.v
 inline bool cache_shape_ok(const Kv8Cache& c, int64_t S, int64_t past) {
     return c.k8 && c.vt8 && c.ks && c.vs && c.k_stage && c.vt_stage && S <= 16 && past + S > 64 && past + S <= 4096;
 }
-template <class Lin>
-inline int append_and_attend(const Kv8Cache& c, int64_t l, const void* x, int64_t D, const void* ln1, float eps, const Lin* qkv, void* q, const void* cs,
+inline int append_and_attend(const Kv8Cache& c, int64_t l, const void* x, int64_t D, const void* ln1, float eps, const ull_linear* qkv, void* q, const void* cs,
                              const void* sn, void* att, const void* key_mask, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t smax, int64_t past,
                              float scale, const void* zeros, void* stream) {
     TRY(gemv_qkv_rope_append(x, D, ln1, eps, qkv, q, D, cs, sn, c.k_stage, c.vt_stage, B, S, H, hd, 128, past & 63, stream));
@@ -223,9 +201,9 @@ inline int append_and_attend(const Kv8Cache& c, int64_t l, const void* x, int64_
 }
 #endif  // !ULL_ELEM_F16
 
-// The decode-step layer loop over either layer struct and either cache format.  Every layer is checked before anything is enqueued.
-template <class Layer, class Cache>
-int llama_decode_layers(const Layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn, void* q, void* att, void* act,
+// The decode-step layer loop over either cache format.  Every layer is checked before anything is enqueued.
+template <class Cache>
+int llama_decode_layers(const ull_llama_layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid, void* xn, void* q, void* att, void* act,
                         const void* rope_cos, const void* rope_sin, const void* key_mask, const Cache& cache, int64_t B, int64_t S, int64_t H,
                         int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
     if (!layers || !x_in || !x_out || !x_mid || !xn || !q || !att || !act || !rope_cos || !rope_sin || !zeros || n_layers <= 0) return ULL_ERR_ARG;
@@ -233,17 +211,17 @@ int llama_decode_layers(const Layer* layers, int64_t n_layers, const void* x_in,
     if (T > 4 || T <= 0 || past <= 0 || (hd & 1) || D % 8 || I <= 0 || I % 8 || T * D * 2 > 32768 || past + S > smax) return ULL_ERR_SHAPE;
     if (!cache_shape_ok(cache, S, past)) return ULL_ERR_ARG;
     for (int64_t l = 0; l < n_layers; ++l) {
-        const Layer& w = layers[l];
+        const ull_llama_layer& w = layers[l];
         if (w.qkv.n != 3 * D || w.qkv.k != D || w.o.n != D || w.o.k != D || w.gu.n != 2 * I || w.gu.k != D || w.down.n != D || w.down.k != I)
             return ULL_ERR_SHAPE;
         for (const auto* L : {&w.qkv, &w.o, &w.gu, &w.down})
-            if (!has_weight(L) || !pitch_ok(L)) return ULL_ERR_ARG;
+            if (!format_ok(L) || !has_weight(L) || !pitch_ok(L)) return ULL_ERR_ARG;
         if (!w.ln1 || !w.ln2 || !cache_layer_ok(cache, l) || !x_out[l]) return ULL_ERR_ARG;
     }
     const float scale = 1.0f / sqrtf((float)hd);
     const void* x = x_in;
     for (int64_t l = 0; l < n_layers; ++l) {
-        const Layer& w = layers[l];
+        const ull_llama_layer& w = layers[l];
         TRY(append_and_attend(cache, l, x, D, w.ln1, eps, &w.qkv, q, rope_cos, rope_sin, att, key_mask, B, S, H, hd, smax, past, scale, zeros, stream));
         TRY(lin_decode(att, D, nullptr, 0.f, xn, &w.o, x_mid, D, x, D, T, 0, stream));
         TRY(lin_decode(x_mid, D, w.ln2, eps, xn, &w.gu, act, I, nullptr, 0, T, ULL_EPI_SWIGLU, stream));
@@ -264,14 +242,6 @@ extern "C" int FN(ull_llama_decode_layers_)(const ull_llama_layer* layers, int64
 }
 
 #ifndef ULL_ELEM_F16
-extern "C" int ull_llama_decode_layers_w8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid,
-                                               void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
-                                               const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H,
-                                               int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
-    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask, BfCache{k_cache, vt_cache}, B, S, H,
-                               hd, I, smax, past, eps, zeros, stream);
-}
-
 extern "C" int ull_llama_decode_layers_kv8_bf16(const ull_llama_layer* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid,
                                                 void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
                                                 const void* key_mask, void* const* k8, void* const* vt8, void* const* k_scale, void* const* vt_scale,
@@ -281,31 +251,6 @@ extern "C" int ull_llama_decode_layers_kv8_bf16(const ull_llama_layer* layers, i
                                Kv8Cache{k8, vt8, k_scale, vt_scale, k_stage, vt_stage}, B, S, H, hd, I, smax, past, eps, zeros, stream);
 }
 
-extern "C" int ull_llama_decode_layers_w8_kv8_bf16(const ull_llama_layer_w8* layers, int64_t n_layers, const void* x_in, void* const* x_out,
-                                                   void* x_mid, void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
-                                                   const void* key_mask, void* const* k8, void* const* vt8, void* const* k_scale,
-                                                   void* const* vt_scale, void* k_stage, void* vt_stage, int64_t B, int64_t S, int64_t H, int64_t hd,
-                                                   int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
-    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask,
-                               Kv8Cache{k8, vt8, k_scale, vt_scale, k_stage, vt_stage}, B, S, H, hd, I, smax, past, eps, zeros, stream);
-}
-
-extern "C" int ull_llama_decode_layers_w4_bf16(const ull_llama_layer_w4* layers, int64_t n_layers, const void* x_in, void* const* x_out, void* x_mid,
-                                               void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
-                                               const void* key_mask, void* const* k_cache, void* const* vt_cache, int64_t B, int64_t S, int64_t H,
-                                               int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
-    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask, BfCache{k_cache, vt_cache}, B, S, H,
-                               hd, I, smax, past, eps, zeros, stream);
-}
-
-extern "C" int ull_llama_decode_layers_w4_kv8_bf16(const ull_llama_layer_w4* layers, int64_t n_layers, const void* x_in, void* const* x_out,
-                                                   void* x_mid, void* xn, void* q, void* att, void* act, const void* rope_cos, const void* rope_sin,
-                                                   const void* key_mask, void* const* k8, void* const* vt8, void* const* k_scale,
-                                                   void* const* vt_scale, void* k_stage, void* vt_stage, int64_t B, int64_t S, int64_t H, int64_t hd,
-                                                   int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
-    return llama_decode_layers(layers, n_layers, x_in, x_out, x_mid, xn, q, att, act, rope_cos, rope_sin, key_mask,
-                               Kv8Cache{k8, vt8, k_scale, vt_scale, k_stage, vt_stage}, B, S, H, hd, I, smax, past, eps, zeros, stream);
-}
 #endif  // !ULL_ELEM_F16
 
 extern "C" int FN(ull_clip_layers_)(const ull_clip_layer* layers, int64_t n_layers, void* h, void* h_mid, void* y, void* qkv, void* att, void* f,
@@ -319,7 +264,8 @@ extern "C" int FN(ull_clip_layers_)(const ull_clip_layer* layers, int64_t n_laye
     const char* q = (const char*)qkv;
     for (int64_t l = 0; l < n_layers; ++l) {
         const ull_clip_layer& w = layers[l];
-        if (w.qkv.n != 3 * D || w.qkv.k != D || w.out.n != D || w.out.k != D || w.fc1.n != I || w.fc1.k != D || w.fc2.n != D || w.fc2.k != I)
+        if (w.qkv.n != 3 * D || w.qkv.k != D || w.out.n != D || w.out.k != D || w.fc1.n != I || w.fc1.k != D || w.fc2.n != D || w.fc2.k != I ||
+            quantized(&w.qkv) || quantized(&w.out) || quantized(&w.fc1) || quantized(&w.fc2))
             return ULL_ERR_ARG;
         TRY(FN(ull_layernorm_)(h, D, w.ln1_w, w.ln1_b, y, D, T, D, eps, stream));
         TRY(lin(y, D, &w.qkv, qkv, 3 * D, nullptr, 0, T, 0, sk, stream));
@@ -345,7 +291,8 @@ extern "C" int FN(ull_sam_blocks_)(const ull_sam_block* blocks, int64_t n_blocks
     for (int64_t i = 0; i < n_blocks; ++i) {
         const ull_sam_block& w = blocks[i];
         if (w.qkv.n != 3 * C || w.qkv.k != C || !w.qkv.bias || w.proj.n != C || w.proj.k != C || w.lin1.n != I || w.lin1.k != C || w.lin2.n != C ||
-            w.lin2.k != I || !w.rel_pos_h || !w.rel_pos_w || (w.window != 0 && w.window != 14))
+            w.lin2.k != I || !w.rel_pos_h || !w.rel_pos_w || (w.window != 0 && w.window != 14) || quantized(&w.qkv) || quantized(&w.proj) || quantized(&w.lin1) ||
+            quantized(&w.lin2))
             return ULL_ERR_ARG;
         TRY(FN(ull_layernorm_)(x, C, w.n1_w, w.n1_b, y, C, T, C, eps, stream));
         TRY(lin(y, C, &w.qkv, qkv, 3 * C, nullptr, 0, T, 0, sk, stream));

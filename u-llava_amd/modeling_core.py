@@ -1120,8 +1120,7 @@ class UllavaCoreForCausalLM(nn.Module):
         all_h = []
         I = cfg.intermediate_size
         coarse = None
-        w4 = pk.get("mxfp4", False)          # quantize_weights(): the Linear weights are ops.Fp8Weight / ops.Mxfp4Weight (ops.linear & co.
-        wq = pk.get("fp8", False) or w4      # dispatch on them)
+        wq = pk.get("fp8", False) or pk.get("mxfp4", False)      # quantize_weights(): the Linear weights are ops.Fp8Weight / ops.Mxfp4Weight
         kv8 = cache is not None and cache.kv_dtype is not None
         if kv8 and x.dtype != BF16:
             _check_kv_dtype(cache.kv_dtype, x.dtype)
@@ -1137,13 +1136,9 @@ class UllavaCoreForCausalLM(nn.Module):
         if coarse is not None:
             # one C call for the whole layer stack (csrc/layers.hip): the same launches as the loop below, bit-identical results
             stack = pk.get("_c_llama")
-            if stack is None and wq:
-                kind = _lib.LlamaLayerW4 if w4 else _lib.LlamaLayerW8
-                stack = pk["_c_llama"] = ops.LayerStack(kind, [dict(ln1=w["ln1"], ln2=w["ln2"], qkv=w["w_qkv"], o=w["w_o"], gu=w["w_gu"],
-                                                                    down=w["w_down"]) for w in pk["llama"]])
-            elif stack is None:
-                stack = pk["_c_llama"] = ops.LayerStack(_lib.LlamaLayer, [dict(ln1=w["ln1"], ln2=w["ln2"], qkv=(w["w_qkv"], None), o=(w["w_o"], None),
-                                                                                gu=(w["w_gu"], None), down=(w["w_down"], None)) for w in pk["llama"]])
+            if stack is None:
+                stack = pk["_c_llama"] = ops.LayerStack(_lib.LlamaLayer, [dict(ln1=w["ln1"], ln2=w["ln2"], qkv=w["w_qkv"], o=w["w_o"], gu=w["w_gu"],
+                                                                               down=w["w_down"]) for w in pk["llama"]])
             L = len(pk["llama"])
             if output_hidden_states:
                 outs = [torch.empty(T, D, device=dev, dtype=x.dtype) for _ in range(L)]

@@ -145,8 +145,12 @@ class Fp8Weight:
     """A Linear weight [N, K] as e4m3fn codes (uint8 [N, K]) plus one fp32 power-of-two scale per row: dequant = float(code) * scale, exactly
     a bf16 value.  `linear` / `linear_qkv_rope` / `linear_qkv_rope_append` take it in place of a bf16 weight and compute exactly what they
     compute on the dequantized bf16 weight (the fp8 forms of the GEMV / skinny kernels at decode shapes; dequantize + the bf16 GEMM at
-    prefill shapes).  Immutable once built."""
+    prefill shapes).  Immutable once built.
+
+    What the Linear dispatch needs of a quantized weight, here and on Mxfp4Weight: `fmt_name`, `wf` (its ULL_WF_* code), `route_pitch` (the row
+    pitch `_linear_route` sees), `c_args()` (the weight arguments of a *_wq_bf16 entry / the fields of an ull_linear) and `dequantize_into`."""
     __slots__ = ("codes", "scales")
+    fmt_name, wf = "fp8", _lib.WF_FP8
 
     def __init__(self, codes: torch.Tensor, scales: torch.Tensor):
         if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or scales.dtype != F32 or scales.shape != (codes.shape[0],):
@@ -164,6 +168,18 @@ class Fp8Weight:
     def nbytes(self) -> int:
         return self.codes.numel() + 4 * self.scales.numel()
 
+    @property
+    def route_pitch(self) -> int:
+        return self.codes.stride(0)          # code bytes = elements
+
+    def c_args(self):
+        """(wfmt, Q, ldq, scales, lds): lds is unused."""
+        return self.wf, self.codes.data_ptr(), self.codes.stride(0), self.scales.data_ptr(), 0
+
+    def dequantize_into(self, out: torch.Tensor, tiled: bool) -> None:
+        N, K = self.shape
+        _lib.call("ull_dequantize_rows_fp8_bf16", _p(self.codes), self.codes.stride(0), _p(self.scales), N, K, _p(out), int(tiled), _stream())
+
 
 def quantize_fp8(w: torch.Tensor) -> Fp8Weight:
     """Per-row e4m3 quantization of a bf16 weight [N, K] on the GPU (ull_quantize_rows_fp8_bf16): the row's scale is 2^s with s the smallest
@@ -179,16 +195,19 @@ def quantize_fp8(w: torch.Tensor) -> Fp8Weight:
     return Fp8Weight(codes, scales)
 
 
-def dequantize_fp8(q: Fp8Weight, tiled: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dequant(q) as bf16: [N, K] row-major, or (tiled) the ULL_EPI_W_TILED layout `tile_major` produces."""
+def dequantize(q, tiled: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dequant(q) of an Fp8Weight / Mxfp4Weight as bf16: [N, K] row-major, or (tiled) the ULL_EPI_W_TILED layout `tile_major` produces."""
     N, K = q.shape
     rows = -(-N // 256) * 256 if tiled else N
     if out is None:
         out = torch.empty(rows * K, device=q.device, dtype=BF16)
     elif out.dtype != BF16 or out.numel() < rows * K or not out.is_contiguous():
-        raise RuntimeError("u-llava_amd.dequantize_fp8: `out` must be a contiguous bf16 buffer of at least the result's size")
-    _lib.call("ull_dequantize_rows_fp8_bf16", _p(q.codes), q.codes.stride(0), _p(q.scales), N, K, _p(out), int(tiled), _stream())
+        raise RuntimeError(f"u-llava_amd.dequantize_{q.fmt_name}: `out` must be a contiguous bf16 buffer of at least the result's size")
+    q.dequantize_into(out, tiled)
     return out[:rows * K].view(rows // 256, K // 64, 256, 64) if tiled else out[:N * K].view(N, K)
+
+
+dequantize_fp8 = dequantize_mxfp4 = dequantize
 
 
 # ---- MXFP4 weight-only storage (UllavaCoreForCausalLM.quantize_weights("mxfp4")) -------------------------------------------------------
@@ -220,6 +239,7 @@ class Mxfp4Weight:
     of each row permuted, see include/ullava_hip.h.  `linear` / `linear_qkv_rope` / `linear_qkv_rope_append` take it in place of a bf16
     weight and compute exactly what they compute on the dequantized bf16 weight.  Immutable once built."""
     __slots__ = ("codes", "scales", "K")
+    fmt_name, wf = "mxfp4", _lib.WF_MXFP4
 
     def __init__(self, codes: torch.Tensor, scales: torch.Tensor, K: int):
         if (codes.dtype != torch.uint8 or codes.dim() != 2 or K % 32 or codes.shape[1] != K // 2 or not codes.is_contiguous() or
@@ -241,6 +261,19 @@ class Mxfp4Weight:
 
     def nbytes(self) -> int:
         return self.codes.numel() + self.scales.numel()
+
+    @property
+    def route_pitch(self) -> int:
+        return self.K                        # its rows are always whole
+
+    def c_args(self):
+        """(wfmt, Q, ldq, scales, lds)."""
+        return self.wf, self.codes.data_ptr(), self.codes.stride(0), self.scales.data_ptr(), self.scales.stride(0)
+
+    def dequantize_into(self, out: torch.Tensor, tiled: bool) -> None:
+        N, K = self.shape
+        _lib.call("ull_dequantize_rows_mxfp4_bf16", _p(self.codes), self.codes.stride(0), _p(self.scales), self.scales.stride(0), N, K, _p(out),
+                  int(tiled), 1, _stream())
 
     def to_standard(self):
         """(codes uint8 [N, K / 2], scales uint8 [N, K / 32]) in the standard layout."""
@@ -279,19 +312,6 @@ def quantize_mxfp4(w: torch.Tensor) -> Mxfp4Weight:
     return Mxfp4Weight(codes, scales, K)
 
 
-def dequantize_mxfp4(q: Mxfp4Weight, tiled: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dequant(q) as bf16: [N, K] row-major, or (tiled) the ULL_EPI_W_TILED layout `tile_major` produces."""
-    N, K = q.shape
-    rows = -(-N // 256) * 256 if tiled else N
-    if out is None:
-        out = torch.empty(rows * K, device=q.device, dtype=BF16)
-    elif out.dtype != BF16 or out.numel() < rows * K or not out.is_contiguous():
-        raise RuntimeError("u-llava_amd.dequantize_mxfp4: `out` must be a contiguous bf16 buffer of at least the result's size")
-    _lib.call("ull_dequantize_rows_mxfp4_bf16", _p(q.codes), q.codes.stride(0), _p(q.scales), q.scales.stride(0), N, K, _p(out), int(tiled), 1,
-              _stream())
-    return out[:rows * K].view(rows // 256, K // 64, 256, 64) if tiled else out[:N * K].view(N, K)
-
-
 QuantWeight = (Fp8Weight, Mxfp4Weight)      # the quantized weight types the Linear dispatch rule takes beside a 16-bit tensor
 
 _WQ_SCRATCH = {}     # (device, stream) -> the bf16 buffer prefill-shape fp8 / mxfp4 Linears dequantize into (reused in stream order)
@@ -312,32 +332,17 @@ def _wq_dequant_for_gemm(q, M: int):
     N, K = q.shape
     tiled = _big(M, N, K) and K % 64 == 0
     buf = _wq_scratch(q.device, _stream(), (-(-N // 256) * 256 if tiled else N) * K)
-    wd = (dequantize_mxfp4 if isinstance(q, Mxfp4Weight) else dequantize_fp8)(q, tiled=tiled, out=buf)
+    wd = dequantize(q, tiled=tiled, out=buf)
     if tiled:
         return buf[:N * K].view(N, K), wd          # (the row-major view only carries the shape: the GEMM reads the tile-major copy)
     return wd, None
 
 
-def _fmt_name(w) -> str:
-    return "mxfp4" if isinstance(w, Mxfp4Weight) else "fp8"
-
-
-def _route_pitch(w) -> int:
-    """the row pitch `_linear_route` sees: elements for a 16-bit weight, code bytes (= elements) for an Fp8Weight, K for an Mxfp4Weight
-    (its rows are always whole)."""
-    if isinstance(w, Mxfp4Weight):
-        return w.K
-    return (w.codes if isinstance(w, Fp8Weight) else w).stride(0)
-
-
 def _weight_args(w):
     """(entry suffix, weight arguments) of a decode-shape entry (skinny GEMM, GEMV, GEMV + RMSNorm, q|k|v + RoPE + cache append): a 16-bit
-    weight passes (pointer, row pitch), an Fp8Weight (codes, row pitch, scales) to the *_w8_bf16 form, an Mxfp4Weight (codes, row pitch,
-    scales, row pitch) to the *_w4_bf16 form."""
-    if isinstance(w, Mxfp4Weight):
-        return "w4_bf16", (w.codes.data_ptr(), w.codes.stride(0), w.scales.data_ptr(), w.scales.stride(0))
-    if isinstance(w, Fp8Weight):
-        return "w8_bf16", (w.codes.data_ptr(), w.codes.stride(0), w.scales.data_ptr())
+    weight passes (pointer, row pitch), a quantized one (format, codes, row pitch, scales, row pitch) to the *_wq_bf16 form."""
+    if isinstance(w, QuantWeight):
+        return "wq_bf16", w.c_args()
     return _SFX[w.dtype], (w.data_ptr(), w.stride(0))
 
 
@@ -449,7 +454,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     w may be an `Fp8Weight` or an `Mxfp4Weight` (bf16 x only): the same result as on its dequantized bf16 weight, bit for bit."""
     wq = isinstance(w, QuantWeight)
     if wq and x.dtype != BF16:
-        raise RuntimeError(f"u-llava_amd.linear: {_fmt_name(w)} weights need bf16 activations, got {x.dtype}")
+        raise RuntimeError(f"u-llava_amd.linear: {w.fmt_name} weights need bf16 activations, got {x.dtype}")
     _chk(x, "x")
     if not wq:
         _chk(w, "w", x.dtype)
@@ -464,7 +469,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         route, rms_first = "f32", True
         out_f32 = bias_after_rounding = False
     else:
-        route, rms_first = _linear_route(M, N, K, _route_pitch(w), tune)
+        route, rms_first = _linear_route(M, N, K, w.route_pitch if wq else w.stride(0), tune)
         if wq and route == "gemm":
             # prefill shapes: dequantize into the stream's scratch, then the bf16 flow on dequant(w)
             w, wt = _wq_dequant_for_gemm(w, M)
@@ -539,7 +544,7 @@ def linear_qkv_rope(x: torch.Tensor, w: torch.Tensor, rope_cos: torch.Tensor, ro
     wt = None
     if isinstance(w, QuantWeight):
         if x.dtype != BF16:
-            raise RuntimeError(f"u-llava_amd.linear_qkv_rope: {_fmt_name(w)} weights need bf16 activations, got {x.dtype}")
+            raise RuntimeError(f"u-llava_amd.linear_qkv_rope: {w.fmt_name} weights need bf16 activations, got {x.dtype}")
         w, wt = _wq_dequant_for_gemm(w, _rows(x)[0])
     _chk(x, "x"); _chk(w, "w", x.dtype); _chk(rope_cos, "rope_cos", x.dtype); _chk(rope_sin, "rope_sin", x.dtype)
     M, ldx = _rows(x)
@@ -747,7 +752,7 @@ def linear_qkv_rope_append(x: torch.Tensor, w_qkv: torch.Tensor, rope_cos: torch
     if not isinstance(w_qkv, QuantWeight):
         _chk(w_qkv, "w_qkv", x.dtype)
     elif x.dtype != BF16:
-        raise RuntimeError(f"u-llava_amd.linear_qkv_rope_append: {_fmt_name(w_qkv)} weights need bf16 activations, got {x.dtype}")
+        raise RuntimeError(f"u-llava_amd.linear_qkv_rope_append: {w_qkv.fmt_name} weights need bf16 activations, got {x.dtype}")
     _chk(x, "x"); _chk(rope_cos, "rope_cos", x.dtype); _chk(rope_sin, "rope_sin", x.dtype)
     _chk(k_cache, "k_cache", x.dtype); _chk(vt_cache, "vt_cache", x.dtype)
     T, K = x.shape
@@ -1381,21 +1386,41 @@ def coarse_ok() -> bool:
 
 
 class LayerStack:
-    """`kind`: _lib.LlamaLayer / LlamaLayerW8 / LlamaLayerW4 / ClipLayer / SamBlock; `layers`: one dict per layer, field name -> tensor (pointer
-    fields) or (weight, bias-or-None) (ull_linear fields) or Fp8Weight (ull_linear_w8 fields) or Mxfp4Weight (ull_linear_w4 fields) or int
-    (plain fields)."""
+    """`kind`: _lib.LlamaLayer / ClipLayer / SamBlock; `layers`: one dict per layer, field name -> tensor (pointer fields) or int (plain fields) or,
+    for an ull_linear field, (weight, bias-or-None) or a bare weight: a 16-bit tensor or an Fp8Weight / Mxfp4Weight."""
 
     def __init__(self, kind, layers):
         self.kind, self.layers = kind, layers
         self.arr = (kind * len(layers))()
-        self._lin_fields = [n for n, t in kind._fields_ if t is _lib.Linear]
+        lin = [(d, n) for d in layers for n, t in kind._fields_ if t is _lib.Linear]
+        # the fields that hold a 16-bit weight, whose re-binding and in-place updates `refresh` follows; a quantized weight is immutable: nothing of
+        # it enters the fingerprint (and no version counter is read)
+        self._w16 = [(d, n) for d, n in lin if not isinstance(d[n][0] if type(d[n]) is tuple else d[n], QuantWeight)]
+        self.quantized = len(self._w16) < len(lin)
         self._seen = None
         self.refresh()
 
     def _fingerprint(self):
         # (address, version) of every weight: an in-place update (optimizer step, load_state_dict) bumps the version, and only then is the
         # tile-major copy re-made (`_tiled_of`, in refresh below) -- between updates the copy's address cannot change
-        return [v for d in self.layers for n in self._lin_fields for v in (d[n][0].data_ptr(), d[n][0]._version)]
+        fp = []
+        for d, n in self._w16:
+            w = d[n]
+            if type(w) is tuple:
+                w = w[0]
+            fp += (w.data_ptr(), w._version)
+        return fp
+
+    @staticmethod
+    def _linear(v):
+        w, b = v if type(v) is tuple else (v, None)
+        if isinstance(w, QuantWeight):
+            wf, q, ldq, scales, lds = w.c_args()
+            return _lib.Linear(q, None, None, w.shape[0], w.shape[1], ldq, wf, scales, lds)
+        if w.dim() != 2 or w.stride(1) != 1:
+            raise RuntimeError("u-llava_amd: coarse entries need row-major 2-D weights")
+        wt = _tiled_of(w)
+        return _lib.Linear(w.data_ptr(), None if wt is None else wt.data_ptr(), _p(b), w.shape[0], w.shape[1], w.stride(0))
 
     def refresh(self):
         fp = self._fingerprint()
@@ -1405,18 +1430,8 @@ class LayerStack:
             s = self.arr[i]
             for n, t in self.kind._fields_:
                 v = d[n]
-                if t is _lib.LinearW4:
-                    # an Mxfp4Weight: immutable like an Fp8Weight
-                    setattr(s, n, _lib.LinearW4(v.codes.data_ptr(), v.scales.data_ptr(), v.shape[0], v.shape[1], v.codes.stride(0), v.scales.stride(0)))
-                elif t is _lib.LinearW8:
-                    # an Fp8Weight: immutable, so nothing of it enters the fingerprint (and no version counter is read)
-                    setattr(s, n, _lib.LinearW8(v.codes.data_ptr(), v.scales.data_ptr(), v.shape[0], v.shape[1], v.codes.stride(0)))
-                elif t is _lib.Linear:
-                    w, b = v
-                    if w.dim() != 2 or w.stride(1) != 1:
-                        raise RuntimeError("u-llava_amd: coarse entries need row-major 2-D weights")
-                    wt = _tiled_of(w)
-                    setattr(s, n, _lib.Linear(w.data_ptr(), None if wt is None else wt.data_ptr(), _p(b), w.shape[0], w.shape[1], w.stride(0)))
+                if t is _lib.Linear:
+                    setattr(s, n, self._linear(v))
                 elif isinstance(v, int):
                     setattr(s, n, v)
                 else:
@@ -1457,12 +1472,10 @@ def llama_prefill_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos,
 
 def llama_decode_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos, rope_sin, key_mask, k_ptrs, vt_ptrs, B: int, S: int, H: int, hd: int,
                         I: int, smax: int, past: int, eps: float, kv8=None):
-    """One generation step through all layers (T = B*S <= 4).  k_ptrs / vt_ptrs: ctypes void* arrays of the per-layer caches.  A stack of
-    _lib.LlamaLayerW8 (fp8 weights, bf16 activations) goes to ull_llama_decode_layers_w8_bf16, one of _lib.LlamaLayerW4 (mxfp4 weights) to
-    ull_llama_decode_layers_w4_bf16.  kv8 = (k8, vt8, k_scale, vt_scale pointer
-    arrays, k_stage, vt_stage) of an fp8 cache (KVCache.c_ptrs): the *_kv8_bf16 entries, k_ptrs / vt_ptrs unused."""
-    wq = {_lib.LlamaLayerW8: "w8_", _lib.LlamaLayerW4: "w4_"}.get(stack.kind)       # the quantized-weight forms of the entry
-    _chk(x_in, "x_in", BF16 if (wq or kv8 is not None) else None)
+    """One generation step through all layers (T = B*S <= 4).  k_ptrs / vt_ptrs: ctypes void* arrays of the per-layer caches.  The stack's
+    Linears may be quantized (bf16 activations).  kv8 = (k8, vt8, k_scale, vt_scale pointer arrays, k_stage, vt_stage) of an fp8 cache
+    (KVCache.c_ptrs): ull_llama_decode_layers_kv8_bf16, k_ptrs / vt_ptrs unused."""
+    _chk(x_in, "x_in", BF16 if (stack.quantized or kv8 is not None) else None)
     T, D = x_in.shape
     dev, dt = x_in.device, x_in.dtype
     scratch = torch.empty(T * (4 * D + 2 * max(D, I)), device=dev, dtype=dt)
@@ -1471,11 +1484,11 @@ def llama_decode_layers(stack: LayerStack, x_in: torch.Tensor, x_out, rope_cos, 
     act = scratch[3 * T * D + T * max(D, I):3 * T * D + T * max(D, I) + T * I]
     if kv8 is not None:
         k8, vt8, ks, vs, k_stage, vt_stage = kv8
-        _lib.call("ull_llama_decode_layers_" + (wq or "") + "kv8_bf16", stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out),
+        _lib.call("ull_llama_decode_layers_kv8_bf16", stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out),
                   _p(x_mid), _p(xn), _p(q), _p(att), _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k8, vt8, ks, vs, _p(k_stage), _p(vt_stage),
                   B, S, H, hd, I, smax, past, float(eps), _zeros(dev).data_ptr(), _stream())
         return
-    _lib.call("ull_llama_decode_layers_" + (wq + "bf16" if wq else _SFX[dt]), stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid),
+    _lib.call("ull_llama_decode_layers_" + _SFX[dt], stack.refresh(), len(stack.layers), _p(x_in), _ptr_array(x_out), _p(x_mid),
               _p(xn), _p(q), _p(att), _p(act), _p(rope_cos), _p(rope_sin), _p(key_mask), k_ptrs, vt_ptrs, B, S, H, hd, I, smax, past, float(eps),
               _zeros(dev).data_ptr(), _stream())
 
