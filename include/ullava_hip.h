@@ -167,6 +167,21 @@ int ull_gemv_qkv_rope_append_wq_bf16(const void* X, int64_t ldx, const void* nor
                                      void* k_cache, void* vt_cache, int64_t B, int64_t S, int64_t H, int64_t hd, int64_t K, int64_t smax, int64_t past,
                                      void* stream);
 
+/* ---- FP8 activations on FP8 weights: the W8A8 prefill Linear (bf16 build only: no *_f16 twin) -----------------------------------------
+ * UllavaCoreForCausalLM.quantize_weights("fp8_e4m3", activations="fp8_e4m3"): at prefill shapes the four LLaMA-layer Linears quantize their
+ * input rows with ull_quantize_rows_fp8_bf16 (one scale 2^t_m per token) and multiply codes by codes on the block-scaled matrix instruction
+ * (v_mfma_scale_f32_16x16x128_f8f6f4, e4m3 A and B, unit block scales):
+ *   acc[m, n] = sum_k float(Xq[m, k]) * float(Q[n, k])     every product exact in fp32; fp32 accumulation in ascending 128-code K-tiles,
+ *                                                          the same order for every M, N and batch (K is never split)
+ *   y[m, n]   = acc[m, n] * 2^(t_m + s_n)                  exact
+ * followed by ull_gemm_bf16's epilogue on y with its rounding points.  The contract is ull_gemm_bf16's with (X, ldx) replaced by
+ * (Xq, ldxq, x_scales) and (W, ldw) by (Q, ldq, w_scales): codes uint8, row pitches in bytes and multiples of 16, base pointers 16-byte
+ * aligned, scales fp32 powers of two [M] / [N]; K % 128 == 0 (pad with zero codes: exact).  flags: ULL_EPI_RESID, ULL_EPI_SWIGLU (Q rows in
+ * the gate|up interleave), ULL_EPI_OUT_F32 only -- any other bit, or a null pointer: ULL_ERR_ARG; a shape or alignment it cannot take:
+ * ULL_ERR_SHAPE; nothing is launched in either case. */
+int ull_gemm_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, void* C, int64_t ldc,
+                       const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+
 /* ---- FP8 (e4m3) KV cache (bf16 build only) ------------------------------------------------------------------------------------------
  * KVCache(kv_dtype="fp8_e4m3") keeps, per layer, K codes [B, H, smax, hd] and V^T codes [B, H, hd, smax] (the key-permuted slot order of
  * ull_transpose_v) plus one fp32 scale 2^s per (batch, head, position) for the K row (k_scale [B, H, smax], by key) and one for the V column

@@ -533,6 +533,126 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(GemmArgs p) {
     staged_epilogue<SWIGLU, 4, ROPE>(p, acc, smem + wave * (64 * 144), lane, m0 + wm * 64, n0 + wn * 64, smem + (wave ^ 1) * (64 * 144));
 }
 
+#ifndef ULL_ELEM_F16
+// ---- W8A8: e4m3 activations x e4m3 weights on the block-scaled matrix instruction (ull_gemm_a8w8_bf16, bf16 build only) --------------
+// y[m, n] = 2^(t_m + s_n) * sum_k float(xq[m, k]) * float(wq[n, k]): both operands are e4m3fn codes with one power-of-two scale per row
+// (ull_quantize_rows_fp8_bf16), every product is exact in fp32, and the row scales are applied to the fp32 sum in the epilogue (exact).
+// The kernel is gemm128_kernel with bytes for elements: the same 128 x 128 tile on 4 waves, the same lane-linear LDS image of 128-byte rows
+// filled by 16-byte LDS-DMA pieces with the chunk index XOR-swizzled by (row & 7), the same one-barrier K-step -- a K-tile is 128 codes
+// instead of 64 bf16 -- and, because v_mfma_scale_f32_16x16x128_f8f6f4 has the C/D layout of the 16x16x32 form, the same staged_epilogue.
+// One K-tile is ONE matrix instruction per accumulator: lane l feeds row (l & 15) and the 32 consecutive codes [32 (l >> 4), +32) of the
+// K-tile (8 VGPRs = two 16-byte LDS reads) for both operands; the E8M0 scale operands are the constant 127 (2^0).  The map was found with
+// one-hot integer data (tools/probes/mfma_scale_lane_map.hip); the kernel only relies on A and B pairing the same (lane >> 4, byte).
+// K is walked in order by every block and never split, so the fp32 summation order of an output row depends on nothing but K.
+struct A8Args {
+    const uint8_t* Xq; const uint8_t* Wq;
+    const float* xs; const float* ws;                 // 2^t_m [M], 2^s_n [N]
+    long ldxq, ldq;                                   // row pitches in bytes
+};
+using i32x8_t = __attribute__((ext_vector_type(8))) int;
+constexpr int BK8 = 128;                              // codes per K-tile = bytes per LDS row: TILE_BYTES / BUF_BYTES / GEMM_LDS as above
+
+template <bool SWIGLU>
+__global__ __launch_bounds__(256, 2) void gemm128_a8w8_kernel(GemmArgs p, A8Args q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(BM * BK8 == TILE_BYTES, "the fp8 tile has the bf16 tile's bytes");
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = wave & 1, wm = wave >> 1;
+
+    int bid = blockIdx.x;                              // XCD-contiguous chunks, grouped raster inside (as gemm128_kernel)
+    {
+        const int nwg = p.nbm * p.nbn;
+        const int qq = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
+        bid = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + k;
+    }
+    const int per_group = GROUP_M * p.nbn;
+    const int gid = bid / per_group;
+    const int first_m = gid * GROUP_M;
+    const int gsz = min(p.nbm - first_m, GROUP_M);
+    const int bm = first_m + (bid % per_group) % gsz;
+    const int bn = (bid % per_group) / gsz;
+    const int m0 = bm * BM, n0 = bn * BN;
+
+    // wave w, step i stages rows (w*4+i)*8 .. +8 of each tile; lane -> (row l>>3, physical chunk l&7) fetches LOGICAL chunk (l&7) ^ (row&7);
+    // rows past M / N re-read the last row (their outputs are never stored)
+    const int srow = lane >> 3;
+    const int schunk = (lane & 7) ^ srow;
+    const uint8_t* xsrc[4];
+    const uint8_t* wsrc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = (wave * 4 + i) * 8 + srow;
+        xsrc[i] = q.Xq + (long)min(m0 + r, p.M - 1) * q.ldxq + schunk * 16;
+        wsrc[i] = q.Wq + (long)min(n0 + r, p.N - 1) * q.ldq + schunk * 16;
+    }
+    const int stage_off = wave * 4 * 8 * BK8;
+    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
+    auto stage = [&](int buf, int kt) {
+        const uint32_t bx = lds_base + buf * BUF_BYTES + stage_off;
+        const uint32_t bw = bx + TILE_BYTES;
+        const long ko = (long)kt * BK8;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            glds16(xsrc[i] + ko, bx + i * 1024);
+            glds16(wsrc[i] + ko, bw + i * 1024);
+        }
+    };
+
+    // fragment: row (l & 15) of a 16-row group, logical chunks 2 (l >> 4) and 2 (l >> 4) + 1
+    const int frow = lane & 15, fgrp = lane >> 4;
+    const int swz0 = ((2 * fgrp) ^ (lane & 7)) << 4, swz1 = ((2 * fgrp + 1) ^ (lane & 7)) << 4;
+    const int xrow_off = (wm * 64 + frow) * BK8;
+    const int wrow_off = TILE_BYTES + (wn * 64 + frow) * BK8;
+
+    f32x4_t acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    const int nk = p.K / BK8;
+    stage(0, 0);
+    for (int kt = 0; kt < nk; ++kt) {
+        const int cur = kt & 1;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile kt: the only DMA in flight for this wave
+        __builtin_amdgcn_s_barrier();                      // tile kt is in LDS; buffer cur^1 (tile kt-1) has been consumed by every wave
+        if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
+        const char* base = smem + cur * BUF_BYTES;
+        i32x8_t wf[4], xf[4];
+        auto frag = [&](int off) {
+            const uint4 lo = *(const uint4*)(base + off + swz0), hi = *(const uint4*)(base + off + swz1);
+            return i32x8_t{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+        };
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wf[i] = frag(wrow_off + i * 16 * BK8);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xf[j] = frag(xrow_off + j * 16 * BK8);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)      // cbsz = blgp = 0: e4m3 A and B; scale bytes 127 = 2^0
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[i], xf[j], acc[i][j], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+    }
+
+    // acc[i][j][r] = D[n = n0 + wn*64 + i*16 + 4*(l>>4) + r][m = m0 + wm*64 + j*16 + (l&15)]: times 2^(t_m + s_n), one exact v_ldexp_f32
+    int ex[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ex[j] = ilogbf(q.xs[min(m0 + wm * 64 + j * 16 + frow, p.M - 1)]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ew = ilogbf(q.ws[min(n0 + wn * 64 + i * 16 + 4 * fgrp + r, p.N - 1)]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j][r] = ldexpf(acc[i][j][r], ew + ex[j]);
+        }
+    __builtin_amdgcn_s_barrier();                          // every wave has consumed the last K-tile: LDS is free
+    staged_epilogue<SWIGLU, 4>(p, acc, smem + wave * (64 * 144), lane, m0 + wm * 64, n0 + wn * 64);
+}
+#endif  // !ULL_ELEM_F16
+
 
 // ---- fused ViT patchify: Conv2d(C, N, kernel = stride = ps) as a GEMM whose A tile is DMA'd straight from the image ----------
 // reference: transformers CLIPVisionEmbeddings.patch_embedding (models/ullava_core.py:131-159 encode_image) and SAM PatchEmbed
@@ -1770,6 +1890,10 @@ static int gemm_device_state(int* n_cu_out) {
         (void)hipFuncSetAttribute((const void*)gemm128_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
         (void)hipFuncSetAttribute((const void*)gemm128_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
         (void)hipFuncSetAttribute((const void*)patchify_gemm_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
+#ifndef ULL_ELEM_F16
+        (void)hipFuncSetAttribute((const void*)gemm128_a8w8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
+        (void)hipFuncSetAttribute((const void*)gemm128_a8w8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
+#endif
         (void)hipFuncSetAttribute((const void*)big::patchify_strip_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (288 + 256) * 128 + 256);
         (void)hipFuncSetAttribute((const void*)big::patchify_strip_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 256) * 128 + 256);
         n_cu[dev] = n;                   // last: a racing first call on another thread repeats the (idempotent) attribute calls
@@ -1903,6 +2027,38 @@ extern "C" int ULL_FN(ull_gemm_)(const void* X, int64_t ldx, const void* W, int6
                              int64_t M, int64_t N, int64_t K, int flags, void* ws, int64_t ws_bytes, void* stream) {
     return gemm_dispatch(X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, ws, ws_bytes, stream, nullptr, nullptr, 0);
 }
+
+#ifndef ULL_ELEM_F16
+// W8A8 Linear (bf16 build only): C[M, N] = epilogue(2^(t_m + s_n) * sum_k float(Xq[m, k]) * float(Q[n, k])), both operands e4m3fn codes with
+// one fp32 power-of-two scale per row (ull_quantize_rows_fp8_bf16 on the activation rows and on the weight rows).  ull_gemm_bf16's contract
+// with (X, ldx) -> (Xq, ldxq, x_scales) and (W, ldw) -> (Q, ldq, w_scales); no bias, no workspace (K is never split).
+extern "C" int ull_gemm_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, void* C,
+                                  int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
+    if (!Xq || !x_scales || !Q || !w_scales || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if (flags & ~(EPI_RESID | EPI_SWIGLU | EPI_OUT_F32)) return ULL_ERR_ARG;
+    if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
+    if (K % BK8 != 0 || (ldxq & 15) || (ldq & 15) || ldxq < K || ldq < K || (((uintptr_t)Xq | (uintptr_t)Q) & 15)) return ULL_ERR_SHAPE;   // 16-byte DMA pieces
+    if ((flags & EPI_SWIGLU) && (N & 31)) return ULL_ERR_SHAPE;
+    if (ldc < ((flags & EPI_SWIGLU) ? N / 2 : N) || ((flags & EPI_RESID) && ldr < ((flags & EPI_SWIGLU) ? N / 2 : N))) return ULL_ERR_SHAPE;
+    if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return ULL_ERR_SHAPE;
+    int n_cu = 0;
+    if (const int rc = gemm_device_state(&n_cu)) return rc;
+    GemmArgs a;
+    a.X = nullptr; a.W = nullptr; a.C = C; a.bias = nullptr; a.R = (const elem_t*)R;
+    a.ldx = 0; a.ldw = 0; a.ldc = ldc; a.ldr = ldr;
+    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.flags = flags;
+    a.nbm = (int)((M + BM - 1) / BM); a.nbn = (int)((N + BN - 1) / BN);
+    a.t_full = 0; a.sk = 1; a.ws = nullptr; a.group_m = GROUP_M;
+    a.rope_cos = a.rope_sin = nullptr; a.rope_cols = 0;
+    if ((long)a.nbm * a.nbn > (1L << 30)) return ULL_ERR_SHAPE;
+    const A8Args q{(const uint8_t*)Xq, (const uint8_t*)Q, (const float*)x_scales, (const float*)w_scales, (long)ldxq, (long)ldq};
+    if (flags & EPI_SWIGLU)
+        hipLaunchKernelGGL(gemm128_a8w8_kernel<true>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
+    else
+        hipLaunchKernelGGL(gemm128_a8w8_kernel<false>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
+    return ull_check_launch();
+}
+#endif  // !ULL_ELEM_F16
 
 // The fused q|k|v projection of LlamaAttention (hf modeling_llama.py:214-277): C[M, N] = X W^T (no bias) with
 // apply_rotary_pos_emb applied in the epilogue to the output columns [0, rope_cols) = the q and k heads (head_dim must be 128; the v

@@ -406,6 +406,7 @@ def check_sampler(sampler) -> bool:
 class UllavaCoreForCausalLM(nn.Module):
     config_class = UllavaCoreConfig
     weight_quantization = None             # "fp8_e4m3" / "mxfp4" after quantize_weights()
+    activation_quantization = None         # "fp8_e4m3" after quantize_weights("fp8_e4m3", activations="fp8_e4m3")
 
     def __init__(self, config: UllavaCoreConfig, device=None, dtype=BF16):
         super().__init__()
@@ -598,7 +599,7 @@ class UllavaCoreForCausalLM(nn.Module):
                     mod.weight.data = torch.empty(0, device=mod.weight.device, dtype=mod.weight.dtype)
         return self
 
-    def quantize_weights(self, fmt: str = "fp8_e4m3"):
+    def quantize_weights(self, fmt: str = "fp8_e4m3", activations: Optional[str] = None):
         """FP8 (e4m3) weight-only inference: store every LLaMA Linear (q/k/v/o/gate/up/down_proj of every layer) and lm_head as e4m3fn
         codes with one power-of-two fp32 scale per output row (ops.quantize_fp8); activations stay bf16, accumulation fp32.  Everything
         else (embeddings, norms, CLIP, projector) keeps its dtype.  Returns self.
@@ -614,12 +615,31 @@ class UllavaCoreForCausalLM(nn.Module):
         and block of 32 consecutive K elements, 4.25 bits per weight.  dequant = e2m1 * 2^s is a bf16 value too, so the same twin rule holds
         bit for bit, through the mxfp4 forms of the same kernels; everything said above about the fp8 model applies.  Weight-only
         round-to-nearest without calibration: the weights lose far more precision than with fp8 (profiles/mxfp4_decode.txt).  A model
-        quantized to one format cannot be re-quantized to the other."""
+        quantized to one format cannot be re-quantized to the other.
+
+        activations="fp8_e4m3" (with fmt="fp8_e4m3" only; default None = everything above, unchanged): FP8 activations in the LLaMA prefill
+        (W8A8, DESIGN f8).  Wherever the Linear dispatch rule sends one of the four LLaMA-layer Linears (q|k|v, o_proj, gate|up, down_proj) to
+        the tiled GEMM -- more than 16 rows, or 5 to 16 rows against a small weight -- its input rows are quantized to e4m3 with one
+        power-of-two scale per token (the weights' own rule) and the product runs on the fp8 matrix instruction from the resident codes
+        (ops.linear_a8w8): no dequantized copy of the weight, twice the bf16 matrix rate.  The q|k|v projection is followed by the stand-alone
+        RoPE kernel.  Decode-shape launches (GEMV / skinny) and lm_head stay W8A16, bit-identical to the weight-only model.  So this model is
+        NOT the bit-exact twin of a bf16 model any more (the activations lose precision: profiles/a8w8_prefill.txt), and cached and uncached
+        generation can differ: with a KV cache the prompt is prefilled in A8 and every later token is a W8A16 decode step, while
+        use_cache=False re-runs the whole sequence in A8 each step.  Sample b of a batch still equals its single-sample run bit for bit
+        when both run at prefill shapes.  May be called on a model that is already fp8-quantized to switch the mode on; no weight changes.
+        `model.activation_quantization` reports the mode."""
         if fmt not in ("fp8_e4m3", "mxfp4"):
             raise ValueError(f"quantize_weights: unknown format {fmt!r} (supported: 'fp8_e4m3', 'mxfp4')")
+        if activations not in (None, "fp8_e4m3"):
+            raise ValueError(f"quantize_weights: unknown activation format {activations!r} (supported: None, 'fp8_e4m3')")
         mx = fmt == "mxfp4"
+        if activations is not None and mx:
+            raise NotImplementedError("quantize_weights('mxfp4', activations='fp8_e4m3'): fp8 activations are implemented on fp8_e4m3 weights "
+                                      "only (there is no mxfp4 x fp8 prefill kernel)")
         if self.weight_quantization is not None:
             if self.weight_quantization == fmt:
+                if activations is not None:
+                    self.activation_quantization = activations
                 return self
             self._refuse_quantized(f"quantize_weights({fmt!r})")
         if self.dtype != BF16:
@@ -683,6 +703,7 @@ class UllavaCoreForCausalLM(nn.Module):
             self._reset_alias_slots()
             _clear_transposes()
         self.weight_quantization = fmt
+        self.activation_quantization = activations
         return self
 
     # The version tuples are read on EVERY forward (a decode step too): walking the module tree for them cost 0.5 ms of host time per step
@@ -1116,11 +1137,23 @@ class UllavaCoreForCausalLM(nn.Module):
         # (that kernel stages the T x D activations in 32 KB of LDS: LLaMA-7B at T = 4 is exactly the limit; wider models / more rows take the
         # stand-alone RMSNorm + RoPE-append kernels below)
         fuse_append = cache is not None and past > 0 and T <= 4 and hd % 2 == 0 and D % 8 == 0 and T * D * 2 <= 32768 and not f32
+        a8 = self.activation_quantization is not None and pk.get("fp8", False)      # quantize_weights(activations=): W8A8 at GEMM shapes
+        if a8 and fuse_rope and pk["llama"] and ops.a8w8_takes(T, 3 * D, D, pk["llama"][0]["w_qkv"]):
+            fuse_rope = False                # A8 q|k|v: the plain projection, then the stand-alone RoPE kernel
         rope_cs = ops.rope_table(pos, inv_freq, x.dtype) if (fuse_rope or fuse_append) else None
         all_h = []
         I = cfg.intermediate_size
         coarse = None
         wq = pk.get("fp8", False) or pk.get("mxfp4", False)      # quantize_weights(): the Linear weights are ops.Fp8Weight / ops.Mxfp4Weight
+
+        def lin(x_, w_, residual=None, swiglu=False, rms_w=None):
+            """A LLaMA-layer Linear: fp8 activations (quantize_weights(activations=)) wherever the dispatch rule takes the tiled GEMM."""
+            if a8 and ops.a8w8_takes(x_.shape[0], w_.shape[0], w_.shape[1], w_):
+                if rms_w is not None:
+                    x_ = ops.rmsnorm(x_, rms_w, cfg.rms_norm_eps)
+                return ops.linear_a8w8(x_, w_, residual=residual, swiglu=swiglu)
+            return ops.linear(x_, w_, residual=residual, swiglu=swiglu, rms_w=rms_w, rms_eps=cfg.rms_norm_eps)
+
         kv8 = cache is not None and cache.kv_dtype is not None
         if kv8 and x.dtype != BF16:
             _check_kv_dtype(cache.kv_dtype, x.dtype)
@@ -1178,7 +1211,7 @@ class UllavaCoreForCausalLM(nn.Module):
             if fuse_rope:
                 qkv = ops.linear_qkv_rope(ops.rmsnorm(x, w["ln1"], cfg.rms_norm_eps), w["w_qkv"], rope_cs[0], rope_cs[1], 2 * D, hd)
             else:
-                qkv = ops.linear(x, w["w_qkv"], rms_w=w["ln1"], rms_eps=cfg.rms_norm_eps)      # input_layernorm -> q|k|v
+                qkv = lin(x, w["w_qkv"], rms_w=w["ln1"])                                       # input_layernorm -> q|k|v
             att = torch.empty(T, D, device=dev, dtype=x.dtype)
             if decode:
                 # generation step: RoPE + cache append in one launch, then the split-key attention over the cache
@@ -1207,9 +1240,9 @@ class UllavaCoreForCausalLM(nn.Module):
                     ops.transpose_v(qkv[:, 2 * D:], S * 3 * D, 3 * D, B, S, H, hd, pitch=cache.smax, out=vt)
                     ops.attention(qkv, qkv[:, D:], vt, att, B, H, S, S, hd, st, st, (S * D, hd, D), key_mask, causal=True, scale_mode=1,
                                   scale=hd ** -0.5)
-            x = ops.linear(att, w["w_o"], residual=x)
-            a = ops.linear(x, w["w_gu"], swiglu=True, rms_w=w["ln2"], rms_eps=cfg.rms_norm_eps)  # post_attention_layernorm -> gate|up
-            x = ops.linear(a, w["w_down"], residual=x)
+            x = lin(att, w["w_o"], residual=x)
+            a = lin(x, w["w_gu"], swiglu=True, rms_w=w["ln2"])                                   # post_attention_layernorm -> gate|up
+            x = lin(a, w["w_down"], residual=x)
         x = ops.rmsnorm(x, self.model.norm.weight, cfg.rms_norm_eps)
         last = x.view(B, S, D)
         if cache is not None:

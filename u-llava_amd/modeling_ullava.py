@@ -67,10 +67,14 @@ class UllavaForCausalLM(nn.Module):
     def weight_quantization(self):
         return self.llm.weight_quantization
 
-    def quantize_weights(self, fmt: str = "fp8_e4m3"):
+    @property
+    def activation_quantization(self):
+        return self.llm.activation_quantization
+
+    def quantize_weights(self, fmt: str = "fp8_e4m3", activations=None):
         """FP8 ("fp8_e4m3") or MXFP4 ("mxfp4") weight-only inference for the language model (UllavaCoreForCausalLM.quantize_weights); SAM and
-        the heads keep their dtype."""
-        self.llm.quantize_weights(fmt)
+        the heads keep their dtype.  activations="fp8_e4m3" (fp8 weights only): fp8 activations in the LLaMA prefill as well."""
+        self.llm.quantize_weights(fmt, activations=activations)
         return self
 
     def save_pretrained(self, save_directory, **kwargs):

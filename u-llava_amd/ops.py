@@ -149,13 +149,14 @@ class Fp8Weight:
 
     What the Linear dispatch needs of a quantized weight, here and on Mxfp4Weight: `fmt_name`, `wf` (its ULL_WF_* code), `route_pitch` (the row
     pitch `_linear_route` sees), `c_args()` (the weight arguments of a *_wq_bf16 entry / the fields of an ull_linear) and `dequantize_into`."""
-    __slots__ = ("codes", "scales")
+    __slots__ = ("codes", "scales", "_kpad")
     fmt_name, wf = "fp8", _lib.WF_FP8
 
     def __init__(self, codes: torch.Tensor, scales: torch.Tensor):
         if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or scales.dtype != F32 or scales.shape != (codes.shape[0],):
             raise RuntimeError("u-llava_amd.Fp8Weight: codes uint8 [N, K] (rows contiguous), scales fp32 [N]")
         self.codes, self.scales = codes, scales
+        self._kpad = None                    # linear_a8w8: the codes zero-padded to K % 128 == 0 (tiny test models only; real K never needs it)
 
     @property
     def shape(self):
@@ -519,6 +520,63 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
                       flags, st)
         else:
             _lib.call("ull_gemv_" + sfx, _p(x), ldx, *wargs, _p(out), ldc, _p(bias), _p(residual), ldr, M, N, K, flags, st)
+    return out
+
+
+# ---- FP8 activations on FP8 weights (quantize_weights("fp8_e4m3", activations="fp8_e4m3")) ---------------------------------------------
+A8W8_BK = 128        # K-tile of ull_gemm_a8w8_bf16 (one block-scaled matrix instruction)
+
+
+def quantize_rows_fp8(x: torch.Tensor):
+    """(codes uint8 [M, K], scales fp32 [M]) of bf16 rows x [..., K] (one row pitch): quantize_fp8's rule per row, so every token gets its own
+    power-of-two scale 2^t, t the smallest integer with amax|row| * 2^-t <= 448 (0 for an all-zero row); codes = e4m3fn(x * 2^-t), nearest even."""
+    _chk(x, "x", BF16)
+    M, ldx = _rows(x)
+    K = x.shape[-1]
+    codes = torch.empty(M, K, device=x.device, dtype=torch.uint8)
+    scales = torch.empty(M, device=x.device, dtype=F32)
+    _lib.call("ull_quantize_rows_fp8_bf16", _p(x), ldx, M, K, _p(codes), _p(scales), _stream())
+    return codes, scales
+
+
+def a8w8_takes(M: int, N: int, K: int, w) -> bool:
+    """Whether a LLaMA-layer Linear x [M, K] @ w.T of an activation-quantized model runs as W8A8: exactly the shapes `_linear_route` sends to
+    the tiled GEMM (prefill).  Decode shapes ("gemv" / "skinny") stay W8A16."""
+    return isinstance(w, Fp8Weight) and _linear_route(M, N, K, w.route_pitch, 0)[0] == "gemm"
+
+
+def linear_a8w8(x: torch.Tensor, w: "Fp8Weight", residual: Optional[torch.Tensor] = None, swiglu: bool = False,
+                out: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
+    """y = epilogue(x @ w.T) with e4m3 activations on e4m3 weights (ull_gemm_a8w8_bf16; the only call site of that entry):
+        xq, 2^t_m = quantize_rows_fp8(x)                        per token
+        acc[m, n] = sum_k float(xq[m, k]) * float(wq[n, k])     exact products, fp32 accumulation in the kernel's fixed K order
+        y[m, n]   = acc[m, n] * 2^(t_m + s_n)                   exact
+    then `linear`'s epilogue on y (residual / swiglu / out_f32, same rounding points).  A K that is no multiple of 128 (tiny test models) is
+    padded with zero codes, which adds 0 * 0 terms; the padded weight codes are kept on the Fp8Weight."""
+    if not isinstance(w, Fp8Weight):
+        raise RuntimeError("u-llava_amd.linear_a8w8: w must be an Fp8Weight")
+    _chk(x, "x", BF16)
+    M, _ = _rows(x)
+    N, K = w.shape
+    if x.shape[-1] != K:
+        raise RuntimeError(f"u-llava_amd.linear_a8w8: K mismatch {x.shape[-1]} vs {K}")
+    xq, xs = quantize_rows_fp8(x)
+    wq = w.codes
+    if K % A8W8_BK or wq.stride(0) % 16 or wq.data_ptr() % 16:
+        if w._kpad is None:
+            w._kpad = torch.nn.functional.pad(wq, (0, -K % A8W8_BK)).contiguous()
+        wq = w._kpad
+        xq = torch.nn.functional.pad(xq, (0, -K % A8W8_BK))
+    if out is None:
+        out = torch.empty(*x.shape[:-1], N // 2 if swiglu else N, device=x.device, dtype=F32 if out_f32 else BF16)
+    flags = (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0)
+    ldr = 0
+    if residual is not None:
+        _chk(residual, "residual", BF16)
+        flags |= EPI_RESID
+        ldr = _rows(residual)[1]
+    _lib.call("ull_gemm_a8w8_bf16", _p(xq), xq.stride(0), _p(xs), _p(wq), wq.stride(0), _p(w.scales), _p(out), _rows(out)[1], _p(residual), ldr,
+              M, N, xq.shape[1], flags, _stream())
     return out
 
 
