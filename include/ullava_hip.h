@@ -182,6 +182,37 @@ int ull_gemv_qkv_rope_append_wq_bf16(const void* X, int64_t ldx, const void* nor
 int ull_gemm_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, void* C, int64_t ldc,
                        const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
 
+/* ---- MXFP8 activations on MXFP4 weights: the W4A8 prefill Linear (bf16 build only: no *_f16 twins) ------------------------------------
+ * UllavaCoreForCausalLM.quantize_weights("mxfp4", activations="mxfp8_e4m3"): at prefill shapes the four LLaMA-layer Linears quantize their
+ * input rows to OCP MXFP8 and multiply them by the resident MXFP4 weight on the block-scaled matrix instruction
+ * (v_mfma_scale_f32_16x16x128_f8f6f4, e2m1 first operand, e4m3 second operand, one E8M0 scale per operand, row and 32 K elements).
+ * For x [M, K] @ w^T, w in MXFP4 with codes wq and scales 2^s[n, j] (j = the blocks of 32 consecutive K elements):
+ *   1. xq, t = ull_quantize_rows_mxfp8_bf16(x): per row m and block j, t[m, j] is the smallest integer with amax|block| * 2^-t <= 448 (an
+ *      all-zero block: 0), clamped to [-127, 127] and stored as the byte t + 127; xq = e4m3fn(x * 2^-t), round to nearest even --
+ *      bit-identical to torch's CPU cast (x.float() * 2^-t).to(torch.float8_e4m3fn), the fp8 rule above per block.
+ *   2. y[m, n] = sum_j 2^(t[m, j] + s[n, j]) * sum_{k in block j} float(xq[m, k]) * e2m1(wq[n, k]).  Every product is exact in fp32 (6
+ *      significant bits, power-of-two scales, applied by the instruction's two scale operands); the accumulation is fp32 in one fixed K
+ *      order that depends on K alone -- not on M, N, the batch or the grid: whole 2048-element superblocks first, inside superblock b the
+ *      128-element K-tiles in the order b * 2048 + g * 512 + t * 128 with t = 0 .. 3 outer and g = 0 .. 3 inner (the resident layout's order),
+ *      then the K-tiles after the last whole superblock ascending; K is never split.  The definition covers inputs whose scaled terms
+ *      2^(t + s) * xq * wq are normal floats or zero; what the instruction does with subnormal terms is not specified here.
+ *   3. ull_gemm_bf16's epilogue on y with its rounding points.
+ * ull_quantize_rows_mxfp8_bf16: X [M, K] bf16 (row pitch ldx elements, 16-byte aligned rows), K % 32 == 0; codes [M, K] row-major (row pitch
+ * ldq bytes, a multiple of 8); scales: one byte per (row, block), row pitch lds bytes >= K / 32 and a multiple of 4, pointer 4-byte aligned
+ * (what ull_gemm_w4a8_bf16 reads; ULL_ERR_SHAPE otherwise), the byte of block j at the position the
+ * resident MXFP4 layout gives the scale byte of block j of a weight row of the same K (inside whole superblock b, block b * 64 + g * 16 + i
+ * at byte b * 64 + i * 4 + g; standard order after the last whole superblock) -- private to this pair of entries; bytes of a scale row that
+ * belong to no block are not written.
+ * ull_gemm_w4a8_bf16: ull_gemm_a8w8_bf16's contract with (Xq, ldxq, x_scales, ldxs) from the quantizer above and (Q, ldq, w_scales, lds) a
+ * resident MXFP4 weight (ULL_WF_MXFP4 above): code pitches multiples of 16 bytes and base pointers 16-byte aligned, scale pitches multiples
+ * of 4 bytes >= K / 32 and scale pointers 4-byte aligned, K % 128 == 0.  flags: ULL_EPI_RESID, ULL_EPI_SWIGLU (Q rows in the gate|up
+ * interleave, N % 32 == 0), ULL_EPI_OUT_F32 only -- any other bit, or a null pointer: ULL_ERR_ARG; a shape or alignment it cannot take:
+ * ULL_ERR_SHAPE; nothing is launched in either case. */
+int ull_quantize_rows_mxfp8_bf16(const void* X, int64_t ldx, int64_t M, int64_t K, void* codes, int64_t ldq, void* scales, int64_t lds,
+                                 void* stream);
+int ull_gemm_w4a8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, int64_t ldxs, const void* Q, int64_t ldq, const void* w_scales,
+                       int64_t lds, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+
 /* ---- FP8 (e4m3) KV cache (bf16 build only) ------------------------------------------------------------------------------------------
  * KVCache(kv_dtype="fp8_e4m3") keeps, per layer, K codes [B, H, smax, hd] and V^T codes [B, H, hd, smax] (the key-permuted slot order of
  * ull_transpose_v) plus one fp32 scale 2^s per (batch, head, position) for the K row (k_scale [B, H, smax], by key) and one for the V column

@@ -148,6 +148,10 @@ SIGNATURES.update({
 # fp8 activations on fp8 weights (W8A8 prefill Linear): bf16-only entry point (no fp16 twin)
 SIGNATURES["ull_gemm_a8w8_bf16"] = [_ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr]
 
+# MXFP8 activations on MXFP4 weights (W4A8 prefill Linear): bf16-only entry points (no fp16 twin)
+SIGNATURES["ull_quantize_rows_mxfp8_bf16"] = [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr]
+SIGNATURES["ull_gemm_w4a8_bf16"] = [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr]
+
 # fp16-only entry points (no bf16 twin): the fp32 neck of an fp16 SAM encoder (image_encoder.py:117-124)
 SIGNATURES["ull_neck_layernorm2d_f32in_f16"] = [_ptr, _ptr, _f32, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr]
 

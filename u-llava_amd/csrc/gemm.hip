@@ -651,6 +651,268 @@ __global__ __launch_bounds__(256, 2) void gemm128_a8w8_kernel(GemmArgs p, A8Args
     __builtin_amdgcn_s_barrier();                          // every wave has consumed the last K-tile: LDS is free
     staged_epilogue<SWIGLU, 4>(p, acc, smem + wave * (64 * 144), lane, m0 + wm * 64, n0 + wn * 64);
 }
+
+// ---- W4A8: MXFP8 activations x resident MXFP4 weights on the block-scaled matrix instruction (ull_gemm_w4a8_bf16, bf16 build only) --------
+// y[m, n] = sum_j 2^(t[m, j] + s[n, j]) * sum_{k in block j} float(xq[m, k]) * e2m1(wq[n, k]), j the blocks of 32 consecutive K elements
+// (include/ullava_hip.h).  Activation scale bytes [M, pitch]: the E8M0 byte of (row, block) sits where the RESIDENT weight layout puts the
+// scale byte of that block (mx_scale_pos), so that one rule addresses both scale operands.
+//
+// ull_quantize_rows_mxfp8_bf16: one row per wave; a lane owns 8 consecutive elements (one 16-byte load), the four lanes of a 32-block share
+// its amax through two xor-shuffles, and each lane writes its 8 codes.
+__global__ __launch_bounds__(256) void quantize_rows_mxfp8_kernel(const elem_t* __restrict__ X, long ldx, int M, int K, uint8_t* __restrict__ codes,
+                                                                  long ldq, uint8_t* __restrict__ scales, long lds) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const elem_t* x = X + (long)row * ldx;
+    uint8_t* q = codes + (long)row * ldq;
+    uint8_t* sc = scales + (long)row * lds;
+    const int nchunk = K >> 3, nsb = K >> 11;
+    for (int c0 = 0; c0 < nchunk; c0 += 64) {              // K % 32 == 0: the four lanes of a block are in or out together
+        const int c = c0 + lane;
+        const bool on = c < nchunk;
+        float v[8];
+        unpack8(on ? *(const uint4*)(x + c * 8) : make_uint4(0, 0, 0, 0), v);
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+        amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+        if (!on) continue;
+        const int t = min(max(fp8_scale_exp(amax), -127), 127);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = ldexpf(v[j], -t);     // exact; |v| <= 448: the conversion cannot overflow
+        int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
+        int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], 0, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
+        *(uint2*)(q + c * 8) = make_uint2((uint32_t)lo, (uint32_t)hi);
+        if ((c & 3) == 0) sc[mx_scale_pos(c >> 2, nsb)] = (uint8_t)(t + 127);
+    }
+}
+
+// gemm128_w4a8_kernel is gemm128_a8w8_kernel with the weight operand taken from the resident MXFP4 row: the same 128 x 128 tile on 4 waves
+// of 64 x 64, the same activation K-tile of 128 codes as 128-byte LDS rows (16-byte LDS-DMA, chunk index XOR-swizzled by row & 7), one
+// matrix instruction per accumulator and K-tile, the same C/D layout and staged_epilogue.  The weights are the instruction's first operand
+// with format code 4 (e2m1): lane l feeds row (l & 15) and the 32 codes of block (l >> 4) of the K-tile, 16 bytes in the first 4 of the
+// operand's 8 registers (element 2i in the low nibble of byte i); the E8M0 byte of that (row, block) is the lane's scale, picked from its
+// scale register by the instruction's byte select.  The 8-bit operand counts k differently -- lane l holds k = 16 (l >> 4) + [0, 16) in its
+// first 16 bytes and 64 + 16 (l >> 4) + [0, 16) in the rest (with two 8-bit operands, as in gemm128_a8w8_kernel, that cannot show) -- while
+// the scale of block j of either operand comes from the lanes 16 j + row: the activation lane of group l >> 4 reads the 16-byte chunks
+// (l >> 4) and 4 + (l >> 4) of the K-tile and carries the scale of block (l >> 4).  Map and rates measured with one-hot integer data:
+// tools/probes/mfma_scale_w4a8_lane_map.hip, profiles/mfma_scale_w4a8_lane_map.txt.
+// K order (fixed by K alone; never split):
+//   inside whole superblock b (2048 elements) a SUPER TILE (b, t), t < 4, is the 256 contiguous resident code bytes [b*1024 + t*256, +256) of a
+//   row = the 16-byte pieces 16t .. 16t + 15; lane l takes the pieces 16t + 4 (l >> 4) + c, c < 4, and component g of piece c is chunk
+//   (8 elements) c of block 4t + (l >> 4) of the K-tile at element b*2048 + g*512 + t*128.  So the four steps g = 0 .. 3 of a super tile take
+//   their fragments by register selection, and their scale bytes are byte g of the aligned dword at scale byte b*64 + (4t + (l >> 4)) * 4.
+//   Steps run b, t, g ascending: the activation K-tiles are visited in the order b*2048 + g*512 + t*128.
+//   After the last whole superblock the row is in standard order: K-tile kt is 64 contiguous code bytes (16 per lane) and one scale byte per lane.
+// A super tile's weights go through LDS: a 128-row x 256-byte image (32 KiB, single-buffered beside the two 16 KiB activation buffers =
+// the GEMM's 64 KiB), requested by LDS-DMA at step 1 of the previous super tile and waited for at its step 3, and read into registers once
+// per super tile (16 reads of 16 bytes per lane).  Tail tiles and all scale operands go global -> registers one step (scales: a super
+// tile's step 0 for the next super tile) ahead; the first tail tile after superblocks is requested when the last super tile is done.  Global -> registers for the super
+// tiles (64 contiguous bytes per lane and row, requested after the previous super tile's last step) measured 275 - 320 TFLOP/s on the
+// LLaMA launches and spilled; this form is what profiles/w4a8_prefill.txt records.
+struct W4A8Args {
+    const uint8_t* Xq; const uint8_t* xs; const uint8_t* Wq; const uint8_t* ws;
+    long ldxq, ldxs, ldq, lds;                        // row pitches in bytes
+};
+using u32x4_t = __attribute__((ext_vector_type(4))) uint32_t;
+
+template <bool SWIGLU>
+__global__ __launch_bounds__(256, 2) void gemm128_w4a8_kernel(GemmArgs p, W4A8Args q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = wave & 1, wm = wave >> 1;
+
+    int bid = blockIdx.x;                              // XCD-contiguous chunks, grouped raster inside (as gemm128_kernel)
+    {
+        const int nwg = p.nbm * p.nbn;
+        const int qq = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
+        bid = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + k;
+    }
+    const int per_group = GROUP_M * p.nbn;
+    const int gid = bid / per_group;
+    const int first_m = gid * GROUP_M;
+    const int gsz = min(p.nbm - first_m, GROUP_M);
+    const int bm = first_m + (bid % per_group) % gsz;
+    const int bn = (bid % per_group) / gsz;
+    const int m0 = bm * BM, n0 = bn * BN;
+
+    // LDS: two activation K-tile buffers of 16 KiB (as gemm128_a8w8_kernel's: rows past M re-read the last row), then the 32 KiB weight image
+    constexpr int WOFF = 2 * TILE_BYTES;
+    static_assert(WOFF + BN * 256 == GEMM_LDS, "two activation tiles and one super tile of weights fill the GEMM's LDS");
+    const int srow = lane >> 3;
+    const int schunk = (lane & 7) ^ srow;
+    // every global address is a wave-uniform base plus a 32-bit lane offset (the entry refuses operands of 2 GiB and more)
+    uint32_t xsrc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xsrc[i] = (uint32_t)min(m0 + (wave * 4 + i) * 8 + srow, p.M - 1) * (uint32_t)q.ldxq + schunk * 16;
+    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
+    auto stage = [&](int buf, int tile) {
+        const uint32_t bx = lds_base + buf * TILE_BYTES + wave * 4 * 8 * BK8;
+        const uint8_t* src = q.Xq + (long)tile * BK8;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) glds16s(src, xsrc[i], bx + i * 1024);
+    };
+    // weight image of super tile (b, t): 128 rows of 256 bytes = 16 pieces of 16 bytes, piece index XOR-swizzled by (row & 15).  One DMA
+    // instruction fills 4 rows (lane -> row l >> 4, physical piece l & 15, fetching logical piece (l & 15) ^ (row & 15)); wave w fills rows
+    // [32 w, 32 w + 32) with 8 instructions; rows past N re-read the last row
+    // (the 8 lane offsets are recomputed per super tile from an opaque copy of the lane: kept across the loop they are spilled, and
+    // their reloads wait for every outstanding request)
+    auto stage_w = [&](int st) {
+        const uint8_t* src = q.Wq + ((long)(st >> 2) * 1024 + (st & 3) * 256);
+        const uint32_t bw = lds_base + WOFF + wave * 8192;
+        int l = lane;
+        asm volatile("" : "+v"(l));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int row = wave * 32 + i * 4 + (l >> 4);
+            glds16s(src, (uint32_t)min(n0 + row, p.N - 1) * (uint32_t)q.ldq + (((l & 15) ^ (row & 15)) << 4), bw + i * 1024);
+        }
+    };
+
+    // activation fragment: the 8-bit operand holds k = 64 (byte >> 4) + 16 (l >> 4) + (byte & 15) of the K-tile: logical chunks (l >> 4) and 4 + (l >> 4)
+    const int frow = lane & 15, fgrp = lane >> 4;
+    const int swz0 = (fgrp ^ (lane & 7)) << 4, swz1 = ((4 + fgrp) ^ (lane & 7)) << 4;
+    const int xrow_off = (wm * 64 + frow) * BK8;
+    // weight fragment: row wn*64 + i*16 + frow of the image, logical pieces 4 fgrp + c at physical (4 fgrp + c) ^ frow: 16 lanes of a
+    // group read 16 different pieces = all 64 banks
+    const int wread = WOFF + (wn * 64 + frow) * 256;
+    int wpo[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) wpo[c] = ((4 * fgrp + c) ^ frow) << 4;
+    uint32_t wrow[4], wsrow[4], xsrow[4];              // the lane's weight rows (tail tiles) / scale rows (rows past N / M re-read the last row)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t n = min(n0 + wn * 64 + i * 16 + frow, p.N - 1), m = min(m0 + wm * 64 + i * 16 + frow, p.M - 1);
+        wrow[i] = n * (uint32_t)q.ldq + fgrp * 16;
+        wsrow[i] = n * (uint32_t)q.lds;
+        xsrow[i] = m * (uint32_t)q.ldxs;
+    }
+
+    f32x4_t acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    const int nk = p.K / BK8;
+    const int nsup = (p.K >> 11) * 4;                  // super tiles; steps [0, 4 nsup) walk them, steps [4 nsup, nk) the standard-order tail
+    // activation K-tile of step s: s = b*16 + t*4 + g -> tile b*16 + g*4 + t inside the superblocks
+    auto xtile = [&](int s) { return s < nsup * 4 ? (s & ~15) + ((s & 3) << 2) + ((s >> 2) & 3) : s; };
+    auto xfrag = [&](const char* base, int j) {
+        const int off = xrow_off + j * 16 * BK8;
+        const uint4 lo = *(const uint4*)(base + off + swz0), hi = *(const uint4*)(base + off + swz1);
+        return i32x8_t{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+    };
+
+    u32x4_t wc[4][4], wnx[4];                           // [i][c]: the lane's four pieces of the super tile; the next tail tile's fragments
+    uint32_t wsc[4], xsc[4], wscn[4], xscn[4];         // scale registers (four bytes: steps g = 0 .. 3), current and next
+    auto load_scales = [&](int st, uint32_t (&a)[4], uint32_t (&b)[4]) {      // the aligned dword at scale byte b*64 + (4t + fgrp) * 4
+        const long so = (long)(st >> 2) * 64 + (st & 3) * 16;
+        const uint8_t* wsb = q.ws + so;                        // wave-uniform bases, 32-bit lane offsets
+        const uint8_t* xsb = q.xs + so;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            a[i] = *(const uint32_t*)(wsb + (uint32_t)(wsrow[i] + fgrp * 4));
+            b[i] = *(const uint32_t*)(xsb + (uint32_t)(xsrow[i] + fgrp * 4));
+        }
+    };
+    auto load_tail = [&](int kt, u32x4_t (&w)[4], uint32_t (&a)[4], uint32_t (&b)[4]) {       // 16 code bytes and one scale byte per lane
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            w[i] = *(const u32x4_t*)(q.Wq + (long)kt * 64 + wrow[i]);
+            a[i] = (q.ws + kt * 4)[wsrow[i] + fgrp];
+            b[i] = (q.xs + kt * 4)[xsrow[i] + fgrp];
+        }
+    };
+
+    // Schedule of a super tile: step 0 waits for everything, requests the next activation tile, reads the weight image into registers
+    // and requests the next super tile's scales; step 1 (every wave has read the image) requests the next activation tile, then the next
+    // image; step 2 waits for all but those 8 image requests; step 3 waits for everything again.  The image is in flight for two steps.
+    int s = 0;
+    if (nsup) { stage_w(0); load_scales(0, wscn, xscn); }
+    else load_tail(0, wnx, wscn, xscn);
+    stage(0, xtile(0));
+    for (int st = 0; st < nsup; ++st) {
+        auto step = [&](auto G) {
+            constexpr int g = decltype(G)::value;
+            // requests retire in order.  Step 2 of a super tile that has a successor: outstanding are this step's 4 activation requests and,
+            // younger, the 8 image requests of step 1, which may stay in flight.  Every other step waits for everything (in the last
+            // super tile nothing follows the activation requests, so a counted wait would let them through)
+            if (g == 2 && st + 1 < nsup) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                      // this step's activation tile is in LDS for every wave; the other buffer is free
+            if (s + 1 < nk) stage((s + 1) & 1, xtile(s + 1));
+            if constexpr (g == 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) wc[i][c] = *(const u32x4_t*)(smem + wread + i * 4096 + wpo[c]);
+                    wsc[i] = wscn[i]; xsc[i] = xscn[i];
+                }
+                load_scales(min(st + 1, nsup - 1), wscn, xscn);    // (the last super tile re-reads its own: one path, no copies)
+            }
+            if constexpr (g == 1) {
+                if (st + 1 < nsup) stage_w(st + 1);                // every wave has read the image: the next one, 8 requests, the youngest
+            }
+            const char* base = smem + (s & 1) * TILE_BYTES;
+            i32x8_t xf[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xf[j] = xfrag(base, j);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const i32x8_t wf{(int)wc[i][0][g], (int)wc[i][1][g], (int)wc[i][2][g], (int)wc[i][3][g], 0, 0, 0, 0};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)   // cbsz = 4: e2m1 A; blgp = 0: e4m3 B; scale byte g of both registers
+                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf, xf[j], acc[i][j], 4, 0, g, (int)wsc[i], g, (int)xsc[j]);
+            }
+            // keep a step's matrix instructions in the step: they have no side effect, and left alone the compiler sinks all four steps'
+            // below the last barrier (past the branches above), with every step's fragments alive until then
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(acc[i][j]));
+            ++s;
+        };
+        step(std::integral_constant<int, 0>{});
+        step(std::integral_constant<int, 1>{});
+        step(std::integral_constant<int, 2>{});
+        step(std::integral_constant<int, 3>{});
+    }
+    if (nsup && s < nk) load_tail(s, wnx, wscn, xscn);         // the first tail tile after superblocks (waited for at the top of its step)
+    for (; s < nk; ++s) {                                      // standard-order tail: weights global -> registers one step ahead, scale byte 0
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        u32x4_t wt[4];
+        uint32_t a0[4], b0[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { wt[i] = wnx[i]; a0[i] = wscn[i]; b0[i] = xscn[i]; }
+        if (s + 1 < nk) {
+            stage((s + 1) & 1, s + 1);
+            load_tail(s + 1, wnx, wscn, xscn);
+        }
+        const char* base = smem + (s & 1) * TILE_BYTES;
+        i32x8_t xf[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xf[j] = xfrag(base, j);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const i32x8_t wf{(int)wt[i][0], (int)wt[i][1], (int)wt[i][2], (int)wt[i][3], 0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf, xf[j], acc[i][j], 4, 0, 0, (int)a0[i], 0, (int)b0[j]);
+        }
+    }
+
+    // acc[i][j][r] = D[n = n0 + wn*64 + i*16 + 4*(l>>4) + r][m = m0 + wm*64 + j*16 + (l&15)], scales already applied by the instruction
+    __builtin_amdgcn_s_barrier();                          // every wave has consumed the last K-tile: LDS is free
+    staged_epilogue<SWIGLU, 4>(p, acc, smem + wave * (64 * 144), lane, m0 + wm * 64, n0 + wn * 64);
+}
 #endif  // !ULL_ELEM_F16
 
 
@@ -1893,6 +2155,8 @@ static int gemm_device_state(int* n_cu_out) {
 #ifndef ULL_ELEM_F16
         (void)hipFuncSetAttribute((const void*)gemm128_a8w8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
         (void)hipFuncSetAttribute((const void*)gemm128_a8w8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
+        (void)hipFuncSetAttribute((const void*)gemm128_w4a8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
+        (void)hipFuncSetAttribute((const void*)gemm128_w4a8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
 #endif
         (void)hipFuncSetAttribute((const void*)big::patchify_strip_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (288 + 256) * 128 + 256);
         (void)hipFuncSetAttribute((const void*)big::patchify_strip_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 256) * 128 + 256);
@@ -2056,6 +2320,53 @@ extern "C" int ull_gemm_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_sc
         hipLaunchKernelGGL(gemm128_a8w8_kernel<true>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
     else
         hipLaunchKernelGGL(gemm128_a8w8_kernel<false>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
+    return ull_check_launch();
+}
+
+// MXFP8 quantization of activation rows X [M, K] (bf16, row pitch ldx elements; K % 32 == 0): e4m3fn codes [M, K] (row pitch ldq bytes) and one
+// E8M0 byte per row and block of 32 K elements (row pitch lds bytes >= K / 32 and a multiple of 4, 4-byte aligned), the byte of block j at mx_scale_pos(j) of the row -- the
+// resident MXFP4 scale order, which ull_gemm_w4a8_bf16 reads.  Bytes of a scale row that belong to no block are left as they are.
+extern "C" int ull_quantize_rows_mxfp8_bf16(const void* X, int64_t ldx, int64_t M, int64_t K, void* codes, int64_t ldq, void* scales, int64_t lds,
+                                            void* stream) {
+    if (!X || !codes || !scales || M <= 0 || K <= 0) return ULL_ERR_ARG;
+    if ((K & 31) || (ldx & 7) || ldx < K || ldq < K || (ldq & 7) || lds < K / 32 || (lds & 3) || M > (1 << 28) || K > (1 << 30) ||
+        (((uintptr_t)X & 15) | ((uintptr_t)codes & 7) | ((uintptr_t)scales & 3)))
+        return ULL_ERR_SHAPE;
+    hipLaunchKernelGGL(quantize_rows_mxfp8_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const elem_t*)X, (long)ldx,
+                       (int)M, (int)K, (uint8_t*)codes, (long)ldq, (uint8_t*)scales, (long)lds);
+    return ull_check_launch();
+}
+
+// W4A8 Linear (bf16 build only): C[M, N] = epilogue(sum_j 2^(t[m, j] + s[n, j]) * sum_{k in block j} float(Xq[m, k]) * e2m1(Q[n, k])) with
+// (Xq, x_scales) from ull_quantize_rows_mxfp8_bf16 and (Q, w_scales) a resident MXFP4 weight.  ull_gemm_a8w8_bf16's contract otherwise.
+extern "C" int ull_gemm_w4a8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, int64_t ldxs, const void* Q, int64_t ldq, const void* w_scales,
+                                  int64_t lds, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
+                                  void* stream) {
+    if (!Xq || !x_scales || !Q || !w_scales || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if (flags & ~(EPI_RESID | EPI_SWIGLU | EPI_OUT_F32)) return ULL_ERR_ARG;
+    if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
+    if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return ULL_ERR_SHAPE;
+    if (K % BK8 != 0 || (ldxq & 15) || (ldq & 15) || ldxq < K || ldq < K / 2 || (((uintptr_t)Xq | (uintptr_t)Q) & 15)) return ULL_ERR_SHAPE;   // 16-byte pieces
+    if ((ldxs & 3) || (lds & 3) || ldxs < K / 32 || lds < K / 32 || (((uintptr_t)x_scales | (uintptr_t)w_scales) & 3)) return ULL_ERR_SHAPE;   // 4-byte scale loads
+    if ((M - 1) * ldxq + K >= (1LL << 31) || (N - 1) * ldq + K / 2 >= (1LL << 31) || M * ldxs >= (1LL << 31) || N * lds >= (1LL << 31))
+        return ULL_ERR_SHAPE;                                                                         // 32-bit lane offsets in the kernel
+    if ((flags & EPI_SWIGLU) && (N & 31)) return ULL_ERR_SHAPE;
+    if (ldc < ((flags & EPI_SWIGLU) ? N / 2 : N) || ((flags & EPI_RESID) && ldr < ((flags & EPI_SWIGLU) ? N / 2 : N))) return ULL_ERR_SHAPE;
+    int n_cu = 0;
+    if (const int rc = gemm_device_state(&n_cu)) return rc;
+    GemmArgs a;
+    a.X = nullptr; a.W = nullptr; a.C = C; a.bias = nullptr; a.R = (const elem_t*)R;
+    a.ldx = 0; a.ldw = 0; a.ldc = ldc; a.ldr = ldr;
+    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.flags = flags;
+    a.nbm = (int)((M + BM - 1) / BM); a.nbn = (int)((N + BN - 1) / BN);
+    a.t_full = 0; a.sk = 1; a.ws = nullptr; a.group_m = GROUP_M;
+    a.rope_cos = a.rope_sin = nullptr; a.rope_cols = 0;
+    if ((long)a.nbm * a.nbn > (1L << 30)) return ULL_ERR_SHAPE;
+    const W4A8Args q{(const uint8_t*)Xq, (const uint8_t*)x_scales, (const uint8_t*)Q, (const uint8_t*)w_scales, (long)ldxq, (long)ldxs, (long)ldq, (long)lds};
+    if (flags & EPI_SWIGLU)
+        hipLaunchKernelGGL(gemm128_w4a8_kernel<true>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
+    else
+        hipLaunchKernelGGL(gemm128_w4a8_kernel<false>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
     return ull_check_launch();
 }
 #endif  // !ULL_ELEM_F16

@@ -406,7 +406,7 @@ def check_sampler(sampler) -> bool:
 class UllavaCoreForCausalLM(nn.Module):
     config_class = UllavaCoreConfig
     weight_quantization = None             # "fp8_e4m3" / "mxfp4" after quantize_weights()
-    activation_quantization = None         # "fp8_e4m3" after quantize_weights("fp8_e4m3", activations="fp8_e4m3")
+    activation_quantization = None         # "fp8_e4m3" / "mxfp8_e4m3" after quantize_weights(fmt, activations=...)
 
     def __init__(self, config: UllavaCoreConfig, device=None, dtype=BF16):
         super().__init__()
@@ -627,15 +627,31 @@ class UllavaCoreForCausalLM(nn.Module):
         generation can differ: with a KV cache the prompt is prefilled in A8 and every later token is a W8A16 decode step, while
         use_cache=False re-runs the whole sequence in A8 each step.  Sample b of a batch still equals its single-sample run bit for bit
         when both run at prefill shapes.  May be called on a model that is already fp8-quantized to switch the mode on; no weight changes.
-        `model.activation_quantization` reports the mode."""
+        `model.activation_quantization` reports the mode.
+
+        activations="mxfp8_e4m3" (with fmt="mxfp4" only): MXFP8 activations in the LLaMA prefill (W4A8, DESIGN f9).  The same Linears at the
+        same shapes quantize their input rows to OCP MXFP8 -- e4m3 codes with one E8M0 power-of-two scale per row and block of 32 K elements,
+        the weights' own granularity -- and the product runs on the block-scaled matrix instruction straight from the resident MXFP4 codes
+        and scale bytes (ops.linear_w4a8): no dequantized copy, no second weight copy.  Everything said about the fp8 mode holds with W4A16
+        for W8A16 (profiles/w4a8_prefill.txt).  May be called on a model that is already mxfp4-quantized; no weight changes.  The spelling
+        differs from "fp8_e4m3" on purpose: that value means one scale per token."""
         if fmt not in ("fp8_e4m3", "mxfp4"):
             raise ValueError(f"quantize_weights: unknown format {fmt!r} (supported: 'fp8_e4m3', 'mxfp4')")
-        if activations not in (None, "fp8_e4m3"):
-            raise ValueError(f"quantize_weights: unknown activation format {activations!r} (supported: None, 'fp8_e4m3')")
+        if activations not in (None, "fp8_e4m3", "mxfp8_e4m3"):
+            raise ValueError(f"quantize_weights: unknown activation format {activations!r} (supported: None, 'fp8_e4m3', 'mxfp8_e4m3')")
         mx = fmt == "mxfp4"
-        if activations is not None and mx:
-            raise NotImplementedError("quantize_weights('mxfp4', activations='fp8_e4m3'): fp8 activations are implemented on fp8_e4m3 weights "
-                                      "only (there is no mxfp4 x fp8 prefill kernel)")
+        if activations == "fp8_e4m3" and mx:
+            raise NotImplementedError("quantize_weights('mxfp4', activations='fp8_e4m3'): per-token fp8 activations are implemented on fp8_e4m3 "
+                                      "weights only; mxfp4 weights take block-scaled activations, activations='mxfp8_e4m3'")
+        if activations == "mxfp8_e4m3" and not mx:
+            raise NotImplementedError("quantize_weights('fp8_e4m3', activations='mxfp8_e4m3'): block-scaled fp8 activations are implemented on "
+                                      "mxfp4 weights only; fp8_e4m3 weights take activations='fp8_e4m3'")
+        if activations == "mxfp8_e4m3":      # (refused before any device work: the W4A8 kernel walks K in 128-code tiles; smaller K is padded)
+            cfg_ = self.config
+            for k_ in (cfg_.hidden_size, cfg_.intermediate_size):
+                if k_ % 32 == 0 and not ops.w4a8_k_ok(k_):
+                    raise NotImplementedError(f"quantize_weights('mxfp4', activations='mxfp8_e4m3'): K = {k_} is not a multiple of 128 and cannot "
+                                              "be padded (the resident layout of its first 2048 elements would change)")
         if self.weight_quantization is not None:
             if self.weight_quantization == fmt:
                 if activations is not None:
@@ -1137,8 +1153,10 @@ class UllavaCoreForCausalLM(nn.Module):
         # (that kernel stages the T x D activations in 32 KB of LDS: LLaMA-7B at T = 4 is exactly the limit; wider models / more rows take the
         # stand-alone RMSNorm + RoPE-append kernels below)
         fuse_append = cache is not None and past > 0 and T <= 4 and hd % 2 == 0 and D % 8 == 0 and T * D * 2 <= 32768 and not f32
-        a8 = self.activation_quantization is not None and pk.get("fp8", False)      # quantize_weights(activations=): W8A8 at GEMM shapes
-        if a8 and fuse_rope and pk["llama"] and ops.a8w8_takes(T, 3 * D, D, pk["llama"][0]["w_qkv"]):
+        # quantize_weights(activations=): W8A8 on fp8 weights / W4A8 on mxfp4 weights at GEMM shapes
+        a8 = self.activation_quantization is not None and (pk.get("fp8", False) or pk.get("mxfp4", False))
+        a8_takes, a8_linear = (ops.w4a8_takes, ops.linear_w4a8) if pk.get("mxfp4", False) else (ops.a8w8_takes, ops.linear_a8w8)
+        if a8 and fuse_rope and pk["llama"] and a8_takes(T, 3 * D, D, pk["llama"][0]["w_qkv"]):
             fuse_rope = False                # A8 q|k|v: the plain projection, then the stand-alone RoPE kernel
         rope_cs = ops.rope_table(pos, inv_freq, x.dtype) if (fuse_rope or fuse_append) else None
         all_h = []
@@ -1147,11 +1165,12 @@ class UllavaCoreForCausalLM(nn.Module):
         wq = pk.get("fp8", False) or pk.get("mxfp4", False)      # quantize_weights(): the Linear weights are ops.Fp8Weight / ops.Mxfp4Weight
 
         def lin(x_, w_, residual=None, swiglu=False, rms_w=None):
-            """A LLaMA-layer Linear: fp8 activations (quantize_weights(activations=)) wherever the dispatch rule takes the tiled GEMM."""
-            if a8 and ops.a8w8_takes(x_.shape[0], w_.shape[0], w_.shape[1], w_):
+            """A LLaMA-layer Linear: fp8 activations (quantize_weights(activations=)) wherever the dispatch rule takes the tiled GEMM, by
+            the weight's type."""
+            if a8 and a8_takes(x_.shape[0], w_.shape[0], w_.shape[1], w_):
                 if rms_w is not None:
                     x_ = ops.rmsnorm(x_, rms_w, cfg.rms_norm_eps)
-                return ops.linear_a8w8(x_, w_, residual=residual, swiglu=swiglu)
+                return a8_linear(x_, w_, residual=residual, swiglu=swiglu)
             return ops.linear(x_, w_, residual=residual, swiglu=swiglu, rms_w=rms_w, rms_eps=cfg.rms_norm_eps)
 
         kv8 = cache is not None and cache.kv_dtype is not None

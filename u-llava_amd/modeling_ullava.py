@@ -73,7 +73,8 @@ class UllavaForCausalLM(nn.Module):
 
     def quantize_weights(self, fmt: str = "fp8_e4m3", activations=None):
         """FP8 ("fp8_e4m3") or MXFP4 ("mxfp4") weight-only inference for the language model (UllavaCoreForCausalLM.quantize_weights); SAM and
-        the heads keep their dtype.  activations="fp8_e4m3" (fp8 weights only): fp8 activations in the LLaMA prefill as well."""
+        the heads keep their dtype.  activations="fp8_e4m3" (fp8 weights only) / "mxfp8_e4m3" (mxfp4 weights only): fp8 activations in the LLaMA
+        prefill as well."""
         self.llm.quantize_weights(fmt, activations=activations)
         return self
 

@@ -239,7 +239,7 @@ class Mxfp4Weight:
     (`to_standard()`: codes [N, K / 2] with element 2i in the low nibble -- torch.float4_e2m1fn_x2 -- and scales [N, K / 32]) with the bytes
     of each row permuted, see include/ullava_hip.h.  `linear` / `linear_qkv_rope` / `linear_qkv_rope_append` take it in place of a bf16
     weight and compute exactly what they compute on the dequantized bf16 weight.  Immutable once built."""
-    __slots__ = ("codes", "scales", "K")
+    __slots__ = ("codes", "scales", "K", "_kpad")
     fmt_name, wf = "mxfp4", _lib.WF_MXFP4
 
     def __init__(self, codes: torch.Tensor, scales: torch.Tensor, K: int):
@@ -247,6 +247,7 @@ class Mxfp4Weight:
                 scales.dtype != torch.uint8 or scales.shape != (codes.shape[0], self.scale_pitch(K)) or not scales.is_contiguous()):
             raise RuntimeError("u-llava_amd.Mxfp4Weight: codes uint8 [N, K / 2], scales uint8 [N, K / 32 rounded up to 4], contiguous, K % 32 == 0")
         self.codes, self.scales, self.K = codes, scales, K
+        self._kpad = None                    # linear_w4a8: (codes, scales) padded to K % 128 == 0 (tiny test models only; real K never needs it)
 
     @staticmethod
     def scale_pitch(K: int) -> int:
@@ -577,6 +578,89 @@ def linear_a8w8(x: torch.Tensor, w: "Fp8Weight", residual: Optional[torch.Tensor
         ldr = _rows(residual)[1]
     _lib.call("ull_gemm_a8w8_bf16", _p(xq), xq.stride(0), _p(xs), _p(wq), wq.stride(0), _p(w.scales), _p(out), _rows(out)[1], _p(residual), ldr,
               M, N, xq.shape[1], flags, _stream())
+    return out
+
+
+# ---- MXFP8 activations on MXFP4 weights (quantize_weights("mxfp4", activations="mxfp8_e4m3")) ------------------------------------------
+def w4a8_k_ok(K: int) -> bool:
+    """Whether ull_gemm_w4a8_bf16 takes a weight of this K (K % 32 == 0): a multiple of its 128-code K-tile, or a K that padding brings there
+    without creating a superblock (the resident layout of a padded row must stay the standard order: K < 2048 before and after)."""
+    return K % A8W8_BK == 0 or K + (-K % A8W8_BK) < 2048
+
+
+def _quantize_rows_mxfp8(x: torch.Tensor, Kp: int):
+    """(codes uint8 [M, Kp], scale bytes uint8 [M, Mxfp4Weight.scale_pitch(Kp)]) as ull_gemm_w4a8_bf16 reads them: the scale byte of block j
+    sits where the resident MXFP4 layout puts a weight's (`_mx_perm`); columns past K are zero codes, and every scale byte that belongs to
+    no block of x (padding blocks, spare bytes of the pitch) is 127 (2^0)."""
+    _chk(x, "x", BF16)
+    M, ldx = _rows(x)
+    K = x.shape[-1]
+    if K % 32:
+        raise RuntimeError(f"u-llava_amd.quantize_rows_mxfp8: K must be a multiple of 32, got {K}")
+    lds = Mxfp4Weight.scale_pitch(Kp)
+    codes = (torch.empty if Kp == K else torch.zeros)(M, Kp, device=x.device, dtype=torch.uint8)
+    if lds == K // 32:
+        scales = torch.empty(M, lds, device=x.device, dtype=torch.uint8)
+    else:
+        scales = torch.full((M, lds), 127, device=x.device, dtype=torch.uint8)
+    _lib.call("ull_quantize_rows_mxfp8_bf16", _p(x), ldx, M, K, _p(codes), Kp, _p(scales), lds, _stream())
+    return codes, scales
+
+
+def quantize_rows_mxfp8(x: torch.Tensor):
+    """(codes uint8 [M, K], scales uint8 [M, K / 32]) of bf16 rows x [..., K] (one row pitch, K % 32 == 0) in OCP MXFP8: per row and block of
+    32 consecutive K elements the E8M0 byte t + 127, t the smallest integer with amax|block| * 2^-t <= 448 (0 for an all-zero block), clamped
+    to [-127, 127]; codes = e4m3fn(x * 2^-t), nearest even -- bit-identical to torch's CPU cast `(x.float() * 2**-t).to(torch.float8_e4m3fn)`.
+    The scales come back in block order; the W4A8 GEMM reads them in a private order (`_quantize_rows_mxfp8`)."""
+    K = x.shape[-1]
+    codes, raw = _quantize_rows_mxfp8(x, K)
+    return codes, raw[:, _mx_perm(K, x.device)[1]]
+
+
+def w4a8_takes(M: int, N: int, K: int, w) -> bool:
+    """Whether a LLaMA-layer Linear x [M, K] @ w.T of an activation-quantized mxfp4 model runs as W4A8: exactly the shapes `_linear_route`
+    sends to the tiled GEMM (prefill).  Decode shapes ("gemv" / "skinny") stay W4A16."""
+    return isinstance(w, Mxfp4Weight) and _linear_route(M, N, K, w.route_pitch, 0)[0] == "gemm"
+
+
+def linear_w4a8(x: torch.Tensor, w: "Mxfp4Weight", residual: Optional[torch.Tensor] = None, swiglu: bool = False,
+                out: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
+    """y = epilogue(x @ w.T) with MXFP8 activations on the resident MXFP4 weight (ull_gemm_w4a8_bf16; the only call site of that entry):
+        xq, t = quantize_rows_mxfp8(x)                                         per row and block j of 32 K elements
+        y[m, n] = sum_j 2^(t[m, j] + s[n, j]) * sum_{k in j} float(xq[m, k]) * e2m1(wq[n, k])     exact products, scales applied by the
+                                                                               instruction, fp32 accumulation in the kernel's fixed K order
+    then `linear`'s epilogue on y (residual / swiglu / out_f32, same rounding points).  A K below 2048 that is no multiple of 128 (tiny test
+    models) is padded with zero codes and the scale byte 127 on both sides, which adds 0 * 0 terms; the padded weight is kept on the
+    Mxfp4Weight."""
+    if not isinstance(w, Mxfp4Weight):
+        raise RuntimeError("u-llava_amd.linear_w4a8: w must be an Mxfp4Weight")
+    _chk(x, "x", BF16)
+    M, _ = _rows(x)
+    N, K = w.shape
+    if x.shape[-1] != K:
+        raise RuntimeError(f"u-llava_amd.linear_w4a8: K mismatch {x.shape[-1]} vs {K}")
+    if not w4a8_k_ok(K):
+        raise NotImplementedError(f"u-llava_amd.linear_w4a8: K = {K} is no multiple of 128 and cannot be padded (it would gain a superblock)")
+    Kp = K + (-K % A8W8_BK)
+    wq, wsc = w.codes, w.scales
+    if Kp != K:
+        if w._kpad is None:                  # K < 2048: the row is in standard order, so padding appends
+            pc = torch.nn.functional.pad(wq, (0, (Kp - K) // 2)).contiguous()
+            ps = torch.full((N, Mxfp4Weight.scale_pitch(Kp)), 127, device=wq.device, dtype=torch.uint8)
+            ps[:, :K // 32] = wsc[:, :K // 32]
+            w._kpad = (pc, ps)
+        wq, wsc = w._kpad
+    xq, xsc = _quantize_rows_mxfp8(x, Kp)
+    if out is None:
+        out = torch.empty(*x.shape[:-1], N // 2 if swiglu else N, device=x.device, dtype=F32 if out_f32 else BF16)
+    flags = (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0)
+    ldr = 0
+    if residual is not None:
+        _chk(residual, "residual", BF16)
+        flags |= EPI_RESID
+        ldr = _rows(residual)[1]
+    _lib.call("ull_gemm_w4a8_bf16", _p(xq), xq.stride(0), _p(xsc), xsc.stride(0), _p(wq), wq.stride(0), _p(wsc), wsc.stride(0), _p(out),
+              _rows(out)[1], _p(residual), ldr, M, N, Kp, flags, _stream())
     return out
 
 
