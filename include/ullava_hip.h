@@ -182,6 +182,31 @@ int ull_gemv_qkv_rope_append_wq_bf16(const void* X, int64_t ldx, const void* nor
 int ull_gemm_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, void* C, int64_t ldc,
                        const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
 
+/* ---- FP8 activations on FP8 weights at decode shapes: the W8A8 skinny Linear (bf16 build only: no *_f16 twins) ---------------------------
+ * UllavaCoreForCausalLM.quantize_weights("fp8_e4m3", activations="fp8_e4m3", activation_scope="prefill+decode"): batched decode steps of
+ * 5 to 32 tokens take the four LLaMA-layer Linears through a weight-streaming kernel on the same matrix instruction.  For a Linear
+ * x [M, K] @ w^T on an fp8 weight (codes wq, scales 2^s_n) with M <= 32:
+ *   xq, 2^t_m = ull_quantize_rows_fp8_bf16(x)              the per-token rule above
+ *   acc[m, n] = sum_k float(xq[m, k]) * float(wq[n, k])    every product exact in fp32; fp32 accumulation
+ *   the summation order is a function of K alone -- not of M, N, the row index m or what the other rows hold: with nkt = K / 128 K-tiles,
+ *   partial sum w (w = 0 .. 7) adds the tiles [nkt w / 8, nkt (w + 1) / 8) in ascending order from zero (one matrix instruction per tile),
+ *   and the eight partial sums are added in ascending w
+ *   y[m, n]   = acc[m, n] * 2^(t_m + s_n)                  one exact ldexp
+ * then the epilogue of ull_gemm_skinny_bf16 with its rounding points (the same points as ull_gemm_bf16's): none: bf16(y); ULL_EPI_RESID:
+ * bf16(R + bf16(y)); ULL_EPI_SWIGLU on the gate|up 16-row interleave: bf16(bf16(silu(bf16(g))) * bf16(u)); ULL_EPI_OUT_F32: C is float32 (y
+ * itself when no other flag is set).
+ * ull_gemm_skinny_a8w8_bf16: ull_gemm_a8w8_bf16's operands: codes uint8, row pitches in bytes, multiples of 16 and >= K, base pointers 16-byte
+ * aligned, scales fp32 powers of two [M] / [N]; 1 <= M <= 32, K % 128 == 0.  flags: ULL_EPI_RESID, ULL_EPI_SWIGLU (N % 32 == 0),
+ * ULL_EPI_OUT_F32 only -- any other bit, or a null pointer: ULL_ERR_ARG; a shape or alignment it cannot take: ULL_ERR_SHAPE; nothing is
+ * launched in either case.
+ * ull_rmsnorm_quantize_rows_fp8_bf16: codes, scales = ull_quantize_rows_fp8_bf16(ull_rmsnorm_bf16(X; rms_w, eps)) bit for bit -- the same
+ * bf16 rounding of the normed row, the same scale rule, the same codes -- without writing the normed rows.  X [M, K] bf16 (row pitch ldx
+ * elements, 16-byte aligned rows), any M, K % 8 == 0; codes [M, K] (row pitch ldq bytes, a multiple of 8), scales fp32 [M]. */
+int ull_gemm_skinny_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, void* C,
+                              int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+int ull_rmsnorm_quantize_rows_fp8_bf16(const void* X, int64_t ldx, const void* rms_w, float eps, int64_t M, int64_t K, void* codes, int64_t ldq,
+                                       void* scales, void* stream);
+
 /* ---- MXFP8 activations on MXFP4 weights: the W4A8 prefill Linear (bf16 build only: no *_f16 twins) ------------------------------------
  * UllavaCoreForCausalLM.quantize_weights("mxfp4", activations="mxfp8_e4m3"): at prefill shapes the four LLaMA-layer Linears quantize their
  * input rows to OCP MXFP8 and multiply them by the resident MXFP4 weight on the block-scaled matrix instruction
@@ -236,7 +261,7 @@ int ull_kv8_quantize_bf16(const void* K, int64_t k_bs, int64_t k_hs, int64_t k_s
 int ull_kv8_dequantize_bf16(const void* k8, const void* vt8, const void* k_scale, const void* vt_scale, int64_t B, int64_t H, int64_t hd, int64_t smax,
                             int64_t n, void* K_out, int64_t k_pitch, void* Vt_out, int64_t vt_pitch, void* stream);
 
-/* y = w * bf16(x * rsqrt(mean(x^2) + eps)).  hf: LlamaRMSNorm.forward. */
+/* y = w * bf16(x * rsqrt(mean(x^2) + eps)).  hf: LlamaRMSNorm.forward.  D % 8 == 0, D <= 12288. */
 int ull_rmsnorm_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int64_t rows, int64_t D, float eps, void* stream);
 
 /* models/ullava_core.py:327-338: shifted CrossEntropyLoss(logits[:, :-1], labels[:, 1:]), ignore_index -100.

@@ -148,6 +148,10 @@ SIGNATURES.update({
 # fp8 activations on fp8 weights (W8A8 prefill Linear): bf16-only entry point (no fp16 twin)
 SIGNATURES["ull_gemm_a8w8_bf16"] = [_ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr]
 
+# fp8 activations on fp8 weights at decode shapes (W8A8 skinny Linear, fused RMSNorm + row quantization): bf16-only entry points (no fp16 twin)
+SIGNATURES["ull_gemm_skinny_a8w8_bf16"] = SIGNATURES["ull_gemm_a8w8_bf16"]
+SIGNATURES["ull_rmsnorm_quantize_rows_fp8_bf16"] = [_ptr, _i64, _ptr, _f32, _i64, _i64, _ptr, _i64, _ptr, _ptr]
+
 # MXFP8 activations on MXFP4 weights (W4A8 prefill Linear): bf16-only entry points (no fp16 twin)
 SIGNATURES["ull_quantize_rows_mxfp8_bf16"] = [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr]
 SIGNATURES["ull_gemm_w4a8_bf16"] = [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr]

@@ -114,7 +114,9 @@ int launch_rownorm(const elem_t* x, long ldx, const elem_t* w, const elem_t* b, 
     else if (nch <= 4) ULL_RN(4);
     else if (nch <= 8) ULL_RN(8);
     else if (nch <= 16) ULL_RN(16);
-    else return ULL_ERR_SHAPE;   // D > 8192 never occurs on this path
+    else if (MODE == 0 && nch <= 24) {   // RMSNorm, 8192 < D <= 12288: LLaMA's intermediate width (the reference of the fused norm + quantize, a8_decode.hip)
+        if constexpr (MODE == 0) ULL_RN(24);
+    } else return ULL_ERR_SHAPE;   // wider rows never occur on this path
 #undef ULL_RN
     return ull_check_launch();
 }

@@ -407,6 +407,7 @@ class UllavaCoreForCausalLM(nn.Module):
     config_class = UllavaCoreConfig
     weight_quantization = None             # "fp8_e4m3" / "mxfp4" after quantize_weights()
     activation_quantization = None         # "fp8_e4m3" / "mxfp8_e4m3" after quantize_weights(fmt, activations=...)
+    activation_scope = "prefill"           # "prefill+decode" after quantize_weights(..., activation_scope="prefill+decode")
 
     def __init__(self, config: UllavaCoreConfig, device=None, dtype=BF16):
         super().__init__()
@@ -599,7 +600,7 @@ class UllavaCoreForCausalLM(nn.Module):
                     mod.weight.data = torch.empty(0, device=mod.weight.device, dtype=mod.weight.dtype)
         return self
 
-    def quantize_weights(self, fmt: str = "fp8_e4m3", activations: Optional[str] = None):
+    def quantize_weights(self, fmt: str = "fp8_e4m3", activations: Optional[str] = None, activation_scope: str = "prefill"):
         """FP8 (e4m3) weight-only inference: store every LLaMA Linear (q/k/v/o/gate/up/down_proj of every layer) and lm_head as e4m3fn
         codes with one power-of-two fp32 scale per output row (ops.quantize_fp8); activations stay bf16, accumulation fp32.  Everything
         else (embeddings, norms, CLIP, projector) keeps its dtype.  Returns self.
@@ -634,12 +635,29 @@ class UllavaCoreForCausalLM(nn.Module):
         the weights' own granularity -- and the product runs on the block-scaled matrix instruction straight from the resident MXFP4 codes
         and scale bytes (ops.linear_w4a8): no dequantized copy, no second weight copy.  Everything said about the fp8 mode holds with W4A16
         for W8A16 (profiles/w4a8_prefill.txt).  May be called on a model that is already mxfp4-quantized; no weight changes.  The spelling
-        differs from "fp8_e4m3" on purpose: that value means one scale per token."""
+        differs from "fp8_e4m3" on purpose: that value means one scale per token.
+
+        activation_scope="prefill+decode" (with fmt="fp8_e4m3", activations="fp8_e4m3" only; default "prefill" = everything above, unchanged):
+        FP8 activations in batched decode steps too (DESIGN f10).  Wherever ops.a8w8_decode_takes says so -- 5 to 32 rows against a LLaMA-sized
+        weight -- the four layer Linears quantize their input rows per token (q|k|v and gate|up inside the RMSNorm launch they already pay,
+        ops.rmsnorm_quantize_rows_fp8; o_proj and down_proj by ops.quantize_rows_fp8) and run the weight-streaming W8A8 kernel
+        (ops.linear_a8w8_skinny) in place of the W8A16 skinny kernel (5 to 16 rows) or the 128 x 128 W8A8 GEMM (17 to 32 rows).  Steps of at
+        most 4 tokens, lm_head and the coarse entries are untouched, so decoding at batch <= 4 is bit-identical to the weight-only model even
+        under this scope.  Measured in profiles/a8_decode.txt.  May be switched on for a model that is already fp8 / A8-quantized;
+        `model.activation_scope` reports the setting."""
         if fmt not in ("fp8_e4m3", "mxfp4"):
             raise ValueError(f"quantize_weights: unknown format {fmt!r} (supported: 'fp8_e4m3', 'mxfp4')")
         if activations not in (None, "fp8_e4m3", "mxfp8_e4m3"):
             raise ValueError(f"quantize_weights: unknown activation format {activations!r} (supported: None, 'fp8_e4m3', 'mxfp8_e4m3')")
+        if activation_scope not in ("prefill", "prefill+decode"):
+            raise ValueError(f"quantize_weights: unknown activation scope {activation_scope!r} (supported: 'prefill', 'prefill+decode')")
         mx = fmt == "mxfp4"
+        if activation_scope == "prefill+decode":
+            if mx:
+                raise NotImplementedError("quantize_weights('mxfp4', activation_scope='prefill+decode'): fp8 activations in decode steps are "
+                                          "implemented on fp8_e4m3 weights only; the mxfp4 (W4A8) lane map and resident layout differ")
+            if activations is None:
+                raise ValueError("quantize_weights: activation_scope='prefill+decode' needs activations='fp8_e4m3'")
         if activations == "fp8_e4m3" and mx:
             raise NotImplementedError("quantize_weights('mxfp4', activations='fp8_e4m3'): per-token fp8 activations are implemented on fp8_e4m3 "
                                       "weights only; mxfp4 weights take block-scaled activations, activations='mxfp8_e4m3'")
@@ -656,6 +674,8 @@ class UllavaCoreForCausalLM(nn.Module):
             if self.weight_quantization == fmt:
                 if activations is not None:
                     self.activation_quantization = activations
+                if activation_scope != "prefill":
+                    self.activation_scope = activation_scope
                 return self
             self._refuse_quantized(f"quantize_weights({fmt!r})")
         if self.dtype != BF16:
@@ -720,6 +740,7 @@ class UllavaCoreForCausalLM(nn.Module):
             _clear_transposes()
         self.weight_quantization = fmt
         self.activation_quantization = activations
+        self.activation_scope = activation_scope
         return self
 
     # The version tuples are read on EVERY forward (a decode step too): walking the module tree for them cost 0.5 ms of host time per step
@@ -1156,7 +1177,10 @@ class UllavaCoreForCausalLM(nn.Module):
         # quantize_weights(activations=): W8A8 on fp8 weights / W4A8 on mxfp4 weights at GEMM shapes
         a8 = self.activation_quantization is not None and (pk.get("fp8", False) or pk.get("mxfp4", False))
         a8_takes, a8_linear = (ops.w4a8_takes, ops.linear_w4a8) if pk.get("mxfp4", False) else (ops.a8w8_takes, ops.linear_a8w8)
-        if a8 and fuse_rope and pk["llama"] and a8_takes(T, 3 * D, D, pk["llama"][0]["w_qkv"]):
+        # activation_scope="prefill+decode": the weight-streaming W8A8 kernel wherever ops.a8w8_decode_takes says so (5 to 32 rows)
+        a8_skinny = a8 and self.activation_scope == "prefill+decode" and pk.get("fp8", False)
+        if a8 and fuse_rope and pk["llama"] and (a8_takes(T, 3 * D, D, pk["llama"][0]["w_qkv"]) or
+                                                 (a8_skinny and ops.a8w8_decode_takes(T, 3 * D, D, pk["llama"][0]["w_qkv"]))):
             fuse_rope = False                # A8 q|k|v: the plain projection, then the stand-alone RoPE kernel
         rope_cs = ops.rope_table(pos, inv_freq, x.dtype) if (fuse_rope or fuse_append) else None
         all_h = []
@@ -1166,7 +1190,14 @@ class UllavaCoreForCausalLM(nn.Module):
 
         def lin(x_, w_, residual=None, swiglu=False, rms_w=None):
             """A LLaMA-layer Linear: fp8 activations (quantize_weights(activations=)) wherever the dispatch rule takes the tiled GEMM, by
-            the weight's type."""
+            the weight's type; under activation_scope="prefill+decode" also at the skinny shapes of ops.a8w8_decode_takes, where the row
+            quantization rides in the RMSNorm launch when there is one."""
+            if a8_skinny and ops.a8w8_decode_takes(x_.shape[0], w_.shape[0], w_.shape[1], w_):
+                if rms_w is not None:
+                    xq, xs = ops.rmsnorm_quantize_rows_fp8(x_, rms_w, cfg.rms_norm_eps)
+                else:
+                    xq, xs = ops.quantize_rows_fp8(x_)
+                return ops.linear_a8w8_skinny(xq, xs, w_, residual=residual, swiglu=swiglu)
             if a8 and a8_takes(x_.shape[0], w_.shape[0], w_.shape[1], w_):
                 if rms_w is not None:
                     x_ = ops.rmsnorm(x_, rms_w, cfg.rms_norm_eps)

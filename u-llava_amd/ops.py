@@ -581,6 +581,63 @@ def linear_a8w8(x: torch.Tensor, w: "Fp8Weight", residual: Optional[torch.Tensor
     return out
 
 
+# ---- FP8 activations on FP8 weights at decode shapes (quantize_weights(..., activation_scope="prefill+decode")) -------------------------
+A8W8_SKINNY_MAX_M = 32        # ull_gemm_skinny_a8w8_bf16: two 16-row activation fragments
+
+
+def rmsnorm_quantize_rows_fp8(x: torch.Tensor, w: torch.Tensor, eps: float):
+    """quantize_rows_fp8(rmsnorm(x, w, eps)) in one launch (ull_rmsnorm_quantize_rows_fp8_bf16), bit for bit: (codes uint8 [M, K], scales
+    fp32 [M]) of the normed bf16 rows, which are never written."""
+    _chk(x, "x", BF16); _chk(w, "w", BF16)
+    M, ldx = _rows(x)
+    K = x.shape[-1]
+    codes = torch.empty(M, K, device=x.device, dtype=torch.uint8)
+    scales = torch.empty(M, device=x.device, dtype=F32)
+    _lib.call("ull_rmsnorm_quantize_rows_fp8_bf16", _p(x), ldx, _p(w), float(eps), M, K, _p(codes), K, _p(scales), _stream())
+    return codes, scales
+
+
+def a8w8_decode_takes(M: int, N: int, K: int, w) -> bool:
+    """Whether a LLaMA-layer Linear x [M, K] @ w.T of a model quantized with activation_scope="prefill+decode" runs on the W8A8 skinny kernel
+    (linear_a8w8_skinny).  The rule mirrors `_linear_route`'s "skinny" size rule -- a LLaMA-sized weight, N * K >= 2^22, whose row pitch
+    the kernel can stream -- starting above the 4 tokens the fused q|k|v + RoPE + cache-append GEMV takes and extended to the kernel's 32
+    rows (at 17 .. 32 rows it replaces the 128 x 128 W8A8 GEMM of `a8w8_takes`), with K a whole number of the instruction's 128-code
+    K-tiles."""
+    return isinstance(w, Fp8Weight) and 5 <= M <= A8W8_SKINNY_MAX_M and K % A8W8_BK == 0 and N * K >= (1 << 22) and w.route_pitch % 8 == 0
+
+
+def linear_a8w8_skinny(xq: torch.Tensor, xs: torch.Tensor, w: "Fp8Weight", residual: Optional[torch.Tensor] = None, swiglu: bool = False,
+                       out: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
+    """y = epilogue(dequant(xq, xs) @ w.T) at M <= 32 rows from activation codes xq uint8 [M, K] (rows contiguous, pitch a multiple of 16) and
+    their scales xs fp32 [M] (quantize_rows_fp8 / rmsnorm_quantize_rows_fp8), on the weight-streaming W8A8 kernel (ull_gemm_skinny_a8w8_bf16;
+    the only call site of that entry): linear_a8w8's arithmetic with a summation order that depends on K alone, then `linear`'s skinny
+    epilogue (residual / swiglu / out_f32, same rounding points).  K % 128 == 0."""
+    if not isinstance(w, Fp8Weight):
+        raise RuntimeError("u-llava_amd.linear_a8w8_skinny: w must be an Fp8Weight")
+    if xq.dtype != torch.uint8 or xq.dim() != 2 or xq.stride(1) != 1 or xs.dtype != F32 or xs.shape != (xq.shape[0],) or not xs.is_contiguous():
+        raise RuntimeError("u-llava_amd.linear_a8w8_skinny: xq uint8 [M, K] (rows contiguous), xs fp32 [M]")
+    M, K = xq.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise RuntimeError(f"u-llava_amd.linear_a8w8_skinny: K mismatch {K} vs {w.shape[1]}")
+    wq = w.codes
+    if wq.stride(0) % 16 or wq.data_ptr() % 16:          # (a view into a wider buffer: the 16-byte loads need aligned rows; kept as linear_a8w8's copy)
+        if w._kpad is None:
+            w._kpad = torch.nn.functional.pad(wq, (0, -K % A8W8_BK)).contiguous()
+        wq = w._kpad
+    if out is None:
+        out = torch.empty(M, N // 2 if swiglu else N, device=xq.device, dtype=F32 if out_f32 else BF16)
+    flags = (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0)
+    ldr = 0
+    if residual is not None:
+        _chk(residual, "residual", BF16)
+        flags |= EPI_RESID
+        ldr = _rows(residual)[1]
+    _lib.call("ull_gemm_skinny_a8w8_bf16", _p(xq), xq.stride(0), _p(xs), _p(wq), wq.stride(0), _p(w.scales), _p(out), _rows(out)[1],
+              _p(residual), ldr, M, N, K, flags, _stream())
+    return out
+
+
 # ---- MXFP8 activations on MXFP4 weights (quantize_weights("mxfp4", activations="mxfp8_e4m3")) ------------------------------------------
 def w4a8_k_ok(K: int) -> bool:
     """Whether ull_gemm_w4a8_bf16 takes a weight of this K (K % 32 == 0): a multiple of its 128-code K-tile, or a K that padding brings there
