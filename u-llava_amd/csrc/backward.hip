@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs p) {
     }
 }
 
-// ---- the same backward on the matrix cores (head dim 64 / 128: the LLaMA block) ------------------------------------------------------
+// ---- the same backward on the matrix cores, fragments from global memory (head dim 64; head dim 128 runs the LDS-tile kernels below) --
 // Mirrors the forward kernel's "swapped" products: an MFMA of A = key rows and B = query rows leaves, in lane (fr, fg), the scores of
 // query fr against keys 4fg + r of a 16-key block -- and eight of those values, packed, ARE the B operand of the next product over the
 // keys of a 32-key block, provided the other operand comes with its keys permuted the same way (slot 8g + 4a + r <- key 16a + 4g + r:
@@ -527,7 +527,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma_kernel(AttnBwdArgs p, c
         }
     }
     const bool key_ok = j < p.Sk && (p.key_mask == nullptr || p.key_mask[(long)b * p.Sk + j] != 0);
-    const int qbeg = p.causal ? max(0, blockIdx.x * 64 - shift) : 0;        // first query that can see a key of this block
+    // first query that can see a key of this block.  In int: blockIdx.x is unsigned, and `blockIdx.x * 64 - shift` wrapped for every key
+    // block in front of the offset (Sk > Sq, block * 64 < shift), which put qbeg past the last query tile: dK = dV = 0 for those keys
+    const int qbeg = p.causal ? max(0, (int)blockIdx.x * 64 - shift) : 0;
     const int nqt = (p.Sq + 63) / 64;
     const elem_t* qbase = p.Q + b * p.q_bs + h * p.q_hs;
     const elem_t* gbase = p.dO + b * p.g_bs + h * p.g_hs;
@@ -808,7 +810,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_tiles_kernel(AttnBwdArgs 
         }
     }
     const bool key_ok = j < p.Sk && (p.key_mask == nullptr || p.key_mask[(long)b * p.Sk + j] != 0);
-    const int qbeg = p.causal ? max(0, blockIdx.x * 64 - shift) : 0;        // first query that can see a key of this block
+    // first query that can see a key of this block.  In int: blockIdx.x is unsigned, and `blockIdx.x * 64 - shift` wrapped for every key
+    // block in front of the offset (Sk > Sq, block * 64 < shift), which put qbeg past the last query tile: dK = dV = 0 for those keys
+    const int qbeg = p.causal ? max(0, (int)blockIdx.x * 64 - shift) : 0;
     const int nqt = (p.Sq + 63) / 64, qt0 = qbeg / 64;
     const elem_t* qbase = p.Q + b * p.q_bs + h * p.q_hs;
     const elem_t* gbase = p.dO + b * p.g_bs + h * p.g_hs;
@@ -1212,8 +1216,12 @@ extern "C" int ULL_FN(ull_attention_bwd_)(const void* Q, const void* K, const vo
     return ull_check_launch();
 }
 
-// MFMA form (head dim 64 or 128, hd contiguous, 8-byte aligned rows).  Qt / Kt / dOt: transpose_v images [B, H, hd, pitch] of Q, K and dO
-// (keys permuted inside 32-blocks, zero-filled behind the sequence); scratch: float [2, B, H, ceil64(Sq)].
+// The two matrix-core families (hd contiguous, 8-byte aligned strides, 16-byte aligned token strides); every other call takes the scalar
+// kernels of ull_attention_bwd_ above.  scratch: float [2, B, H, ceil64(Sq)].
+//   hd 64  (attn_bwd_*_mfma_kernel<64>): fragments from global memory; Qt / Kt / dOt: transpose_v images [B, H, hd, pitch] of Q, K and dO
+//          (keys permuted inside 32-blocks, zero-filled behind the sequence).
+//   hd 128 (attn_bwd_*_tiles_kernel): 64-row tiles by LDS-DMA, transposed fragments from the transposing LDS read; no images (Qt / Kt /
+//          dOt may be null), and the head strides of Q, K, V, O and dO must be 16-byte aligned as well.
 extern "C" int ULL_FN(ull_attention_bwd_mfma_)(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* Qt, const void* Kt,
                                            const void* dOt, int64_t pitch, void* dQ, void* dK, void* dV, const int64_t* strides, const void* key_mask,
                                            int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t hd, int causal, float mult, void* scratch, void* stream) {
@@ -1244,9 +1252,6 @@ extern "C" int ULL_FN(ull_attention_bwd_mfma_)(const void* Q, const void* K, con
             if (s[i] & 7) return ULL_ERR_SHAPE;                // head strides of Q, K, V, O, dO: the DMA copies 16-byte chunks
         hipLaunchKernelGGL(attn_bwd_dq_tiles_kernel, gq, dim3(256), 4 * BW_TILE, (hipStream_t)stream, p, sqp);
         hipLaunchKernelGGL(attn_bwd_dkv_tiles_kernel, gk, dim3(256), 4 * BW_TILE, (hipStream_t)stream, p, sqp);
-    } else if (hd == 128) {
-        hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<128>, gq, dim3(256), 0, (hipStream_t)stream, p, (const elem_t*)Kt, (int)pitch, sqp);
-        hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<128>, gk, dim3(256), 0, (hipStream_t)stream, p, (const elem_t*)Qt, (const elem_t*)dOt, (int)pitch, sqp);
     } else {
         hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<64>, gq, dim3(256), 0, (hipStream_t)stream, p, (const elem_t*)Kt, (int)pitch, sqp);
         hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<64>, gk, dim3(256), 0, (hipStream_t)stream, p, (const elem_t*)Qt, (const elem_t*)dOt, (int)pitch, sqp);

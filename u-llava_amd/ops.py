@@ -1276,10 +1276,16 @@ def attention_bwd(q, k, v, o, do, dq, dk, dv, strides, key_mask, B: int, H: int,
     flat = [int(x) for tr in strides for x in tr]
     assert len(flat) == 24
     arr = (ctypes.c_int64 * 24)(*flat)
-    (q_bs, q_hs, q_ss), (k_bs, k_hs, k_ss), _, _, (g_bs, g_hs, g_ss) = strides[:5]
-    if hd in (64, 128) and q_hs == hd and k_hs == hd and g_hs == hd and all(x % 4 == 0 for x in flat) and all(flat[i] % 8 == 0 for i in range(2, 24, 3)):
-        # matrix-core kernels.  hd 128 (the LLaMA block): operand tiles staged through the LDS, transposed fragments from the
-        # transposing LDS read.  hd 64: fragments straight from global memory; Q, K and dO also as transpose_v images.
+    (q_bs, q_hs, q_ss), (k_bs, k_hs, k_ss), (_, v_hs, _), (_, o_hs, _), (g_bs, g_hs, g_ss) = strides[:5]
+    # Three kernel families.  The two matrix-core ones need the heads of Q, K and dO side by side (head stride == hd), every stride 8-byte
+    # and every token stride 16-byte aligned, and at hd 128 the head strides of V and O 16-byte aligned too (what ull_attention_bwd_mfma_
+    # checks); any other layout or head dim runs the scalar kernels below.
+    matrix = (hd in (64, 128) and q_hs == hd and k_hs == hd and g_hs == hd and all(x % 4 == 0 for x in flat)
+              and all(flat[i] % 8 == 0 for i in range(2, 24, 3)) and (hd != 128 or (v_hs % 8 == 0 and o_hs % 8 == 0)))
+    if matrix:
+        # hd 128 (the LLaMA block): attn_bwd_*_tiles_kernel -- operand tiles staged through the LDS, transposed fragments from the
+        # transposing LDS read.  hd 64: attn_bwd_*_mfma_kernel<64> -- fragments straight from global memory; Q, K and dO also as
+        # transpose_v images.
         pitch = ((max(Sq, Sk) + 63) // 64) * 64
         qt = kt = gt = None
         if hd != 128:
@@ -1290,6 +1296,7 @@ def attention_bwd(q, k, v, o, do, dq, dk, dv, strides, key_mask, B: int, H: int,
         _lib.call("ull_attention_bwd_mfma_" + _SFX[q.dtype], _p(q), _p(k), _p(v), _p(o), _p(do), _p(qt), _p(kt), _p(gt), pitch, _p(dq), _p(dk), _p(dv),
                   arr, _p(key_mask), B, H, Sq, Sk, hd, int(causal), float(mult), _p(scratch), _stream())
         return
+    # scalar kernels: any head dim <= 128, any strides
     scratch = torch.empty(2 * B * H * Sq, device=q.device, dtype=torch.float32)
     _lib.call("ull_attention_bwd_" + _SFX[q.dtype], _p(q), _p(k), _p(v), _p(o), _p(do), _p(dq), _p(dk), _p(dv), arr, _p(key_mask), B, H, Sq, Sk, hd,
               int(causal), float(mult), _p(scratch), _stream())
