@@ -385,6 +385,23 @@ int ull_sam_window_attention_bf16(const void* qkv, int64_t ld, const void* pad_r
                                   int64_t ldo, int64_t B, int64_t H, int64_t W, int64_t nH, int64_t hd, int64_t ws, float q_scale,
                                   const void* zeros, void* stream);
 
+/* image_encoder.py:196-260 Attention.forward of a GLOBAL block on the 64 x 64 grid (4096 keys, hd = 80) with the reference's rounding point:
+ * the softmax is normalised in fp32 and rounded AFTER the division (:251-253), where ull_attention_bf16's streaming kernel for this shape
+ * rounds exp(s - running max) and divides at the end.  Per query, r16 = rounding to the element type:
+ *     s[k] = r16(r16(r16(q * q_scale) . k) + rel_h[q, kh]) + rel_w[q, kw])        (the same instructions as ull_attention_bf16, rel_mode 2)
+ *     m = max_k s[k];   l = sum_k exp(s[k] - m)                                   (fp32; summation order a function of the key index alone)
+ *     P[k] = r16(exp(s[k] - m) / l)                                               (correctly rounded fp32 quotient)
+ *     O[d] = r16(sum_k P[k] * v[k, d])                                            (fp32 MFMA accumulation, no final division)
+ * One launch, two passes over K.  Q / K / V / O: [B, H, side * side, hd] by (batch, head, token) strides in elements, rows hd-contiguous
+ * (q | k | v of a fused projection are consumed in place, V as rows); rel_pos_h / rel_pos_w: the raw [2 * side - 1, hd] tables.
+ * side = 64 and hd = 80 only (ULL_ERR_SHAPE otherwise); every stride a multiple of 8 and >= hd along tokens, every base 16-byte
+ * aligned, 128 * k_ss and 128 * v_ss below 2^31 (ULL_ERR_SHAPE); null pointer or B, H <= 0: ULL_ERR_ARG.  Nothing is launched on an error.
+ * 16-bit builds only (the fp32 build's attention is exact already). */
+int ull_sam_global_attention_exact_bf16(const void* Q, int64_t q_bs, int64_t q_hs, int64_t q_ss, const void* K, int64_t k_bs, int64_t k_hs,
+                                        int64_t k_ss, const void* V, int64_t v_bs, int64_t v_hs, int64_t v_ss, const void* rel_pos_h,
+                                        const void* rel_pos_w, int64_t B, int64_t H, int64_t side, int64_t hd, float q_scale, void* O,
+                                        int64_t o_bs, int64_t o_hs, int64_t o_ss, void* stream);
+
 /* image_encoder.py:336-343: the linear resize get_rel_pos applies to a rel-pos table whose length differs from 2*size-1:
  * x [L, C] -> y [M, C] = F.interpolate(x as [1, C, L], size = M, mode = "linear") with ATen's CPU rounding (weights rounded to the element type). */
 int ull_interp_rows_linear_bf16(const void* x, void* y, int64_t L, int64_t M, int64_t C, void* stream);
@@ -728,6 +745,7 @@ int ull_window_partition_f16(const void* x, void* out, int64_t B, int64_t H, int
 int ull_window_unpartition_add_f16(const void* win, const void* shortcut, void* out, int64_t B, int64_t H, int64_t W, int64_t C, int64_t ws, void* stream);
 int ull_sam_relpos_f16(const void* q, int64_t q_bs, int64_t q_hs, int64_t q_ss, const void* rel_pos_h, const void* rel_pos_w, void* out_h, void* out_w, int64_t NB, int64_t nH, int64_t KH, int64_t KW, int64_t hd, void* stream);
 int ull_sam_window_attention_f16(const void* qkv, int64_t ld, const void* pad_row, const void* rel_pos_h, const void* rel_pos_w, void* out, int64_t ldo, int64_t B, int64_t H, int64_t W, int64_t nH, int64_t hd, int64_t ws, float q_scale, const void* zeros, void* stream);
+int ull_sam_global_attention_exact_f16(const void* Q, int64_t q_bs, int64_t q_hs, int64_t q_ss, const void* K, int64_t k_bs, int64_t k_hs, int64_t k_ss, const void* V, int64_t v_bs, int64_t v_hs, int64_t v_ss, const void* rel_pos_h, const void* rel_pos_w, int64_t B, int64_t H, int64_t side, int64_t hd, float q_scale, void* O, int64_t o_bs, int64_t o_hs, int64_t o_ss, void* stream);
 int ull_interp_rows_linear_f16(const void* x, void* y, int64_t L, int64_t M, int64_t C, void* stream);
 int ull_layernorm2d_cl_f16(const void* x, const void* w, const void* b, void* y, int64_t rows, int64_t C, float eps, int gelu, void* stream);
 int ull_im2col3x3_f16(const void* x, void* out, int64_t B, int64_t H, int64_t W, int64_t C, void* stream);

@@ -1585,6 +1585,339 @@ __global__ __launch_bounds__(256, 2) void sam_global_kernel(AttnArgs p) {
     }
 }
 
+// The same attention with the reference's rounding point (image_encoder.py:251-253: softmax, THEN the cast, then attn @ v):
+//   pass 1: m = max_k s[k], l = sum_k exp(s[k] - m) (fp32);  pass 2: P[k] = rnd(exp(s[k] - m) / l), O = rnd(sum_k P[k] v[k]) -- no final division.
+// One launch: Q fragments, the rel_w registers and the rel_h table are built once; K is streamed twice (640 KiB per head: it stays in L2),
+// V once; s[k] is recomputed in pass 2 with the same instructions, so both passes see the same bits.
+// Issue budget per 16 queries x 64 keys from the bf16 build's instruction census, with the figures above (MFMA 16.1 cycles, packed fp32 /
+// converts / other vector 4.3, v_exp 8.2):
+//   one-pass form: 24 MFMAs, 17 v_exp, 40 packed, 33 converts, 78 other vector                      ->  386 + 139 + 649 = ~ 1175
+//   pass 1:        12 MFMAs (S), 17 v_exp, 40 packed, 25 converts, 73 other vector                  ->  193 + 139 + 593 = ~  925
+//                  (the whole score epilogue -- three roundings per score -- the maximum, the exponentials and their fp32 sums)
+//   pass 2:        22 MFMAs (S and P V), 16 v_exp, 62 packed, 32 converts, 70 other vector           ->  354 + 131 + 705 = ~ 1190
+//                  (the score epilogue again, without the maximum; the quotient: 5 packed operations per pair of keys, where the one-pass
+//                  form has two row-sum MFMAs and the rescaling)
+// so ~ 1.8 x the one-pass form by the count; measured 1.63 - 1.74 x (2.2 - 2.3 ms against 1.3 - 1.4 ms per layer at B = 8, H = 16; the generic
+// exact route, attn_long_kernel, 8.5 - 8.9 ms: profiles/sam_global_exact.txt).  216 (bf16) / 232 (fp16) VGPRs, no scratch, 80 KB of LDS.
+// Everything up to the tile loops (fragments, bias tables, DMA pieces, the S tile and its score epilogue) is sam_global_kernel's text, and
+// pass 2's P V is its second half: kept as a sibling, because moving the one-pass kernel's body into a shared template changed its
+// register allocation (tools/kernel_isa_diff.py), and that kernel's code is what every default run is measured on.
+__global__ __launch_bounds__(256, 2) void sam_global_exact_kernel(AttnArgs p) {
+    extern __shared__ __attribute__((aligned(256))) char smem[];
+    constexpr int NWV = 4, NG = 2, BQ = 16 * NG * NWV, HDP = 128, hd = 80;
+    constexpr int KROW = HDP * 2, NKS = 3 /* 96 = 3 x 32 >= hd */, NDS = 5 /* 80 = 5 x 16 */;
+    constexpr int TILE = 64 * KROW;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fg = lane >> 4;
+    const int nq = p.Sq / BQ;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int head = (slot / nq) * 8 + xcd;
+    if (head >= p.B * p.H) return;
+    const int qt = slot % nq;
+    const int b = head / p.H, h = head % p.H;
+    const int q0 = qt * BQ + wave * 16 * NG;                   // this wave's first query; its 32 queries share the grid row qy
+    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
+    elem_t* ghl = (elem_t*)(smem + 4 * TILE) + wave * (64 * 16 * NG);     // [64 key rows][32 queries]: rel_h, 16-bit (a tile's read = 64 B)
+
+    uint4 qf[NG][NKS];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const elem_t* qp = p.Q + (long)b * p.q_bs + (long)h * p.q_hs + (long)(q0 + g * 16 + fr) * p.q_ss;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const int d = ks * 32 + fg * 8;
+            qf[g][ks] = d < hd ? *(const uint4*)(qp + d) : make_uint4(0, 0, 0, 0);
+        }
+    }
+    // G[q][t] = 16-bit(q . rel_pos[t]) on the MFMA (A = table rows, B = the UNSCALED query fragments): rel_w[q][kw] = Gw[q][qx - kw + 63],
+    // rel_h[q][kh] = Gh[q][qy - kh + 63].  Gw: all 127 rows -> this wave's pad (aliases the tile slots, not in use yet) -> 16 registers per
+    // group; Gh: the 64 rows qy - kh + 63 -> the wave's LDS table.
+    float rw[NG][16];
+    {
+        elem_t* gw = (elem_t*)(smem + wave * (NG * 4096));      // [group][16 queries][128]
+        const int qy = q0 >> 6;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+#pragma unroll 2
+            for (int st = 0; st < 8; ++st) {
+                f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+                const elem_t* tr = p.rel_w + (long)min(st * 16 + fr, 126) * hd + fg * 8;
+#pragma unroll
+                for (int ks = 0; ks < NKS; ++ks) {
+                    const uint4 a = (ks * 32 + fg * 8 < hd) ? *(const uint4*)(tr + ks * 32) : make_uint4(0, 0, 0, 0);
+                    acc = mfma16(a, qf[g][ks], acc);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) gw[g * 2048 + fr * 128 + st * 16 + fg * 4 + r] = f2e(acc[r]);   // G[t = st*16 + 4*fg + r][query fr]
+            }
+#pragma unroll 2
+            for (int st = 0; st < 4; ++st) {
+                f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+                const elem_t* tr = p.rel_h + (long)(qy - (st * 16 + fr) + 63) * hd + fg * 8;               // row of key-grid row kh = st*16 + fr
+#pragma unroll
+                for (int ks = 0; ks < NKS; ++ks) {
+                    const uint4 a = (ks * 32 + fg * 8 < hd) ? *(const uint4*)(tr + ks * 32) : make_uint4(0, 0, 0, 0);
+                    acc = mfma16(a, qf[g][ks], acc);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ghl[(st * 16 + fg * 4 + r) * (16 * NG) + g * 16 + fr] = f2e(acc[r]);  // Gh[kh = st*16 + 4*fg + r][query fr]
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // own pad only
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const int qx = (q0 + g * 16 + fr) & 63;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) rw[g][i] = e2f(gw[g * 2048 + fr * 128 + qx - ((i >> 2) * 16 + fg * 4 + (i & 3)) + 63]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    if (p.q_scale != 1.0f) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) qf[g][ks] = scale_q8(qf[g][ks], p.q_scale);
+    }
+    __builtin_amdgcn_s_barrier();                              // every wave is done with its pad before tile 0 is DMA'd over it
+
+    // LDS: K ring [2][64 x 256 B] at 0, V ring [2][64 x 256 B] at 2 TILE, rel_h tables behind.  DMA: a tile is 16 pieces of 1 KiB (4 key rows x
+    // 16 chunks); a wave issues 4 K + 4 V pieces per step.  The per-lane byte offset of every piece is the same for all 64 tiles; the six
+    // chunks of a row that are head-dim padding are not transferred: chunks 10 / 11 of every K row (dims 80..95, read by the last QK k-step)
+    // are zeroed once per buffer, the rest is never read.
+    const elem_t* kbase = p.K + (long)b * p.k_bs + (long)h * p.k_hs;
+    const elem_t* vbase = p.Vt + (long)b * p.vt_bs + (long)h * p.vt_hs;
+    uint32_t dko[4], dvo[4];
+    bool dk_real[4], dv_real[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = wave + j * NWV, row = i * 4 + (lane >> 4), cpos = lane & 15;
+        const int ck = cpos ^ (row & 15), cv = ((((cpos >> 1) ^ (row & 7)) << 1) | (cpos & 1));
+        dko[j] = (uint32_t)(((long)row * p.k_ss + ck * 8) * 2);
+        dvo[j] = (uint32_t)(((long)row * p.vt_ds + cv * 8) * 2);
+        dk_real[j] = ck * 8 < hd;
+        dv_real[j] = cv * 8 < hd;
+    }
+    for (int t = tid; t < 2 * 64 * 2; t += 64 * NWV) {
+        const int sl = t >> 7, row = (t & 127) >> 1, c = 10 + (t & 1);
+        *(uint4*)(smem + sl * TILE + row * KROW + ((c ^ (row & 15)) << 4)) = make_uint4(0, 0, 0, 0);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // (the first barrier below orders these writes before every read)
+    auto issue_k = [&](int kt) {
+        if (kt >= 64) return;
+        const uint32_t dst = lds_base + (kt & 1) * TILE;
+        const elem_t* tk = kbase + (long)kt * KT * p.k_ss;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (dk_real[j]) glds16s(tk, dko[j], dst + (wave + j * NWV) * 1024);
+    };
+    auto issue_v = [&](int kt) {
+        if (kt >= 64) return;
+        const uint32_t dst = lds_base + (2 + (kt & 1)) * TILE;
+        const elem_t* tv = vbase + (long)kt * KT * p.vt_ds;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (dv_real[j]) glds16s(tv, dvo[j], dst + (wave + j * NWV) * 1024);
+    };
+    // LDS fragment addresses, per lane and once: K fragment of k-step ks in rows fr, fr + 16, ... (the swizzle term of row 16 ns + fr is fr);
+    // V fragment base of the transposing reads (see attn_reg_kernel)
+    uint32_t kfo[NKS];
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) kfo[ks] = fr * KROW + (((ks * 4 + fg) ^ fr) << 4);
+    const int swr = 4 * (fg & 1) + (fr >> 2);
+    const uint32_t vfo = 2 * TILE + (4 * fg + (fr >> 2)) * KROW + ((fr & 2) << 3) + ((fr & 1) << 3);
+
+    f32x4_t oacc[NG][NDS];
+    float m[NG], mn[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        m[g] = -INFINITY;
+#pragma unroll
+        for (int ds = 0; ds < NDS; ++ds) oacc[g][ds] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    }
+    // S tile kt on the matrix pipe: 4 x 3 K fragments, each into both groups' chains (24 MFMAs)
+    auto qk = [&](int kt, f32x4_t (&acc)[NG][4]) {
+        const char* tb = smem + (kt & 1) * TILE;
+#pragma unroll
+        for (int ns = 0; ns < 4; ++ns) {
+#pragma unroll
+            for (int g = 0; g < NG; ++g) acc[g][ns] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) {
+                const uint4 kf = *(const uint4*)(tb + ns * 16 * KROW + kfo[ks]);
+#pragma unroll
+                for (int g = 0; g < NG; ++g) acc[g][ns] = mfma16(kf, qf[g][ks], acc[g][ns]);
+            }
+        }
+    };
+    // score epilogue of tile kt: rnd(rnd(rnd(acc) + rel_h) + rel_w) as 16-bit pairs sq[g][2 ns + half] (keys 16 ns + 4 fg + {0,1 | 2,3}), the
+    // tile maximum folded into mn[g] = the row maximum including tile kt; returns whether some query of the wave saw a new maximum
+    auto scores = [&](int kt, const f32x4_t (&acc)[NG][4], uint32_t (&sq)[NG][8]) -> bool {
+        bool grew = false;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const float rh = e2f(ghl[kt * (16 * NG) + g * 16 + fr]);
+            float tm = -INFINITY;
+#pragma unroll
+            for (int ns = 0; ns < 4; ++ns)
+                score_quad_win(acc[g][ns], rh, f32x2_t{rw[g][ns * 4], rw[g][ns * 4 + 1]}, f32x2_t{rw[g][ns * 4 + 2], rw[g][ns * 4 + 3]}, sq[g][ns * 2],
+                               sq[g][ns * 2 + 1], tm);
+            tm = rnd(tm);
+            tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
+            tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+            mn[g] = fmaxf(m[g], tm);                           // finite from tile 0 on
+            grew = grew || mn[g] > m[g];
+        }
+        return __builtin_amdgcn_ballot_w64(grew) != 0;
+    };
+    // O += V(kt)^T P(kt) on the matrix pipe: 2 x 5 V fragments (two transposing reads each), each into both groups' chains (20 MFMAs)
+    auto pv = [&](int kt, const uint32_t (&pk)[NG][8]) {
+        const uint32_t vb = lds_base + (kt & 1) * TILE + vfo;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            u32x2_t va[4], vc[4], wa[1], wc[1];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t ad = vb + ((j ^ swr) << 5);
+                if (kk == 0) { va[j] = lds_tr_b64<0>(ad); vc[j] = lds_tr_b64<16 * KROW>(ad); }
+                else { va[j] = lds_tr_b64<32 * KROW>(ad); vc[j] = lds_tr_b64<48 * KROW>(ad); }
+            }
+            {
+                const uint32_t ad = vb + ((4 ^ swr) << 5);
+                if (kk == 0) { wa[0] = lds_tr_b64<0>(ad); wc[0] = lds_tr_b64<16 * KROW>(ad); }
+                else { wa[0] = lds_tr_b64<32 * KROW>(ad); wc[0] = lds_tr_b64<48 * KROW>(ad); }
+            }
+            lds_tr_wait<4, 2>(va, vc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint4 vf = make_uint4(va[j].x, va[j].y, vc[j].x, vc[j].y);
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+                    oacc[g][j] = mfma16(vf, make_uint4(pk[g][4 * kk], pk[g][4 * kk + 1], pk[g][4 * kk + 2], pk[g][4 * kk + 3]), oacc[g][j]);
+            }
+            lds_tr_wait<1, 0>(wa, wc);
+            {
+                const uint4 vf = make_uint4(wa[0].x, wa[0].y, wc[0].x, wc[0].y);
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+                    oacc[g][4] = mfma16(vf, make_uint4(pk[g][4 * kk], pk[g][4 * kk + 1], pk[g][4 * kk + 2], pk[g][4 * kk + 3]), oacc[g][4]);
+            }
+        }
+    };
+    // Two passes over the keys, one launch (see sam_global_exact_kernel).  The K ring never stops: pass 1's last two steps request tiles
+    // 0 and 1 again (64 tiles = an even number of ring slots), its last step also V(0) and S(0) of pass 2.
+    // the score epilogue without the maximum (pass 2 knows it: the folding into tm is dead code)
+    auto scores2 = [&](int kt, const f32x4_t (&acc)[NG][4], uint32_t (&sq)[NG][8]) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const float rh = e2f(ghl[kt * (16 * NG) + g * 16 + fr]);
+            float tm = 0.f;
+#pragma unroll
+            for (int ns = 0; ns < 4; ++ns)
+                score_quad_win(acc[g][ns], rh, f32x2_t{rw[g][ns * 4], rw[g][ns * 4 + 1]}, f32x2_t{rw[g][ns * 4 + 2], rw[g][ns * 4 + 3]}, sq[g][ns * 2],
+                               sq[g][ns * 2 + 1], tm);
+        }
+    };
+    // ---- pass 1: m = max_k s[k], l = sum_k exp(s[k] - m) in fp32.  A lane adds the exponentials of its own 16 keys of every tile, in
+    // key-tile order, into one pair of partial sums per group (rescaled when the running maximum grows); the four lanes of a query
+    // are added at the end, 16 + 32 apart: the order is a function of the key index alone.
+    f32x2_t ls[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) ls[g] = f32x2_t{0.f, 0.f};
+    issue_k(0);
+    issue_k(1);
+    f32x4_t acc[NG][4];
+    uint32_t sq[NG][8];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    qk(0, acc);
+    bool grew = scores(0, acc, sq);
+    auto step1 = [&](int kt, auto last_c) {
+        constexpr bool LAST = decltype(last_c)::value;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (this wave's pieces of K(kt + 1))
+        __builtin_amdgcn_s_barrier();                      // ... and everybody's; every wave is done with K(kt)
+        issue_k((kt + 2) & 63);
+        if constexpr (LAST) issue_v(0);
+        if (grew) {
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                ls[g] *= __expf(m[g] - mn[g]);             // exp(-inf) = 0 on the first tile
+                m[g] = mn[g];
+            }
+        }
+        qk((kt + 1) & 63, acc);                            // LAST: S(0) of pass 2
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const f32x2_t t = (f32x2_t{pk_lo(sq[g][i]), pk_hi(sq[g][i])} - m[g]) * 1.4426950408889634f;
+                ls[g] += f32x2_t{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+            }
+        }
+        if constexpr (!LAST) grew = scores(kt + 1, acc, sq);
+    };
+#pragma unroll 2
+    for (int kt = 0; kt < 63; ++kt) step1(kt, std::false_type{});
+    step1(63, std::true_type{});
+    float l[NG], rl[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        float s = ls[g].x + ls[g].y;
+        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 32, 64);
+        l[g] = s;
+        rl[g] = 1.0f / s;                                  // correctly rounded (1 <= l <= 4096)
+    }
+    scores2(0, acc, sq);
+    // ---- pass 2: P = rnd(exp(s - m) / l), O += V^T P; the streamed form's step without the maximum, the rescaling and the row sum.
+    // e / l is the correctly rounded quotient, by the compiler's own fp32 division sequence without its range scaling and with 1 / l hoisted:
+    // y = RN(1 / l) per query; q0 = RN(e y); q1 = fma(fma(-q0, l, e), y, q0) is within half an ulp (+ 2^-23 of one) of e / l, so the
+    // remainder e - q1 l is exact in one fma and RN(q1 + r y) = RN(e / l) (Markstein's theorem) -- five packed operations per pair
+    // instead of the ~ 20 instructions of two divisions (tests/test_sam_exact_cpu.py).  For e < 2^-100 (s - m < -69) the remainder's last
+    // bit, 2^-47 e, leaves the fp32 range and it is no longer exact: such a P may be one fp32 ulp off the quotient, and is under 2^-100
+    // of the row's largest.
+    auto step2 = [&](int kt, auto last_c) {
+        constexpr bool LAST = decltype(last_c)::value;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (this wave's pieces of K(kt + 1) and V(kt))
+        __builtin_amdgcn_s_barrier();                      // ... and everybody's; every wave is done with K(kt) and V(kt - 1)
+        if constexpr (!LAST) {
+            issue_k(kt + 2);
+            issue_v(kt + 1);
+            qk(kt + 1, acc);
+        }
+        uint32_t pk[NG][8];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const f32x2_t l2 = {l[g], l[g]}, y2 = {rl[g], rl[g]};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const f32x2_t t = (f32x2_t{pk_lo(sq[g][i]), pk_hi(sq[g][i])} - m[g]) * 1.4426950408889634f;
+                const f32x2_t e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+                const f32x2_t qa = e * y2;
+                const f32x2_t qb = __builtin_elementwise_fma(__builtin_elementwise_fma(-qa, l2, e), y2, qa);
+                const f32x2_t q = __builtin_elementwise_fma(__builtin_elementwise_fma(-qb, l2, e), y2, qb);
+                pk[g][i] = pack2e(q.x, q.y);
+            }
+        }
+        pv(kt, pk);
+        if constexpr (!LAST) scores2(kt + 1, acc, sq);
+    };
+#pragma unroll 2
+    for (int kt = 0; kt < 63; ++kt) step2(kt, std::false_type{});
+    step2(63, std::true_type{});
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        elem_t* op = p.O + (long)b * p.o_bs + (long)h * p.o_hs + (long)(q0 + g * 16 + fr) * p.o_ss;
+#pragma unroll
+        for (int ds = 0; ds < NDS; ++ds) {
+            uint2 o;
+            o.x = pack2e(oacc[g][ds][0], oacc[g][ds][1]);
+            o.y = pack2e(oacc[g][ds][2], oacc[g][ds][3]);
+            *(uint2*)(op + ds * 16 + fg * 4) = o;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // At most 16 queries per (batch, head): KV-cached decoding (1 query against the whole cache) and the mask decoder's
 // token -> image attention (7..16 queries against 4096 keys).  The kernels above give such a call ONE working wave per head
@@ -1939,6 +2272,16 @@ int launch_sam_global(const AttnArgs& a, hipStream_t st) {
     return ull_check_launch();
 }
 
+int launch_sam_global_exact(const AttnArgs& a, hipStream_t st) {
+    constexpr int LDS = 4 * 64 * 256 + 4 * 32 * 64 * 2;        // as launch_sam_global
+    static UllOncePerDevice once;
+    if (once.first()) (void)hipFuncSetAttribute((const void*)sam_global_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const int nq = a.Sq / 128;
+    const dim3 grid(((a.B * a.H + 7) / 8) * 8 * nq);
+    hipLaunchKernelGGL(sam_global_exact_kernel, grid, dim3(256), LDS, st, a);
+    return ull_check_launch();
+}
+
 template <int HDP, int FL, int TPW>
 int launch_fewq_t(const AttnArgs& a, int nwv, hipStream_t st) {
     const int lds = 2 * 16 * 16 * 4 + nwv * HDP * 16 * 4;
@@ -2077,6 +2420,37 @@ extern "C" int ULL_FN(ull_attention_)(const void* Q, int64_t q_bs, int64_t q_hs,
     if (hd <= 32) return dispatch_nt<32>(a, st);
     if (hd <= 64) return dispatch_nt<64>(a, st);
     return dispatch_nt<128>(a, st);
+}
+
+// SAM global attention on the 64 x 64 grid with the reference's rounding point (sam_global_exact_kernel; definition in the header).
+// Q / K / V / O: [B, H, side * side, hd] by (batch, head, token) strides in elements, rows hd-contiguous; rel_pos_h / rel_pos_w: the raw
+// [2 side - 1, hd] tables, contiguous.  Everything is checked before the launch.
+extern "C" int ULL_FN(ull_sam_global_attention_exact_)(const void* Q, int64_t q_bs, int64_t q_hs, int64_t q_ss, const void* K, int64_t k_bs,
+                                                   int64_t k_hs, int64_t k_ss, const void* V, int64_t v_bs, int64_t v_hs, int64_t v_ss,
+                                                   const void* rel_pos_h, const void* rel_pos_w, int64_t B, int64_t H, int64_t side, int64_t hd,
+                                                   float q_scale, void* O, int64_t o_bs, int64_t o_hs, int64_t o_ss, void* stream) {
+    if (!Q || !K || !V || !rel_pos_h || !rel_pos_w || !O || B <= 0 || H <= 0) return ULL_ERR_ARG;
+    if (side != 64 || hd != 80 || B * H > (1 << 20)) return ULL_ERR_SHAPE;
+    // 16-byte fragment reads / DMA pieces / O stores: 8-element strides, 16-byte bases (as the V-as-rows form of ull_attention)
+    if (((q_ss | q_hs | q_bs | k_ss | k_hs | k_bs | v_ss | v_hs | v_bs | o_ss | o_hs | o_bs) & 7) ||
+        (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)O | (uintptr_t)rel_pos_h | (uintptr_t)rel_pos_w) & 15))
+        return ULL_ERR_SHAPE;
+    // rows do not overlap; 32-bit per-lane DMA offsets inside a 64-key tile
+    if (q_ss < hd || k_ss < hd || v_ss < hd || o_ss < hd || 64 * k_ss * 2 >= (1L << 31) || 64 * v_ss * 2 >= (1L << 31)) return ULL_ERR_SHAPE;
+    AttnArgs a;
+    a.Q = (const elem_t*)Q; a.K = (const elem_t*)K; a.Vt = (const elem_t*)V; a.O = (elem_t*)O;
+    a.key_mask = nullptr;
+    a.q_bs = q_bs; a.q_hs = q_hs; a.q_ss = q_ss; a.k_bs = k_bs; a.k_hs = k_hs; a.k_ss = k_ss;
+    a.vt_bs = v_bs; a.vt_hs = v_hs; a.vt_ds = v_ss; a.o_bs = o_bs; a.o_hs = o_hs; a.o_ss = o_ss;
+    a.B = (int)B; a.H = (int)H; a.Sq = a.Sk = (int)(side * side); a.hd = (int)hd; a.vt_len = 0;
+    a.causal = 0; a.scale_mode = 0; a.scale = 1.0f;
+    a.zeros = nullptr;
+    a.rel_h = (const elem_t*)rel_pos_h; a.rel_w = (const elem_t*)rel_pos_w; a.KH = a.KW = (int)side; a.q_scale = q_scale;
+    a.inv_kw = 1.0f / (float)side;
+    a.rel_mode = 2; a.win16 = 0; a.mg_h = a.mg_nwx = a.mg_nwy = a.mg_nw = 0;
+    a.v_rows = 1;
+    a.img_h = a.img_w = a.nwy = a.nwx = 0; a.k_pad = a.v_pad = nullptr;
+    return launch_sam_global_exact(a, (hipStream_t)stream);
 }
 
 // x: first of `n_heads` consecutive heads (q heads then k heads of a fused QKV row); positions int64 [tokens];

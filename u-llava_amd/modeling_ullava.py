@@ -78,6 +78,21 @@ class UllavaForCausalLM(nn.Module):
         self.llm.quantize_weights(fmt, activations=activations, activation_scope=activation_scope)
         return self
 
+    @property
+    def sam_attention(self) -> str:
+        return self._sam.global_attention
+
+    def set_sam_attention(self, mode: str = "exact"):
+        """How the SAM image encoder's global blocks (64 x 64 grid, 4096 keys) round their softmax in inference encodes (`forward` without
+        gradients through SAM and `evaluate`; the encoder is frozen, the training graph does not contain it and is not affected):
+        "streamed" (default) rounds exp(s - running max) and divides by the row sum at the end; "exact" normalises in fp32 and rounds
+        afterwards, as the reference does (image_encoder.py:251-253), at about twice the attention time -- the per-op block loop with
+        `ops.sam_global_attention_exact`.  A global block without such a kernel then raises NotImplementedError."""
+        if mode not in SamEngine.GLOBAL_ATTENTION_MODES:
+            raise ValueError(f"sam attention mode must be one of {SamEngine.GLOBAL_ATTENTION_MODES}, got {mode!r}")
+        self._sam.global_attention = mode
+        return self
+
     def save_pretrained(self, save_directory, **kwargs):
         if self.llm.weight_quantization is not None:
             self.llm._refuse_quantized("save_pretrained")

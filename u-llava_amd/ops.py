@@ -928,6 +928,39 @@ def sam_window_attention(qkv: torch.Tensor, pad_row: torch.Tensor, rel_pos_h: to
     return out
 
 
+def sam_global_exact_takes(side: int, hd: int, dtype) -> bool:
+    """Whether `sam_global_attention_exact` has a kernel for a global block on a side x side grid: the ViT-H shape (64 x 64 tokens, head
+    dim 80) in the two 16-bit builds.  (The fp32 build's attention already normalises before it rounds -- it rounds nothing.)"""
+    return side == 64 and hd == 80 and dtype in (BF16, F16)
+
+
+def sam_global_attention_exact(qkv: torch.Tensor, rel_pos_h: torch.Tensor, rel_pos_w: torch.Tensor, B: int, H: int, side: int, hd: int,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention.forward of a SAM global block (image_encoder.py:196-260) with the reference's rounding point: softmax normalised in fp32,
+    THEN rounded, then attn @ v (the default route, `attention` with rel_pos_hw, rounds exp(s - running max) and divides at the end).
+    qkv [B * side * side, >= 3 * H * hd] rows q | k | v (any row pitch that is a multiple of 8) -> out [B * side * side, H * hd] (a view
+    with a wider row pitch is fine).  Two passes over the keys in one launch; `sam_global_exact_takes` says which shapes have a kernel."""
+    _chk(qkv, "qkv"); _chk(rel_pos_h, "rel_pos_h", qkv.dtype); _chk(rel_pos_w, "rel_pos_w", qkv.dtype)
+    if not sam_global_exact_takes(side, hd, qkv.dtype):
+        raise NotImplementedError(f"u-llava_amd: no exact SAM global-attention kernel for a {side} x {side} grid with head dim {hd} in {qkv.dtype}")
+    S, C = side * side, H * hd
+    if qkv.dim() != 2 or qkv.shape[0] != B * S or qkv.shape[1] < 3 * C:
+        raise ValueError(f"qkv {tuple(qkv.shape)} for B={B} side={side} C={C}")
+    rel_pos_h, rel_pos_w = fit_rel_pos(rel_pos_h, side), fit_rel_pos(rel_pos_w, side)
+    if rel_pos_h.shape[1] != hd or rel_pos_w.shape[1] != hd:
+        raise ValueError(f"rel_pos tables of width {rel_pos_h.shape[1]} / {rel_pos_w.shape[1]} for head_dim {hd}")
+    if out is None:
+        out = torch.empty(B * S, C, device=qkv.device, dtype=qkv.dtype)
+    _chk(out, "out", qkv.dtype)
+    if out.dim() != 2 or out.shape != (B * S, C):
+        raise ValueError(f"out {tuple(out.shape)} for B={B} side={side} C={C}")
+    ld, ldo = qkv.stride(0), out.stride(0)
+    st = (S * ld, hd, ld)
+    _lib.call("ull_sam_global_attention_exact_" + _SFX[qkv.dtype], _p(qkv), *st, _p(qkv[:, C:]), *st, _p(qkv[:, 2 * C:]), *st,
+              _p(rel_pos_h.contiguous()), _p(rel_pos_w.contiguous()), B, H, side, hd, float(hd ** -0.5), _p(out), S * ldo, hd, ldo, _stream())
+    return out
+
+
 def rope_inplace(x: torch.Tensor, row_stride: int, positions: torch.Tensor, inv_freq: torch.Tensor, tokens: int, n_heads: int, hd: int):
     _chk(x, "x"); _chk(positions, "positions", torch.int64); _chk(inv_freq, "inv_freq", torch.float32)
     _lib.call("ull_rope_inplace_" + _SFX[x.dtype], _p(x), row_stride, _p(positions), _p(inv_freq), tokens, n_heads, hd, _stream())

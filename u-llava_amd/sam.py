@@ -114,6 +114,15 @@ def build_sam_holder(cfg: SamConfig, device=None, dtype=BF16) -> nn.Module:
 class SamEngine:
     """Runs the SAM sub-models of a `build_sam_holder` tree on the HIP path (weights re-laid out once)."""
 
+    # How the image encoder's GLOBAL blocks with more than 1024 keys round their softmax (inference encodes only; blocks with at most 1024
+    # keys -- windows, small grids -- and the fp32 build normalise before they round in either mode):
+    #   "streamed"  one pass over the keys, P = r16(exp(s - running max)), divided by the row sum at the end (the fast default);
+    #   "exact"     the reference's order (image_encoder.py:251-253): softmax normalised in fp32, then rounded, then attn @ v --
+    #               ops.sam_global_attention_exact, per-op loop (the coarse ops.sam_blocks entry is not taken).  A global block that has no
+    #               such kernel raises NotImplementedError: it is never run in the streamed form instead.
+    GLOBAL_ATTENTION_MODES = ("streamed", "exact")
+    global_attention = "streamed"
+
     def __init__(self, sam: nn.Module, cfg: SamConfig):
         self.sam, self.cfg = sam, cfg
         self._pk = None
@@ -154,11 +163,20 @@ class SamEngine:
     # -- image encoder (image_encoder.py:110-125) ------------------------------------------------------------------
     def encode(self, pixel_values: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
         """[B,3,S,S] -> token-major embeddings [B, g*g, out_chans].  trace: optional dict receiving the stage outputs [B, g, g, C]."""
-        cfg, enc, pk = self.cfg, self.sam.image_encoder, self.pk()
+        if self.global_attention not in self.GLOBAL_ATTENTION_MODES:
+            raise ValueError(f"SamEngine.global_attention must be one of {self.GLOBAL_ATTENTION_MODES}, got {self.global_attention!r}")
+        cfg, enc = self.cfg, self.sam.image_encoder
         B = pixel_values.shape[0]
         C, nH = cfg.embed_dim, cfg.num_heads
         hd = C // nH
         g = cfg.img_size // cfg.patch_size
+        dtype = enc.pos_embed.dtype
+        if (self.global_attention == "exact" and dtype != torch.float32 and g * g > 1024 and any(i < len(enc.blocks) for i in cfg.global_attn_indexes)
+                and not ops.sam_global_exact_takes(g, hd, dtype)):
+            # (before anything is launched)
+            raise NotImplementedError(f"global_attention='exact': no exact kernel for a global block on a {g} x {g} grid with head dim {hd} "
+                                      f"({dtype}); the streamed form is not substituted")
+        pk = self.pk()
         if pk["patch_wp"] is not None:                                       # fused: A tiles DMA'd straight from the pixels
             x = ops.patchify(pixel_values.to(enc.pos_embed.dtype).contiguous(), pk["patch_wp"], cfg.patch_size, enc.patch_embed.proj.bias)
         else:
@@ -168,7 +186,8 @@ class SamEngine:
         if trace is not None:
             trace["embed"] = x.view(B, g, g, C)
         I = enc.blocks[0].mlp.lin1.weight.shape[0] if len(enc.blocks) else 0
-        coarse = (trace is None and ops.coarse_ok() and len(enc.blocks) > 0 and hd == 80 and g == 64 and cfg.window_size == 14 and C % 64 == 0
+        exact = self.global_attention == "exact" and x.dtype != torch.float32
+        coarse = (not exact and trace is None and ops.coarse_ok() and len(enc.blocks) > 0 and hd == 80 and g == 64 and cfg.window_size == 14 and C % 64 == 0
                   and I % 64 == 0 and all(b.attn.qkv.bias is not None for b in enc.blocks) and x.dtype != torch.float32)
         if coarse:
             # one C call for all blocks (csrc/layers.hip): the same launches as the loop below, bit-identical results
@@ -205,7 +224,9 @@ class SamEngine:
                 qkv = ops.linear(y, blk.attn.qkv.weight, blk.attn.qkv.bias)          # [NB*S, 3C]: q | k | v, heads contiguous
                 strides = (S * 3 * C, hd, 3 * C)
                 att = torch.empty(NB * S, C, device=x.device, dtype=x.dtype)
-                if glob and side != 64:
+                if exact and glob and S > 1024:
+                    ops.sam_global_attention_exact(qkv, blk.attn.rel_pos_h, blk.attn.rel_pos_w, NB, nH, side, hd, out=att)
+                elif glob and side != 64:
                     # other grid sizes: per-query bias tables from their own kernel, looked up by the attention kernel
                     rel_h, rel_w = ops.sam_relpos(qkv, strides, blk.attn.rel_pos_h, blk.attn.rel_pos_w, NB, nH, side, side, hd)
                     ops.attention(qkv, qkv[:, C:], qkv[:, 2 * C:], att, NB, nH, S, S, hd, strides, strides, (S * C, hd, C), None, causal=False,
