@@ -1,5 +1,5 @@
 """No GPU: FP8 activations in batched decode steps (quantize_weights("fp8_e4m3", activations="fp8_e4m3", activation_scope="prefill+decode"),
-DESIGN f10) -- the two exported entries and their refusals, the routing rule ops.a8w8_decode_takes, and the argument validation of
+DESIGN f10) -- the two exported entries and their refusals, the "a8w8_skinny" route of the dispatch rule (ops.linear_route), and the argument validation of
 activation_scope.  The arithmetic is the definition restated in tests/test_a8w8_cpu.py (a8w8_exact / a8w8_reference); the GPU tests are in
 tests/test_a8_decode_gpu.py."""
 import inspect
@@ -80,29 +80,38 @@ def _fp8(N, K, pitch=None):
 
 def test_truth_table_of_a8w8_decode_takes():
     ops = pkg("ops")
+
+    def a8w8_decode_takes(M, N, K, w):                           # the one rule's answer under activation_scope="prefill+decode"
+        assert tuple(w.shape) == (N, K)
+        return ops.linear_route(M, w, ops.ActQuant("fp8_e4m3", decode=True)) == "a8w8_skinny"
+
+    def a8w8_takes(M, N, K, w):                                  # ... and under the default scope
+        assert tuple(w.shape) == (N, K)
+        return ops.linear_route(M, w, ops.ActQuant("fp8_e4m3")) == "a8w8"
+
     w = _fp8(4096, 4096)
-    assert [ops.a8w8_decode_takes(M, 4096, 4096, w) for M in (4, 5, 16, 17, 32, 33)] == [False, True, True, True, True, False]
-    assert [M for M in range(0, 70) if ops.a8w8_decode_takes(M, 4096, 4096, w)] == list(range(5, 33))
+    assert [a8w8_decode_takes(M, 4096, 4096, w) for M in (4, 5, 16, 17, 32, 33)] == [False, True, True, True, True, False]
+    assert [M for M in range(0, 70) if a8w8_decode_takes(M, 4096, 4096, w)] == list(range(5, 33))
     # N * K just below and at 2^22
-    assert not ops.a8w8_decode_takes(8, 2047, 2048, _fp8(2047, 2048))
-    assert ops.a8w8_decode_takes(8, 2048, 2048, _fp8(2048, 2048))
-    assert not ops.a8w8_decode_takes(8, 32768 - 256, 128, _fp8(32768 - 256, 128)) and ops.a8w8_decode_takes(8, 32768, 128, _fp8(32768, 128))
+    assert not a8w8_decode_takes(8, 2047, 2048, _fp8(2047, 2048))
+    assert a8w8_decode_takes(8, 2048, 2048, _fp8(2048, 2048))
+    assert not a8w8_decode_takes(8, 32768 - 256, 128, _fp8(32768 - 256, 128)) and a8w8_decode_takes(8, 32768, 128, _fp8(32768, 128))
     # K = 4096 + 64: a multiple of 32 (the W8A16 skinny kernel takes it) but no whole number of 128-code K-tiles
     K = 4096 + 64
-    assert ops._linear_route(8, 4096, K, K, 0)[0] == "skinny" and not ops.a8w8_decode_takes(8, 4096, K, _fp8(4096, K))
+    assert ops._linear_route(8, 4096, K, K, 0)[0] == "skinny" and not a8w8_decode_takes(8, 4096, K, _fp8(4096, K))
     # a row pitch the kernels cannot stream
-    assert not ops.a8w8_decode_takes(8, 4096, 4096, _fp8(4096, 4096, pitch=4100)) and ops.a8w8_decode_takes(8, 4096, 4096, _fp8(4096, 4096, pitch=4104))
+    assert not a8w8_decode_takes(8, 4096, 4096, _fp8(4096, 4096, pitch=4100)) and a8w8_decode_takes(8, 4096, 4096, _fp8(4096, 4096, pitch=4104))
     # only fp8 weights
-    assert not ops.a8w8_decode_takes(8, 4096, 4096, torch.empty(4096, 4096, dtype=BF, device="meta"))
+    assert not a8w8_decode_takes(8, 4096, 4096, torch.empty(4096, 4096, dtype=BF, device="meta"))
     mx = ops.Mxfp4Weight(torch.empty(4096, 2048, dtype=torch.uint8, device="meta"),
                          torch.empty(4096, ops.Mxfp4Weight.scale_pitch(4096), dtype=torch.uint8, device="meta"), 4096)
-    assert not ops.a8w8_decode_takes(8, 4096, 4096, mx)
+    assert not a8w8_decode_takes(8, 4096, 4096, mx) and ops.linear_route(8, mx, ops.ActQuant("mxfp8_e4m3", decode=True)) == "skinny"
     # the LLaMA-7B layer Linears are all on the rule, and it mirrors the skinny route at 5 .. 16 rows
     for N, K in ((12288, 4096), (4096, 4096), (22016, 4096), (4096, 11008)):
         for M in (5, 8, 16):
-            assert ops._linear_route(M, N, K, K, 0)[0] == "skinny" and ops.a8w8_decode_takes(M, N, K, _fp8(N, K))
+            assert ops._linear_route(M, N, K, K, 0)[0] == "skinny" and a8w8_decode_takes(M, N, K, _fp8(N, K))
         for M in (17, 32):
-            assert ops.a8w8_takes(M, N, K, _fp8(N, K)) and ops.a8w8_decode_takes(M, N, K, _fp8(N, K))
+            assert a8w8_takes(M, N, K, _fp8(N, K)) and a8w8_decode_takes(M, N, K, _fp8(N, K))
 
 
 # ---- activation_scope: argument validation (before any device work) -------------------------------------------------------------------------

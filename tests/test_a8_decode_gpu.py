@@ -188,7 +188,7 @@ def models():
     ops = pkg("ops")
     for w in m["a8d"]._packed["llama"]:
         for k in ("w_qkv", "w_o", "w_gu", "w_down"):
-            assert all(ops.a8w8_decode_takes(B, *w[k].shape, w[k]) for B in (8, 32)), "the layer Linears are on the rule"
+            assert all(ops.linear_route(B, w[k], ops.ActQuant("fp8_e4m3", decode=True)) == "a8w8_skinny" for B in (8, 32)), "the layer Linears are on the rule"
     return m
 
 

@@ -129,6 +129,10 @@ def test_non_bf16_model_is_refused(dtype):
 # ---- the routing rule -----------------------------------------------------------------------------------------------------------------
 def test_a8_is_taken_exactly_on_the_gemm_route():
     ops = pkg("ops")
+
+    def a8w8_takes(M, N, K, w):                                  # the one rule's answer for an fp8-activation model (prefill scope)
+        assert tuple(w.shape) == (N, K)
+        return ops.linear_route(M, w, ops.ActQuant("fp8_e4m3")) == "a8w8"
     shapes = [(N, K) for N, K in ((4096, 4096), (12288, 4096), (22016, 4096), (4096, 11008), (192, 64), (64, 128), (1000, 2048))]
     seen = set()
     for N, K in shapes:
@@ -136,13 +140,13 @@ def test_a8_is_taken_exactly_on_the_gemm_route():
         for M in (1, 2, 3, 4, 5, 8, 16, 17, 26, 128, 643, 20576):
             route = ops._linear_route(M, N, K, w.route_pitch, 0)[0]
             seen.add(route)
-            assert ops.a8w8_takes(M, N, K, w) == (route == "gemm"), (M, N, K, route)
+            assert a8w8_takes(M, N, K, w) == (route == "gemm"), (M, N, K, route)
     assert seen == {"gemv", "skinny", "gemm"}
     # the LLaMA-7B shapes: decode steps never, 17 rows and more always
     w = ops.Fp8Weight(torch.empty(4096, 4096, dtype=torch.uint8, device="meta"), torch.empty(4096, dtype=torch.float32, device="meta"))
-    assert [M for M in range(1, 40) if ops.a8w8_takes(M, 4096, 4096, w)] == list(range(17, 40))
+    assert [M for M in range(1, 40) if a8w8_takes(M, 4096, 4096, w)] == list(range(17, 40))
     # only fp8 weights: a bf16 tensor or an mxfp4 weight never takes it
-    assert not ops.a8w8_takes(643, 4096, 4096, torch.empty(4096, 4096, dtype=BF, device="meta"))
+    assert not a8w8_takes(643, 4096, 4096, torch.empty(4096, 4096, dtype=BF, device="meta"))
 
 
 # ---- the C entry ----------------------------------------------------------------------------------------------------------------------

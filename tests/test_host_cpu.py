@@ -613,6 +613,159 @@ def test_linear_route_table(shape, want):
     assert (*ops._linear_route(*shape), ops._big(*shape[:3])) == want
 
 
+# The unified rule with the weight's format and the activation mode (ops.linear_route): one row per (weight kind, mode, (N, K, row pitch)), one
+# letter per M of ROUTE_MS -- v gemv (RMSNorm fused), V gemv (RMSNorm first), s skinny, g gemm, 8 a8w8, 4 w4a8, k a8w8_skinny (RMSNorm fused
+# into the row quantization).  Expected values composed from the parent of the change that made it one rule: its `_linear_route` and the
+# three predicates the model asked beside it, in the model's order (decode predicate, GEMM predicate, weight-only rule).
+ROUTE_MS = (1, 2, 3, 4, 5, 8, 16, 17, 32, 33, 128, 643, 1024)
+ROUTE_LETTER = {("gemv", False): "v", ("gemv", True): "V", ("skinny", True): "s", ("gemm", True): "g", ("a8w8", True): "8", ("w4a8", True): "4",
+                ("a8w8_skinny", False): "k"}
+UNIFIED_ROUTES = [
+    # bf16, none
+    ("bf16", "none", (12288, 4096, 4096), "vvsssssgggggg"),
+    ("bf16", "none", (4096, 4096, 4096), "vvsssssgggggg"),
+    ("bf16", "none", (22016, 4096, 4096), "vvsssssgggggg"),
+    ("bf16", "none", (4096, 11008, 11008), "vVsssssgggggg"),
+    ("bf16", "none", (4096, 4096, 4100), "vvvvggggggggg"),
+    ("bf16", "none", (4096, 4096, 4104), "vvsssssgggggg"),
+    ("bf16", "none", (4096, 4160, 4160), "vvsssssgggggg"),
+    ("bf16", "none", (2048, 2048, 2048), "vvsssssgggggg"),
+    ("bf16", "none", (2047, 2048, 2048), "vvvvggggggggg"),
+    ("bf16", "none", (192, 64, 64), "vvvvggggggggg"),
+    ("bf16", "none", (32768, 128, 128), "vvsssssgggggg"),
+    ("bf16", "none", (32512, 128, 128), "vvvvggggggggg"),
+    # bf16, a8
+    ("bf16", "a8", (12288, 4096, 4096), "vvsssssgggggg"),
+    ("bf16", "a8", (4096, 4096, 4096), "vvsssssgggggg"),
+    ("bf16", "a8", (22016, 4096, 4096), "vvsssssgggggg"),
+    ("bf16", "a8", (4096, 11008, 11008), "vVsssssgggggg"),
+    ("bf16", "a8", (4096, 4096, 4100), "vvvvggggggggg"),
+    ("bf16", "a8", (4096, 4096, 4104), "vvsssssgggggg"),
+    ("bf16", "a8", (4096, 4160, 4160), "vvsssssgggggg"),
+    ("bf16", "a8", (2048, 2048, 2048), "vvsssssgggggg"),
+    ("bf16", "a8", (2047, 2048, 2048), "vvvvggggggggg"),
+    ("bf16", "a8", (192, 64, 64), "vvvvggggggggg"),
+    ("bf16", "a8", (32768, 128, 128), "vvsssssgggggg"),
+    ("bf16", "a8", (32512, 128, 128), "vvvvggggggggg"),
+    # bf16, a8+decode
+    ("bf16", "a8+decode", (12288, 4096, 4096), "vvsssssgggggg"),
+    ("bf16", "a8+decode", (4096, 4096, 4096), "vvsssssgggggg"),
+    ("bf16", "a8+decode", (22016, 4096, 4096), "vvsssssgggggg"),
+    ("bf16", "a8+decode", (4096, 11008, 11008), "vVsssssgggggg"),
+    ("bf16", "a8+decode", (4096, 4096, 4100), "vvvvggggggggg"),
+    ("bf16", "a8+decode", (4096, 4096, 4104), "vvsssssgggggg"),
+    ("bf16", "a8+decode", (4096, 4160, 4160), "vvsssssgggggg"),
+    ("bf16", "a8+decode", (2048, 2048, 2048), "vvsssssgggggg"),
+    ("bf16", "a8+decode", (2047, 2048, 2048), "vvvvggggggggg"),
+    ("bf16", "a8+decode", (192, 64, 64), "vvvvggggggggg"),
+    ("bf16", "a8+decode", (32768, 128, 128), "vvsssssgggggg"),
+    ("bf16", "a8+decode", (32512, 128, 128), "vvvvggggggggg"),
+    # fp8, none
+    ("fp8", "none", (12288, 4096, 4096), "vvsssssgggggg"),
+    ("fp8", "none", (4096, 4096, 4096), "vvsssssgggggg"),
+    ("fp8", "none", (22016, 4096, 4096), "vvsssssgggggg"),
+    ("fp8", "none", (4096, 11008, 11008), "vVsssssgggggg"),
+    ("fp8", "none", (4096, 4096, 4100), "vvvvggggggggg"),
+    ("fp8", "none", (4096, 4096, 4104), "vvsssssgggggg"),
+    ("fp8", "none", (4096, 4160, 4160), "vvsssssgggggg"),
+    ("fp8", "none", (2048, 2048, 2048), "vvsssssgggggg"),
+    ("fp8", "none", (2047, 2048, 2048), "vvvvggggggggg"),
+    ("fp8", "none", (192, 64, 64), "vvvvggggggggg"),
+    ("fp8", "none", (32768, 128, 128), "vvsssssgggggg"),
+    ("fp8", "none", (32512, 128, 128), "vvvvggggggggg"),
+    # fp8, a8
+    ("fp8", "a8", (12288, 4096, 4096), "vvsssss888888"),
+    ("fp8", "a8", (4096, 4096, 4096), "vvsssss888888"),
+    ("fp8", "a8", (22016, 4096, 4096), "vvsssss888888"),
+    ("fp8", "a8", (4096, 11008, 11008), "vVsssss888888"),
+    ("fp8", "a8", (4096, 4096, 4100), "vvvv888888888"),
+    ("fp8", "a8", (4096, 4096, 4104), "vvsssss888888"),
+    ("fp8", "a8", (4096, 4160, 4160), "vvsssss888888"),
+    ("fp8", "a8", (2048, 2048, 2048), "vvsssss888888"),
+    ("fp8", "a8", (2047, 2048, 2048), "vvvv888888888"),
+    ("fp8", "a8", (192, 64, 64), "vvvv888888888"),
+    ("fp8", "a8", (32768, 128, 128), "vvsssss888888"),
+    ("fp8", "a8", (32512, 128, 128), "vvvv888888888"),
+    # fp8, a8+decode
+    ("fp8", "a8+decode", (12288, 4096, 4096), "vvsskkkkk8888"),
+    ("fp8", "a8+decode", (4096, 4096, 4096), "vvsskkkkk8888"),
+    ("fp8", "a8+decode", (22016, 4096, 4096), "vvsskkkkk8888"),
+    ("fp8", "a8+decode", (4096, 11008, 11008), "vVsskkkkk8888"),
+    ("fp8", "a8+decode", (4096, 4096, 4100), "vvvv888888888"),
+    ("fp8", "a8+decode", (4096, 4096, 4104), "vvsskkkkk8888"),
+    ("fp8", "a8+decode", (4096, 4160, 4160), "vvsssss888888"),
+    ("fp8", "a8+decode", (2048, 2048, 2048), "vvsskkkkk8888"),
+    ("fp8", "a8+decode", (2047, 2048, 2048), "vvvv888888888"),
+    ("fp8", "a8+decode", (192, 64, 64), "vvvv888888888"),
+    ("fp8", "a8+decode", (32768, 128, 128), "vvsskkkkk8888"),
+    ("fp8", "a8+decode", (32512, 128, 128), "vvvv888888888"),
+    # mxfp4, none
+    ("mxfp4", "none", (12288, 4096, 4096), "vvsssssgggggg"),
+    ("mxfp4", "none", (4096, 4096, 4096), "vvsssssgggggg"),
+    ("mxfp4", "none", (22016, 4096, 4096), "vvsssssgggggg"),
+    ("mxfp4", "none", (4096, 11008, 11008), "vVsssssgggggg"),
+    ("mxfp4", "none", (4096, 4160, 4160), "vvsssssgggggg"),
+    ("mxfp4", "none", (2048, 2048, 2048), "vvsssssgggggg"),
+    ("mxfp4", "none", (2047, 2048, 2048), "vvvvggggggggg"),
+    ("mxfp4", "none", (192, 64, 64), "vvvvggggggggg"),
+    ("mxfp4", "none", (32768, 128, 128), "vvsssssgggggg"),
+    ("mxfp4", "none", (32512, 128, 128), "vvvvggggggggg"),
+    # mxfp4, a8
+    ("mxfp4", "a8", (12288, 4096, 4096), "vvsssss444444"),
+    ("mxfp4", "a8", (4096, 4096, 4096), "vvsssss444444"),
+    ("mxfp4", "a8", (22016, 4096, 4096), "vvsssss444444"),
+    ("mxfp4", "a8", (4096, 11008, 11008), "vVsssss444444"),
+    ("mxfp4", "a8", (4096, 4160, 4160), "vvsssss444444"),
+    ("mxfp4", "a8", (2048, 2048, 2048), "vvsssss444444"),
+    ("mxfp4", "a8", (2047, 2048, 2048), "vvvv444444444"),
+    ("mxfp4", "a8", (192, 64, 64), "vvvv444444444"),
+    ("mxfp4", "a8", (32768, 128, 128), "vvsssss444444"),
+    ("mxfp4", "a8", (32512, 128, 128), "vvvv444444444"),
+]
+
+
+def _route_weight(ops, kind, N, K, pitch):
+    if kind == "bf16":
+        return torch.empty(N, pitch, dtype=torch.bfloat16, device="meta")[:, :K]
+    if kind == "fp8":
+        return ops.Fp8Weight(torch.empty(N, pitch, dtype=torch.uint8, device="meta")[:, :K], torch.empty(N, dtype=torch.float32, device="meta"))
+    assert pitch == K
+    return ops.Mxfp4Weight(torch.empty(N, K // 2, dtype=torch.uint8, device="meta"),
+                           torch.empty(N, ops.Mxfp4Weight.scale_pitch(K), dtype=torch.uint8, device="meta"), K)
+
+
+def test_unified_route_table_counts():
+    """The table is whole: 1196 cases, and per weight kind and mode the outcome counts of the parent's composition."""
+    assert sum(len(r[3]) for r in UNIFIED_ROUTES) == 1196 and all(len(r[3]) == len(ROUTE_MS) for r in UNIFIED_ROUTES)
+    assert len({r[:3] for r in UNIFIED_ROUTES}) == len(UNIFIED_ROUTES)
+
+    def count(kind, mode):
+        s = "".join(r[3] for r in UNIFIED_ROUTES if r[:2] == (kind, mode)).replace("V", "v")
+        return {c: s.count(c) for c in set(s)}
+    assert count("fp8", "a8+decode") == {"k": 35, "8": 70, "s": 19, "v": 32}
+    assert count("fp8", "a8") == {"8": 84, "s": 40, "v": 32}
+    assert count("mxfp4", "a8") == {"4": 69, "s": 35, "v": 26}
+    for kind, mode, shape, want in UNIFIED_ROUTES:               # a 16-bit weight, or no mode: the weight-only rows
+        if kind == "bf16" or mode == "none":
+            assert want == next(r[3] for r in UNIFIED_ROUTES if r[0] == kind and r[1] == "none" and r[2] == shape)
+            assert not set(want) & set("84k")
+
+
+@pytest.mark.parametrize("kind,mode,shape,want", UNIFIED_ROUTES)
+def test_unified_route_table(kind, mode, shape, want):
+    ops = pkg("ops")
+    N, K, pitch = shape
+    w = _route_weight(ops, kind, N, K, pitch)
+    aq = None if mode == "none" else ops.ActQuant("mxfp8_e4m3" if kind == "mxfp4" else "fp8_e4m3", mode == "a8+decode")
+    ldw, wfmt = (w.route_pitch, w.fmt_name) if kind != "bf16" else (w.stride(0), None)
+    assert ldw == pitch
+    got = "".join(ROUTE_LETTER[ops._linear_route(M, N, K, ldw, 0, wfmt, aq)] for M in ROUTE_MS)
+    assert got == want
+    assert [ops.linear_route(M, w, aq) for M in ROUTE_MS] == [ops._linear_route(M, N, K, ldw, 0, wfmt, aq)[0] for M in ROUTE_MS]
+    if aq is None:                                               # no mode: exactly the five-argument rule
+        assert [ops._linear_route(M, N, K, ldw, 0, wfmt) for M in ROUTE_MS] == [ops._linear_route(M, N, K, ldw, 0) for M in ROUTE_MS]
+
+
 # ---- the weight format travels with the weight (ULL_WF_*): refusals, all of which return before any launch --------------------------------
 _ADDR = 0x10000                 # a non-null address that is never dereferenced: every call below returns from its argument checks
 ERR_ARG, ERR_SHAPE = -1, -2

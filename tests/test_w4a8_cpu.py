@@ -176,22 +176,29 @@ def _meta_mx(N, K):
 
 def test_w4a8_is_taken_exactly_on_the_gemm_route():
     ops = pkg("ops")
+
+    def w4a8_takes(M, N, K, w):                                  # the one rule's answers for the two activation formats (prefill scope)
+        assert tuple(w.shape) == (N, K)
+        return ops.linear_route(M, w, ops.ActQuant("mxfp8_e4m3")) == "w4a8"
+
+    def a8w8_takes(M, N, K, w):                                  # (asked about a weight of another format: its own N, K)
+        return ops.linear_route(M, w, ops.ActQuant("fp8_e4m3")) == "a8w8"
     seen = set()
     for N, K in ((4096, 4096), (12288, 4096), (22016, 4096), (4096, 11008), (192, 64), (64, 128), (1000, 2048)):
         w = _meta_mx(N, K)
         for M in (1, 2, 3, 4, 5, 8, 16, 17, 26, 128, 643, 20576):
             route = ops._linear_route(M, N, K, w.route_pitch, 0)[0]
             seen.add(route)
-            assert ops.w4a8_takes(M, N, K, w) == (route == "gemm"), (M, N, K, route)
+            assert w4a8_takes(M, N, K, w) == (route == "gemm"), (M, N, K, route)
     assert seen == {"gemv", "skinny", "gemm"}
     w = _meta_mx(4096, 4096)                                     # LLaMA-7B: decode steps (M <= 16) never, 17 rows and more always
-    assert [M for M in range(1, 40) if ops.w4a8_takes(M, 4096, 4096, w)] == list(range(17, 40))
+    assert [M for M in range(1, 40) if w4a8_takes(M, 4096, 4096, w)] == list(range(17, 40))
     w = _meta_mx(192, 64)                                        # a small weight: the GEMV up to 4 rows, the GEMM from 5 on
-    assert [M for M in range(1, 20) if ops.w4a8_takes(M, 192, 64, w)] == list(range(5, 20))
+    assert [M for M in range(1, 20) if w4a8_takes(M, 192, 64, w)] == list(range(5, 20))
     # only mxfp4 weights: a bf16 tensor or an fp8 weight never takes it
-    assert not ops.w4a8_takes(643, 4096, 4096, torch.empty(4096, 4096, dtype=BF, device="meta"))
+    assert not w4a8_takes(643, 4096, 4096, torch.empty(4096, 4096, dtype=BF, device="meta"))
     f8 = ops.Fp8Weight(torch.empty(4096, 4096, dtype=torch.uint8, device="meta"), torch.empty(4096, dtype=torch.float32, device="meta"))
-    assert not ops.w4a8_takes(643, 4096, 4096, f8) and not ops.a8w8_takes(643, 4096, 4096, w)
+    assert not w4a8_takes(643, 4096, 4096, f8) and not a8w8_takes(643, 4096, 4096, w)
 
 
 # ---- the C entries --------------------------------------------------------------------------------------------------------------------

@@ -197,13 +197,10 @@ __global__ __launch_bounds__(64) void rmsnorm_quantize_rows_fp8_kernel(const ele
 extern "C" int ull_gemm_skinny_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, void* C,
                                          int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
     if (!Xq || !x_scales || !Q || !w_scales || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
-    if (flags & ~(EPI_RESID | EPI_SWIGLU | EPI_OUT_F32)) return ULL_ERR_ARG;
-    if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
+    if (const int rc = ull_a8_epilogue_check(flags, R, N, ldc, ldr)) return rc;
     if (M > MAXM8 || K % BK8 != 0 || (ldxq & 15) || (ldq & 15) || ldxq < K || ldq < K || (((uintptr_t)Xq | (uintptr_t)Q) & 15)) return ULL_ERR_SHAPE;
-    if ((flags & EPI_SWIGLU) && (N & 31)) return ULL_ERR_SHAPE;
-    const int64_t n_out = (flags & EPI_SWIGLU) ? N / 2 : N;
-    if (ldc < n_out || ((flags & EPI_RESID) && ldr < n_out)) return ULL_ERR_SHAPE;
     if (N > (1 << 30) || K > (1 << 30)) return ULL_ERR_SHAPE;
+    const int64_t n_out = (flags & EPI_SWIGLU) ? N / 2 : N;
     const A8SkinnyArgs a{(const uint8_t*)Xq, (const uint8_t*)Q, (const float*)x_scales, (const float*)w_scales, C, (const elem_t*)R,
                          (long)ldxq, (long)ldq, (long)ldc, (long)ldr, (int)M, (int)N, (int)K, flags, (int)n_out};
     const dim3 grid((unsigned)((n_out + 15) / 16));

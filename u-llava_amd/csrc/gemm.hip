@@ -2293,27 +2293,28 @@ extern "C" int ULL_FN(ull_gemm_)(const void* X, int64_t ldx, const void* W, int6
 }
 
 #ifndef ULL_ELEM_F16
+// GemmArgs of a 128 x 128 launch whose operands travel in a struct of their own (A8Args / W4A8Args): output, residual, sizes and the tile grid
+static GemmArgs gemm128_a8_args(void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags) {
+    GemmArgs a{};                        // no X / W / bias / workspace / RoPE tables
+    a.C = C; a.R = (const elem_t*)R; a.ldc = ldc; a.ldr = ldr;
+    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.flags = flags;
+    a.nbm = (int)((M + BM - 1) / BM); a.nbn = (int)((N + BN - 1) / BN);
+    a.sk = 1; a.group_m = GROUP_M;
+    return a;
+}
+
 // W8A8 Linear (bf16 build only): C[M, N] = epilogue(2^(t_m + s_n) * sum_k float(Xq[m, k]) * float(Q[n, k])), both operands e4m3fn codes with
 // one fp32 power-of-two scale per row (ull_quantize_rows_fp8_bf16 on the activation rows and on the weight rows).  ull_gemm_bf16's contract
 // with (X, ldx) -> (Xq, ldxq, x_scales) and (W, ldw) -> (Q, ldq, w_scales); no bias, no workspace (K is never split).
 extern "C" int ull_gemm_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, void* C,
                                   int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
     if (!Xq || !x_scales || !Q || !w_scales || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
-    if (flags & ~(EPI_RESID | EPI_SWIGLU | EPI_OUT_F32)) return ULL_ERR_ARG;
-    if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
+    if (const int rc = ull_a8_epilogue_check(flags, R, N, ldc, ldr)) return rc;
     if (K % BK8 != 0 || (ldxq & 15) || (ldq & 15) || ldxq < K || ldq < K || (((uintptr_t)Xq | (uintptr_t)Q) & 15)) return ULL_ERR_SHAPE;   // 16-byte DMA pieces
-    if ((flags & EPI_SWIGLU) && (N & 31)) return ULL_ERR_SHAPE;
-    if (ldc < ((flags & EPI_SWIGLU) ? N / 2 : N) || ((flags & EPI_RESID) && ldr < ((flags & EPI_SWIGLU) ? N / 2 : N))) return ULL_ERR_SHAPE;
     if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return ULL_ERR_SHAPE;
     int n_cu = 0;
     if (const int rc = gemm_device_state(&n_cu)) return rc;
-    GemmArgs a;
-    a.X = nullptr; a.W = nullptr; a.C = C; a.bias = nullptr; a.R = (const elem_t*)R;
-    a.ldx = 0; a.ldw = 0; a.ldc = ldc; a.ldr = ldr;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.flags = flags;
-    a.nbm = (int)((M + BM - 1) / BM); a.nbn = (int)((N + BN - 1) / BN);
-    a.t_full = 0; a.sk = 1; a.ws = nullptr; a.group_m = GROUP_M;
-    a.rope_cos = a.rope_sin = nullptr; a.rope_cols = 0;
+    const GemmArgs a = gemm128_a8_args(C, ldc, R, ldr, M, N, K, flags);
     if ((long)a.nbm * a.nbn > (1L << 30)) return ULL_ERR_SHAPE;
     const A8Args q{(const uint8_t*)Xq, (const uint8_t*)Q, (const float*)x_scales, (const float*)w_scales, (long)ldxq, (long)ldq};
     if (flags & EPI_SWIGLU)
@@ -2343,24 +2344,15 @@ extern "C" int ull_gemm_w4a8_bf16(const void* Xq, int64_t ldxq, const void* x_sc
                                   int64_t lds, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
                                   void* stream) {
     if (!Xq || !x_scales || !Q || !w_scales || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
-    if (flags & ~(EPI_RESID | EPI_SWIGLU | EPI_OUT_F32)) return ULL_ERR_ARG;
-    if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
+    if (const int rc = ull_a8_epilogue_check(flags, R, N, ldc, ldr)) return rc;
     if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return ULL_ERR_SHAPE;
     if (K % BK8 != 0 || (ldxq & 15) || (ldq & 15) || ldxq < K || ldq < K / 2 || (((uintptr_t)Xq | (uintptr_t)Q) & 15)) return ULL_ERR_SHAPE;   // 16-byte pieces
     if ((ldxs & 3) || (lds & 3) || ldxs < K / 32 || lds < K / 32 || (((uintptr_t)x_scales | (uintptr_t)w_scales) & 3)) return ULL_ERR_SHAPE;   // 4-byte scale loads
     if ((M - 1) * ldxq + K >= (1LL << 31) || (N - 1) * ldq + K / 2 >= (1LL << 31) || M * ldxs >= (1LL << 31) || N * lds >= (1LL << 31))
         return ULL_ERR_SHAPE;                                                                         // 32-bit lane offsets in the kernel
-    if ((flags & EPI_SWIGLU) && (N & 31)) return ULL_ERR_SHAPE;
-    if (ldc < ((flags & EPI_SWIGLU) ? N / 2 : N) || ((flags & EPI_RESID) && ldr < ((flags & EPI_SWIGLU) ? N / 2 : N))) return ULL_ERR_SHAPE;
     int n_cu = 0;
     if (const int rc = gemm_device_state(&n_cu)) return rc;
-    GemmArgs a;
-    a.X = nullptr; a.W = nullptr; a.C = C; a.bias = nullptr; a.R = (const elem_t*)R;
-    a.ldx = 0; a.ldw = 0; a.ldc = ldc; a.ldr = ldr;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.flags = flags;
-    a.nbm = (int)((M + BM - 1) / BM); a.nbn = (int)((N + BN - 1) / BN);
-    a.t_full = 0; a.sk = 1; a.ws = nullptr; a.group_m = GROUP_M;
-    a.rope_cos = a.rope_sin = nullptr; a.rope_cols = 0;
+    const GemmArgs a = gemm128_a8_args(C, ldc, R, ldr, M, N, K, flags);
     if ((long)a.nbm * a.nbn > (1L << 30)) return ULL_ERR_SHAPE;
     const W4A8Args q{(const uint8_t*)Xq, (const uint8_t*)x_scales, (const uint8_t*)Q, (const uint8_t*)w_scales, (long)ldxq, (long)ldxs, (long)ldq, (long)lds};
     if (flags & EPI_SWIGLU)

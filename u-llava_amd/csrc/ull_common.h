@@ -337,6 +337,15 @@ static inline int ull_cu_count() {
     return n_cu[dev];
 }
 
+// The epilogue checks the three A8 Linear entries share: only ULL_EPI_RESID (8) | ULL_EPI_SWIGLU (16) | ULL_EPI_OUT_F32 (32) and a residual where
+// its flag is set (else ULL_ERR_ARG); SwiGLU on whole 32-row gate|up groups, output / residual rows no shorter than the output (else ULL_ERR_SHAPE).
+static inline int ull_a8_epilogue_check(int flags, const void* R, int64_t N, int64_t ldc, int64_t ldr) {
+    if ((flags & ~(8 | 16 | 32)) || ((flags & 8) && !R)) return ULL_ERR_ARG;
+    const int64_t n_out = (flags & 16) ? N / 2 : N;
+    if (((flags & 16) && (N & 31)) || ldc < n_out || ((flags & 8) && ldr < n_out)) return ULL_ERR_SHAPE;
+    return ULL_OK;
+}
+
 static inline int ull_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ULL_OK : ULL_ERR_LAUNCH;

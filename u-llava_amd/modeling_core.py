@@ -638,8 +638,8 @@ class UllavaCoreForCausalLM(nn.Module):
         differs from "fp8_e4m3" on purpose: that value means one scale per token.
 
         activation_scope="prefill+decode" (with fmt="fp8_e4m3", activations="fp8_e4m3" only; default "prefill" = everything above, unchanged):
-        FP8 activations in batched decode steps too (DESIGN f10).  Wherever ops.a8w8_decode_takes says so -- 5 to 32 rows against a LLaMA-sized
-        weight -- the four layer Linears quantize their input rows per token (q|k|v and gate|up inside the RMSNorm launch they already pay,
+        FP8 activations in batched decode steps too (DESIGN f10).  Wherever the same dispatch rule (ops.linear_route) says "a8w8_skinny" -- 5 to
+        32 rows against a LLaMA-sized weight -- the four layer Linears quantize their input rows per token (q|k|v and gate|up inside the RMSNorm launch they already pay,
         ops.rmsnorm_quantize_rows_fp8; o_proj and down_proj by ops.quantize_rows_fp8) and run the weight-streaming W8A8 kernel
         (ops.linear_a8w8_skinny) in place of the W8A16 skinny kernel (5 to 16 rows) or the 128 x 128 W8A8 GEMM (17 to 32 rows).  Steps of at
         most 4 tokens, lm_head and the coarse entries are untouched, so decoding at batch <= 4 is bit-identical to the weight-only model even
@@ -1174,36 +1174,17 @@ class UllavaCoreForCausalLM(nn.Module):
         # (that kernel stages the T x D activations in 32 KB of LDS: LLaMA-7B at T = 4 is exactly the limit; wider models / more rows take the
         # stand-alone RMSNorm + RoPE-append kernels below)
         fuse_append = cache is not None and past > 0 and T <= 4 and hd % 2 == 0 and D % 8 == 0 and T * D * 2 <= 32768 and not f32
-        # quantize_weights(activations=): W8A8 on fp8 weights / W4A8 on mxfp4 weights at GEMM shapes
-        a8 = self.activation_quantization is not None and (pk.get("fp8", False) or pk.get("mxfp4", False))
-        a8_takes, a8_linear = (ops.w4a8_takes, ops.linear_w4a8) if pk.get("mxfp4", False) else (ops.a8w8_takes, ops.linear_a8w8)
-        # activation_scope="prefill+decode": the weight-streaming W8A8 kernel wherever ops.a8w8_decode_takes says so (5 to 32 rows)
-        a8_skinny = a8 and self.activation_scope == "prefill+decode" and pk.get("fp8", False)
-        if a8 and fuse_rope and pk["llama"] and (a8_takes(T, 3 * D, D, pk["llama"][0]["w_qkv"]) or
-                                                 (a8_skinny and ops.a8w8_decode_takes(T, 3 * D, D, pk["llama"][0]["w_qkv"]))):
+        wq = pk.get("fp8", False) or pk.get("mxfp4", False)      # quantize_weights(): the Linear weights are ops.Fp8Weight / ops.Mxfp4Weight
+        # quantize_weights(activations=, activation_scope=): the layer Linears hand the mode to the dispatch rule (ops.linear(act_quant=))
+        aq = None
+        if wq and self.activation_quantization is not None:
+            aq = ops.ActQuant(self.activation_quantization, self.activation_scope == "prefill+decode")
+        if aq is not None and fuse_rope and pk["llama"] and ops.linear_route(T, pk["llama"][0]["w_qkv"], aq) in ops.A8_ROUTES:
             fuse_rope = False                # A8 q|k|v: the plain projection, then the stand-alone RoPE kernel
         rope_cs = ops.rope_table(pos, inv_freq, x.dtype) if (fuse_rope or fuse_append) else None
         all_h = []
         I = cfg.intermediate_size
         coarse = None
-        wq = pk.get("fp8", False) or pk.get("mxfp4", False)      # quantize_weights(): the Linear weights are ops.Fp8Weight / ops.Mxfp4Weight
-
-        def lin(x_, w_, residual=None, swiglu=False, rms_w=None):
-            """A LLaMA-layer Linear: fp8 activations (quantize_weights(activations=)) wherever the dispatch rule takes the tiled GEMM, by
-            the weight's type; under activation_scope="prefill+decode" also at the skinny shapes of ops.a8w8_decode_takes, where the row
-            quantization rides in the RMSNorm launch when there is one."""
-            if a8_skinny and ops.a8w8_decode_takes(x_.shape[0], w_.shape[0], w_.shape[1], w_):
-                if rms_w is not None:
-                    xq, xs = ops.rmsnorm_quantize_rows_fp8(x_, rms_w, cfg.rms_norm_eps)
-                else:
-                    xq, xs = ops.quantize_rows_fp8(x_)
-                return ops.linear_a8w8_skinny(xq, xs, w_, residual=residual, swiglu=swiglu)
-            if a8 and a8_takes(x_.shape[0], w_.shape[0], w_.shape[1], w_):
-                if rms_w is not None:
-                    x_ = ops.rmsnorm(x_, rms_w, cfg.rms_norm_eps)
-                return a8_linear(x_, w_, residual=residual, swiglu=swiglu)
-            return ops.linear(x_, w_, residual=residual, swiglu=swiglu, rms_w=rms_w, rms_eps=cfg.rms_norm_eps)
-
         kv8 = cache is not None and cache.kv_dtype is not None
         if kv8 and x.dtype != BF16:
             _check_kv_dtype(cache.kv_dtype, x.dtype)
@@ -1254,14 +1235,14 @@ class UllavaCoreForCausalLM(nn.Module):
                 else:
                     ops.attention(q, kc, vtc, att, B, H, S, past + S, hd, (S * D, hd, D), (H * cache.smax * hd, cache.smax * hd, hd),
                                   (S * D, hd, D), key_mask, causal=True, scale_mode=1, scale=hd ** -0.5)
-                x = ops.linear(att, w["w_o"], residual=x)
-                a = ops.linear(x, w["w_gu"], swiglu=True, rms_w=w["ln2"], rms_eps=cfg.rms_norm_eps)
-                x = ops.linear(a, w["w_down"], residual=x)
+                x = ops.linear(att, w["w_o"], residual=x, act_quant=aq)
+                a = ops.linear(x, w["w_gu"], swiglu=True, rms_w=w["ln2"], rms_eps=cfg.rms_norm_eps, act_quant=aq)
+                x = ops.linear(a, w["w_down"], residual=x, act_quant=aq)
                 continue
             if fuse_rope:
                 qkv = ops.linear_qkv_rope(ops.rmsnorm(x, w["ln1"], cfg.rms_norm_eps), w["w_qkv"], rope_cs[0], rope_cs[1], 2 * D, hd)
             else:
-                qkv = lin(x, w["w_qkv"], rms_w=w["ln1"])                                       # input_layernorm -> q|k|v
+                qkv = ops.linear(x, w["w_qkv"], rms_w=w["ln1"], rms_eps=cfg.rms_norm_eps, act_quant=aq)    # input_layernorm -> q|k|v
             att = torch.empty(T, D, device=dev, dtype=x.dtype)
             if decode:
                 # generation step: RoPE + cache append in one launch, then the split-key attention over the cache
@@ -1290,9 +1271,9 @@ class UllavaCoreForCausalLM(nn.Module):
                     ops.transpose_v(qkv[:, 2 * D:], S * 3 * D, 3 * D, B, S, H, hd, pitch=cache.smax, out=vt)
                     ops.attention(qkv, qkv[:, D:], vt, att, B, H, S, S, hd, st, st, (S * D, hd, D), key_mask, causal=True, scale_mode=1,
                                   scale=hd ** -0.5)
-            x = lin(att, w["w_o"], residual=x)
-            a = lin(x, w["w_gu"], swiglu=True, rms_w=w["ln2"])                                   # post_attention_layernorm -> gate|up
-            x = lin(a, w["w_down"], residual=x)
+            x = ops.linear(att, w["w_o"], residual=x, act_quant=aq)
+            a = ops.linear(x, w["w_gu"], swiglu=True, rms_w=w["ln2"], rms_eps=cfg.rms_norm_eps, act_quant=aq)    # post_attention_layernorm -> gate|up
+            x = ops.linear(a, w["w_down"], residual=x, act_quant=aq)
         x = ops.rmsnorm(x, self.model.norm.weight, cfg.rms_norm_eps)
         last = x.view(B, S, D)
         if cache is not None:

@@ -5,7 +5,7 @@ libullava_hip.so.  Activations are 16-bit (bf16 or fp16: every kernel exists in 
 operand; the other operands must match), row-major, last dim contiguous.
 """
 import weakref
-from typing import Optional
+from typing import NamedTuple, Optional
 
 
 import torch
@@ -156,7 +156,7 @@ class Fp8Weight:
         if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.stride(1) != 1 or scales.dtype != F32 or scales.shape != (codes.shape[0],):
             raise RuntimeError("u-llava_amd.Fp8Weight: codes uint8 [N, K] (rows contiguous), scales fp32 [N]")
         self.codes, self.scales = codes, scales
-        self._kpad = None                    # linear_a8w8: the codes zero-padded to K % 128 == 0 (tiny test models only; real K never needs it)
+        self._kpad = None                    # a8_codes(): the aligned, zero-padded copy (tiny test models and views only; real weights never need it)
 
     @property
     def shape(self):
@@ -172,6 +172,16 @@ class Fp8Weight:
     @property
     def route_pitch(self) -> int:
         return self.codes.stride(0)          # code bytes = elements
+
+    def a8_codes(self) -> torch.Tensor:
+        """The codes as the 16-byte loads of the W8A8 kernels can take them: `codes` itself when K is a whole number of 128-code K-tiles and
+        the rows are 16-byte aligned, else a contiguous copy zero-padded to K % 128 == 0, made once and kept."""
+        c = self.codes
+        if c.size(1) % A8W8_BK or c.stride(0) % 16 or c.data_ptr() % 16:
+            if self._kpad is None:
+                self._kpad = torch.nn.functional.pad(c, (0, -c.size(1) % A8W8_BK)).contiguous()
+            c = self._kpad
+        return c
 
     def c_args(self):
         """(wfmt, Q, ldq, scales, lds): lds is unused."""
@@ -406,19 +416,51 @@ class streamk_policy:
 
 
 # ---- the Linear dispatch rule: every route of `linear` / `linear_qkv_rope` is decided here ------------------------------------------------
-def _linear_route(M: int, N: int, K: int, ldw: int, tune: int):
-    """(route, rms_first) of a 16-bit or fp8 Linear x [M, K] @ w.T, w [N, K] with row pitch ldw.
+class ActQuant(NamedTuple):
+    """quantize_weights(activations=fmt, activation_scope=): "fp8_e4m3" (one scale per token, on an Fp8Weight) or "mxfp8_e4m3" (one per block of
+    32, on an Mxfp4Weight); decode: also at the batched decode shapes ("prefill+decode").  None in its place means weight-only."""
+    fmt: str
+    decode: bool = False
+
+
+_A8_GEMM = {("fp8", "fp8_e4m3"): "a8w8", ("mxfp4", "mxfp8_e4m3"): "w4a8"}      # (weight format, activation format) -> route of the pair
+A8W8_BK = 128                 # K-tile of the A8 kernels (one block-scaled matrix instruction)
+A8W8_SKINNY_MAX_M = 32        # ull_gemm_skinny_a8w8_bf16: two 16-row activation fragments
+
+
+def _linear_route(M: int, N: int, K: int, ldw: int, tune: int, wfmt: Optional[str] = None, aq: Optional[ActQuant] = None):
+    """(route, rms_first) of a Linear x [M, K] @ w.T, w [N, K] with row pitch ldw; wfmt: None for a 16-bit weight, else its `fmt_name`.
     route "skinny": batched decode steps against LLaMA-sized weights put the weight stream on the matrix cores (the GEMV is FMA-bound from
     M = 4 on and measured slower from M = 3 on (decode step at batch 3: 4.47 vs 4.24 ms; at batch 2 the GEMV wins, 4.00 vs 4.08); the tiled
     GEMM's grid is a few dozen blocks at these M).  Small weights stay where they were.  "gemv": the weight-streaming GEMV at decode shapes
     (no padding, no MFMA).  "gemm": the tiled GEMM.
+    aq on the weight format it pairs with (_A8_GEMM; any other pair is weight-only) quantizes the activations wherever the weight-only rule
+    says "gemm": "a8w8" (linear_a8w8) / "w4a8" (linear_w4a8), no dequantized weight.  aq.decode on fp8 weights adds "a8w8_skinny"
+    (linear_a8w8_skinny), ahead of everything else: the "skinny" size rule, starting above the 4 tokens the fused q|k|v + RoPE + cache-append
+    GEMV takes and extended to that kernel's 32 rows (so at 17 .. 32 rows it replaces "a8w8"), with K a whole number of 128-code K-tiles.
     rms_first: a requested RMSNorm is a launch of its own ahead of the Linear; the GEMV fuses it into its prologue while the M x K
-    activations fit its LDS staging.  csrc/layers.hip `lin_decode` mirrors this rule for the coarse decode entries."""
+    activations fit its LDS staging, "a8w8_skinny" into its row quantization.  csrc/layers.hip `lin_decode` mirrors the weight-only
+    "skinny" / "gemv" part of this rule for the coarse decode entries, which never take an activation-quantized route."""
+    a8 = None if aq is None else _A8_GEMM.get((wfmt, aq.fmt))
+    if a8 == "a8w8" and aq.decode and 5 <= M <= A8W8_SKINNY_MAX_M and K % A8W8_BK == 0 and N * K >= (1 << 22) and ldw % 8 == 0 and tune == 0:
+        return "a8w8_skinny", False
     if 3 <= M <= 16 and K % 32 == 0 and N * K >= (1 << 22) and ldw % 8 == 0 and tune == 0:
         return "skinny", True
     if M <= 4 and K % 8 == 0:
         return "gemv", M * K > 16384
-    return "gemm", True
+    return a8 or "gemm", True
+
+
+def linear_route(M: int, w, act_quant: Optional[ActQuant] = None) -> str:
+    """The route `linear` takes for M rows against the weight w (16-bit tensor / Fp8Weight / Mxfp4Weight) under act_quant."""
+    wq = isinstance(w, QuantWeight)
+    return _linear_route(M, w.shape[0], w.shape[1], w.route_pitch if wq else w.stride(0), 0, w.fmt_name if wq else None, act_quant)[0]
+
+
+# the rule read as a boolean, for callers that ask about one A8 route (N and K are w's own)
+a8w8_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("fp8_e4m3")) == "a8w8"                          # noqa: E731
+w4a8_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("mxfp8_e4m3")) == "w4a8"                        # noqa: E731
+a8w8_decode_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("fp8_e4m3", True)) == "a8w8_skinny"      # noqa: E731
 
 
 def _big(M: int, N: int, K: int) -> bool:
@@ -445,15 +487,30 @@ def _gemm_ws(device: torch.device, stream_id: int, big: bool, M: int, N: int, K:
     return ws.data_ptr(), ws.numel()
 
 
+def _epilogue(x: torch.Tensor, N: int, swiglu: bool, out_f32: bool, residual: Optional[torch.Tensor], out: Optional[torch.Tensor], dtype=None):
+    """(out, flags, ldr) of a Linear on the rows x [..., K] (or their codes) with 16-bit type `dtype` (default: x's): `out`, allocated on x's
+    leading dims unless given, the swiglu / out_f32 / residual flag bits, and the checked residual's row pitch (0 without one)."""
+    if out is None:
+        out = torch.empty(*x.shape[:-1], N // 2 if swiglu else N, device=x.device, dtype=F32 if out_f32 else dtype or x.dtype)
+    flags = (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0)
+    ldr = 0
+    if residual is not None:
+        _chk(residual, "residual", dtype or x.dtype)
+        flags |= EPI_RESID
+        ldr = _rows(residual)[1]
+    return out, flags, ldr
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act: Optional[str] = None,
            residual: Optional[torch.Tensor] = None, swiglu: bool = False, out: Optional[torch.Tensor] = None,
            out_f32: bool = False, rms_w: Optional[torch.Tensor] = None, rms_eps: float = 0.0, tune: int = 0,
-           bias_after_rounding: bool = False) -> torch.Tensor:
+           bias_after_rounding: bool = False, act_quant: Optional[ActQuant] = None) -> torch.Tensor:
     """y = epilogue(x @ w.T).  x [..., K]; w [N, K] (nn.Linear layout).  swiglu: w is the 16-row interleaved gate/up pack.
     rms_w/rms_eps: apply LlamaRMSNorm to x first (fused into the GEMV prologue at decode shapes, a separate kernel otherwise).
     tune: ULL_GEMM_TUNE_* bits (tools/ only).  bias_after_rounding: y = round(round(x @ w.T) + bias) -- what at::linear computes
     for a NON-contiguous 3-D input (matmul + add_ instead of the fused addmm).
-    w may be an `Fp8Weight` or an `Mxfp4Weight` (bf16 x only): the same result as on its dequantized bf16 weight, bit for bit."""
+    w may be an `Fp8Weight` or an `Mxfp4Weight` (bf16 x only): the same result as on its dequantized bf16 weight, bit for bit.
+    act_quant: quantize the activations too wherever `_linear_route` gives an A8 route (residual / swiglu / out / out_f32 / rms_w only)."""
     wq = isinstance(w, QuantWeight)
     if wq and x.dtype != BF16:
         raise RuntimeError(f"u-llava_amd.linear: {w.fmt_name} weights need bf16 activations, got {x.dtype}")
@@ -471,7 +528,12 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         route, rms_first = "f32", True
         out_f32 = bias_after_rounding = False
     else:
-        route, rms_first = _linear_route(M, N, K, w.route_pitch if wq else w.stride(0), tune)
+        route, rms_first = _linear_route(M, N, K, w.route_pitch if wq else w.stride(0), tune, w.fmt_name if wq else None, act_quant)
+        if act_quant is not None and route in A8_ROUTES:
+            for name, given in (("bias", bias is not None), ("act", act), ("bias_after_rounding", bias_after_rounding), ("tune", tune)):
+                if given:
+                    raise RuntimeError(f"u-llava_amd.linear: `{name}` is not supported on the activation-quantized route {route!r}")
+            return _linear_a8(route, x, w, residual, swiglu, out, out_f32, rms_w, rms_eps)
         if wq and route == "gemm":
             # prefill shapes: dequantize into the stream's scratch, then the bf16 flow on dequant(w)
             w, wt = _wq_dequant_for_gemm(w, M)
@@ -480,17 +542,11 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         x = rmsnorm(x, rms_w, rms_eps)
         rms_w = None
         M, ldx = _rows(x)
-    if out is None:
-        out = torch.empty(*x.shape[:-1], N // 2 if swiglu else N, device=x.device, dtype=F32 if out_f32 else x.dtype)
-    flags = ACTS[act] | (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0) | (EPI_BIAS_ROUNDED if bias_after_rounding else 0)
+    out, flags, ldr = _epilogue(x, N, swiglu, out_f32, residual, out)
+    flags |= ACTS[act] | (EPI_BIAS_ROUNDED if bias_after_rounding else 0)
     if bias is not None:
         _chk(bias, "bias", x.dtype)
         flags |= EPI_BIAS
-    ldr = 0
-    if residual is not None:
-        _chk(residual, "residual", x.dtype)
-        flags |= EPI_RESID
-        ldr = _rows(residual)[1]
     ldc = _rows(out)[1]
     st = _stream()
     if route == "f32":
@@ -524,10 +580,25 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     return out
 
 
-# ---- FP8 activations on FP8 weights (quantize_weights("fp8_e4m3", activations="fp8_e4m3")) ---------------------------------------------
-A8W8_BK = 128        # K-tile of ull_gemm_a8w8_bf16 (one block-scaled matrix instruction)
+# ---- quantized activations on quantized weights (quantize_weights(activations=, activation_scope=)) ---------------------------------------
+# Which Linear takes which kernel is `_linear_route`'s decision alone; `linear(..., act_quant=)` carries it out (`_linear_a8`) through the
+# per-kernel wrappers linear_a8w8 / linear_w4a8 / linear_a8w8_skinny, each the only call site of its entry.
+A8_ROUTES = ("a8w8", "w4a8", "a8w8_skinny")
 
 
+def _linear_a8(route: str, x, w, residual, swiglu: bool, out, out_f32: bool, rms_w, rms_eps: float) -> torch.Tensor:
+    """`linear` on an A8 route: the RMSNorm rides in the row quantization ("a8w8_skinny") or is a launch of its own, then the route's wrapper."""
+    kw = dict(residual=residual, swiglu=swiglu, out=out, out_f32=out_f32)
+    if route == "a8w8_skinny":
+        xq, xs = quantize_rows_fp8(x) if rms_w is None else rmsnorm_quantize_rows_fp8(x, rms_w, rms_eps)
+        y = linear_a8w8_skinny(xq, xs, w, **kw)
+        return y if x.dim() == 2 or out is not None else y.view(*x.shape[:-1], y.shape[-1])
+    if rms_w is not None:
+        x = rmsnorm(x, rms_w, rms_eps)
+    return (linear_a8w8 if route == "a8w8" else linear_w4a8)(x, w, **kw)
+
+
+# ---- FP8 activations on FP8 weights: route "a8w8" ---------------------------------------------------------------------------------------
 def quantize_rows_fp8(x: torch.Tensor):
     """(codes uint8 [M, K], scales fp32 [M]) of bf16 rows x [..., K] (one row pitch): quantize_fp8's rule per row, so every token gets its own
     power-of-two scale 2^t, t the smallest integer with amax|row| * 2^-t <= 448 (0 for an all-zero row); codes = e4m3fn(x * 2^-t), nearest even."""
@@ -538,12 +609,6 @@ def quantize_rows_fp8(x: torch.Tensor):
     scales = torch.empty(M, device=x.device, dtype=F32)
     _lib.call("ull_quantize_rows_fp8_bf16", _p(x), ldx, M, K, _p(codes), _p(scales), _stream())
     return codes, scales
-
-
-def a8w8_takes(M: int, N: int, K: int, w) -> bool:
-    """Whether a LLaMA-layer Linear x [M, K] @ w.T of an activation-quantized model runs as W8A8: exactly the shapes `_linear_route` sends to
-    the tiled GEMM (prefill).  Decode shapes ("gemv" / "skinny") stay W8A16."""
-    return isinstance(w, Fp8Weight) and _linear_route(M, N, K, w.route_pitch, 0)[0] == "gemm"
 
 
 def linear_a8w8(x: torch.Tensor, w: "Fp8Weight", residual: Optional[torch.Tensor] = None, swiglu: bool = False,
@@ -562,29 +627,16 @@ def linear_a8w8(x: torch.Tensor, w: "Fp8Weight", residual: Optional[torch.Tensor
     if x.shape[-1] != K:
         raise RuntimeError(f"u-llava_amd.linear_a8w8: K mismatch {x.shape[-1]} vs {K}")
     xq, xs = quantize_rows_fp8(x)
-    wq = w.codes
-    if K % A8W8_BK or wq.stride(0) % 16 or wq.data_ptr() % 16:
-        if w._kpad is None:
-            w._kpad = torch.nn.functional.pad(wq, (0, -K % A8W8_BK)).contiguous()
-        wq = w._kpad
+    wq = w.a8_codes()
+    if wq is not w.codes:
         xq = torch.nn.functional.pad(xq, (0, -K % A8W8_BK))
-    if out is None:
-        out = torch.empty(*x.shape[:-1], N // 2 if swiglu else N, device=x.device, dtype=F32 if out_f32 else BF16)
-    flags = (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0)
-    ldr = 0
-    if residual is not None:
-        _chk(residual, "residual", BF16)
-        flags |= EPI_RESID
-        ldr = _rows(residual)[1]
+    out, flags, ldr = _epilogue(x, N, swiglu, out_f32, residual, out, BF16)
     _lib.call("ull_gemm_a8w8_bf16", _p(xq), xq.stride(0), _p(xs), _p(wq), wq.stride(0), _p(w.scales), _p(out), _rows(out)[1], _p(residual), ldr,
               M, N, xq.shape[1], flags, _stream())
     return out
 
 
-# ---- FP8 activations on FP8 weights at decode shapes (quantize_weights(..., activation_scope="prefill+decode")) -------------------------
-A8W8_SKINNY_MAX_M = 32        # ull_gemm_skinny_a8w8_bf16: two 16-row activation fragments
-
-
+# ---- FP8 activations on FP8 weights at decode shapes: route "a8w8_skinny" -------------------------------------------------------------
 def rmsnorm_quantize_rows_fp8(x: torch.Tensor, w: torch.Tensor, eps: float):
     """quantize_rows_fp8(rmsnorm(x, w, eps)) in one launch (ull_rmsnorm_quantize_rows_fp8_bf16), bit for bit: (codes uint8 [M, K], scales
     fp32 [M]) of the normed bf16 rows, which are never written."""
@@ -595,15 +647,6 @@ def rmsnorm_quantize_rows_fp8(x: torch.Tensor, w: torch.Tensor, eps: float):
     scales = torch.empty(M, device=x.device, dtype=F32)
     _lib.call("ull_rmsnorm_quantize_rows_fp8_bf16", _p(x), ldx, _p(w), float(eps), M, K, _p(codes), K, _p(scales), _stream())
     return codes, scales
-
-
-def a8w8_decode_takes(M: int, N: int, K: int, w) -> bool:
-    """Whether a LLaMA-layer Linear x [M, K] @ w.T of a model quantized with activation_scope="prefill+decode" runs on the W8A8 skinny kernel
-    (linear_a8w8_skinny).  The rule mirrors `_linear_route`'s "skinny" size rule -- a LLaMA-sized weight, N * K >= 2^22, whose row pitch
-    the kernel can stream -- starting above the 4 tokens the fused q|k|v + RoPE + cache-append GEMV takes and extended to the kernel's 32
-    rows (at 17 .. 32 rows it replaces the 128 x 128 W8A8 GEMM of `a8w8_takes`), with K a whole number of the instruction's 128-code
-    K-tiles."""
-    return isinstance(w, Fp8Weight) and 5 <= M <= A8W8_SKINNY_MAX_M and K % A8W8_BK == 0 and N * K >= (1 << 22) and w.route_pitch % 8 == 0
 
 
 def linear_a8w8_skinny(xq: torch.Tensor, xs: torch.Tensor, w: "Fp8Weight", residual: Optional[torch.Tensor] = None, swiglu: bool = False,
@@ -620,25 +663,14 @@ def linear_a8w8_skinny(xq: torch.Tensor, xs: torch.Tensor, w: "Fp8Weight", resid
     N = w.shape[0]
     if w.shape[1] != K:
         raise RuntimeError(f"u-llava_amd.linear_a8w8_skinny: K mismatch {K} vs {w.shape[1]}")
-    wq = w.codes
-    if wq.stride(0) % 16 or wq.data_ptr() % 16:          # (a view into a wider buffer: the 16-byte loads need aligned rows; kept as linear_a8w8's copy)
-        if w._kpad is None:
-            w._kpad = torch.nn.functional.pad(wq, (0, -K % A8W8_BK)).contiguous()
-        wq = w._kpad
-    if out is None:
-        out = torch.empty(M, N // 2 if swiglu else N, device=xq.device, dtype=F32 if out_f32 else BF16)
-    flags = (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0)
-    ldr = 0
-    if residual is not None:
-        _chk(residual, "residual", BF16)
-        flags |= EPI_RESID
-        ldr = _rows(residual)[1]
+    wq = w.a8_codes()                                    # (aligned rows; a K that is no multiple of 128 is still the entry's to refuse)
+    out, flags, ldr = _epilogue(xq, N, swiglu, out_f32, residual, out, BF16)
     _lib.call("ull_gemm_skinny_a8w8_bf16", _p(xq), xq.stride(0), _p(xs), _p(wq), wq.stride(0), _p(w.scales), _p(out), _rows(out)[1],
               _p(residual), ldr, M, N, K, flags, _stream())
     return out
 
 
-# ---- MXFP8 activations on MXFP4 weights (quantize_weights("mxfp4", activations="mxfp8_e4m3")) ------------------------------------------
+# ---- MXFP8 activations on MXFP4 weights: route "w4a8" -----------------------------------------------------------------------------------
 def w4a8_k_ok(K: int) -> bool:
     """Whether ull_gemm_w4a8_bf16 takes a weight of this K (K % 32 == 0): a multiple of its 128-code K-tile, or a K that padding brings there
     without creating a superblock (the resident layout of a padded row must stay the standard order: K < 2048 before and after)."""
@@ -674,12 +706,6 @@ def quantize_rows_mxfp8(x: torch.Tensor):
     return codes, raw[:, _mx_perm(K, x.device)[1]]
 
 
-def w4a8_takes(M: int, N: int, K: int, w) -> bool:
-    """Whether a LLaMA-layer Linear x [M, K] @ w.T of an activation-quantized mxfp4 model runs as W4A8: exactly the shapes `_linear_route`
-    sends to the tiled GEMM (prefill).  Decode shapes ("gemv" / "skinny") stay W4A16."""
-    return isinstance(w, Mxfp4Weight) and _linear_route(M, N, K, w.route_pitch, 0)[0] == "gemm"
-
-
 def linear_w4a8(x: torch.Tensor, w: "Mxfp4Weight", residual: Optional[torch.Tensor] = None, swiglu: bool = False,
                 out: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
     """y = epilogue(x @ w.T) with MXFP8 activations on the resident MXFP4 weight (ull_gemm_w4a8_bf16; the only call site of that entry):
@@ -708,14 +734,7 @@ def linear_w4a8(x: torch.Tensor, w: "Mxfp4Weight", residual: Optional[torch.Tens
             w._kpad = (pc, ps)
         wq, wsc = w._kpad
     xq, xsc = _quantize_rows_mxfp8(x, Kp)
-    if out is None:
-        out = torch.empty(*x.shape[:-1], N // 2 if swiglu else N, device=x.device, dtype=F32 if out_f32 else BF16)
-    flags = (EPI_SWIGLU if swiglu else 0) | (EPI_F32 if out_f32 else 0)
-    ldr = 0
-    if residual is not None:
-        _chk(residual, "residual", BF16)
-        flags |= EPI_RESID
-        ldr = _rows(residual)[1]
+    out, flags, ldr = _epilogue(x, N, swiglu, out_f32, residual, out, BF16)
     _lib.call("ull_gemm_w4a8_bf16", _p(xq), xq.stride(0), _p(xsc), xsc.stride(0), _p(wq), wq.stride(0), _p(wsc), wsc.stride(0), _p(out),
               _rows(out)[1], _p(residual), ldr, M, N, Kp, flags, _stream())
     return out
@@ -1602,7 +1621,7 @@ def sumsq(g: torch.Tensor, out: torch.Tensor) -> None:
 # The per-op wrappers above cost a ctypes round trip + Python marshalling per LAUNCH (~15 us); a C4 step has ~400 launches, a decode step ~160.
 # A LayerStack holds the ctypes array of per-layer structs (weight / bias / norm pointers) and refreshes it when a pointer it recorded has
 # moved (a re-made tile-major copy after an optimizer step, a re-pack).  Results are bit-identical to the per-op path: same entries, same
-# dispatch rules (layers.hip `lin_decode` mirrors `_linear_route`, `tiled` mirrors `_big` and the stream-K tail of `_gemm_ws`).
+# dispatch rules (layers.hip `lin_decode` mirrors the weight-only decode part of `_linear_route`, `tiled` mirrors `_big` and the stream-K tail of `_gemm_ws`).
 COARSE = [True]     # `with ops.per_op_layers():` = the per-op path (tests A/B the two)
 
 
