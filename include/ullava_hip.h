@@ -207,6 +207,23 @@ int ull_gemm_skinny_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales
 int ull_rmsnorm_quantize_rows_fp8_bf16(const void* X, int64_t ldx, const void* rms_w, float eps, int64_t M, int64_t K, void* codes, int64_t ldq,
                                        void* scales, void* stream);
 
+/* ---- FP8 Linears of the SAM image encoder (bf16 build only: no *_f16 twins) ---------------------------------------------------------------
+ * UllavaForCausalLM.set_sam_precision("fp8_e4m3"): qkv, proj, lin1 and lin2 of every ViT block run W8A8 with the definition of
+ * ull_gemm_a8w8_bf16 above (per-token activation scales, per-row weight scales, exact products, a summation order that depends on K alone).
+ * ull_layernorm_quantize_rows_fp8_bf16: codes, scales = ull_quantize_rows_fp8_bf16(ull_layernorm_bf16(X; w, b, eps)) bit for bit -- the same
+ * statistics, the same bf16 rounding of the normed row, the same scale rule, the same codes -- without writing the normed rows.  X [M, K] bf16
+ * (row pitch ldx elements, 16-byte aligned rows), w / b bf16 [K] (16-byte aligned), any M, K % 8 == 0, K <= 8192; codes [M, K] (row pitch ldq
+ * bytes, a multiple of 8, pointer 8-byte aligned), scales fp32 [M].
+ * ull_gemm_a8w8_epi_bf16: ull_gemm_a8w8_bf16's contract plus a bf16 bias [N] (ULL_EPI_BIAS) and ull_gemm_bf16's activation bits: on
+ * y = acc * 2^(t_m + s_n), bf16(act(bf16(y + bias))), then ULL_EPI_RESID: bf16(R + that) -- ull_gemm_bf16's rounding points.  flags:
+ * ULL_EPI_BIAS, ULL_EPI_ACT_*, ULL_EPI_RESID, ULL_EPI_SWIGLU (without bias or activation: ULL_ERR_SHAPE otherwise), ULL_EPI_OUT_F32 only -- any
+ * other bit, ULL_EPI_BIAS without a bias, or a null pointer: ULL_ERR_ARG; a shape or alignment it cannot take: ULL_ERR_SHAPE; nothing is
+ * launched in either case. */
+int ull_layernorm_quantize_rows_fp8_bf16(const void* X, int64_t ldx, const void* w, const void* b, float eps, int64_t M, int64_t K, void* codes,
+                                         int64_t ldq, void* scales, void* stream);
+int ull_gemm_a8w8_epi_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, const void* bias,
+                           void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+
 /* ---- MXFP8 activations on MXFP4 weights: the W4A8 prefill Linear (bf16 build only: no *_f16 twins) ------------------------------------
  * UllavaCoreForCausalLM.quantize_weights("mxfp4", activations="mxfp8_e4m3"): at prefill shapes the four LLaMA-layer Linears quantize their
  * input rows to OCP MXFP8 and multiply them by the resident MXFP4 weight on the block-scaled matrix instruction

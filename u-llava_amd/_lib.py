@@ -154,6 +154,10 @@ SIGNATURES["ull_gemm_a8w8_bf16"] = [_ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i
 SIGNATURES["ull_gemm_skinny_a8w8_bf16"] = SIGNATURES["ull_gemm_a8w8_bf16"]
 SIGNATURES["ull_rmsnorm_quantize_rows_fp8_bf16"] = [_ptr, _i64, _ptr, _f32, _i64, _i64, _ptr, _i64, _ptr, _ptr]
 
+# fp8 Linears of the SAM image encoder (fused LayerNorm + row quantization, W8A8 Linear with bias / activation): bf16-only entry points (no fp16 twin)
+SIGNATURES["ull_layernorm_quantize_rows_fp8_bf16"] = [_ptr, _i64, _ptr, _ptr, _f32, _i64, _i64, _ptr, _i64, _ptr, _ptr]
+SIGNATURES["ull_gemm_a8w8_epi_bf16"] = [_ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr]
+
 # MXFP8 activations on MXFP4 weights (W4A8 prefill Linear): bf16-only entry points (no fp16 twin)
 SIGNATURES["ull_quantize_rows_mxfp8_bf16"] = [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr]
 SIGNATURES["ull_gemm_w4a8_bf16"] = [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr]

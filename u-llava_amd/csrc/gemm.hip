@@ -2306,15 +2306,15 @@ static GemmArgs gemm128_a8_args(void* C, int64_t ldc, const void* R, int64_t ldr
 // W8A8 Linear (bf16 build only): C[M, N] = epilogue(2^(t_m + s_n) * sum_k float(Xq[m, k]) * float(Q[n, k])), both operands e4m3fn codes with
 // one fp32 power-of-two scale per row (ull_quantize_rows_fp8_bf16 on the activation rows and on the weight rows).  ull_gemm_bf16's contract
 // with (X, ldx) -> (Xq, ldxq, x_scales) and (W, ldw) -> (Q, ldq, w_scales); no bias, no workspace (K is never split).
-extern "C" int ull_gemm_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, void* C,
-                                  int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
-    if (!Xq || !x_scales || !Q || !w_scales || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
-    if (const int rc = ull_a8_epilogue_check(flags, R, N, ldc, ldr)) return rc;
+// (the shape checks and the launch both W8A8 entries share; `flags` has passed the caller's own epilogue check)
+static int gemm_a8w8_launch(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, const void* bias,
+                            void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
     if (K % BK8 != 0 || (ldxq & 15) || (ldq & 15) || ldxq < K || ldq < K || (((uintptr_t)Xq | (uintptr_t)Q) & 15)) return ULL_ERR_SHAPE;   // 16-byte DMA pieces
     if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return ULL_ERR_SHAPE;
     int n_cu = 0;
     if (const int rc = gemm_device_state(&n_cu)) return rc;
-    const GemmArgs a = gemm128_a8_args(C, ldc, R, ldr, M, N, K, flags);
+    GemmArgs a = gemm128_a8_args(C, ldc, R, ldr, M, N, K, flags);
+    a.bias = (const elem_t*)bias;
     if ((long)a.nbm * a.nbn > (1L << 30)) return ULL_ERR_SHAPE;
     const A8Args q{(const uint8_t*)Xq, (const uint8_t*)Q, (const float*)x_scales, (const float*)w_scales, (long)ldxq, (long)ldq};
     if (flags & EPI_SWIGLU)
@@ -2322,6 +2322,28 @@ extern "C" int ull_gemm_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_sc
     else
         hipLaunchKernelGGL(gemm128_a8w8_kernel<false>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
     return ull_check_launch();
+}
+
+extern "C" int ull_gemm_a8w8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales, void* C,
+                                  int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream) {
+    if (!Xq || !x_scales || !Q || !w_scales || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if (const int rc = ull_a8_epilogue_check(flags, R, N, ldc, ldr)) return rc;
+    return gemm_a8w8_launch(Xq, ldxq, x_scales, Q, ldq, w_scales, nullptr, C, ldc, R, ldr, M, N, K, flags, stream);
+}
+
+// The W8A8 Linear with ull_gemm_bf16's bias and activation (bf16 build only; the four Linears of a SAM encoder block under
+// SamEngine.linear_precision = "fp8_e4m3"): ull_gemm_a8w8_bf16's contract plus a bf16 bias [N].  The same kernel with GemmArgs.bias set: the
+// row scales are applied to the fp32 sum first (exact), then bias -> activation -> rounding -> residual as staged_epilogue applies them for
+// the bf16 GEMM.  flags: ULL_EPI_BIAS, the activation bits, ULL_EPI_RESID, ULL_EPI_SWIGLU, ULL_EPI_OUT_F32; SwiGLU with a bias or an
+// activation is refused as in ull_gemm_bf16.
+extern "C" int ull_gemm_a8w8_epi_bf16(const void* Xq, int64_t ldxq, const void* x_scales, const void* Q, int64_t ldq, const void* w_scales,
+                                      const void* bias, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
+                                      void* stream) {
+    if (!Xq || !x_scales || !Q || !w_scales || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if ((flags & EPI_BIAS) && !bias) return ULL_ERR_ARG;
+    if (const int rc = ull_a8_epilogue_check(flags & ~(EPI_BIAS | EPI_ACT_MASK), R, N, ldc, ldr)) return rc;
+    if ((flags & EPI_SWIGLU) && (flags & (EPI_BIAS | EPI_ACT_MASK))) return ULL_ERR_SHAPE;
+    return gemm_a8w8_launch(Xq, ldxq, x_scales, Q, ldq, w_scales, (flags & EPI_BIAS) ? bias : nullptr, C, ldc, R, ldr, M, N, K, flags, stream);
 }
 
 // MXFP8 quantization of activation rows X [M, K] (bf16, row pitch ldx elements; K % 32 == 0): e4m3fn codes [M, K] (row pitch ldq bytes) and one

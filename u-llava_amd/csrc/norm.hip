@@ -145,6 +145,110 @@ extern "C" int ULL_FN(ull_clip_embed_ln_)(const void* patch, int64_t ldp, const 
                              (const elem_t*)cls, (const elem_t*)pos, (int)tokens, (hipStream_t)stream);
 }
 
+#ifndef ULL_ELEM_F16
+// ---------------------------------------------------------------------------------------------------------------------
+// LayerNorm + per-token e4m3 quantization in one launch (bf16 build only): ull_quantize_rows_fp8_bf16(ull_layernorm_bf16(x)) bit for bit,
+// without the normed rows going to memory -- the LayerNorm sibling of ull_rmsnorm_quantize_rows_fp8_bf16 (a8_decode.hip), for the fp8 Linears of
+// the SAM image encoder.  The operations of rownorm_kernel<NCH, 1> and of quantize_rows_fp8_kernel (gemv.hip) in their order.  One row per
+// wave, held in registers: lane l owns the 8-element chunks l, l + 64, ... -- rownorm_kernel's assignment for a row (the sub-wave groups it
+// gives narrower rows add the same terms: the lanes past the row hold zeros here, and x + 0 is x).
+namespace {
+template <int NCH>
+__global__ __launch_bounds__(256) void layernorm_quantize_rows_fp8_kernel(const elem_t* __restrict__ x, long ldx, const elem_t* __restrict__ w,
+                                                                          const elem_t* __restrict__ b, float eps, long rows, int D,
+                                                                          uint8_t* __restrict__ codes, long ldq, float* __restrict__ scales) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                               // wave-uniform
+    const int nchunk = D >> 3;
+    const elem_t* xr = x + row * ldx;
+    float v[NCH][8];
+    float s1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = lane + i * 64;
+        if (c < nchunk) {
+            unpack8(*(const uint4*)(xr + c * 8), v[i]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s1 += v[i][j];
+    }
+    const float invD = 1.0f / (float)D;
+    s1 = group_sum(s1, 64);
+    const float mean = s1 * invD;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = lane + i * 64;
+        if (c < nchunk) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float d = v[i][j] - mean; q += d * d; }
+        }
+    }
+    q = group_sum(q, 64);
+    const float rstd = 1.0f / sqrtf(q * invD + eps);
+    // the normed row as ull_layernorm_bf16 stores it: bf16(((x - mean) * rstd) * g + b), kept in the registers of x
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = lane + i * 64;
+        if (c < nchunk) {
+            float wv[8], bv[8];
+            unpack8(*(const uint4*)(w + c * 8), wv);
+            unpack8(*(const uint4*)(b + c * 8), bv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                v[i][j] = rnd(((v[i][j] - mean) * rstd) * wv[j] + bv[j]);
+                amax = fmaxf(amax, fabsf(v[i][j]));
+            }
+        }
+    }
+    amax = wave_max(amax);
+    const int s = fp8_scale_exp(amax);
+    if (lane == 0) scales[row] = ldexpf(1.f, s);
+    uint8_t* qr = codes + row * ldq;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = lane + i * 64;
+        if (c < nchunk) {
+            float o[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = ldexpf(v[i][j], -s);   // exact; |o| <= 448: the conversion cannot overflow
+            int lo = __builtin_amdgcn_cvt_pk_fp8_f32(o[0], o[1], 0, false);
+            lo = __builtin_amdgcn_cvt_pk_fp8_f32(o[2], o[3], lo, true);
+            int hi = __builtin_amdgcn_cvt_pk_fp8_f32(o[4], o[5], 0, false);
+            hi = __builtin_amdgcn_cvt_pk_fp8_f32(o[6], o[7], hi, true);
+            *(uint2*)(qr + c * 8) = make_uint2((uint32_t)lo, (uint32_t)hi);
+        }
+    }
+}
+}  // namespace
+
+// codes, scales = ull_quantize_rows_fp8_bf16(ull_layernorm_bf16(X; w, b, eps)) without the normed rows: X [M, K] bf16 (row pitch ldx), codes
+// [M, K] (row pitch ldq bytes), scales fp32 [M].  Any M; K % 8 == 0, K <= 8192 (ull_layernorm_bf16's widest row).
+extern "C" int ull_layernorm_quantize_rows_fp8_bf16(const void* X, int64_t ldx, const void* w, const void* b, float eps, int64_t M, int64_t K,
+                                                    void* codes, int64_t ldq, void* scales, void* stream) {
+    if (!X || !w || !b || !codes || !scales || M <= 0 || K <= 0) return ULL_ERR_ARG;
+    if ((K & 7) || K > 8192 || (ldx & 7) || ldx < K || (ldq & 7) || ldq < K || M > (1 << 30) ||
+        (((uintptr_t)X | (uintptr_t)w | (uintptr_t)b) & 15) || ((uintptr_t)codes & 7))
+        return ULL_ERR_SHAPE;
+    const int nch = (int)(((K >> 3) + 63) / 64);
+    const dim3 grid((unsigned)((M + 3) / 4));
+#define ULL_LNQ(N) hipLaunchKernelGGL(layernorm_quantize_rows_fp8_kernel<N>, grid, dim3(256), 0, (hipStream_t)stream, (const elem_t*)X, (long)ldx, \
+                                      (const elem_t*)w, (const elem_t*)b, eps, (long)M, (int)K, (uint8_t*)codes, (long)ldq, (float*)scales)
+    if (nch <= 1) ULL_LNQ(1);
+    else if (nch <= 2) ULL_LNQ(2);
+    else if (nch <= 4) ULL_LNQ(4);
+    else if (nch <= 8) ULL_LNQ(8);
+    else ULL_LNQ(16);
+#undef ULL_LNQ
+    return ull_check_launch();
+}
+#endif  // !ULL_ELEM_F16
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Shifted next-token cross entropy (reference models/ullava_core.py:327-338: CrossEntropyLoss over logits[..., :-1, :] vs
 // labels[..., 1:], ignore_index = -100, mean over the counted tokens).  One wave per (b, t) row: fp32 log-sum-exp over the

@@ -93,6 +93,33 @@ class UllavaForCausalLM(nn.Module):
         self._sam.global_attention = mode
         return self
 
+    @property
+    def sam_precision(self):
+        return self._sam.linear_precision
+
+    def set_sam_precision(self, mode="fp8_e4m3"):
+        """The number format of the SAM image encoder's Linears in inference encodes (`forward` and `evaluate`; the encoder is frozen and the
+        training graph does not contain it).  None (default): the model's bf16 GEMMs, bit-identical to a model never switched.  "fp8_e4m3"
+        (bf16 models only; NotImplementedError names any other dtype): qkv, proj, lin1 and lin2 of all ViT blocks run W8A8 -- weights as
+        `ops.quantize_fp8` codes with one power-of-two scale per row, input rows quantized per token by the same rule (inside the LayerNorm
+        launch where the normed rows feed nothing else), the product on the block-scaled fp8 matrix instruction, bias / GELU / residual at the
+        bf16 Linear's rounding points.  Patch and position embedding, attention and rel-pos, the neck, the prompt encoder and the mask decoder
+        stay bf16.  The per-op block loop runs (as under set_sam_attention("exact"), with which it combines).  The fp8 codes are derived data
+        beside the bf16 parameters -- about 0.63 GB more for ViT-H, built at the first fp8 encode and dropped by a reload or a cast -- so
+        state_dict, save_pretrained, training and switching back to None keep working.
+        Measured on one MI355X (profiles/sam_fp8.txt, random-init weights, arms interleaved): the 32-block encoder 9.90 -> 8.31 ms at B = 1
+        (0.84 x) and 51.4 -> 48.1 ms at B = 8 (0.94 x); one RES step at batch 8 88.2 -> 85.8 ms (0.974 x, just outside the 2 % box spread).
+        At B = 8 the fp8 GEMM alone is 0.78-0.92 x the bf16 launch, qkv and lin1 with the fused norm 0.87-0.89 x, but proj and lin2 with their
+        row quantization launch are SLOWER than bf16 (1.10 x, 1.12 x).  Encoder output against bf16: mean |d| 1.2e-3, max 2.0e-2 on mean |y|
+        1.2e-2; mask logits mean |d| 7.6e-7 on mean 2.9e-5, 99.1 % of the signs equal.  Task accuracy on real checkpoints is not measured."""
+        if mode not in SamEngine.LINEAR_PRECISIONS:
+            raise ValueError(f"sam precision must be one of {SamEngine.LINEAR_PRECISIONS}, got {mode!r}")
+        dtype = self.visual_model.image_encoder.pos_embed.dtype
+        if mode is not None and dtype != BF16:
+            raise NotImplementedError(f"set_sam_precision({mode!r}) needs a bfloat16 model, this one is {dtype}")
+        self._sam.linear_precision = mode
+        return self
+
     def save_pretrained(self, save_directory, **kwargs):
         if self.llm.weight_quantization is not None:
             self.llm._refuse_quantized("save_pretrained")

@@ -636,6 +636,47 @@ def linear_a8w8(x: torch.Tensor, w: "Fp8Weight", residual: Optional[torch.Tensor
     return out
 
 
+# ---- FP8 Linears of the SAM image encoder (SamEngine.linear_precision = "fp8_e4m3") -----------------------------------------------------
+# Not a route of `linear`: the SAM block loop calls these two directly, at any M (the 128-tile kernel handles M < 128).
+def layernorm_quantize_rows_fp8(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float):
+    """quantize_rows_fp8(layernorm(x, w, b, eps)) in one launch (ull_layernorm_quantize_rows_fp8_bf16), bit for bit: (codes uint8 [M, K], scales
+    fp32 [M]) of the normed bf16 rows, which are never written."""
+    _chk(x, "x", BF16); _chk(w, "w", BF16); _chk(b, "b", BF16)
+    M, ldx = _rows(x)
+    K = x.shape[-1]
+    codes = torch.empty(M, K, device=x.device, dtype=torch.uint8)
+    scales = torch.empty(M, device=x.device, dtype=F32)
+    _lib.call("ull_layernorm_quantize_rows_fp8_bf16", _p(x), ldx, _p(w), _p(b), float(eps), M, K, _p(codes), K, _p(scales), _stream())
+    return codes, scales
+
+
+def linear_a8w8_rows(xq: torch.Tensor, xs: torch.Tensor, w: "Fp8Weight", bias: Optional[torch.Tensor] = None, act: Optional[str] = None,
+                     residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
+    """y = epilogue(dequant(xq, xs) @ w.T) from activation codes xq uint8 [M, K] (rows contiguous) and their scales xs fp32 [M]
+    (quantize_rows_fp8 / layernorm_quantize_rows_fp8) on an Fp8Weight, any M (ull_gemm_a8w8_epi_bf16; the only call site of that entry):
+    linear_a8w8's arithmetic, then `linear`'s epilogue with its rounding points -- bf16 bias added to the fp32 sum, activation, residual,
+    out_f32.  A K that is no multiple of 128 (tiny test models) is padded with zero codes, as linear_a8w8 does."""
+    if not isinstance(w, Fp8Weight):
+        raise RuntimeError("u-llava_amd.linear_a8w8_rows: w must be an Fp8Weight")
+    if xq.dtype != torch.uint8 or xq.dim() != 2 or xq.stride(1) != 1 or xs.dtype != F32 or xs.shape != (xq.shape[0],) or not xs.is_contiguous():
+        raise RuntimeError("u-llava_amd.linear_a8w8_rows: xq uint8 [M, K] (rows contiguous), xs fp32 [M]")
+    M, K = xq.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise RuntimeError(f"u-llava_amd.linear_a8w8_rows: K mismatch {K} vs {w.shape[1]}")
+    wq = w.a8_codes()
+    if wq.shape[1] != K or xq.stride(0) % 16 or xq.data_ptr() % 16:
+        xq = torch.nn.functional.pad(xq, (0, wq.shape[1] - K)).contiguous()
+    out, flags, ldr = _epilogue(xq, N, False, out_f32, residual, out, BF16)
+    flags |= ACTS[act]
+    if bias is not None:
+        _chk(bias, "bias", BF16)
+        flags |= EPI_BIAS
+    _lib.call("ull_gemm_a8w8_epi_bf16", _p(xq), xq.stride(0), _p(xs), _p(wq), wq.stride(0), _p(w.scales), _p(bias), _p(out), _rows(out)[1],
+              _p(residual), ldr, M, N, xq.shape[1], flags, _stream())
+    return out
+
+
 # ---- FP8 activations on FP8 weights at decode shapes: route "a8w8_skinny" -------------------------------------------------------------
 def rmsnorm_quantize_rows_fp8(x: torch.Tensor, w: torch.Tensor, eps: float):
     """quantize_rows_fp8(rmsnorm(x, w, eps)) in one launch (ull_rmsnorm_quantize_rows_fp8_bf16), bit for bit: (codes uint8 [M, K], scales

@@ -123,6 +123,16 @@ class SamEngine:
     GLOBAL_ATTENTION_MODES = ("streamed", "exact")
     global_attention = "streamed"
 
+    # The number format of the image encoder's four Linears per block (qkv, proj, lin1, lin2) in inference encodes of a bf16 model:
+    #   None        the model's 16-bit GEMMs (the default);
+    #   "fp8_e4m3"  W8A8 on the block-scaled fp8 matrix instruction: weights as ops.quantize_fp8 codes (derived data in the pack, built at the
+    #               first such encode, dropped by invalidate(); the bf16 parameters stay), input rows quantized per token
+    #               (ops.quantize_rows_fp8, fused into the LayerNorm where the normed rows feed nothing else), bias / GELU / residual at the
+    #               bf16 Linear's rounding points.  Per-op block loop (the coarse ops.sam_blocks entry is not taken); everything else --
+    #               patch / pos embed, attention and rel-pos, the window kernel's padded q|k|v from the bf16 qkv bias, neck -- stays bf16.
+    LINEAR_PRECISIONS = (None, "fp8_e4m3")
+    linear_precision = None
+
     def __init__(self, sam: nn.Module, cfg: SamConfig):
         self.sam, self.cfg = sam, cfg
         self._pk = None
@@ -160,17 +170,33 @@ class SamEngine:
     def pk(self):
         return self._pk if self._pk is not None else self.pack()
 
+    def _fp8_blocks(self, pk):
+        """Per block, the Fp8Weight of qkv / proj / lin1 / lin2 (linear_precision = "fp8_e4m3"): derived data kept in the pack, re-made when a
+        weight was updated in place since."""
+        lins = [(b.attn.qkv, b.attn.proj, b.mlp.lin1, b.mlp.lin2) for b in self.sam.image_encoder.blocks]
+        versions = [l.weight._version for ls in lins for l in ls]
+        e = pk.get("_fp8")
+        if e is None or e[1] != versions:
+            e = pk["_fp8"] = ([tuple(ops.quantize_fp8(l.weight.detach()) for l in ls) for ls in lins], versions)
+        return e[0]
+
     # -- image encoder (image_encoder.py:110-125) ------------------------------------------------------------------
     def encode(self, pixel_values: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
         """[B,3,S,S] -> token-major embeddings [B, g*g, out_chans].  trace: optional dict receiving the stage outputs [B, g, g, C]."""
         if self.global_attention not in self.GLOBAL_ATTENTION_MODES:
             raise ValueError(f"SamEngine.global_attention must be one of {self.GLOBAL_ATTENTION_MODES}, got {self.global_attention!r}")
+        if self.linear_precision not in self.LINEAR_PRECISIONS:
+            raise ValueError(f"SamEngine.linear_precision must be one of {self.LINEAR_PRECISIONS}, got {self.linear_precision!r}")
         cfg, enc = self.cfg, self.sam.image_encoder
         B = pixel_values.shape[0]
         C, nH = cfg.embed_dim, cfg.num_heads
         hd = C // nH
         g = cfg.img_size // cfg.patch_size
         dtype = enc.pos_embed.dtype
+        fp8 = self.linear_precision is not None
+        if fp8 and dtype != BF16:
+            # (before anything is launched)
+            raise NotImplementedError(f"linear_precision={self.linear_precision!r} needs a bfloat16 SAM encoder, this one is {dtype}")
         if (self.global_attention == "exact" and dtype != torch.float32 and g * g > 1024 and any(i < len(enc.blocks) for i in cfg.global_attn_indexes)
                 and not ops.sam_global_exact_takes(g, hd, dtype)):
             # (before anything is launched)
@@ -187,7 +213,7 @@ class SamEngine:
             trace["embed"] = x.view(B, g, g, C)
         I = enc.blocks[0].mlp.lin1.weight.shape[0] if len(enc.blocks) else 0
         exact = self.global_attention == "exact" and x.dtype != torch.float32
-        coarse = (not exact and trace is None and ops.coarse_ok() and len(enc.blocks) > 0 and hd == 80 and g == 64 and cfg.window_size == 14 and C % 64 == 0
+        coarse = (not exact and not fp8 and trace is None and ops.coarse_ok() and len(enc.blocks) > 0 and hd == 80 and g == 64 and cfg.window_size == 14 and C % 64 == 0
                   and I % 64 == 0 and all(b.attn.qkv.bias is not None for b in enc.blocks) and x.dtype != torch.float32)
         if coarse:
             # one C call for all blocks (csrc/layers.hip): the same launches as the loop below, bit-identical results
@@ -201,27 +227,43 @@ class SamEngine:
                     rel_pos_h=rel(b.attn.rel_pos_h, i in cfg.global_attn_indexes), rel_pos_w=rel(b.attn.rel_pos_w, i in cfg.global_attn_indexes),
                     window=0 if i in cfg.global_attn_indexes else cfg.window_size) for i, b in enumerate(enc.blocks)])
             ops.sam_blocks(stack, x, B, g, nH, hd, I, 1e-6)
+        q8 = self._fp8_blocks(pk) if fp8 else None
+
+        def lin(rows, l, q, **kw):
+            """Linear l on bf16 rows; q: its Fp8Weight in fp8 mode (the rows are quantized in a launch of their own)."""
+            if q is None:
+                return ops.linear(rows, l.weight, l.bias, **kw)
+            return ops.linear_a8w8_rows(*ops.quantize_rows_fp8(rows), q, bias=l.bias, **kw)
+
+        def norm_lin(rows, n, l, q, **kw):
+            """l(LayerNorm n(rows)) where the normed rows feed nothing else: in fp8 mode they are quantized by the norm's own launch."""
+            if q is None:
+                return ops.linear(ops.layernorm(rows, n.weight, n.bias, 1e-6), l.weight, l.bias, **kw)
+            return ops.linear_a8w8_rows(*ops.layernorm_quantize_rows_fp8(rows, n.weight, n.bias, 1e-6), q, bias=l.bias, **kw)
+
         for i, blk in enumerate(() if coarse else enc.blocks):
             glob = i in cfg.global_attn_indexes
             ws = 0 if glob else cfg.window_size
-            y = ops.layernorm(x, blk.norm1.weight, blk.norm1.bias, 1e-6)
+            q_qkv, q_proj, q_lin1, q_lin2 = q8[i] if fp8 else (None,) * 4
             if ws == 14 and hd == 80 and blk.attn.qkv.bias is not None and x.dtype != torch.float32:
                 # the path's own window shape: the tokens stay in image order, the attention kernel does the window addressing and
                 # takes the q|k|v of the reference's zero-padded positions from the qkv bias -- no partition / unpartition passes
                 # and no GEMM rows for the padding (25 windows x 196 = 4900 positions for 4096 tokens), and reads V through the
                 # transposing LDS load, so there is no V^T pass either
-                qkv = ops.linear(y, blk.attn.qkv.weight, blk.attn.qkv.bias)
+                qkv = norm_lin(x, blk.norm1, blk.attn.qkv, q_qkv)
                 att = ops.sam_window_attention(qkv, blk.attn.qkv.bias, blk.attn.rel_pos_h, blk.attn.rel_pos_w, B, g, g, nH, hd, ws)
-                x = ops.linear(att, blk.attn.proj.weight, blk.attn.proj.bias, residual=x)
+                x = lin(att, blk.attn.proj, q_proj, residual=x)
             else:
                 if ws:
-                    y = ops.window_partition(y, B, g, g, ws)
+                    # (the partition needs the normed bf16 rows: the norm stays a launch of its own in fp8 mode too)
+                    y = ops.window_partition(ops.layernorm(x, blk.norm1.weight, blk.norm1.bias, 1e-6), B, g, g, ws)
                     side = ws
                     NB = B * ((g + ws - 1) // ws) ** 2
+                    qkv = lin(y, blk.attn.qkv, q_qkv)                                # [NB*S, 3C]: q | k | v, heads contiguous
                 else:
                     side, NB = g, B
+                    qkv = norm_lin(x, blk.norm1, blk.attn.qkv, q_qkv)
                 S = side * side
-                qkv = ops.linear(y, blk.attn.qkv.weight, blk.attn.qkv.bias)          # [NB*S, 3C]: q | k | v, heads contiguous
                 strides = (S * 3 * C, hd, 3 * C)
                 att = torch.empty(NB * S, C, device=x.device, dtype=x.dtype)
                 if exact and glob and S > 1024:
@@ -239,15 +281,13 @@ class SamEngine:
                                   scale_mode=0, q_scale=hd ** -0.5, rel_h=blk.attn.rel_pos_h, rel_w=blk.attn.rel_pos_w,
                                   rel_pos_hw=(side, side), v_strides=strides)
                 if ws:
-                    o = ops.linear(att, blk.attn.proj.weight, blk.attn.proj.bias)
-                    x = ops.window_unpartition_add(o, x, B, g, g, ws)
+                    x = ops.window_unpartition_add(lin(att, blk.attn.proj, q_proj), x, B, g, g, ws)
                 else:
-                    x = ops.linear(att, blk.attn.proj.weight, blk.attn.proj.bias, residual=x)
+                    x = lin(att, blk.attn.proj, q_proj, residual=x)
             if trace is not None:
                 trace[f"block{i}.attn"] = x.view(B, g, g, C)
-            y = ops.layernorm(x, blk.norm2.weight, blk.norm2.bias, 1e-6)
-            f = ops.linear(y, blk.mlp.lin1.weight, blk.mlp.lin1.bias, act="gelu")
-            x = ops.linear(f, blk.mlp.lin2.weight, blk.mlp.lin2.bias, residual=x)
+            f = norm_lin(x, blk.norm2, blk.mlp.lin1, q_lin1, act="gelu")
+            x = lin(f, blk.mlp.lin2, q_lin2, residual=x)
             if trace is not None:
                 trace[f"block{i}"] = x.view(B, g, g, C)
         if x.dtype == torch.float16:
