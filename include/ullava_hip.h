@@ -357,6 +357,20 @@ int ull_sample_step(const void* logits, int logits_dtype, int64_t row_stride, in
                     int64_t top_k, float top_p, void* unfinished, const void* eos, int64_t n_eos, int64_t pad, int has_pad, void* seq,
                     int64_t seq_ld, int64_t pos, void* alive, void* stream);
 
+/* One step of prompt-lookup speculative decoding at batch 1 (HF `generate(prompt_lookup_num_tokens=)`), in two launches.  buf (int64, buf_len
+ * ids) holds n valid ids followed by the d drafts of this step (0 <= d <= ULL_SPEC_MAX_DRAFT); logits are the 1 + d rows (V entries,
+ * row_stride elements apart, logits_dtype ULL_DT_F32 0 / BF16 1 / F16 2) of the forward over buf[n-1 .. n+d).  Every row's token t_i is
+ * picked as the plain loop picks it: noise == NULL: ull_greedy_step_*'s argmax (lowest index on ties); else ull_sample_step's rule on
+ * temperature / top_k / top_p and noise fp32 [1 + d, V].  The accepted prefix a = the leading i < d with t_i == buf[n+i]; t_0 .. t_a are
+ * emitted into buf[n ...], cut so that at most n_max ids are valid and cut after the first of the n_eos ids in `eos` (int64; the row is then
+ * finished).  With n' valid ids the next drafts are looked up: for g = min(max_ngram, n'-1) .. 1 the earliest window equal to the trailing g
+ * ids with a non-empty continuation; the continuation, at most min(num_tokens, n_max - n' - 1) ids, cut at n' and before the first EOS id, is
+ * written to buf[n' ...] (no drafts for a finished row).  picks: int32 [16] scratch (the t_i); record: int32 [3] = (emitted, finished, d'). */
+#define ULL_SPEC_MAX_DRAFT 15
+int ull_spec_step(const void* logits, int logits_dtype, int64_t row_stride, int64_t V, const void* noise, float temperature, int64_t top_k,
+                  float top_p, void* buf, int64_t buf_len, int64_t n, int64_t d, int64_t n_max, const void* eos, int64_t n_eos,
+                  int64_t num_tokens, int64_t max_ngram, void* picks, void* record, void* stream);
+
 /* models/ullava_core.py:191,243-245,266-268: token-embedding lookup with the projected visual tokens spliced in after
  * the first start token (the torch.cat of the reference, done as one gather).  Image i's n_img_tok feature rows start
  * at row i*img_pitch + img_off of img_feat (pitch = patches + 1, off = 1 skips the CLS row without a copy).

@@ -116,6 +116,7 @@ SIGNATURES = {
     "ull_adamw_step_f32": [_ptr, _ptr, _ptr, _ptr, _i32, _ptr, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _ptr],
     "ull_sumsq_f32": [_ptr, _i32, _i64, _ptr, _ptr],
     "ull_sample_step": [_ptr, _i32, _i64, _i64, _i64, _ptr, _f32, _i64, _f32, _ptr, _ptr, _i64, _i64, _i32, _ptr, _i64, _i64, _ptr, _ptr],
+    "ull_spec_step": [_ptr, _i32, _i64, _i64, _ptr, _f32, _i64, _f32, _ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr],
 }
 
 # every dtype-dependent entry point exists twice: ull_*_bf16 (bfloat16 build) and ull_*_f16 (IEEE binary16 build), same signature

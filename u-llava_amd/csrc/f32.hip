@@ -11,6 +11,7 @@
 // ull_transpose2d_f32, which with ull_gemm_f32 makes the backward of a plain fp32 Linear (autograd_ops._Linear: dX and dW; no fp32 bias
 // sum or ReLU mask).
 #include "ull_common.h"
+#include "select.h"
 
 #define ULL_EPI_BIAS 1
 #define ULL_EPI_ACT_MASK (3 << 1)
@@ -453,25 +454,8 @@ __global__ __launch_bounds__(1024) void greedy_step_f32_kernel(const float* __re
     __shared__ float bv[16];
     __shared__ int bi[16];
     const int b = blockIdx.x;
-    const float* row = logits + (long)b * row_stride;
-    float best = -INFINITY;
-    int idx = 0x7fffffff;
-    for (int c = threadIdx.x; c < V; c += 1024) {
-        const float v = row[c];
-        if (v > best || (v == best && c < idx)) { best = v; idx = c; }
-    }
-    if (idx == 0x7fffffff) idx = threadIdx.x < V ? threadIdx.x : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
+    const int idx = greedy_pick<ULL_DT_F32>(logits + (long)b * row_stride, V, bv, bi);      // select.h: the rule every greedy path shares
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w)
-            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
         const int live = unfinished[b];
         long tok = idx;
         if (!live && has_pad) tok = pad;

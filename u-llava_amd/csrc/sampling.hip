@@ -18,6 +18,7 @@
 //   5. pad fill / EOS / alive bookkeeping as greedy_step_kernel.
 // Every sum is taken in a fixed order (no floating-point atomics): the same inputs give the same token on every run.
 #include "ull_common.h"
+#include "select.h"
 
 namespace {
 
@@ -112,32 +113,16 @@ ULL_DEV int block_argmax(float best, int idx, Scratch& sc) {
     return idx;
 }
 
-template <int DT> ULL_DEV void unpack_chunk(const uint4& q, float* f) {       // 16 bytes = 4 fp32 or 8 16-bit elements
-    if constexpr (DT == ULL_DT_F32) {
-        f[0] = __uint_as_float(q.x); f[1] = __uint_as_float(q.y); f[2] = __uint_as_float(q.z); f[3] = __uint_as_float(q.w);
-    } else {
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if constexpr (DT == ULL_DT_BF16) { f[2 * j] = __uint_as_float(w[j] << 16); f[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u); }
-            else { f[2 * j] = f16_bits_to_f32((uint16_t)(w[j] & 0xffffu)); f[2 * j + 1] = f16_bits_to_f32((uint16_t)(w[j] >> 16)); }
-        }
-    }
-}
-
+// The sampled selection rule (steps 1-4 above) for one row, by one SS_THREADS block: `row` the logits of the row, nz its noise, lds the block's
+// dynamic LDS ([V] keys + SS_HIST words).  Every thread returns the token index (outside [0, V) only for a row of NaNs).  Shared by
+// sample_step_kernel and the speculative step's spec_pick_kernel.
 template <int DT>
-__global__ __launch_bounds__(SS_THREADS) void sample_step_kernel(const void* __restrict__ logits, long row_stride, int V, const float* __restrict__ noise,
-                                                                 float temperature, int top_k, float top_p, int32_t* __restrict__ unfinished,
-                                                                 const int64_t* __restrict__ eos, int n_eos, long pad, int has_pad,
-                                                                 int64_t* __restrict__ seq, long seq_ld, int pos, int32_t* __restrict__ alive) {
-    extern __shared__ uint32_t lds[];
+ULL_DEV int sample_pick(const char* __restrict__ row, int V, const float* __restrict__ nz, float temperature, int top_k, float top_p,
+                        uint32_t* lds, Scratch& sc) {
     uint32_t* keys = lds;                              // [V]
     uint32_t* hist = lds + ((V + 3) & ~3);             // [SS_HIST]
-    __shared__ Scratch sc;
     constexpr int ESZ = DT == ULL_DT_F32 ? 4 : 2, EPC = 16 / ESZ;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const char* row = (const char*)logits + (long)b * row_stride * ESZ;
-    const float* nz = noise + (long)b * V;
+    const int tid = threadIdx.x;
 
     // ---- 1. stage the row as keys of s = logit / temperature
     uint32_t kmax = 0;
@@ -314,9 +299,22 @@ __global__ __launch_bounds__(SS_THREADS) void sample_step_kernel(const void* __r
         }
     }
 
-    // ---- 4. the race, 5. bookkeeping (greedy_step_kernel's)
-    idx = block_argmax(best, idx, sc);
-    if (tid == 0) {
+    // ---- 4. the race
+    return block_argmax(best, idx, sc);
+}
+
+template <int DT>
+__global__ __launch_bounds__(SS_THREADS) void sample_step_kernel(const void* __restrict__ logits, long row_stride, int V, const float* __restrict__ noise,
+                                                                 float temperature, int top_k, float top_p, int32_t* __restrict__ unfinished,
+                                                                 const int64_t* __restrict__ eos, int n_eos, long pad, int has_pad,
+                                                                 int64_t* __restrict__ seq, long seq_ld, int pos, int32_t* __restrict__ alive) {
+    extern __shared__ uint32_t lds[];
+    __shared__ Scratch sc;
+    constexpr int ESZ = DT == ULL_DT_F32 ? 4 : 2;
+    const int b = blockIdx.x;
+    int idx = sample_pick<DT>((const char*)logits + (long)b * row_stride * ESZ, V, noise + (long)b * V, temperature, top_k, top_p, lds, sc);
+    // ---- 5. bookkeeping (greedy_step_kernel's)
+    if (threadIdx.x == 0) {
         if (idx < 0 || idx >= V) idx = 0;              // a row of NaNs: any valid index
         int live = unfinished[b];
         long tok = idx;
@@ -344,7 +342,124 @@ int launch_sample_step(const void* logits, int64_t row_stride, int64_t B, int64_
     return ull_check_launch();
 }
 
+// ---- one step of prompt-lookup speculative decoding (batch 1), two launches ---------------------------------------------------------
+// The forward ran on buf[n - 1 : n + d] (the last valid id and the d drafts that already sit in buf[n : n + d]) and left 1 + d rows of logits.
+// spec_pick_kernel: one block per row picks that row's token t_i by the plain loop's rule (greedy_pick, or sample_pick on the row's noise).
+// spec_accept_kernel (one block): a = the leading i < d with t_i == buf[n + i]; t_0 .. t_a are emitted into buf[n ...], cut at n_max valid ids
+// and after the first EOS id (finished); then the next step's drafts are looked up (modeling_core.prompt_lookup_candidates restated) over the
+// n' valid ids and written to buf[n' : n' + d'], and record = (emitted, finished, d').  No block waits on another; every loop is bounded by
+// an argument of the launch.
+template <int DT>
+__global__ __launch_bounds__(SS_THREADS) void spec_pick_kernel(const void* __restrict__ logits, long row_stride, int V, const float* __restrict__ noise,
+                                                               float temperature, int top_k, float top_p, int32_t* __restrict__ picks) {
+    extern __shared__ uint32_t lds[];
+    __shared__ Scratch sc;
+    constexpr int ESZ = DT == ULL_DT_F32 ? 4 : 2;
+    const int b = blockIdx.x;
+    const char* row = (const char*)logits + (long)b * row_stride * ESZ;
+    int idx;
+    if (noise) {
+        idx = sample_pick<DT>(row, V, noise + (long)b * V, temperature, top_k, top_p, lds, sc);
+        if (idx < 0 || idx >= V) idx = 0;              // a row of NaNs: any valid index
+    } else {
+        idx = greedy_pick<DT>(row, V, sc.f, sc.i);
+    }
+    if (threadIdx.x == 0) picks[b] = idx;
+}
+
+ULL_DEV bool is_eos(int64_t tok, const int64_t* __restrict__ eos, int n_eos) {
+    for (int e = 0; e < n_eos; ++e)
+        if (eos[e] == tok) return true;
+    return false;
+}
+
+__global__ __launch_bounds__(SS_THREADS) void spec_accept_kernel(const int32_t* __restrict__ picks, int64_t* buf, int n, int d, int n_max,
+                                                                 const int64_t* __restrict__ eos, int n_eos, int num_tokens, int max_ngram,
+                                                                 int32_t* __restrict__ record) {
+    __shared__ int s_emit, s_fin, s_min[16];
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int a = 0;
+        while (a < d && (int64_t)picks[a] == buf[n + a]) ++a;
+        int m = min(a + 1, n_max - n), fin = 0;
+        for (int j = 0; j < m; ++j)
+            if (is_eos(picks[j], eos, n_eos)) { m = j + 1; fin = 1; break; }
+        for (int j = 0; j < m; ++j) buf[n + j] = picks[j];
+        s_emit = m;
+        s_fin = fin;
+    }
+    __syncthreads();                                   // (also orders thread 0's stores to buf before the scan's loads)
+    const int emitted = s_emit, fin = s_fin, n2 = n + emitted;
+    const int limit = n_max - n2 - 1;                  // a step never proposes more than it may emit
+    int d2 = 0;
+    if (!fin && limit > 0) {
+        const int want = min(num_tokens, limit);
+#pragma unroll 1
+        for (int ng = min(max_ngram, n2 - 1); ng >= 1; --ng) {
+            // the earliest window [s, s + ng) equal to the trailing ng ids with a non-empty continuation: s <= n2 - ng - 1
+            const int64_t* tail = buf + (n2 - ng);
+            int first = 0x7fffffff;
+            for (int s = tid; s <= n2 - ng - 1; s += SS_THREADS) {       // any history length: the last round is partial
+                bool eq = true;
+                for (int j = 0; j < ng && eq; ++j) eq = buf[s + j] == tail[j];
+                if (eq) { first = s; break; }          // increasing s per thread: its earliest
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+            __syncthreads();
+            if ((tid & 63) == 0) s_min[tid >> 6] = first;
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < 16; ++w) first = min(first, s_min[w]);
+            if (first != 0x7fffffff) {                 // (the same value in every thread)
+                const int start = first + ng, end = min(start + want, n2);
+                if (tid == 0)
+                    for (int c = start; c < end; ++c) {              // cut before the first EOS id
+                        const int64_t tok = buf[c];
+                        if (is_eos(tok, eos, n_eos)) break;
+                        buf[n2 + d2++] = tok;
+                    }
+                break;
+            }
+        }
+    }
+    if (tid == 0) { record[0] = emitted; record[1] = fin; record[2] = d2; }
+}
+
+template <int DT>
+int launch_spec_pick(const void* logits, int64_t row_stride, int64_t R, int64_t V, const void* noise, float temperature, int64_t top_k, float top_p,
+                     void* picks, hipStream_t st) {
+    const int lds = noise ? (((int)V + 3) & ~3) * 4 + SS_HIST * 4 : 0;
+    static UllOncePerDevice once;
+    if (once.first()) (void)hipFuncSetAttribute((const void*)spec_pick_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - SS_STATIC);
+    hipLaunchKernelGGL(spec_pick_kernel<DT>, dim3((unsigned)R), dim3(SS_THREADS), lds, st, logits, (long)row_stride, (int)V, (const float*)noise,
+                       temperature, (int)(top_k > V ? V : top_k), top_p, (int32_t*)picks);
+    return ull_check_launch();
+}
+
 }  // namespace
+
+extern "C" int ull_spec_step(const void* logits, int logits_dtype, int64_t row_stride, int64_t V, const void* noise, float temperature, int64_t top_k,
+                             float top_p, void* buf, int64_t buf_len, int64_t n, int64_t d, int64_t n_max, const void* eos, int64_t n_eos,
+                             int64_t num_tokens, int64_t max_ngram, void* picks, void* record, void* stream) {
+    if (!logits || !buf || !picks || !record || V <= 0 || (n_eos > 0 && !eos) || n_eos < 0 || logits_dtype < 0 || logits_dtype > 2 || top_k < 0 ||
+        !(top_p == top_p) || (noise && !(temperature > 0.f)))
+        return ULL_ERR_ARG;
+    // n valid ids, d drafts behind them, at most n_max valid ids in the end: the kernels read buf[0, max(n + d, n_max)) and write buf[n, n_max)
+    if (n < 1 || d < 0 || d > ULL_SPEC_MAX_DRAFT || num_tokens < 1 || num_tokens > ULL_SPEC_MAX_DRAFT || max_ngram < 1 || n >= n_max || n + d > buf_len ||
+        n_max > buf_len || n_max > 0x7fffffff)
+        return ULL_ERR_ARG;
+    if (noise && V > SS_MAX_V) return ULL_ERR_SHAPE;  // the sampled pick stages the row in LDS as 4-byte keys
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (logits_dtype == ULL_DT_BF16) rc = launch_spec_pick<ULL_DT_BF16>(logits, row_stride, 1 + d, V, noise, temperature, top_k, top_p, picks, st);
+    else if (logits_dtype == ULL_DT_F16) rc = launch_spec_pick<ULL_DT_F16>(logits, row_stride, 1 + d, V, noise, temperature, top_k, top_p, picks, st);
+    else rc = launch_spec_pick<ULL_DT_F32>(logits, row_stride, 1 + d, V, noise, temperature, top_k, top_p, picks, st);
+    if (rc != ULL_OK) return rc;
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(SS_THREADS), 0, st, (const int32_t*)picks, (int64_t*)buf, (int)n, (int)d, (int)n_max,
+                       (const int64_t*)eos, (int)n_eos, (int)num_tokens, (int)max_ngram, (int32_t*)record);
+    return ull_check_launch();
+}
 
 extern "C" int ull_sample_step(const void* logits, int logits_dtype, int64_t row_stride, int64_t B, int64_t V, const void* noise, float temperature,
                                int64_t top_k, float top_p, void* unfinished, const void* eos, int64_t n_eos, int64_t pad, int has_pad, void* seq,

@@ -310,6 +310,7 @@ ULL_DEV float act_quick_gelu_e(float t) {
 #define ULL_ERR_LAUNCH (-3)
 #define ULL_ERR_LDS (-4)
 #define ULL_SAMPLE_MAX_V 36608    // longest row ull_sample_step stages in LDS (sampling.hip)
+#define ULL_SPEC_MAX_DRAFT 15      // most draft tokens of one ull_spec_step: 16 rows, the few-query limit of the fp8-cache attention
 
 // hipFuncSetAttribute is per device: one of these per kernel instantiation remembers which devices already have it
 // (a racing first call repeats an idempotent attribute call; nothing else is shared between host threads or streams).

@@ -6,6 +6,7 @@
 //   * video spatio-temporal pooling (models/ullava_core.py:160-180 encode_video)
 //   * row gather, bf16 add
 #include "ull_common.h"
+#include "select.h"
 
 namespace {
 
@@ -214,43 +215,13 @@ __global__ __launch_bounds__(1024) void greedy_step_kernel(const elem_t* __restr
     __shared__ float bv[16];
     __shared__ int bi[16];
     const int b = blockIdx.x;
-    const elem_t* row = logits + (long)b * row_stride;
-    float best = -INFINITY;
-    int idx = 0x7fffffff;
-    // 16-byte chunks, four of them in flight per thread (a 32 064-entry row is 4 008 chunks: one round of 1024 threads); the scalar form
-    // of this loop -- 125 dependent 2-byte loads per thread -- took 39 us per token
-    const int nchunk = (((uintptr_t)row & 15) == 0) ? (V >> 3) : 0;
-    for (int c0 = threadIdx.x; c0 < nchunk; c0 += 4 * 1024) {
-        uint4 q[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) q[u] = c0 + u * 1024 < nchunk ? *(const uint4*)(row + (long)(c0 + u * 1024) * 8) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (c0 + u * 1024 < nchunk) {
-                float f[8];
-                unpack8(q[u], f);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (f[j] > best) { best = f[j]; idx = (c0 + u * 1024) * 8 + j; }      // increasing index per thread: the first maximum stays
-            }
-        }
-    }
-    for (int c = nchunk * 8 + threadIdx.x; c < V; c += 1024) {
-        const float v = e2f(row[c]);
-        if (v > best || (v == best && c < idx)) { best = v; idx = c; }
-    }
-    if (idx == 0x7fffffff) idx = threadIdx.x < V ? threadIdx.x : 0;   // a row of NaNs: any valid index (torch returns the first NaN)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
+#ifdef ULL_ELEM_F16
+    constexpr int DT = ULL_DT_F16;
+#else
+    constexpr int DT = ULL_DT_BF16;
+#endif
+    const int idx = greedy_pick<DT>(logits + (long)b * row_stride, V, bv, bi);      // select.h: the rule every greedy path shares
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w)
-            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
         int live = unfinished[b];
         long tok = idx;
         if (!live && has_pad) tok = pad;

@@ -258,6 +258,25 @@ class KVCache:
     def __bool__(self):
         return self.length > 0
 
+    def truncate(self, n: int) -> None:
+        """Give back the positions >= n (speculative decoding: the rejected drafts of a verify step): `length` becomes n and `last_hidden`
+        holds exactly the first n positions (the last call's tensor is sliced).  bf16 and fp8 caches alike: the buffers keep the rejected
+        positions' K rows, V^T columns, codes and scales as stale finite data, which no kernel reads -- attention, append and quantization
+        address keys below `length` plus the call's own new positions, and the next call overwrites them."""
+        n = int(n)
+        if n < 0 or n > self.length:
+            raise ValueError(f"KVCache.truncate({n}): the cache holds {self.length} positions")
+        self.length = n
+        have = sum(h.shape[1] for h in self.last_hidden)
+        while self.last_hidden and have > n:
+            last = self.last_hidden[-1]
+            if have - last.shape[1] >= n:
+                self.last_hidden.pop()
+                have -= last.shape[1]
+            else:
+                self.last_hidden[-1] = last[:, :last.shape[1] - (have - n)]
+                have = n
+
     def c_ptrs(self):
         """(void* array of the K buffers, void* array of the V^T buffers) for the coarse decode entry; built once per cache.
         fp8 cache: (k8, vt8, k_scale, vt_scale void* arrays, k_stage, vt_stage) for the *_kv8 entries, rebuilt whenever a list entry has
@@ -372,6 +391,48 @@ def no_repeat_ngram_banned_tokens(rows, ngram_size: int):
                 banned.append(toks[i + ngram_size - 1])
         out.append(banned)
     return out
+
+
+def prompt_lookup_candidates(row, num_tokens: int, max_ngram: int, eos_ids, limit: int):
+    """The draft of prompt-lookup decoding (transformers generation/candidate_generator.py, PromptLookupCandidateGenerator: what HF
+    `generate(prompt_lookup_num_tokens=, max_matching_ngram_size=)` proposes), restated on a plain list; the reference of the device lookup in
+    ops.spec_step.  row: the ids so far, prompt included.  For n = min(max_ngram, len(row) - 1) down to 1: the earliest window equal to the
+    row's trailing n ids whose continuation is non-empty wins; the continuation is the next min(num_tokens, limit) ids, cut at the end of the
+    row and before the first id in eos_ids (what is left may be empty, and is the draft all the same).  No window at any n: no draft.
+    limit = max_new_tokens - tokens generated so far - 1: a step never proposes more than it may emit."""
+    row = list(row)
+    L = len(row)
+    want = min(int(num_tokens), int(limit))
+    if want <= 0:
+        return []
+    eos = set() if eos_ids is None else {int(e) for e in eos_ids}
+    for n in range(min(int(max_ngram), L - 1), 0, -1):
+        tail = row[L - n:]
+        for s in range(L - n):                                   # s + n < L: the continuation has at least one id
+            if row[s:s + n] == tail:
+                out = []
+                for tok in row[s + n:min(s + n + want, L)]:
+                    if tok in eos:
+                        break
+                    out.append(tok)
+                return out
+    return []
+
+
+def check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size):
+    """generate()'s `prompt_lookup_num_tokens` / `max_matching_ngram_size` -> (k, n-gram size), or None when the feature is off."""
+    if prompt_lookup_num_tokens is None:
+        if max_matching_ngram_size is not None:
+            raise ValueError("`max_matching_ngram_size` is an option of prompt-lookup decoding: it needs `prompt_lookup_num_tokens`")
+        return None
+    k = int(prompt_lookup_num_tokens)
+    if k != prompt_lookup_num_tokens or not 1 <= k <= ops.SPEC_MAX_DRAFT:
+        raise ValueError(f"`prompt_lookup_num_tokens` has to be an integer in 1..{ops.SPEC_MAX_DRAFT} (a verify step takes at most "
+                         f"{ops.SPEC_MAX_DRAFT + 1} new tokens), but is {prompt_lookup_num_tokens}")
+    g = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
+    if (max_matching_ngram_size is not None and g != max_matching_ngram_size) or g < 1:
+        raise ValueError(f"`max_matching_ngram_size` has to be an integer >= 1, but is {max_matching_ngram_size}")
+    return k, g
 
 
 def sampling_probs(logits: torch.Tensor, temperature: float, top_k: Optional[int] = 50, top_p: Optional[float] = None) -> torch.Tensor:
@@ -1371,11 +1432,55 @@ class UllavaCoreForCausalLM(nn.Module):
                              "attention_mask": attention_mask, "images": images, "videos": videos})
         return model_inputs
 
+    def _generate_prompt_lookup(self, seq, images, videos, max_new_tokens, lookup, sampling, temperature, top_k, top_p, eos_ids, crit,
+                                kv_cache_dtype, output_hidden_states, return_dict_in_generate):
+        """generate()'s loop under prompt_lookup_num_tokens (batch 1, KV cache, arguments already checked).  The ids live in one device
+        buffer: n valid ids, then the d drafts of the next step.  A step is one forward over buf[n-1 : n+d] and ops.spec_step, which emits,
+        drafts again and leaves (emitted, finished, d') for the one host read of the step -- the next forward's length depends on it."""
+        k, max_ngram = lookup
+        L0 = seq.shape[1]
+        n_max = L0 + max_new_tokens
+        dev = seq.device
+        buf = torch.empty(1, n_max + k, dtype=torch.int64, device=dev)
+        buf[:, :L0] = seq
+        picks = torch.empty(16, dtype=torch.int32, device=dev)
+        record = torch.empty(3, dtype=torch.int32, device=dev)
+        self._cache_headroom = max_new_tokens + k + 1            # (the cache forward() creates for the prefill)
+        cache = None
+        n, d = L0, 0
+        while n < n_max:
+            if cache is None:
+                self._new_cache_kv_dtype = kv_cache_dtype
+                try:
+                    out = self.forward(input_ids=buf[:, :L0], images=images, videos=videos, use_cache=True)
+                finally:
+                    self._new_cache_kv_dtype = None
+                cache = out.past_key_values
+            else:
+                out = self.forward(input_ids=buf[:, n - 1:n + d], past_key_values=cache, use_cache=True)
+            logits = out.logits[0, -(1 + d):]
+            # torch's noise, one row per verified position, drawn in one call per step
+            noise = torch.empty(logits.shape, dtype=torch.float32, device=dev).exponential_() if sampling else None
+            ops.spec_step(logits, noise, temperature, top_k, top_p, buf, n, d, n_max, eos_ids, k, max_ngram, picks, record)
+            emitted, finished, d = record.tolist()               # the step's device -> host read
+            n += emitted
+            cache.truncate(n - 1)                                # the rejected drafts' positions (and the states of the token not yet fed)
+            if finished or (crit and any(bool(torch.as_tensor(c(buf[:, :n], None)).all()) for c in crit)):
+                break
+        seq = buf[:, :n].contiguous()
+        if not return_dict_in_generate:
+            return seq
+        hidden = None
+        if output_hidden_states:
+            hidden = ((torch.cat(cache.last_hidden, dim=1),),) if cache is not None else ()
+        return GenerateOutput(sequences=seq, hidden_states=hidden)
+
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, videos=None, attention_mask=None, max_new_tokens=32, do_sample=False,
                  temperature=1.0, top_p=None, top_k=50, num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, eos_token_id=None,
                  pad_token_id=None, output_hidden_states=False, return_dict_in_generate=False, use_cache=None,
-                 keep_last_step_only=False, kv_cache_dtype=None, sampler=None, **kwargs):
+                 keep_last_step_only=False, kv_cache_dtype=None, sampler=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None,
+                 **kwargs):
         """Token-by-token decoding with HF GenerationMixin's greedy / sampling semantics (the reference inherits `generate`):
         every step goes through `prepare_inputs_for_generation` (position_ids = cumsum(attention_mask) - 1, so left-padded batches
         get the reference's RoPE positions); `eos_token_id` defaults to `config.eos_token_id` (int or list); rows that have emitted
@@ -1391,7 +1496,17 @@ class UllavaCoreForCausalLM(nn.Module):
         same distribution, the same torch noise, so a seeded run draws the host path's tokens) inside the device-resident loop greedy
         decoding uses.  That loop looks at the host every 8 steps, so it may run up to 7 steps past the point where every row had
         finished: the returned ids are trimmed and equal, but the global generator has advanced further than on the host path.
-        It does not combine with `no_repeat_ngram_size` (host-side list work)."""
+        It does not combine with `no_repeat_ngram_size` (host-side list work).
+        prompt_lookup_num_tokens=k (opt-in, 1..15; HF's option of the same name, with max_matching_ngram_size, default 2): prompt-lookup
+        speculative decoding.  Each step drafts up to k tokens by copying what followed an earlier occurrence of the row's trailing n-gram
+        (`prompt_lookup_candidates`), runs ONE forward over the last token and the drafts, and emits the accepted drafts plus one more token
+        (ops.spec_step; the cache gives the rejected positions back, KVCache.truncate).  Every emitted token is the token the usual rule --
+        argmax, or sampler="device"'s draw on that position's own noise row -- picks from the logits at its position; drafts only decide
+        how many positions a forward covers.  The logits of a multi-token forward may differ from a one-token forward's in the last bits, so
+        where two candidates are almost tied the ids can differ from the plain loop's.  Batch 1, use_cache=True, no padding, no
+        `no_repeat_ngram_size`; sampling needs sampler="device".  The host reads a three-int record every step.  Stopping criteria are
+        called once per step on the valid ids, so a criterion can fire up to k tokens later than in the plain loop (HF's assisted decoding
+        behaves the same way)."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not used by the reference callers (num_beams=1)")
         if kwargs:
@@ -1411,6 +1526,19 @@ class UllavaCoreForCausalLM(nn.Module):
             raise ValueError(f'sampler="device" stages a row of logits in LDS: vocab_size {self.config.vocab_size} is above its limit of '
                              f"{ops.SAMPLE_MAX_V} (use sampler=None)")
         use_cache = self.config.use_cache if use_cache is None else use_cache
+        lookup = check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size)
+        if lookup is not None:
+            if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
+                raise ValueError("prompt-lookup decoding takes a batch of one row (as HF's assisted decoding does), got "
+                                 f"{None if input_ids is None else tuple(input_ids.shape)}")
+            if not use_cache:
+                raise ValueError("prompt-lookup decoding needs use_cache=True: a verify step runs over a filled KV cache")
+            if ngram:
+                raise ValueError("prompt-lookup decoding does not combine with `no_repeat_ngram_size`: the n-gram ban is host-side list work")
+            if attention_mask is not None and not bool(attention_mask.ne(0).all()):
+                raise ValueError("prompt-lookup decoding does not take a padded attention mask (one unpadded row)")
+            if sampling and not device_sampler:
+                raise ValueError('prompt-lookup decoding with do_sample=True needs sampler="device": its loop picks the tokens on the device')
         if kv_cache_dtype is not None:
             _check_kv_dtype(kv_cache_dtype, self.dtype)
             if not use_cache:
@@ -1432,6 +1560,11 @@ class UllavaCoreForCausalLM(nn.Module):
         # mask loads, which sit on the latency chain of every decode step.
         no_pad = attention_mask is None or bool(attention_mask.ne(0).all())
         crit = [] if stopping_criteria is None else (list(stopping_criteria) if isinstance(stopping_criteria, (list, tuple)) else [stopping_criteria])
+        if lookup is not None:
+            if not seq.is_cuda:
+                raise RuntimeError("prompt-lookup decoding needs GPU tensors (no CPU path exists)")
+            return self._generate_prompt_lookup(seq, images, videos, max_new_tokens, lookup, sampling, temperature, top_k, top_p, eos_ids, crit,
+                                                kv_cache_dtype, output_hidden_states, return_dict_in_generate)
         # Greedy decoding keeps the whole step on the device: the tokens land in a pre-sized [B, L0 + max_new_tokens] buffer, the
         # argmax / pad-fill / EOS bookkeeping is ONE kernel (ops.greedy_step), and the host looks at the "rows still unfinished"
         # counters only every CHECK steps (every step when a stopping criterion needs the ids on the host anyway).  Steps that run past

@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaConfig
-from .modeling_core import BF16, Linear, UllavaCoreForCausalLM, _Holder, _check_kv_dtype, check_sampler
+from .modeling_core import BF16, Linear, UllavaCoreForCausalLM, _Holder, _check_kv_dtype, check_prompt_lookup, check_sampler
 from .sam import SamEngine, build_sam_holder
 
 
@@ -317,14 +317,25 @@ class UllavaForCausalLM(nn.Module):
 
     @torch.no_grad()
     def evaluate(self, images_sam, images, input_ids, raw_size_list, resize_list, max_new_tokens=32, temperature=0.2, top_p=None,
-                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None, sampler=None):
+                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None,
+                 max_matching_ngram_size=None, sampler=None):
         """reference ullava.py:335-434 -> (output_ids, pred_masks, pred_boxes).  kv_cache_dtype="fp8_e4m3": generate with an fp8 KV cache
         (which implies use_cache=True; see UllavaCoreForCausalLM.generate).  sampler="device": draw the tokens with the on-device sampler
-        (same ids under the same seed; see generate)."""
+        (same ids under the same seed; see generate).  prompt_lookup_num_tokens / max_matching_ngram_size: prompt-lookup speculative decoding
+        (which implies use_cache=True; batch 1; with temperature > 0 it needs sampler="device"; see generate) -- the [SEG] / [LOC] rows are
+        read from the hidden states of the accepted positions."""
         if kv_cache_dtype is not None:
             _check_kv_dtype(kv_cache_dtype, self.llm.dtype)
         if check_sampler(sampler) and no_repeat_ngram_size:
             raise ValueError('sampler="device" does not combine with `no_repeat_ngram_size` (use sampler=None)')
+        lookup = check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size)
+        if lookup is not None:
+            if no_repeat_ngram_size:
+                raise ValueError("prompt-lookup decoding does not combine with `no_repeat_ngram_size`")
+            if temperature > 0 and not check_sampler(sampler):
+                raise ValueError('prompt-lookup decoding with temperature > 0 needs sampler="device": its loop picks the tokens on the device')
+            if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
+                raise ValueError("prompt-lookup decoding takes a batch of one row")
         main = torch.cuda.current_stream()                          # SAM image encoder on the second stream, under the generation loop
         side = self._side_stream()
         side.wait_stream(main)
@@ -334,7 +345,10 @@ class UllavaForCausalLM(nn.Module):
                                     do_sample=True if temperature > 0 else False, temperature=temperature, output_hidden_states=True,
                                     return_dict_in_generate=True, no_repeat_ngram_size=no_repeat_ngram_size,
                                     stopping_criteria=stopping_criteria, keep_last_step_only=True, sampler=sampler,
-                                    **({} if kv_cache_dtype is None else dict(use_cache=True, kv_cache_dtype=kv_cache_dtype)))
+                                    **({} if kv_cache_dtype is None and lookup is None else dict(use_cache=True)),
+                                    **({} if kv_cache_dtype is None else dict(kv_cache_dtype=kv_cache_dtype)),
+                                    **({} if lookup is None else dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+                                                                      max_matching_ngram_size=max_matching_ngram_size)))
         output_ids = outputs.sequences
         last = outputs.hidden_states[-1][-1]                          # last step, last layer: [B, L-1, D]
         seg_token_mask = output_ids[:, 1:] == self.config.seg_token_idx

@@ -1178,6 +1178,39 @@ def sample_step(logits_last: torch.Tensor, noise: torch.Tensor, temperature: flo
               _p(eos_ids), n_eos, int(pad) if pad is not None else 0, int(pad is not None), _p(seq), seq.stride(0), int(pos), _p(alive), _stream())
 
 
+SPEC_MAX_DRAFT = 15         # ULL_SPEC_MAX_DRAFT: most draft tokens of one spec_step (16 rows: the few-query limit of the fp8-cache attention)
+
+
+def spec_step(logits: torch.Tensor, noise: Optional[torch.Tensor], temperature: float, top_k: Optional[int], top_p: Optional[float],
+              buf: torch.Tensor, n: int, d: int, n_max: int, eos_ids: Optional[torch.Tensor], num_tokens: int, max_ngram: int,
+              picks: torch.Tensor, record: torch.Tensor) -> None:
+    """One step of prompt-lookup speculative decoding at batch 1 in two launches (see ull_spec_step): logits [1 + d, V] of the forward over
+    buf[0, n-1 : n+d] (buf int64 [1, L]: n valid ids, then the d drafts); noise None picks every row's token as greedy_step does, else as
+    sample_step does from noise fp32 [1 + d, V].  The accepted drafts' tokens and the bonus token are written to buf[0, n:], cut at n_max
+    valid ids and after the first EOS id; the next step's drafts (`modeling_core.prompt_lookup_candidates` over the new valid ids, at most
+    num_tokens) follow them; record int32 [3] = (emitted, finished, next d).  picks: int32 [16] scratch."""
+    _chk(logits, "logits"); _chk(buf, "buf", torch.int64); _chk(picks, "picks", torch.int32); _chk(record, "record", torch.int32)
+    R, V = logits.shape
+    if R != 1 + d or logits.stride(1) != 1:
+        raise RuntimeError(f"u-llava_amd.spec_step: logits must be [1 + d = {1 + d}, V] with contiguous rows, got {tuple(logits.shape)}")
+    if buf.dim() != 2 or buf.shape[0] != 1 or buf.stride(1) != 1 or picks.numel() < 16 or record.numel() < 3 or not picks.is_contiguous() \
+            or not record.is_contiguous():
+        raise RuntimeError("u-llava_amd.spec_step: buf must be one contiguous row [1, L], picks int32 [16], record int32 [3]")
+    if noise is not None:
+        _chk(noise, "noise", torch.float32)
+        if tuple(noise.shape) != (R, V) or not noise.is_contiguous():
+            raise RuntimeError(f"u-llava_amd.spec_step: noise must be a contiguous fp32 [{R}, {V}] tensor, got {tuple(noise.shape)}")
+        if not temperature > 0:
+            raise ValueError(f"u-llava_amd.spec_step: temperature must be positive, got {temperature}")
+    n_eos = 0
+    if eos_ids is not None:
+        _chk(eos_ids, "eos_ids", torch.int64)
+        n_eos = eos_ids.numel()
+    _lib.call("ull_spec_step", _p(logits), DT_CODE[logits.dtype], logits.stride(0), V, _p(noise), float(temperature) if noise is not None else 1.0,
+              int(top_k) if top_k is not None and top_k > 0 else 0, float(top_p) if top_p is not None and top_p < 1.0 else 1.0, _p(buf),
+              buf.shape[1], int(n), int(d), int(n_max), _p(eos_ids), n_eos, int(num_tokens), int(max_ngram), _p(picks), _p(record), _stream())
+
+
 def video_pool(f: torch.Tensor, B: int, T: int, N: int, tok_pitch: Optional[int] = None, tok_off: int = 0) -> torch.Tensor:
     """f [B*T, tok_pitch, D]; patches are tokens tok_off..tok_off+N of every frame."""
     _chk(f, "f")
