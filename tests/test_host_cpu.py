@@ -20,6 +20,88 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name)
 
 
+_P, _I64, _I32, _F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
+_SNIPPET = """
+#define ULL_T_ONE 1
+#define ULL_T_NEG (-3)      /* a comment
+                             * over two lines */
+#define ULL_T_SHIFT ((2 << 1) | 1 << 20)
+#define ULL_T_FN(g) (((g) & 15) << 16)
+#define ULL_T_TEXT "no integer"
+typedef struct ull_linear {
+    const void* w; /* a pointer */
+    int64_t n, k, ldw;
+    int format;
+    float eps;
+} ull_linear;
+typedef struct ull_t_outer { // a nested struct by value
+    const void *a, *b;
+    ull_linear x, y;
+    int64_t window;
+} ull_t_outer;
+int ull_t_broken(const void* X, int64_t ldx, /* leading dimension, in elements */
+                 void* const* outs, const ull_linear* layers,
+                 float eps, int flags, const int64_t* strides, void* stream);
+int64_t ull_t_query(void);
+"""
+
+
+def test_header_parser_on_a_crafted_snippet():
+    """_lib.parse_header: the exact ctypes lists, fields, return types and macro values of a snippet that holds every form the header uses."""
+    h = pkg("_lib").parse_header(_SNIPPET)
+    assert h.defines == {"ULL_T_ONE": 1, "ULL_T_NEG": -3, "ULL_T_SHIFT": 4 | 1 << 20}      # function-like and non-integer macros are skipped
+    assert h.signatures == {"ull_t_broken": [_P, _I64, _P, _P, _F32, _I32, _P, _P], "ull_t_query": []}
+    assert h.restypes == {"ull_t_broken": _I32, "ull_t_query": _I64}
+    inner, outer = h.structs["ull_linear"], h.structs["ull_t_outer"]
+    assert list(h.structs) == ["ull_linear", "ull_t_outer"] and issubclass(inner, ctypes.Structure)
+    assert inner._fields_ == [("w", _P), ("n", _I64), ("k", _I64), ("ldw", _I64), ("format", _I32), ("eps", _F32)]
+    assert outer._fields_ == [("a", _P), ("b", _P), ("x", inner), ("y", inner), ("window", _I64)]
+    assert (ctypes.sizeof(inner), ctypes.sizeof(outer)) == (40, 104)
+
+
+@pytest.mark.parametrize("bad,names", [
+    ("int ull_t_f(const void* x, double y, void* stream);", "ull_t_f, parameter 2"),
+    ("int ull_t_g(unsigned int n);", "ull_t_g, parameter 1"),
+    ("int ull_t_h(int64_t);", "ull_t_h, parameter 1"),
+    ("typedef struct ull_t_s { int64_t n; double x; } ull_t_s;", "ull_t_s.x"),
+    ("typedef struct ull_t_o { ull_t_s inner; } ull_t_o;", "ull_t_o.inner"),
+    ("typedef struct ull_t_s { int64_t n; } ull_t_s;\nint ull_t_v(ull_t_s by_value);", "ull_t_v, parameter 1"),
+])
+def test_header_parser_refuses_a_type_it_does_not_know(bad, names):
+    """A parameter or field type outside int64_t / int / float / pointer / known struct raises and names the entry: never a guess."""
+    with pytest.raises(TypeError, match=re.escape(names)):
+        pkg("_lib").parse_header(bad)
+
+
+def test_binding_is_the_parsed_header():
+    """What _lib derives from the committed header: the struct sizes are the ones the typedefs imply with 8-byte alignment (ull_linear: 3 pointers
+    + 3 int64 + int (padded) + pointer + int64 = 72; a layer = its pointers and int64 + 4 x 72), a nested ull_linear is the Linear class itself
+    (ops.LayerStack tells the fields apart by it), the one int64_t query keeps its return type, and function-like macros are left out."""
+    L = pkg("_lib")
+    assert [ctypes.sizeof(c) for c in (L.Linear, L.LlamaLayer, L.ClipLayer, L.SamBlock)] == [72, 304, 320, 344]
+    assert L.Linear._fields_ == [("w", _P), ("w_tiled", _P), ("bias", _P), ("n", _I64), ("k", _I64), ("ldw", _I64), ("format", _I32), ("scales", _P),
+                                 ("lds", _I64)]
+    assert L.SamBlock._fields_[4:8] == [(n, L.Linear) for n in ("qkv", "proj", "lin1", "lin2")] and L.SamBlock._fields_[-1] == ("window", _I64)
+    assert [k for k, v in L.RESTYPES.items() if v is not _I32] == ["ull_gemm_streamk_ws_bytes"] and L.RESTYPES["ull_gemm_streamk_ws_bytes"] is _I64
+    assert (L.DEFINES["ULL_OK"], L.DEFINES["ULL_ERR_LDS"], L.DEFINES["ULL_EPI_ACT_RELU"], L.DEFINES["ULL_GEMM_TUNE_WAVES4"]) == (0, -4, 6, 1 << 22)
+    assert "ULL_GEMM_TUNE_GROUP_M" not in L.DEFINES and sorted(L.ERRORS) == [-4, -3, -2, -1]
+
+
+def test_header_holds_the_generated_fp16_section():
+    """The fp16 twins at the end of the header are exactly what tools/gen_header_f16.py derives from the bf16 prototypes above them."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_header_f16", os.path.join(ROOT, "tools", "gen_header_f16.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    header = open(os.path.join(ROOT, "include", "ullava_hip.h")).read()
+    section = gen.fp16_section(header)
+    assert header.count(gen.BEGIN) == header.count(gen.END) == 1
+    assert header[header.index(gen.BEGIN):header.index(gen.END) + len(gen.END)] == section
+    assert gen.regenerate(header) == header
+    twins = {name + "_f16" for name, _ in gen.fp16_twins(header)}
+    assert twins and twins == {n for n in pkg("_lib").SIGNATURES if n.endswith("_f16")} - {"ull_neck_layernorm2d_f32in_f16"}   # (fp16 only: declared by hand)
+
+
 def test_ops_refuse_cpu_tensors():
     ops = pkg("ops")
     with pytest.raises(RuntimeError, match="no CPU path"):

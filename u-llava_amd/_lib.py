@@ -3,173 +3,112 @@
 There is no fallback: if the library is missing or a symbol is absent this raises, and every op in
 `ops.py` goes through here.  The library is built in-tree by `__graft_entry__.build()` /
 `make -C u-llava_amd/csrc` so it travels with the repo snapshot.
+
+The header is the one definition of the ABI.  It is parsed once, at import: every prototype becomes an entry of `SIGNATURES` (with its return
+type in `RESTYPES`), the four `typedef struct` blocks become the ctypes classes below, and every `#define ULL_*` with an integer value lands in
+`DEFINES`.  The C sources include the same header, so the compiler checks each definition against its declaration.  To add an entry point,
+declare it in the header and define it in csrc/: nothing else needs a signature.
 """
+import ast
 import ctypes
 import os
+import re
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ULL_LIB_PATH", os.path.join(_HERE, "csrc", "libullava_hip.so"))   # override: kernel A/B experiments only
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ullava_hip.h")
 
-_i64, _i32, _f32, _ptr = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
-
-
-WF_ELEM, WF_FP8, WF_MXFP4 = 0, 1, 2      # ULL_WF_*: the weight format of a Linear / of a *_wq_bf16 entry
+_SCALARS = {"int64_t": ctypes.c_int64, "int": ctypes.c_int, "float": ctypes.c_float}
 
 
-# the structs of include/ullava_hip.h's coarse entries (one call = a whole stack of layers)
-class Linear(ctypes.Structure):
-    _fields_ = [("w", _ptr), ("w_tiled", _ptr), ("bias", _ptr), ("n", _i64), ("k", _i64), ("ldw", _i64), ("format", _i32), ("scales", _ptr), ("lds", _i64)]
+class Header(NamedTuple):
+    defines: dict       # macro name -> int
+    structs: dict       # typedef name -> ctypes.Structure subclass
+    signatures: dict    # entry point -> argtypes
+    restypes: dict      # entry point -> restype
 
 
-class LlamaLayer(ctypes.Structure):
-    _fields_ = [("ln1", _ptr), ("ln2", _ptr), ("qkv", Linear), ("o", Linear), ("gu", Linear), ("down", Linear)]
+def _int_macro(body: str):
+    """The value of a macro body made of integer literals, parentheses, `<<`, `|` and unary minus; None for anything else."""
+    def ev(n):
+        if isinstance(n, ast.Constant) and type(n.value) is int:
+            return n.value
+        if isinstance(n, ast.UnaryOp) and isinstance(n.op, ast.USub):
+            return -ev(n.operand)
+        if isinstance(n, ast.BinOp) and isinstance(n.op, (ast.LShift, ast.BitOr)):     # same precedence in C and in Python
+            a, b = ev(n.left), ev(n.right)
+            return a << b if isinstance(n.op, ast.LShift) else a | b
+        raise ValueError(body)
+    try:
+        return ev(ast.parse(body.strip(), mode="eval").body)
+    except (SyntaxError, ValueError):
+        return None
 
 
-class ClipLayer(ctypes.Structure):
-    _fields_ = [("ln1_w", _ptr), ("ln1_b", _ptr), ("ln2_w", _ptr), ("ln2_b", _ptr), ("qkv", Linear), ("out", Linear), ("fc1", Linear), ("fc2", Linear)]
+def _ctype(base: str, pointer: bool, structs: dict, where: str):
+    """int64_t / int / float, any pointer as void*, a known struct by value; anything else is an error, never a guess."""
+    if pointer:
+        return ctypes.c_void_p
+    words = [w for w in base.split() if w != "const"]
+    if len(words) == 1 and words[0] in _SCALARS:
+        return _SCALARS[words[0]]
+    if len(words) == 1 and words[0] in structs:
+        return structs[words[0]]
+    raise TypeError(f"u-llava_amd: {where}: no ctypes mapping for the C type `{base.strip()}`")
 
 
-class SamBlock(ctypes.Structure):
-    _fields_ = [("n1_w", _ptr), ("n1_b", _ptr), ("n2_w", _ptr), ("n2_b", _ptr), ("qkv", Linear), ("proj", Linear), ("lin1", Linear), ("lin2", Linear),
-                ("rel_pos_h", _ptr), ("rel_pos_w", _ptr), ("window", _i64)]
+def _declarators(decl: str, where: str):
+    """`const void *a, *b` / `int64_t n, k, ldw` / `const void* const* x` -> (base type, [(name, is pointer), ...])."""
+    first, *more = [p.strip() for p in decl.split(",")]
+    m = re.fullmatch(r"(.*?)(\w+)", first, flags=re.S)
+    if not m or not m.group(1).strip():
+        raise TypeError(f"u-llava_amd: {where}: cannot read the declaration `{decl.strip()}`")
+    names = [(m.group(2), "*" in m.group(1))]
+    for p in more:
+        if not re.fullmatch(r"\**\s*\w+", p):
+            raise TypeError(f"u-llava_amd: {where}: cannot read the declaration `{decl.strip()}`")
+        names.append((p.lstrip("* "), "*" in p))
+    return m.group(1).replace("*", " "), names
 
 
-# name -> argtypes (restype is int = ULL_OK / ULL_ERR_* unless listed in VALUE_RETURNING)
-SIGNATURES = {
-    "ull_gemm_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr],
-    "ull_gemm_streamk_ws_bytes": [],
-    "ull_gemm_qkv_rope_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i32, _ptr, _i64, _ptr],
-    "ull_rope_table_bf16": [_ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr],
-    "ull_sam_self_attn_heads_bf16": [_ptr, _ptr, _i64, _i64, _i32] + [_ptr] * 7 + [_ptr],
-    "ull_sam_out_ln_bf16": [_ptr, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, ctypes.POINTER(_ptr), ctypes.POINTER(_i32), _ptr],
-    "ull_sam_token_mlp_ln_bf16": [_ptr, _ptr, _i64, _i64, _i64] + [_ptr] * 6 + [_f32, _ptr, _ptr, ctypes.POINTER(_ptr), ctypes.POINTER(_i32), _ptr],
-    "ull_sam_small_mlps_bf16": [_ptr, _i64, _i64, ctypes.POINTER(_ptr), _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    "ull_sam_t2i_attention_bf16": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr],
-    "ull_sam_i2t_attention_ln_bf16": [_ptr] * 4 + [_i64] * 3 + [_ptr] * 4 + [_i32, _ptr, _ptr, _f32, _ptr, _ptr],
-    "ull_rmsnorm_bwd_bf16": [_ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _f32, _ptr],
-    "ull_swiglu_fwd_bf16": [_ptr, _ptr, _i64, _i64, _i32, _ptr],
-    "ull_swiglu_bwd_bf16": [_ptr, _ptr, _ptr, _i64, _i64, _i32, _ptr],
-    "ull_relu_mask_bf16": [_ptr, _ptr, _ptr, _i64, _ptr],
-    "ull_rope_bwd_inplace_bf16": [_ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr],
-    "ull_attention_bwd_bf16": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.POINTER(_i64), _ptr, _i64, _i64, _i64, _i64, _i64, _i32,
-                               _f32, _ptr, _ptr],
-    "ull_attention_bwd_mfma_bf16": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, ctypes.POINTER(_i64), _ptr, _i64, _i64,
-                                    _i64, _i64, _i64, _i32, _f32, _ptr, _ptr],
-    "ull_shifted_cross_entropy_bwd_bf16": [_ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr],
-    "ull_embed_splice_bwd_bf16": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_colsum_bf16": [_ptr, _i64, _i64, _i64, _ptr, _ptr],
-    "ull_transpose2d_bf16": [_ptr, _i64, _ptr, _i64, _i64, _i64, _ptr],
-    "ull_sum_slabs_bf16": [_ptr, _ptr, _i64, _i64, _f32, _ptr],
-    "ull_layernorm_bwd_bf16": [_ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _f32, _ptr],
-    "ull_layernorm2d_cl_bwd_bf16": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _f32, _i32, _ptr],
-    "ull_gelu_fwd_bf16": [_ptr, _ptr, _i64, _ptr],
-    "ull_gelu_bwd_bf16": [_ptr, _ptr, _ptr, _i64, _ptr],
-    "ull_mask_matmul_bwd_bf16": [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr],
-    "ull_mask_loss_sums_bwd_f32": [_ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr, _ptr],
-    "ull_box_losses_bwd_f32": [_ptr, _i32, _ptr, _i64, _ptr, _ptr, _ptr],
-    "ull_bilinear_bwd_f32": [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _ptr],
-    "ull_gemv_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_dropout_apply_bf16": [_ptr, _ptr, _ptr, _i64, _f32, _ptr],
-    "ull_gemm_skinny_bf16": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_gemv_rmsnorm_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_gemv_qkv_rope_append_bf16": [_ptr, _i64, _ptr, _f32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                                      _ptr],
-    "ull_rmsnorm_bf16": [_ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _f32, _ptr],
-    "ull_llama_prefill_layers_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _f32, _ptr,
-                                      _i64, _i64, _ptr, _ptr],
-    "ull_llama_decode_layers_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64,
-                                     _i64, _i64, _f32, _ptr, _ptr],
-    "ull_clip_layers_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _f32, _ptr, _i64, _i64, _ptr, _ptr],
-    "ull_sam_blocks_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _f32, _ptr, _i64, _i64, _ptr, _ptr],
-    "ull_shifted_cross_entropy_bf16": [_ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr],
-    "ull_layernorm_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, _f32, _ptr],
-    "ull_clip_embed_ln_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _f32, _ptr],
-    "ull_attention_bf16": [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _i64,
-                           _ptr, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _f32, _f32, _ptr, _ptr, _i64, _i64, _i32, _ptr, _ptr],
-    "ull_rope_inplace_bf16": [_ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr],
-    "ull_rope_append_bf16": [_ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr],
-    "ull_transpose_v_bf16": [_ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr],
-    "ull_sam_window_attention_bf16": [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _ptr, _ptr],
-    "ull_sam_global_attention_exact_bf16": [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _f32, _ptr,
-                                            _i64, _i64, _i64, _ptr],
-    "ull_interp_rows_linear_bf16": [_ptr, _ptr, _i64, _i64, _i64, _ptr],
-    "ull_im2col_bf16": [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr],
-    "ull_mm_spans": [_ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    "ull_greedy_step_bf16": [_ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i32, _ptr, _i64, _i64, _ptr, _ptr],
-    "ull_embed_splice_bf16": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr],
-    "ull_video_pool_bf16": [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr],
-    "ull_gather_rows_bf16": [_ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr],
-    "ull_add_rows_bf16": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
-    "ull_window_partition_bf16": [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr],
-    "ull_window_unpartition_add_bf16": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr],
-    "ull_sam_relpos_bf16": [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr],
-    "ull_layernorm2d_cl_bf16": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _f32, _i32, _ptr],
-    "ull_im2col3x3_bf16": [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr],
-    "ull_mask_matmul_bf16": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr],
-    "ull_bilinear_f32": [_ptr, _i32, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr],
-    "ull_patchify_bf16": [_ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr],
-    "ull_resample_u8": [_ptr, _i64, _i64, _i64, _i32, _i64, _ptr, _ptr, _i64, _ptr, _ptr],
-    "ull_u8_lut_chw": [_ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_mask_iou_counts": [_ptr, _ptr, _i64, _i64, _i32, _ptr, _ptr],
-    "ull_mask_loss_sums_f32": [_ptr, _ptr, _i64, _i64, _f32, _ptr, _ptr],
-    "ull_box_losses_f32": [_ptr, _i32, _ptr, _i64, _ptr, _ptr],
-    "ull_adamw_step_f32": [_ptr, _ptr, _ptr, _ptr, _i32, _ptr, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _ptr],
-    "ull_sumsq_f32": [_ptr, _i32, _i64, _ptr, _ptr],
-    "ull_sample_step": [_ptr, _i32, _i64, _i64, _i64, _ptr, _f32, _i64, _f32, _ptr, _ptr, _i64, _i64, _i32, _ptr, _i64, _i64, _ptr, _ptr],
-    "ull_spec_step": [_ptr, _i32, _i64, _i64, _ptr, _f32, _i64, _f32, _ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-}
+def parse_header(text: str) -> Header:
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    defines = {}
+    for name, body in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(ULL_\w+)[ \t]+(\S.*?)[ \t]*$", text, flags=re.M):   # `NAME(` = function-like: no match
+        value = _int_macro(body)
+        if value is not None:
+            defines[name] = value
+    structs = {}
+    for tag, body, name in re.findall(r"typedef\s+struct\s+(\w*)\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            base, names = _declarators(decl, name)
+            fields += [(n, _ctype(base, ptr, structs, f"{name}.{n}")) for n, ptr in names]
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+    signatures, restypes = {}, {}
+    for ret, name, params in re.findall(r"\b(int64_t|int)\s+(ull_\w+)\s*\(([^()]*)\)\s*;", text):
+        args = []
+        if params.split() != ["void"]:
+            for i, p in enumerate(params.split(",")):
+                where = f"{name}, parameter {i + 1}"
+                base, ((_, pointer),) = _declarators(p, where)
+                args.append(_ctype(base, pointer, {}, where))      # ({}: no struct travels by value in a call)
+        signatures[name], restypes[name] = args, _SCALARS[ret]
+    return Header(defines, structs, signatures, restypes)
 
-# every dtype-dependent entry point exists twice: ull_*_bf16 (bfloat16 build) and ull_*_f16 (IEEE binary16 build), same signature
-SIGNATURES.update({name[:-4] + "f16": args for name, args in list(SIGNATURES.items()) if name.endswith("_bf16")})
 
-# fp32 build of the inference path (csrc/f32.hip): the same signatures as the bf16 entries of the same name
-F32_TWINS = ['ull_gemm', 'ull_attention', 'ull_transpose_v', 'ull_transpose2d', 'ull_rmsnorm', 'ull_layernorm', 'ull_clip_embed_ln', 'ull_layernorm2d_cl', 'ull_rope_inplace', 'ull_rope_append', 'ull_im2col', 'ull_im2col3x3', 'ull_video_pool', 'ull_add_rows', 'ull_window_unpartition_add', 'ull_sam_relpos', 'ull_interp_rows_linear', 'ull_mask_matmul', 'ull_greedy_step', 'ull_shifted_cross_entropy']
-SIGNATURES.update({name + "_f32": SIGNATURES[name + "_bf16"] for name in F32_TWINS})
+_H = parse_header(open(HEADER_PATH).read())
+DEFINES, SIGNATURES, RESTYPES = _H.defines, _H.signatures, _H.restypes      # restype: int = ULL_OK / ULL_ERR_*; int64_t = a plain query's answer
 
-# fp8 (e4m3) weights and KV cache: bf16-only entry points (no fp16 twin)
-SIGNATURES.update({
-    "ull_quantize_rows_fp8_bf16": [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    "ull_dequantize_rows_fp8_bf16": [_ptr, _i64, _ptr, _i64, _i64, _ptr, _i32, _ptr],
-    "ull_attention_kv8_bf16": [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64,
-                               _i64, _f32, _ptr, _ptr],
-    "ull_kv8_quantize_bf16": [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr],
-    "ull_kv8_dequantize_bf16": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr],
-    "ull_llama_decode_layers_kv8_bf16": [_ptr, _i64] + [_ptr] * 16 + [_i64] * 7 + [_f32, _ptr, _ptr],
-})
+# the structs of the coarse entries (one call = a whole stack of layers)
+Linear, LlamaLayer, ClipLayer, SamBlock = (_H.structs[n] for n in ("ull_linear", "ull_llama_layer", "ull_clip_layer", "ull_sam_block"))
 
-# mxfp4 weights, and the decode-shape Linear entries on a quantized weight (wfmt, Q, ldq, scales, lds): bf16-only entry points (no fp16 twin)
-SIGNATURES.update({
-    "ull_quantize_rows_mxfp4_bf16": [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _i32, _ptr],
-    "ull_dequantize_rows_mxfp4_bf16": [_ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i32, _i32, _ptr],
-    "ull_gemv_wq_bf16": [_ptr, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_gemm_skinny_wq_bf16": [_ptr, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_gemv_rmsnorm_wq_bf16": [_ptr, _i64, _ptr, _f32, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr],
-    "ull_gemv_qkv_rope_append_wq_bf16": [_ptr, _i64, _ptr, _f32, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
-                                         _i64, _i64, _i64, _ptr],
-})
+WF_ELEM, WF_FP8, WF_MXFP4 = DEFINES["ULL_WF_ELEM"], DEFINES["ULL_WF_FP8"], DEFINES["ULL_WF_MXFP4"]   # the weight format of a Linear / of a *_wq_bf16 entry
 
-# fp8 activations on fp8 weights (W8A8 prefill Linear): bf16-only entry point (no fp16 twin)
-SIGNATURES["ull_gemm_a8w8_bf16"] = [_ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr]
-
-# fp8 activations on fp8 weights at decode shapes (W8A8 skinny Linear, fused RMSNorm + row quantization): bf16-only entry points (no fp16 twin)
-SIGNATURES["ull_gemm_skinny_a8w8_bf16"] = SIGNATURES["ull_gemm_a8w8_bf16"]
-SIGNATURES["ull_rmsnorm_quantize_rows_fp8_bf16"] = [_ptr, _i64, _ptr, _f32, _i64, _i64, _ptr, _i64, _ptr, _ptr]
-
-# fp8 Linears of the SAM image encoder (fused LayerNorm + row quantization, W8A8 Linear with bias / activation): bf16-only entry points (no fp16 twin)
-SIGNATURES["ull_layernorm_quantize_rows_fp8_bf16"] = [_ptr, _i64, _ptr, _ptr, _f32, _i64, _i64, _ptr, _i64, _ptr, _ptr]
-SIGNATURES["ull_gemm_a8w8_epi_bf16"] = [_ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr]
-
-# MXFP8 activations on MXFP4 weights (W4A8 prefill Linear): bf16-only entry points (no fp16 twin)
-SIGNATURES["ull_quantize_rows_mxfp8_bf16"] = [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr]
-SIGNATURES["ull_gemm_w4a8_bf16"] = [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr]
-
-# fp16-only entry points (no bf16 twin): the fp32 neck of an fp16 SAM encoder (image_encoder.py:117-124)
-SIGNATURES["ull_neck_layernorm2d_f32in_f16"] = [_ptr, _ptr, _f32, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr]
-
-VALUE_RETURNING = {"ull_gemm_streamk_ws_bytes": _i64}      # plain queries: the return value is the answer, not a status
-
-ERRORS = {-1: "ULL_ERR_ARG (null pointer / bad size)", -2: "ULL_ERR_SHAPE (alignment or shape constraint)",
-          -3: "ULL_ERR_LAUNCH (HIP launch failed)", -4: "ULL_ERR_LDS (does not fit the LDS budget)"}
+ERRORS = {DEFINES["ULL_ERR_ARG"]: "ULL_ERR_ARG (null pointer / bad size)", DEFINES["ULL_ERR_SHAPE"]: "ULL_ERR_SHAPE (alignment or shape constraint)",
+          DEFINES["ULL_ERR_LAUNCH"]: "ULL_ERR_LAUNCH (HIP launch failed)", DEFINES["ULL_ERR_LDS"]: "ULL_ERR_LDS (does not fit the LDS budget)"}
 
 _lib = None
 
@@ -187,7 +126,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
-        fn.restype = VALUE_RETURNING.get(name, ctypes.c_int)
+        fn.restype = RESTYPES[name]
     _lib = lib
     return lib
 
@@ -203,7 +142,7 @@ def call(name: str, *args):
 
 
 def query(name: str, *args):
-    """A VALUE_RETURNING entry point: returns its value."""
+    """An entry point whose return value is the answer, not a status (int64_t in the header): returns its value."""
     fn = getattr(load(), name, None)
     if fn is None or name not in SIGNATURES:
         raise RuntimeError(f"u-llava_amd: the library has no entry point `{name}` (no kernel build of this op for that element type)")

@@ -13,7 +13,6 @@
 // ull_rmsnorm_quantize_rows_fp8_bf16 is ull_quantize_rows_fp8_bf16(ull_rmsnorm_bf16(x)) in one launch, bit for bit: the operations of
 // rownorm_kernel<., 0> (norm.hip) and quantize_rows_fp8_kernel (gemv.hip) in their order, without the normed rows going to memory.
 #include "ull_common.h"
-#include "../../include/ullava_hip.h"
 
 namespace {
 

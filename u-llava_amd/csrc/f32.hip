@@ -13,15 +13,7 @@
 #include "ull_common.h"
 #include "select.h"
 
-#define ULL_EPI_BIAS 1
-#define ULL_EPI_ACT_MASK (3 << 1)
-#define ULL_EPI_ACT_QUICK_GELU (1 << 1)
-#define ULL_EPI_ACT_GELU (2 << 1)
-#define ULL_EPI_ACT_RELU (3 << 1)
-#define ULL_EPI_RESID 8
-#define ULL_EPI_SWIGLU 16
-#define ULL_EPI_W_TILED 64
-#define ULL_EPI_X_TILED 128
+#define ULL_EPI_ACT_MASK (3 << 1)    // the activation field of flags (the header names its three values, not the field)
 
 namespace {
 

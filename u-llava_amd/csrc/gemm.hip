@@ -32,17 +32,17 @@ constexpr int BUF_BYTES = 2 * TILE_BYTES;         // X tile + W tile
 constexpr int GEMM_LDS = 2 * BUF_BYTES;           // double buffered: 64 KiB -> 2 blocks / CU
 constexpr int GROUP_M = 8;
 
-// epilogue flag bits (mirrored in include/ullava_hip.h)
-constexpr int EPI_BIAS = 1, EPI_ACT_SHIFT = 1, EPI_ACT_MASK = 3 << 1;  // act: 0 none 1 quick_gelu 2 gelu(erf) 3 relu
-constexpr int EPI_RESID = 8, EPI_SWIGLU = 16, EPI_OUT_F32 = 32;
+// epilogue flag bits: short names for the header's ULL_EPI_*
+constexpr int EPI_BIAS = ULL_EPI_BIAS, EPI_ACT_SHIFT = 1, EPI_ACT_MASK = 3 << 1;  // act: 0 none 1 quick_gelu 2 gelu(erf) 3 relu
+constexpr int EPI_RESID = ULL_EPI_RESID, EPI_SWIGLU = ULL_EPI_SWIGLU, EPI_OUT_F32 = ULL_EPI_OUT_F32;
 // operand stored tile-major [rows/256][K/64][256][64] (every 256 x 64 K-tile = 32 contiguous KiB); big kernel only
-constexpr int EPI_W_TILED = 64, EPI_X_TILED = 128;
+constexpr int EPI_W_TILED = ULL_EPI_W_TILED, EPI_X_TILED = ULL_EPI_X_TILED;
 // The bias is added to the ROUNDED product: out = rnd(rnd(X W^T) + b).  at::linear fuses the bias (one rounding) only for 2-D and
 // contiguous n-D inputs; a non-contiguous 3-D input goes through matmul + add_ (two roundings).  On the path that is layer 0 of
 // SAM's TwoWayTransformer, whose `keys` are still the permuted NCHW view: cross_attn_token_to_image.{k,v}_proj and
 // cross_attn_image_to_token.q_proj (transformer.py:92-93,151-182).
-constexpr int EPI_BIAS_ROUNDED = 256;
-constexpr int ULL_W4_FORCE_STAGED = 512;          // tools / tests: the 4-wave kernel's LDS-staged epilogue where the direct one would run
+constexpr int EPI_BIAS_ROUNDED = ULL_EPI_BIAS_ROUNDED;
+constexpr int ULL_W4_FORCE_STAGED = ULL_GEMM_TUNE_STAGED_EPILOGUE;        // tools / tests: the 4-wave kernel's LDS-staged epilogue where the direct one would run
 
 struct GemmArgs {
     const elem_t* X; const elem_t* W; void* C;
@@ -2183,9 +2183,9 @@ static int gemm_dispatch(const void* X, int64_t ldx, const void* W, int64_t ldw,
     if (const int rc = gemm_device_state(&n_cu)) return rc;
     // per-call tuning overrides (tools/ only; 0 = the shipped policy)
     const int tune_group_m = (flags >> 16) & 15;
-    const bool force_small = flags & (1 << 20);
-    const bool force_waves8 = flags & (1 << 21);
-    const bool force_waves4 = (flags & (1 << 22)) && ldx < (1 << 21) && ldw < (1 << 21);
+    const bool force_small = flags & ULL_GEMM_TUNE_SMALL_KERNEL;
+    const bool force_waves8 = flags & ULL_GEMM_TUNE_WAVES8;
+    const bool force_waves4 = (flags & ULL_GEMM_TUNE_WAVES4) && ldx < (1 << 21) && ldw < (1 << 21);
     flags &= 0xffff;
     if ((flags & EPI_BIAS_ROUNDED) && (flags & EPI_SWIGLU)) return ULL_ERR_SHAPE;
     GemmArgs a;

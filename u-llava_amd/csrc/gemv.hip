@@ -9,12 +9,13 @@
 #include <type_traits>
 
 #include "ull_common.h"
-#include "../../include/ullava_hip.h"
 
 namespace {
 
-constexpr int EPI_BIAS = 1, EPI_ACT_SHIFT = 1, EPI_ACT_MASK = 3 << 1, EPI_RESID = 8, EPI_SWIGLU = 16, EPI_OUT_F32 = 32;
-constexpr int EPI_BIAS_ROUNDED = 256;     // bias added to the already rounded product (at::linear's unfused matmul + add_ path)
+// short names for the header's ULL_EPI_* (the activation field's shift and mask have no name there)
+constexpr int EPI_BIAS = ULL_EPI_BIAS, EPI_ACT_SHIFT = 1, EPI_ACT_MASK = 3 << 1, EPI_RESID = ULL_EPI_RESID, EPI_SWIGLU = ULL_EPI_SWIGLU,
+              EPI_OUT_F32 = ULL_EPI_OUT_F32;
+constexpr int EPI_BIAS_ROUNDED = ULL_EPI_BIAS_ROUNDED;     // bias added to the already rounded product (at::linear's unfused matmul + add_ path)
 constexpr int EPI_ROPE_APPEND = 1 << 20;  // (internal) q|k|v projection of a decode step: RoPE + KV-cache append in the epilogue, see RopeAppend
 constexpr int MAXM = 4;
 

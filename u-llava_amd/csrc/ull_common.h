@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// The C ABI: every entry point's prototype (so the compiler checks each definition against its declaration) and the ULL_DT_* / ULL_OK /
+// ULL_ERR_* / ULL_EPI_* / ULL_WF_* / limit constants, which are defined there and nowhere else.
+#include "../../include/ullava_hip.h"
+
 // ---- element type of the 16-bit tensors: a BUILD-TIME parameter of the translation unit --------------------------------------
 // Every dtype-dependent .hip file is compiled twice (Makefile): as-is for bfloat16 (entry points ull_*_bf16) and with
 // -DULL_ELEM_F16 for IEEE binary16 (entry points ull_*_f16; the reference's `--dtype fp16`, inference_ullava.py:26,164-168).
@@ -18,10 +22,7 @@ using f32x16_t = __attribute__((ext_vector_type(16))) float;  // 32x32 MFMA accu
 #define ULL_CAT_(a, b) a##b
 #define ULL_CAT(a, b) ULL_CAT_(a, b)
 
-// both formats are always available by name (the byte-level pre/post-processing and loss kernels take a dtype code)
-#define ULL_DT_F32 0
-#define ULL_DT_BF16 1
-#define ULL_DT_F16 2
+// both formats are always available by name (the byte-level pre/post-processing and loss kernels take a dtype code, ULL_DT_*)
 ULL_DEV float bf16_bits_to_f32(uint16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 ULL_DEV float f16_bits_to_f32(uint16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
 // f32 -> 16 bit goes through the native types so hipcc emits gfx950's v_cvt_pk_bf16_f32 / v_cvt_f16_f32 (IEEE round-to-nearest-even,
@@ -303,15 +304,6 @@ ULL_DEV float act_quick_gelu_e(float t) {
     return rnd(t * s);
 }
 
-// C-ABI status codes (mirrored in include/ullava_hip.h)
-#define ULL_OK 0
-#define ULL_ERR_ARG (-1)
-#define ULL_ERR_SHAPE (-2)
-#define ULL_ERR_LAUNCH (-3)
-#define ULL_ERR_LDS (-4)
-#define ULL_SAMPLE_MAX_V 36608    // longest row ull_sample_step stages in LDS (sampling.hip)
-#define ULL_SPEC_MAX_DRAFT 15      // most draft tokens of one ull_spec_step: 16 rows, the few-query limit of the fp8-cache attention
-
 // hipFuncSetAttribute is per device: one of these per kernel instantiation remembers which devices already have it
 // (a racing first call repeats an idempotent attribute call; nothing else is shared between host threads or streams).
 struct UllOncePerDevice {
@@ -338,12 +330,12 @@ static inline int ull_cu_count() {
     return n_cu[dev];
 }
 
-// The epilogue checks the three A8 Linear entries share: only ULL_EPI_RESID (8) | ULL_EPI_SWIGLU (16) | ULL_EPI_OUT_F32 (32) and a residual where
+// The epilogue checks the three A8 Linear entries share: only ULL_EPI_RESID | ULL_EPI_SWIGLU | ULL_EPI_OUT_F32 and a residual where
 // its flag is set (else ULL_ERR_ARG); SwiGLU on whole 32-row gate|up groups, output / residual rows no shorter than the output (else ULL_ERR_SHAPE).
 static inline int ull_a8_epilogue_check(int flags, const void* R, int64_t N, int64_t ldc, int64_t ldr) {
-    if ((flags & ~(8 | 16 | 32)) || ((flags & 8) && !R)) return ULL_ERR_ARG;
-    const int64_t n_out = (flags & 16) ? N / 2 : N;
-    if (((flags & 16) && (N & 31)) || ldc < n_out || ((flags & 8) && ldr < n_out)) return ULL_ERR_SHAPE;
+    if ((flags & ~(ULL_EPI_RESID | ULL_EPI_SWIGLU | ULL_EPI_OUT_F32)) || ((flags & ULL_EPI_RESID) && !R)) return ULL_ERR_ARG;
+    const int64_t n_out = (flags & ULL_EPI_SWIGLU) ? N / 2 : N;
+    if (((flags & ULL_EPI_SWIGLU) && (N & 31)) || ldc < n_out || ((flags & ULL_EPI_RESID) && ldr < n_out)) return ULL_ERR_SHAPE;
     return ULL_OK;
 }
 

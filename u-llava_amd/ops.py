@@ -18,9 +18,11 @@ F32 = torch.float32
 # entry-point suffix by element type: the two 16-bit builds of every dtype-dependent kernel, and the fp32 build of the inference path
 # (csrc/f32.hip: `--dtype fp32`, plain kernels on the exact fp32 matrix instruction -- a correctness path, no fused / tiled fast paths)
 _SFX = {BF16: "bf16", F16: "f16", F32: "f32"}
-DT_CODE = {torch.float32: 0, BF16: 1, F16: 2}               # ULL_DT_* of the dtype-coded entry points
-EPI_BIAS, EPI_QGELU, EPI_GELU, EPI_RELU, EPI_RESID, EPI_SWIGLU, EPI_F32 = 1, 1 << 1, 2 << 1, 3 << 1, 8, 16, 32
-EPI_BIAS_ROUNDED = 256
+_D = _lib.DEFINES                                           # every flag / code / limit below is the header's #define ULL_* of that name
+DT_CODE = {torch.float32: _D["ULL_DT_F32"], BF16: _D["ULL_DT_BF16"], F16: _D["ULL_DT_F16"]}      # the dtype-coded entry points
+EPI_BIAS, EPI_QGELU, EPI_GELU, EPI_RELU, EPI_RESID, EPI_SWIGLU, EPI_F32 = (
+    _D["ULL_EPI_" + n] for n in ("BIAS", "ACT_QUICK_GELU", "ACT_GELU", "ACT_RELU", "RESID", "SWIGLU", "OUT_F32"))
+EPI_BIAS_ROUNDED = _D["ULL_EPI_BIAS_ROUNDED"]
 ACTS = {None: 0, "quick_gelu": EPI_QGELU, "gelu": EPI_GELU, "relu": EPI_RELU}
 
 
@@ -88,7 +90,7 @@ def _rows(t: torch.Tensor):
     return t.numel() // t.shape[-1], t.stride(-2)
 
 
-EPI_W_TILED = 64
+EPI_W_TILED = _D["ULL_EPI_W_TILED"]
 _TILED = {}          # data_ptr of a row-major weight -> (weakref to it, its tile-major copy, the weight's ._version the copy was made from)
 
 
@@ -793,7 +795,7 @@ def rope_table(positions: torch.Tensor, inv_freq: torch.Tensor, dtype) -> tuple:
     return cs, sn
 
 
-GEMM_TUNE_WAVES8, GEMM_TUNE_WAVES4 = 1 << 21, 1 << 22     # ULL_GEMM_TUNE_*: force one form of the 256x256 kernel (tests / tools)
+GEMM_TUNE_WAVES8, GEMM_TUNE_WAVES4 = _D["ULL_GEMM_TUNE_WAVES8"], _D["ULL_GEMM_TUNE_WAVES4"]     # force one form of the 256x256 kernel (tests / tools)
 
 
 def linear_qkv_rope(x: torch.Tensor, w: torch.Tensor, rope_cos: torch.Tensor, rope_sin: torch.Tensor, rope_cols: int, head_dim: int,
@@ -1151,7 +1153,7 @@ def greedy_step(logits_last: torch.Tensor, unfinished: torch.Tensor, eos_ids: Op
               int(pad) if pad is not None else 0, int(pad is not None), _p(seq), seq.stride(0), int(pos), _p(alive), _stream())
 
 
-SAMPLE_MAX_V = 36608        # ULL_SAMPLE_MAX_V: the longest row sample_step stages in LDS
+SAMPLE_MAX_V = _D["ULL_SAMPLE_MAX_V"]        # the longest row sample_step stages in LDS
 
 
 def sample_step(logits_last: torch.Tensor, noise: torch.Tensor, temperature: float, top_k: Optional[int], top_p: Optional[float],
@@ -1178,7 +1180,7 @@ def sample_step(logits_last: torch.Tensor, noise: torch.Tensor, temperature: flo
               _p(eos_ids), n_eos, int(pad) if pad is not None else 0, int(pad is not None), _p(seq), seq.stride(0), int(pos), _p(alive), _stream())
 
 
-SPEC_MAX_DRAFT = 15         # ULL_SPEC_MAX_DRAFT: most draft tokens of one spec_step (16 rows: the few-query limit of the fp8-cache attention)
+SPEC_MAX_DRAFT = _D["ULL_SPEC_MAX_DRAFT"]         # most draft tokens of one spec_step (16 rows: the few-query limit of the fp8-cache attention)
 
 
 def spec_step(logits: torch.Tensor, noise: Optional[torch.Tensor], temperature: float, top_k: Optional[int], top_p: Optional[float],
