@@ -371,6 +371,16 @@ int ull_spec_step(const void* logits, int logits_dtype, int64_t row_stride, int6
                   float top_p, void* buf, int64_t buf_len, int64_t n, int64_t d, int64_t n_max, const void* eos, int64_t n_eos,
                   int64_t num_tokens, int64_t max_ngram, void* picks, void* record, void* stream);
 
+/* The log-probability of one chosen token per row (HF `output_scores` + `compute_transition_scores`; torch.log_softmax(logits.float(), -1)
+ * .gather(-1, ids)) in one launch, compiled once (logits_dtype ULL_DT_F32 0 / BF16 1 / F16 2).  logits: R rows of V entries, row_stride
+ * elements apart; ids int64, ids_stride elements apart; out fp32, out_stride elements apart.  Per row, in fp32:
+ * out[r*out_stride] = float(logit[r][id_r]) - max_r - log(sum_i exp(float(logit[r][i]) - max_r)).  A row whose id is outside [0, V)
+ * (-100 included) or whose row_mask[r] == 0 (int32 [R], or NULL: every row counts) gets 0.0f and none of its logits is read.  -inf entries
+ * add 0 to the sum; a row with a NaN, or whose maximum is -inf, gives NaN (as torch does).  Sums and maxima are taken in a fixed order: the
+ * same inputs give the same bits on every run.  Any R >= 0 (the blocks stride over the rows); V <= 2^31 - 1. */
+int ull_token_logprobs(const void* logits, int logits_dtype, int64_t row_stride, int64_t R, int64_t V, const void* ids, int64_t ids_stride,
+                       const void* row_mask, void* out, int64_t out_stride, void* stream);
+
 /* models/ullava_core.py:191,243-245,266-268: token-embedding lookup with the projected visual tokens spliced in after
  * the first start token (the torch.cat of the reference, done as one gather).  Image i's n_img_tok feature rows start
  * at row i*img_pitch + img_off of img_feat (pitch = patches + 1, off = 1 skips the CLS row without a copy).

@@ -177,6 +177,11 @@ class GenerateOutput(dict):
     __getattr__ = dict.__getitem__
 
 
+class ScoreOutput(dict):
+    """What score() returns: token_logprobs, sequence_logprob, num_tokens."""
+    __getattr__ = dict.__getitem__
+
+
 KV_CACHE_DTYPES = ("fp8_e4m3",)
 
 
@@ -1432,11 +1437,43 @@ class UllavaCoreForCausalLM(nn.Module):
                              "attention_mask": attention_mask, "images": images, "videos": videos})
         return model_inputs
 
+    @torch.no_grad()
+    def score(self, input_ids, attention_mask=None, images=None, videos=None, labels=None):
+        """The log-probability the model gives to tokens it is handed (ranking fixed answers, scoring a caption): one forward() without a
+        cache, then ops.token_logprobs per row on logits[b, :-1] against labels[b, 1:] as views -- no [B, L, V] copy, no fp32 logits.
+        Returns token_logprobs fp32 [B, L-1] (column t scores token t+1 given the positions <= t; exactly 0.0 where labels[:, t+1] == -100
+        or attention_mask[:, t+1] == 0), sequence_logprob [B] (the row's plain sum(-1)) and num_tokens int64 [B] (the scored positions).
+        labels defaults to input_ids; pass -100 over the prompt to score only the answer (and over image / video patch positions, whose
+        ids are placeholders)."""
+        if not input_ids.is_cuda:
+            raise RuntimeError("score() needs GPU tensors (no CPU path exists)")
+        labels = input_ids if labels is None else labels
+        logits = self.forward(input_ids=input_ids, attention_mask=attention_mask, images=images, videos=videos, use_cache=False,
+                              return_dict=True).logits
+        B, L = logits.shape[:2]
+        if labels.dim() != 2 or tuple(labels.shape) != (B, L) or labels.dtype != torch.int64:
+            raise ValueError(f"score(): labels must be int64 [{B}, {L}] (one per position of the forward), got {labels.dtype} {tuple(labels.shape)}")
+        keep = None
+        if attention_mask is not None:
+            if tuple(attention_mask.shape) != (B, L):
+                raise ValueError(f"score(): attention_mask must be [{B}, {L}], got {tuple(attention_mask.shape)}")
+            keep = attention_mask[:, 1:].ne(0).to(torch.int32).contiguous()
+        lp = torch.zeros(B, max(L - 1, 0), dtype=torch.float32, device=logits.device)
+        if L > 1:
+            for b in range(B):
+                ops.token_logprobs(logits[b, :-1], labels[b, 1:], None if keep is None else keep[b], out=lp[b])
+        scored = (labels[:, 1:] >= 0) & (labels[:, 1:] < logits.shape[-1])
+        if keep is not None:
+            scored = scored & keep.bool()
+        return ScoreOutput(token_logprobs=lp, sequence_logprob=lp.sum(-1), num_tokens=scored.sum(-1))
+
     def _generate_prompt_lookup(self, seq, images, videos, max_new_tokens, lookup, sampling, temperature, top_k, top_p, eos_ids, crit,
-                                kv_cache_dtype, output_hidden_states, return_dict_in_generate):
+                                kv_cache_dtype, output_hidden_states, return_dict_in_generate, output_logprobs=False):
         """generate()'s loop under prompt_lookup_num_tokens (batch 1, KV cache, arguments already checked).  The ids live in one device
         buffer: n valid ids, then the d drafts of the next step.  A step is one forward over buf[n-1 : n+d] and ops.spec_step, which emits,
-        drafts again and leaves (emitted, finished, d') for the one host read of the step -- the next forward's length depends on it."""
+        drafts again and leaves (emitted, finished, d') for the one host read of the step -- the next forward's length depends on it.
+        output_logprobs: after the step, its 1 + d verify rows are scored against buf[0, n : n+1+d] into columns n-L0 ... of a buffer with
+        buf's k columns of slack; only the first `emitted` are valid, the next step overwrites the rest, and the result is cut at n."""
         k, max_ngram = lookup
         L0 = seq.shape[1]
         n_max = L0 + max_new_tokens
@@ -1445,6 +1482,7 @@ class UllavaCoreForCausalLM(nn.Module):
         buf[:, :L0] = seq
         picks = torch.empty(16, dtype=torch.int32, device=dev)
         record = torch.empty(3, dtype=torch.int32, device=dev)
+        lp = torch.zeros(max_new_tokens + k, dtype=torch.float32, device=dev) if output_logprobs else None
         self._cache_headroom = max_new_tokens + k + 1            # (the cache forward() creates for the prefill)
         cache = None
         n, d = L0, 0
@@ -1462,6 +1500,9 @@ class UllavaCoreForCausalLM(nn.Module):
             # torch's noise, one row per verified position, drawn in one call per step
             noise = torch.empty(logits.shape, dtype=torch.float32, device=dev).exponential_() if sampling else None
             ops.spec_step(logits, noise, temperature, top_k, top_p, buf, n, d, n_max, eos_ids, k, max_ngram, picks, record)
+            if lp is not None:
+                # rows 0 .. emitted-1 hold the emitted tokens (a row past them is scored against whatever id sits there: never returned)
+                ops.token_logprobs(logits, buf[0, n:n + 1 + d], out=lp[n - L0:n - L0 + 1 + d])
             emitted, finished, d = record.tolist()               # the step's device -> host read
             n += emitted
             cache.truncate(n - 1)                                # the rejected drafts' positions (and the states of the token not yet fed)
@@ -1473,14 +1514,17 @@ class UllavaCoreForCausalLM(nn.Module):
         hidden = None
         if output_hidden_states:
             hidden = ((torch.cat(cache.last_hidden, dim=1),),) if cache is not None else ()
-        return GenerateOutput(sequences=seq, hidden_states=hidden)
+        res = GenerateOutput(sequences=seq, hidden_states=hidden)
+        if lp is not None:
+            res["logprobs"] = lp[:n - L0].unsqueeze(0).clone()
+        return res
 
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, videos=None, attention_mask=None, max_new_tokens=32, do_sample=False,
                  temperature=1.0, top_p=None, top_k=50, num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, eos_token_id=None,
                  pad_token_id=None, output_hidden_states=False, return_dict_in_generate=False, use_cache=None,
                  keep_last_step_only=False, kv_cache_dtype=None, sampler=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None,
-                 **kwargs):
+                 output_logprobs=False, **kwargs):
         """Token-by-token decoding with HF GenerationMixin's greedy / sampling semantics (the reference inherits `generate`):
         every step goes through `prepare_inputs_for_generation` (position_ids = cumsum(attention_mask) - 1, so left-padded batches
         get the reference's RoPE positions); `eos_token_id` defaults to `config.eos_token_id` (int or list); rows that have emitted
@@ -1506,7 +1550,13 @@ class UllavaCoreForCausalLM(nn.Module):
         where two candidates are almost tied the ids can differ from the plain loop's.  Batch 1, use_cache=True, no padding, no
         `no_repeat_ngram_size`; sampling needs sampler="device".  The host reads a three-int record every step.  Stopping criteria are
         called once per step on the valid ids, so a criterion can fire up to k tokens later than in the plain loop (HF's assisted decoding
-        behaves the same way)."""
+        behaves the same way).
+        output_logprobs=True (opt-in; needs return_dict_in_generate=True, a ValueError otherwise, as HF asks for scores): the result carries
+        `logprobs`, fp32 [B, n_new] with n_new = sequences.shape[1] - input_ids.shape[1].  Entry [b, j] is the log-probability of the emitted
+        token sequences[b, L0 + j] under softmax of the RAW last-position logits of the step that produced it: before temperature, top-k,
+        top-p and the n-gram ban, so it says how likely the model itself held the token, whatever the sampling settings (HF's
+        `output_logits`, not `output_scores`).  A row that had finished before the step holds a pad-fill token there and gets exactly 0.0;
+        a row's EOS token itself gets its real log-probability.  One launch per step (ops.token_logprobs) in every loop; GPU tensors only."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not used by the reference callers (num_beams=1)")
         if kwargs:
@@ -1514,6 +1564,8 @@ class UllavaCoreForCausalLM(nn.Module):
             # swallowed (a silently ignored `repetition_penalty` changes the ids)
             raise TypeError(f"generate() got unsupported keyword arguments {sorted(kwargs)} (supported: greedy / sampling with temperature, "
                             "top_k, top_p, no_repeat_ngram_size, stopping_criteria, eos_token_id, pad_token_id, max_new_tokens)")
+        if output_logprobs and not return_dict_in_generate:
+            raise ValueError("`output_logprobs=True` needs `return_dict_in_generate=True`: the log-probabilities travel in the returned dict")
         ngram = int(no_repeat_ngram_size) if no_repeat_ngram_size else 0
         if ngram < 0:
             raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer, but is {no_repeat_ngram_size}")
@@ -1564,7 +1616,7 @@ class UllavaCoreForCausalLM(nn.Module):
             if not seq.is_cuda:
                 raise RuntimeError("prompt-lookup decoding needs GPU tensors (no CPU path exists)")
             return self._generate_prompt_lookup(seq, images, videos, max_new_tokens, lookup, sampling, temperature, top_k, top_p, eos_ids, crit,
-                                                kv_cache_dtype, output_hidden_states, return_dict_in_generate)
+                                                kv_cache_dtype, output_hidden_states, return_dict_in_generate, output_logprobs)
         # Greedy decoding keeps the whole step on the device: the tokens land in a pre-sized [B, L0 + max_new_tokens] buffer, the
         # argmax / pad-fill / EOS bookkeeping is ONE kernel (ops.greedy_step), and the host looks at the "rows still unfinished"
         # counters only every CHECK steps (every step when a stopping criterion needs the ids on the host anyway).  Steps that run past
@@ -1572,6 +1624,8 @@ class UllavaCoreForCausalLM(nn.Module):
         # sampler="device": the same loop with ops.sample_step in place of ops.greedy_step.
         if device_sampler and sampling and not seq.is_cuda:
             raise RuntimeError('sampler="device" needs GPU tensors (no CPU path exists)')
+        if output_logprobs and not seq.is_cuda:
+            raise RuntimeError("output_logprobs needs GPU tensors (no CPU path exists)")
         fused = (not sampling or device_sampler) and ngram == 0 and seq.is_cuda
         L0 = seq.shape[1]
         CHECK = 1 if crit else 8
@@ -1580,8 +1634,13 @@ class UllavaCoreForCausalLM(nn.Module):
             buf[:, :L0] = seq
             live = torch.ones(B, dtype=torch.int32, device=seq.device)
             alive = torch.zeros(max_new_tokens, dtype=torch.int32, device=seq.device)
+            if output_logprobs:
+                # the step kernels update `live` in place and the score needs it as it stood BEFORE the step: a snapshot per step
+                lp = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=seq.device)
+                live_before = torch.empty_like(live)
         else:
             unfinished = torch.ones(B, dtype=torch.bool, device=seq.device)
+            lp_cols = []
         n_done = 0                                              # tokens appended so far
         stop_at = None                                          # fused: number of tokens after which every row had finished
         for step in range(max_new_tokens):
@@ -1613,6 +1672,8 @@ class UllavaCoreForCausalLM(nn.Module):
                     else:
                         steps_hidden.append(out.hidden_states)
             if fused:
+                if output_logprobs:
+                    live_before.copy_(live)
                 if sampling:
                     last = out.logits[:, -1]
                     # torch's noise, drawn as torch.multinomial draws it: the generator moves as it does on the host path
@@ -1620,6 +1681,8 @@ class UllavaCoreForCausalLM(nn.Module):
                     ops.sample_step(last, noise, temperature, top_k, top_p, live, eos_ids, pad, buf, L0 + step, alive[step:step + 1])
                 else:
                     ops.greedy_step(out.logits[:, -1], live, eos_ids, pad, buf, L0 + step, alive[step:step + 1])
+                if output_logprobs:
+                    ops.token_logprobs(out.logits[:, -1], buf[:, L0 + step], live_before, out=lp[:, step])
                 n_done = step + 1
                 if crit:
                     if any(bool(torch.as_tensor(c(buf[:, :L0 + n_done], None)).all()) for c in crit):
@@ -1632,6 +1695,8 @@ class UllavaCoreForCausalLM(nn.Module):
                         break
                 continue
             logits = out.logits[:, -1].float()
+            if output_logprobs and ngram > 0 and logits.dtype == out.logits.dtype:
+                logits = logits.clone()                         # an fp32 model: .float() is a view, and the ban must not reach the scored logits
             if ngram > 0:
                 # HF NoRepeatNGramLogitsProcessor (logits processors run before the sampling warpers): tokens that would complete an
                 # n-gram already present in the row (prompt included) get -inf
@@ -1645,6 +1710,9 @@ class UllavaCoreForCausalLM(nn.Module):
             if pad is not None:
                 nxt = torch.where(unfinished.unsqueeze(1), nxt, torch.full_like(nxt, pad))      # finished rows: pad fill
             seq = torch.cat([seq, nxt], dim=1)
+            if output_logprobs:
+                # the raw logits (before the n-gram ban and the warpers), masked by `unfinished` as it stood before this step
+                lp_cols.append(ops.token_logprobs(out.logits[:, -1], nxt.squeeze(1), unfinished.to(torch.int32)))
             if eos_ids is not None:
                 unfinished = unfinished & ~torch.isin(nxt.squeeze(1), eos_ids)
                 if not bool(unfinished.any()):
@@ -1669,5 +1737,10 @@ class UllavaCoreForCausalLM(nn.Module):
             # same tensor the no-cache path returns at its last step: last-layer states of ALL positions fed so far, joined once
             steps_hidden = [(torch.cat(cache.last_hidden, dim=1),)]
         if return_dict_in_generate:
-            return GenerateOutput(sequences=seq, hidden_states=tuple(steps_hidden) if output_hidden_states else None)
+            res = GenerateOutput(sequences=seq, hidden_states=tuple(steps_hidden) if output_hidden_states else None)
+            if output_logprobs:
+                # fused: the columns of the steps that ran past the end go as their ids went
+                res["logprobs"] = lp[:, :n_tok].clone() if fused else (
+                    torch.stack(lp_cols, dim=1) if lp_cols else torch.zeros(B, 0, dtype=torch.float32, device=seq.device))
+            return res
         return seq

@@ -318,12 +318,14 @@ class UllavaForCausalLM(nn.Module):
     @torch.no_grad()
     def evaluate(self, images_sam, images, input_ids, raw_size_list, resize_list, max_new_tokens=32, temperature=0.2, top_p=None,
                  num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None,
-                 max_matching_ngram_size=None, sampler=None):
+                 max_matching_ngram_size=None, output_logprobs=False, sampler=None):
         """reference ullava.py:335-434 -> (output_ids, pred_masks, pred_boxes).  kv_cache_dtype="fp8_e4m3": generate with an fp8 KV cache
         (which implies use_cache=True; see UllavaCoreForCausalLM.generate).  sampler="device": draw the tokens with the on-device sampler
         (same ids under the same seed; see generate).  prompt_lookup_num_tokens / max_matching_ngram_size: prompt-lookup speculative decoding
         (which implies use_cache=True; batch 1; with temperature > 0 it needs sampler="device"; see generate) -- the [SEG] / [LOC] rows are
-        read from the hidden states of the accepted positions."""
+        read from the hidden states of the accepted positions.  output_logprobs=True: the return grows to (output_ids, pred_masks, pred_boxes,
+        logprobs), logprobs fp32 [B, n_new] as generate(output_logprobs=True) gives them (raw distribution; 0.0 after a row's EOS) -- the
+        number to drop an unsure [SEG] / [LOC] by."""
         if kv_cache_dtype is not None:
             _check_kv_dtype(kv_cache_dtype, self.llm.dtype)
         if check_sampler(sampler) and no_repeat_ngram_size:
@@ -345,6 +347,7 @@ class UllavaForCausalLM(nn.Module):
                                     do_sample=True if temperature > 0 else False, temperature=temperature, output_hidden_states=True,
                                     return_dict_in_generate=True, no_repeat_ngram_size=no_repeat_ngram_size,
                                     stopping_criteria=stopping_criteria, keep_last_step_only=True, sampler=sampler,
+                                    **(dict(output_logprobs=True) if output_logprobs else {}),
                                     **({} if kv_cache_dtype is None and lookup is None else dict(use_cache=True)),
                                     **({} if kv_cache_dtype is None else dict(kv_cache_dtype=kv_cache_dtype)),
                                     **({} if lookup is None else dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens,
@@ -360,4 +363,10 @@ class UllavaForCausalLM(nn.Module):
         image_embeddings.record_stream(main)
         pred_masks = self._decode(image_embeddings, pred_embeddings, resize_list, raw_size_list)
         pred_boxes = [self._run_mlp(self.det_decoder, e) if e.shape[0] else e.new_empty(0, 4) for e in pred_loc_embeddings]
+        if output_logprobs:
+            return output_ids, pred_masks, pred_boxes, outputs.logprobs
         return output_ids, pred_masks, pred_boxes
+
+    def score(self, input_ids, attention_mask=None, images=None, videos=None, labels=None):
+        """UllavaCoreForCausalLM.score of the language model (see there)."""
+        return self.llm.score(input_ids, attention_mask=attention_mask, images=images, videos=videos, labels=labels)

@@ -1213,6 +1213,36 @@ def spec_step(logits: torch.Tensor, noise: Optional[torch.Tensor], temperature: 
               buf.shape[1], int(n), int(d), int(n_max), _p(eos_ids), n_eos, int(num_tokens), int(max_ngram), _p(picks), _p(record), _stream())
 
 
+def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, row_mask: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """log_softmax(logits.float(), -1)[r, ids[r]] of every row in one launch (see ull_token_logprobs), fp32 [R].  logits [R, V] bf16 / fp16 /
+    fp32, rows may be strided (`out.logits[:, -1]`); ids int64 [R] with any element stride (a column `buf[:, pos]` of the generate buffer);
+    row_mask int32 [R] contiguous or None.  A row whose id is outside [0, V) (-100 included) or whose row_mask is 0 gets exactly 0.0.
+    out: fp32 [R] with any element stride (a column of a [B, n] buffer), returned."""
+    _chk(logits, "logits")
+    if logits.dim() != 2:
+        raise RuntimeError(f"u-llava_amd.token_logprobs: logits must be [R, V], got {tuple(logits.shape)}")
+    R, V = logits.shape
+    if not ids.is_cuda:
+        raise RuntimeError("u-llava_amd: `ids` must live on the GPU (no CPU path exists)")
+    if ids.dtype != torch.int64 or tuple(ids.shape) != (R,):
+        raise RuntimeError(f"u-llava_amd.token_logprobs: ids must be torch.int64 [{R}], got {ids.dtype} {tuple(ids.shape)}")
+    if row_mask is not None:
+        _chk(row_mask, "row_mask", torch.int32)
+        if tuple(row_mask.shape) != (R,):
+            raise RuntimeError(f"u-llava_amd.token_logprobs: row_mask must be int32 [{R}], got {tuple(row_mask.shape)}")
+    if out is None:
+        out = torch.empty(R, device=logits.device, dtype=F32)
+    elif not out.is_cuda or out.dtype != F32 or tuple(out.shape) != (R,):
+        raise RuntimeError(f"u-llava_amd.token_logprobs: out must be a GPU torch.float32 [{R}] tensor, got {out.dtype} {tuple(out.shape)}")
+    if V == 0 or any(t.dim() and t.stride(0) < 0 for t in (logits, ids, out)):
+        raise RuntimeError("u-llava_amd.token_logprobs: empty rows / negative strides are not supported")
+    if R:
+        _lib.call("ull_token_logprobs", _p(logits), DT_CODE[logits.dtype], logits.stride(0), R, V, _p(ids), ids.stride(0), _p(row_mask), _p(out),
+                  out.stride(0) if R > 1 else 1, _stream())
+    return out
+
+
 def video_pool(f: torch.Tensor, B: int, T: int, N: int, tok_pitch: Optional[int] = None, tok_off: int = 0) -> torch.Tensor:
     """f [B*T, tok_pitch, D]; patches are tokens tok_off..tok_off+N of every frame."""
     _chk(f, "f")
