@@ -1,0 +1,321 @@
+"""Decoding for UllavaCoreForCausalLM.generate(): the HF rules restated on the host (sampling warpers, n-gram ban, prompt-lookup draft), every
+refusal of generate()'s / evaluate()'s arguments in one function, and the three decode loops -- host per-step, fused on the device, prompt-lookup
+-- over what they share (`Decoding`: the step's forward, the stopping test, the result).  The loops take the model; no model class is imported."""
+from typing import Optional
+
+import torch
+
+from . import ops
+from .kv_cache import _check_kv_dtype
+
+
+class GenerateOutput(dict):
+    __getattr__ = dict.__getitem__
+
+
+def no_repeat_ngram_banned_tokens(rows, ngram_size: int):
+    """transformers' NoRepeatNGramLogitsProcessor rule (generation/logits_process.py `_calc_banned_ngram_tokens`; reference
+    models/ullava.py:360 forwards `no_repeat_ngram_size` to HF generate): for every row (list of ids so far, prompt included), the tokens
+    that followed an earlier occurrence of the row's last ngram_size - 1 tokens.  Host-side integer bookkeeping, like HF's."""
+    out = []
+    for toks in rows:
+        cur = len(toks)
+        if ngram_size <= 0 or cur + 1 < ngram_size:
+            out.append([])
+            continue
+        prefix = tuple(toks[cur + 1 - ngram_size:cur])
+        banned = []
+        for i in range(cur - ngram_size + 1):
+            if tuple(toks[i:i + ngram_size - 1]) == prefix:
+                banned.append(toks[i + ngram_size - 1])
+        out.append(banned)
+    return out
+
+
+def prompt_lookup_candidates(row, num_tokens: int, max_ngram: int, eos_ids, limit: int):
+    """The draft of prompt-lookup decoding (transformers generation/candidate_generator.py, PromptLookupCandidateGenerator: what HF
+    `generate(prompt_lookup_num_tokens=, max_matching_ngram_size=)` proposes), restated on a plain list; the reference of the device lookup in
+    ops.spec_step.  row: the ids so far, prompt included.  For n = min(max_ngram, len(row) - 1) down to 1: the earliest window equal to the
+    row's trailing n ids whose continuation is non-empty wins; the continuation is the next min(num_tokens, limit) ids, cut at the end of the
+    row and before the first id in eos_ids (what is left may be empty, and is the draft all the same).  No window at any n: no draft.
+    limit = max_new_tokens - tokens generated so far - 1: a step never proposes more than it may emit."""
+    row = list(row)
+    L = len(row)
+    want = min(int(num_tokens), int(limit))
+    if want <= 0:
+        return []
+    eos = set() if eos_ids is None else {int(e) for e in eos_ids}
+    for n in range(min(int(max_ngram), L - 1), 0, -1):
+        tail = row[L - n:]
+        for s in range(L - n):                                   # s + n < L: the continuation has at least one id
+            if row[s:s + n] == tail:
+                out = []
+                for tok in row[s + n:min(s + n + want, L)]:
+                    if tok in eos:
+                        break
+                    out.append(tok)
+                return out
+    return []
+
+
+def check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size):
+    """generate()'s `prompt_lookup_num_tokens` / `max_matching_ngram_size` -> (k, n-gram size), or None when the feature is off."""
+    if prompt_lookup_num_tokens is None:
+        if max_matching_ngram_size is not None:
+            raise ValueError("`max_matching_ngram_size` is an option of prompt-lookup decoding: it needs `prompt_lookup_num_tokens`")
+        return None
+    k = int(prompt_lookup_num_tokens)
+    if k != prompt_lookup_num_tokens or not 1 <= k <= ops.SPEC_MAX_DRAFT:
+        raise ValueError(f"`prompt_lookup_num_tokens` has to be an integer in 1..{ops.SPEC_MAX_DRAFT} (a verify step takes at most "
+                         f"{ops.SPEC_MAX_DRAFT + 1} new tokens), but is {prompt_lookup_num_tokens}")
+    g = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
+    if (max_matching_ngram_size is not None and g != max_matching_ngram_size) or g < 1:
+        raise ValueError(f"`max_matching_ngram_size` has to be an integer >= 1, but is {max_matching_ngram_size}")
+    return k, g
+
+
+def sampling_probs(logits: torch.Tensor, temperature: float, top_k: Optional[int] = 50, top_p: Optional[float] = None) -> torch.Tensor:
+    """The distribution HF `GenerationMixin._sample` draws from, in its own arithmetic and order (transformers generation/logits_process.py:
+    TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper on fp32 scores, then softmax): the reference's callers pass `temperature`
+    (and optionally `top_p`) and inherit `top_k = 50` from GenerationConfig's defaults (models/ullava.py:350-361, inference_ullava_core.py:73-80).
+    One `torch.multinomial(probs, 1)` per step on these probabilities consumes the RNG exactly as HF does, so a seeded run draws HF's tokens
+    from the same logits.  Integer / fp32 bookkeeping on [B, V] scores (the logits themselves come from the HIP lm_head)."""
+    scores = logits.float()
+    if temperature is not None and temperature != 1.0:
+        scores = scores / temperature
+    if top_k is not None and top_k > 0:
+        k = min(int(top_k), scores.size(-1))
+        scores = scores.masked_fill(scores < torch.topk(scores, k)[0][..., -1, None], float("-inf"))
+    if top_p is not None and top_p < 1.0:
+        sorted_logits, sorted_indices = torch.sort(scores, descending=False)
+        cumulative = sorted_logits.softmax(dim=-1).cumsum(dim=-1)
+        remove = cumulative <= (1 - top_p)
+        remove[..., -1:] = 0                                     # min_tokens_to_keep = 1
+        scores = scores.masked_fill(remove.scatter(1, sorted_indices, remove), float("-inf"))
+    return torch.softmax(scores, dim=-1)
+
+
+def check_sampler(sampler) -> bool:
+    """generate()'s `sampler`: None / "host" = torch's sampling path, "device" = ops.sample_step in the fused loop (True)."""
+    if sampler not in (None, "host", "device"):
+        raise ValueError(f'unknown sampler {sampler!r} (None / "host": the torch path; "device": one HIP launch per token)')
+    return sampler == "device"
+
+
+def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temperature=1.0, num_beams=1, no_repeat_ngram_size=None,
+                        use_cache=None, kv_cache_dtype=None, sampler=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None,
+                        output_logprobs=False, return_dict_in_generate=False, unknown=None, dtype=None, vocab_size=None, config_use_cache=None):
+    """Every refusal of generate()'s arguments that needs no device work, in generate()'s order; evaluate() calls it too, before it starts
+    the SAM encoder on the side stream.  No model is needed: what the model decides comes in as plain values, each read only when the
+    option it belongs to is set -- `dtype` with kv_cache_dtype, `vocab_size` with sampler="device" (None: the caller does not know it
+    and leaves that one refusal to generate(), which always passes it), `config_use_cache` where use_cache is None.  `unknown`: generate()'s
+    **kwargs.  -> (n-gram size or 0, tokens are sampled, on the device, use_cache with the config's default filled in, (k, n-gram size) or None)"""
+    if num_beams != 1:
+        raise NotImplementedError("beam search is not used by the reference callers (num_beams=1)")
+    if unknown:
+        # HF generate() validates its model kwargs and raises on unknown ones; options this loop does not implement must not be
+        # swallowed (a silently ignored `repetition_penalty` changes the ids)
+        raise TypeError(f"generate() got unsupported keyword arguments {sorted(unknown)} (supported: greedy / sampling with temperature, "
+                        "top_k, top_p, no_repeat_ngram_size, stopping_criteria, eos_token_id, pad_token_id, max_new_tokens)")
+    if output_logprobs and not return_dict_in_generate:
+        raise ValueError("`output_logprobs=True` needs `return_dict_in_generate=True`: the log-probabilities travel in the returned dict")
+    ngram = int(no_repeat_ngram_size) if no_repeat_ngram_size else 0
+    if ngram < 0:
+        raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer, but is {no_repeat_ngram_size}")
+    sampling = bool(do_sample and temperature and temperature > 0)
+    device_sampler = check_sampler(sampler)
+    if device_sampler and ngram:
+        raise ValueError('sampler="device" does not combine with `no_repeat_ngram_size`: the n-gram ban is host-side list work '
+                         '(use sampler=None)')
+    if device_sampler and sampling and vocab_size is not None and vocab_size > ops.SAMPLE_MAX_V:
+        raise ValueError(f'sampler="device" stages a row of logits in LDS: vocab_size {vocab_size} is above its limit of '
+                         f"{ops.SAMPLE_MAX_V} (use sampler=None)")
+    use_cache = config_use_cache if use_cache is None else use_cache
+    lookup = check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size)
+    if lookup is not None:
+        if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ValueError("prompt-lookup decoding takes a batch of one row (as HF's assisted decoding does), got "
+                             f"{None if input_ids is None else tuple(input_ids.shape)}")
+        if not use_cache:
+            raise ValueError("prompt-lookup decoding needs use_cache=True: a verify step runs over a filled KV cache")
+        if ngram:
+            raise ValueError("prompt-lookup decoding does not combine with `no_repeat_ngram_size`: the n-gram ban is host-side list work")
+        if attention_mask is not None and not bool(attention_mask.ne(0).all()):
+            raise ValueError("prompt-lookup decoding does not take a padded attention mask (one unpadded row)")
+        if sampling and not device_sampler:
+            raise ValueError('prompt-lookup decoding with do_sample=True needs sampler="device": its loop picks the tokens on the device')
+    if kv_cache_dtype is not None:
+        _check_kv_dtype(kv_cache_dtype, dtype)
+        if not use_cache:
+            raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r} needs use_cache=True: without a KV cache there is nothing to quantize")
+    for on, what in ((lookup is not None, "prompt-lookup decoding"), (device_sampler and sampling, 'sampler="device"'), (output_logprobs, "output_logprobs")):
+        if on and input_ids is not None and not input_ids.is_cuda:
+            raise RuntimeError(f"{what} needs GPU tensors (no CPU path exists)")
+    return ngram, sampling, device_sampler, use_cache, lookup
+
+
+class Decoding:
+    """One generate() call as its loop sees it: the model, the inputs beside the ids, the KV cache generate() made (None: use_cache off),
+    how a token is picked, when to stop, what to return -- and the hidden states collected where there is no cache."""
+
+    def __init__(self, model, images, videos, attention_mask, no_pad, cache, max_new_tokens, sampling, temperature, top_k, top_p, eos_ids, pad,
+                 crit, output_hidden_states, keep_last_step_only, output_logprobs):
+        self.model, self.images, self.videos, self.attention_mask, self.no_pad, self.cache = model, images, videos, attention_mask, no_pad, cache
+        self.sampling, self.temperature, self.top_k, self.top_p = sampling, temperature, top_k, top_p
+        self.max_new_tokens, self.eos_ids, self.pad, self.crit = max_new_tokens, eos_ids, pad, crit
+        self.output_hidden_states, self.keep_last_step_only, self.output_logprobs = output_hidden_states, keep_last_step_only, output_logprobs
+        self.steps_hidden = []
+
+    def forward(self, seq, step: int):
+        """The forward of decode step `step` over the ids so far, through prepare_inputs_for_generation.  With a cache:
+        step 0 is the prefill that fills it, later steps feed one token and vision does not run again.  Without one (the reference's
+        released checkpoints: use_cache=False) every step re-runs the multimodal prefill, and its hidden states are kept when asked for."""
+        m = self.attention_mask
+        mask = None if self.no_pad else torch.cat([m, m.new_ones(seq.shape[0], seq.shape[1] - m.shape[1])], dim=1)
+        inputs = self.model.prepare_inputs_for_generation(input_ids=seq, attention_mask=mask, images=self.images, videos=self.videos,
+                                                          past_key_values=self.cache, use_cache=self.cache is not None)
+        if self.cache is not None:
+            if step > 0:
+                inputs["images"] = inputs["videos"] = None
+            return self.model.forward(**inputs)
+        out = self.model.forward(**inputs, output_hidden_states=self.output_hidden_states)
+        if self.output_hidden_states:
+            if self.keep_last_step_only:
+                self.steps_hidden.clear()                        # evaluate() only reads hidden_states[-1] (the last step)
+            self.steps_hidden.append(out.hidden_states)
+        return out
+
+    def stopped(self, ids) -> bool:
+        """whether a stopping criterion fires on the ids so far (each criterion reads them on the host)."""
+        return any(bool(torch.as_tensor(c(ids, None)).all()) for c in self.crit)
+
+    def result(self, seq, logprobs, return_dict: bool):
+        """what generate() returns.  hidden_states with a cache: the tensor the no-cache path returns at its last step -- last-layer states of
+        ALL positions fed so far, joined once; without one: every step's (the last step's alone under keep_last_step_only)."""
+        if not return_dict:
+            return seq
+        hidden = None
+        if self.output_hidden_states:
+            hidden = tuple(self.steps_hidden) if self.cache is None else ((torch.cat(self.cache.last_hidden, dim=1),),) if self.cache else ()
+        return GenerateOutput(sequences=seq, hidden_states=hidden, **({} if logprobs is None else dict(logprobs=logprobs)))
+
+
+def host_loop(d: Decoding, seq, ngram: int, probs=sampling_probs):
+    """One token per step, picked by torch on the host's schedule: the n-gram ban, torch.multinomial on sampling_probs (or argmax), pad fill
+    and EOS bookkeeping per row, one host read per step.  probs: generate() hands in the `sampling_probs` of its own module, so that a
+    wrapper installed there (the tests record the logits that way) is the one that runs.  -> (ids, logprobs or None)"""
+    B = seq.shape[0]
+    unfinished = torch.ones(B, dtype=torch.bool, device=seq.device)
+    lp_cols = []
+    for step in range(d.max_new_tokens):
+        out = d.forward(seq, step)
+        logits = out.logits[:, -1].float()
+        if d.output_logprobs and ngram > 0 and logits.dtype == out.logits.dtype:
+            logits = logits.clone()                              # an fp32 model: .float() is a view, and the ban must not reach the scored logits
+        if ngram > 0:
+            # HF NoRepeatNGramLogitsProcessor (logits processors run before the sampling warpers): tokens that would complete an
+            # n-gram already present in the row (prompt included) get -inf
+            for b_, banned in enumerate(no_repeat_ngram_banned_tokens(seq.tolist(), ngram)):
+                if banned:
+                    logits[b_, torch.as_tensor(banned, device=logits.device)] = float("-inf")
+        nxt = torch.multinomial(probs(logits, d.temperature, d.top_k, d.top_p), 1) if d.sampling else logits.argmax(-1, keepdim=True)
+        if d.pad is not None:
+            nxt = torch.where(unfinished.unsqueeze(1), nxt, torch.full_like(nxt, d.pad))      # finished rows: pad fill
+        seq = torch.cat([seq, nxt], dim=1)
+        if d.output_logprobs:
+            # the raw logits (before the n-gram ban and the warpers), masked by `unfinished` as it stood before this step
+            lp_cols.append(ops.token_logprobs(out.logits[:, -1], nxt.squeeze(1), unfinished.to(torch.int32)))
+        if d.eos_ids is not None:
+            unfinished = unfinished & ~torch.isin(nxt.squeeze(1), d.eos_ids)
+            if not bool(unfinished.any()):
+                break
+        if d.stopped(seq):
+            break
+    if not d.output_logprobs:
+        return seq, None
+    return seq, torch.stack(lp_cols, dim=1) if lp_cols else torch.zeros(B, 0, dtype=torch.float32, device=seq.device)
+
+
+def fused_loop(d: Decoding, seq):
+    """Greedy decoding, or sampler="device", with the whole step on the device: the tokens land in a pre-sized [B, L0 + max_new_tokens]
+    buffer, the pick / pad-fill / EOS bookkeeping is ONE kernel (ops.greedy_step / ops.sample_step), and the host looks at the "rows still
+    unfinished" counters only every `check` steps (every step when a stopping criterion needs the ids on the host anyway).  Steps that run
+    past the point where every row had finished only produce pad tokens; ids, cache and hidden states are trimmed to what a per-step check
+    returns.  -> (ids, logprobs or None)"""
+    B, L0 = seq.shape
+    n_max, dev = d.max_new_tokens, seq.device
+    buf = torch.empty(B, L0 + n_max, dtype=torch.int64, device=dev)
+    buf[:, :L0] = seq
+    live = torch.ones(B, dtype=torch.int32, device=dev)
+    alive = torch.zeros(n_max, dtype=torch.int32, device=dev)
+    lp = live_before = None
+    if d.output_logprobs:
+        # the step kernels update `live` in place and the score needs it as it stood BEFORE the step: a snapshot per step
+        lp = torch.zeros(B, n_max, dtype=torch.float32, device=dev)
+        live_before = torch.empty_like(live)
+    check = 1 if d.crit else 8
+    n_done = n_tok = 0                                           # tokens appended so far; tokens after which every row had finished
+    for step in range(n_max):
+        last = d.forward(buf[:, :L0 + step], step).logits[:, -1]
+        if lp is not None:
+            live_before.copy_(live)
+        if d.sampling:
+            # torch's noise, drawn as torch.multinomial draws it: the generator moves as it does on the host path
+            noise = torch.empty(last.shape, dtype=torch.float32, device=last.device).exponential_()
+            ops.sample_step(last, noise, d.temperature, d.top_k, d.top_p, live, d.eos_ids, d.pad, buf, L0 + step, alive[step:step + 1])
+        else:
+            ops.greedy_step(last, live, d.eos_ids, d.pad, buf, L0 + step, alive[step:step + 1])
+        if lp is not None:
+            ops.token_logprobs(last, buf[:, L0 + step], live_before, out=lp[:, step])
+        n_done = n_tok = step + 1
+        if d.stopped(buf[:, :L0 + n_done]):
+            break
+        if d.eos_ids is not None and (n_done % check == 0 or n_done == n_max):
+            dead = (alive[:n_done].cpu() == 0).nonzero()         # the only device -> host read: every `check` steps
+            if dead.numel():
+                n_tok = int(dead[0]) + 1
+                break
+    if n_tok < n_done:
+        # steps that ran after every row had finished (at most check - 1): drop their states so that the outputs equal a per-step check's
+        if d.cache is not None:
+            d.cache.truncate(L0 + n_tok - 1)
+        if d.steps_hidden and d.keep_last_step_only:
+            # the kept step saw L0 + n_done - 1 positions; the reference's last step L0 + n_tok - 1
+            d.steps_hidden = [tuple(h[:, :L0 + n_tok - 1] for h in d.steps_hidden[0])]
+        else:
+            del d.steps_hidden[n_tok:]
+    # (the log-probability columns of the steps that ran past the end go as their ids went)
+    return buf[:, :L0 + n_tok].contiguous(), None if lp is None else lp[:, :n_tok].clone()
+
+
+def prompt_lookup_loop(d: Decoding, seq, lookup):
+    """generate()'s loop under prompt_lookup_num_tokens (batch 1, KV cache, arguments already checked).  The ids live in one device
+    buffer: n valid ids, then the dn drafts of the next step.  A step is one forward over buf[n-1 : n+dn] and ops.spec_step, which emits,
+    drafts again and leaves (emitted, finished, dn') for the one host read of the step -- the next forward's length depends on it.
+    output_logprobs: after the step, its 1 + dn verify rows are scored against buf[0, n : n+1+dn] into columns n-L0 ... of a buffer with
+    buf's k columns of slack; only the first `emitted` are valid, the next step overwrites the rest, and the result is cut at n.  -> (ids, logprobs or None)"""
+    k, max_ngram = lookup
+    L0 = seq.shape[1]
+    n_max, dev = L0 + d.max_new_tokens, seq.device
+    buf = torch.empty(1, n_max + k, dtype=torch.int64, device=dev)
+    buf[:, :L0] = seq
+    picks = torch.empty(16, dtype=torch.int32, device=dev)
+    record = torch.empty(3, dtype=torch.int32, device=dev)
+    lp = torch.zeros(d.max_new_tokens + k, dtype=torch.float32, device=dev) if d.output_logprobs else None
+    n, dn = L0, 0
+    while n < n_max:
+        # the prefill through the step forward every loop shares; then the last valid id and the drafts over the filled cache
+        out = d.forward(buf[:, :L0], 0) if not d.cache else d.model.forward(input_ids=buf[:, n - 1:n + dn], past_key_values=d.cache, use_cache=True)
+        logits = out.logits[0, -(1 + dn):]
+        # torch's noise, one row per verified position, drawn in one call per step
+        noise = torch.empty(logits.shape, dtype=torch.float32, device=dev).exponential_() if d.sampling else None
+        ops.spec_step(logits, noise, d.temperature, d.top_k, d.top_p, buf, n, dn, n_max, d.eos_ids, k, max_ngram, picks, record)
+        if lp is not None:
+            # rows 0 .. emitted-1 hold the emitted tokens (a row past them is scored against whatever id sits there: never returned)
+            ops.token_logprobs(logits, buf[0, n:n + 1 + dn], out=lp[n - L0:n - L0 + 1 + dn])
+        emitted, finished, dn = record.tolist()                  # the step's device -> host read
+        n += emitted
+        d.cache.truncate(n - 1)                                  # the rejected drafts' positions (and the states of the token not yet fed)
+        if finished or d.stopped(buf[:, :n]):
+            break
+    return buf[:, :n].contiguous(), None if lp is None else lp[:n - L0].unsqueeze(0).clone()

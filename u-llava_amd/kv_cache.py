@@ -1,0 +1,225 @@
+"""The KV cache of KV-cached LLaMA decoding: per-layer K and V^T in the attention kernels' layouts, in the model dtype or as fp8 (e4m3)
+codes with per-position scales, the HF views of it, and the two steps of a decode layer over an fp8 cache."""
+import torch
+
+from . import ops
+
+BF16 = torch.bfloat16
+
+KV_CACHE_DTYPES = ("fp8_e4m3",)
+
+# positions past the ones it is handed that a cache gets when forward() has to size it on its own (use_cache=True without a cache, an HF
+# tuple as past_key_values): room for a caller-driven decode loop.  generate() sizes its cache from max_new_tokens.
+DEFAULT_HEADROOM = 512
+
+
+def _check_kv_dtype(kv_dtype, dtype):
+    """the cache formats there are: None (the model dtype) or "fp8_e4m3" (bf16 models only)."""
+    if kv_dtype is None:
+        return
+    if not isinstance(kv_dtype, str) or kv_dtype not in KV_CACHE_DTYPES:
+        raise ValueError(f"unknown KV cache dtype {kv_dtype!r} (supported: None, {', '.join(repr(d) for d in KV_CACHE_DTYPES)})")
+    if dtype != BF16:
+        raise NotImplementedError(f"an fp8 KV cache needs a bf16 model, not {dtype}: the dequantized values of a position with a small amax "
+                                  "can fall below the fp16 range, and the fp32 build has no fp8 kernels")
+
+
+class KVCache:
+    """Per-layer K [B,H,Smax,hd] (post-RoPE) and V^T [B,H,hd,Smax] in the attention kernel's key-permuted layout, plus the
+    last-layer hidden states of every position seen so far (what `evaluate()` reads for [SEG]/[LOC] rows).  Truthy once a
+    prefill has been stored, like a non-empty HF past_key_values tuple."""
+
+    kv_dtype = None                        # "fp8_e4m3": see below
+
+    def __init__(self, n_layers, B, H, hd, smax, device, dtype=BF16, kv_dtype=None):
+        """kv_dtype="fp8_e4m3" (bf16 models only): the cache holds e4m3fn codes in the same two layouts (k8 [B,H,Smax,hd], vt8 [B,H,hd,Smax])
+        plus one fp32 power-of-two scale per (batch, head, position) for the K row (k_scale, by key) and the V column (vt_scale, by V^T slot),
+        with the fp8-weight rule (DESIGN f2).  Attention reads the K / V of its own forward call at full bf16 precision and the earlier
+        positions dequantized; the new positions are quantized into the cache.  So the model equals, bit for bit, the same model with a bf16
+        cache holding the dequantized positions (`dequantized()`).  A decode step's new keys pass through a bf16 staging window (k_stage /
+        vt_stage: 128 positions, one window shared by all layers) on their way into the cache."""
+        _check_kv_dtype(kv_dtype, dtype)
+        self.smax = ((smax + 63) // 64) * 64
+        self.length = 0
+        self.last_hidden = []
+        if kv_dtype is None:
+            self.k = [torch.empty(B, H, self.smax, hd, device=device, dtype=dtype) for _ in range(n_layers)]
+            self.vt = [torch.zeros(B, H, hd, self.smax, device=device, dtype=dtype) for _ in range(n_layers)]
+            return
+        self.kv_dtype = kv_dtype
+        self.k = self.vt = None
+        u8, f32 = torch.uint8, torch.float32
+        self.k8 = [torch.zeros(B, H, self.smax, hd, device=device, dtype=u8) for _ in range(n_layers)]
+        self.vt8 = [torch.zeros(B, H, hd, self.smax, device=device, dtype=u8) for _ in range(n_layers)]
+        self.k_scale = [torch.zeros(B, H, self.smax, device=device, dtype=f32) for _ in range(n_layers)]
+        self.vt_scale = [torch.zeros(B, H, self.smax, device=device, dtype=f32) for _ in range(n_layers)]
+        self.k_stage = torch.zeros(B, H, 128, hd, device=device, dtype=dtype)
+        self.vt_stage = torch.zeros(B, H, hd, 128, device=device, dtype=dtype)
+        self._kv8_ptrs = None              # (data_ptr key, ctypes arrays) of c_ptrs()
+
+    def kv8_layer(self, li):
+        """(k8, vt8, k_scale, vt_scale) of layer li of an fp8 cache."""
+        return self.k8[li], self.vt8[li], self.k_scale[li], self.vt_scale[li]
+
+    def bf16_scratch(self):
+        """(fp8 cache) a bf16 K [B,H,Smax,hd] / V^T [B,H,hd,Smax] pair (V^T zero-filled) for the calls the fp8 decode attention does not take
+        (<= 64 keys, > 16 new tokens): each layer is dequantized into it, runs the bf16 path, and its new positions are quantized back.
+        Made per forward call and shared by its layers; the cache itself keeps no bf16 buffer but the staging window."""
+        B, H, smax, hd = self.k8[0].shape
+        dev = self.k8[0].device
+        return torch.empty(B, H, smax, hd, device=dev, dtype=BF16), torch.zeros(B, H, hd, smax, device=dev, dtype=BF16)
+
+    def _kv8_decode_buffers(self, li: int, past: int, fewq: bool, scr: list):
+        """(K, V^T, pitch, position of the first new key) the decode appenders of layer li write into, on an fp8 cache: the staging window
+        (first new key at past mod 64) where the fp8 decode attention takes the call (fewq), else the call's bf16 scratch (scr, made on first
+        use) with positions < past dequantized."""
+        if fewq:
+            return self.k_stage, self.vt_stage, 128, past & 63
+        if not scr:
+            scr.append(self.bf16_scratch())
+        kc, vtc = scr[0]
+        ops.dequantize_kv(*self.kv8_layer(li), past, k_out=kc, vt_out=vtc)
+        return kc, vtc, self.smax, past
+
+    def _kv8_attention(self, q, q_strides, li: int, att, B: int, H: int, S: int, past: int, hd: int, key_mask, fewq: bool, scr: list):
+        """the decode attention of layer li over an fp8 cache, after _kv8_decode_buffers' appenders; the new positions end in the cache."""
+        if fewq:
+            ops.attention_kv8(q, q_strides, self.k_stage, self.vt_stage, *self.kv8_layer(li), att, (S * H * hd, hd, H * hd), B, H, S, past + S,
+                              hd, key_mask, hd ** -0.5)
+            return
+        kc, vtc = scr[0]
+        smax = self.smax
+        ops.attention(q, kc, vtc, att, B, H, S, past + S, hd, q_strides, (H * smax * hd, smax * hd, hd), (S * H * hd, hd, H * hd), key_mask,
+                      causal=True, scale_mode=1, scale=hd ** -0.5)
+        ops.quantize_kv(kc, (H * smax * hd, smax * hd, hd), vtc, (H * hd * smax, hd * smax, smax), *self.kv8_layer(li), past, S, src_p0=past,
+                        v_image=True)
+
+    def nbytes(self) -> int:
+        """bytes of every device buffer the cache keeps (fp8: codes, scales and the staging window; bf16: K and V^T)."""
+        ts = (self.k + self.vt) if self.kv_dtype is None else (self.k8 + self.vt8 + self.k_scale + self.vt_scale + [self.k_stage, self.vt_stage])
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def dequantized(self) -> "KVCache":
+        """The bf16 twin of an fp8 cache: a bf16 KVCache whose positions < length hold dequant(codes) = float(code) * 2^s (same length,
+        same last_hidden).  A bf16 cache returns itself."""
+        if self.kv_dtype is None:
+            return self
+        B, H, smax, hd = self.k8[0].shape
+        c = KVCache(len(self), B, H, hd, smax, self.k8[0].device, BF16)
+        if self.length:
+            for li in range(len(self)):
+                ops.dequantize_kv(*self.kv8_layer(li), self.length, k_out=c.k[li], vt_out=c.vt[li])
+        c.length = self.length
+        c.last_hidden = list(self.last_hidden)
+        return c
+
+    def __bool__(self):
+        return self.length > 0
+
+    def truncate(self, n: int) -> None:
+        """Give back the positions >= n (speculative decoding: the rejected drafts of a verify step): `length` becomes n and `last_hidden`
+        holds exactly the first n positions (the last call's tensor is sliced).  bf16 and fp8 caches alike: the buffers keep the rejected
+        positions' K rows, V^T columns, codes and scales as stale finite data, which no kernel reads -- attention, append and quantization
+        address keys below `length` plus the call's own new positions, and the next call overwrites them."""
+        n = int(n)
+        if n < 0 or n > self.length:
+            raise ValueError(f"KVCache.truncate({n}): the cache holds {self.length} positions")
+        self.length = n
+        have = sum(h.shape[1] for h in self.last_hidden)
+        while self.last_hidden and have > n:
+            last = self.last_hidden[-1]
+            if have - last.shape[1] >= n:
+                self.last_hidden.pop()
+                have -= last.shape[1]
+            else:
+                self.last_hidden[-1] = last[:, :last.shape[1] - (have - n)]
+                have = n
+
+    def c_ptrs(self):
+        """(void* array of the K buffers, void* array of the V^T buffers) for the coarse decode entry; built once per cache.
+        fp8 cache: (k8, vt8, k_scale, vt_scale void* arrays, k_stage, vt_stage) for the *_kv8 entries, rebuilt whenever a list entry has
+        been rebound since (the arrays hold raw pointers)."""
+        if self.kv_dtype is not None:
+            import ctypes
+            lists = (self.k8, self.vt8, self.k_scale, self.vt_scale)
+            key = tuple(t.data_ptr() for l in lists for t in l)
+            if self._kv8_ptrs is None or self._kv8_ptrs[0] != key:
+                arrs = tuple((ctypes.c_void_p * len(l))(*[t.data_ptr() for t in l]) for l in lists)
+                self._kv8_ptrs = (key, arrs + (self.k_stage, self.vt_stage))
+            return self._kv8_ptrs[1]
+        if getattr(self, "_c_ptrs", None) is None:
+            import ctypes
+            self._c_ptrs = ((ctypes.c_void_p * len(self.k))(*[t.data_ptr() for t in self.k]), (ctypes.c_void_p * len(self.vt))(*[t.data_ptr() for t in self.vt]))
+        return self._c_ptrs
+
+    def __len__(self):
+        return len(self.k) if self.kv_dtype is None else len(self.k8)
+
+    def to_legacy_cache(self):
+        """The HF view of this cache (what `outputs.past_key_values` is in the reference under transformers 4.29.1, models/ullava_core.py:349-355):
+        a tuple of per-layer (key, value) pairs, each [B, H, length, hd] with post-RoPE keys.  Pure data movement (a slice of the K buffer;
+        the key-permuted V^T image gathered back into natural key order and transposed); `KVCache.from_hf` is the inverse.  An fp8 cache
+        hands out its dequantized positions: it builds its bf16 twin (`dequantized()`, every layer at once) first, a transient allocation of
+        about twice the fp8 cache's size; `__getitem__` dequantizes one layer only."""
+        if self.kv_dtype is not None:
+            return self.dequantized().to_legacy_cache()
+        n = self.length
+        idx = ops.vt_unpermute_index(self.smax).to(self.k[0].device)[:n]
+        return tuple((k[:, :, :n].contiguous(), vt[..., idx].transpose(-1, -2).contiguous()) for k, vt in zip(self.k, self.vt))
+
+    def __iter__(self):
+        return iter(self.to_legacy_cache())
+
+    def __getitem__(self, i):
+        """layer i's (key, value) pair -- so that code written against a tuple of pairs (`past_key_values[0][0].shape[2]`, the idiom of
+        4.29-era callers) reads this object too.  An fp8 cache dequantizes the layer."""
+        if self.kv_dtype is not None:
+            B, H, smax, hd = self.k8[i].shape
+            k = torch.empty(B, H, max(self.length, 1), hd, device=self.k8[i].device, dtype=BF16)
+            vt = torch.zeros(B, H, hd, smax, device=self.k8[i].device, dtype=BF16)
+            if self.length:
+                ops.dequantize_kv(*self.kv8_layer(i), self.length, k_out=k, vt_out=vt)
+            idx = ops.vt_unpermute_index(smax).to(vt.device)[:self.length]
+            return k[:, :, :self.length], vt[..., idx].transpose(-1, -2)
+        n = self.length
+        idx = ops.vt_unpermute_index(self.smax).to(self.k[i].device)[:n]
+        return self.k[i][:, :, :n], self.vt[i][..., idx].transpose(-1, -2)
+
+    @classmethod
+    def from_hf(cls, past, headroom: int = DEFAULT_HEADROOM, kv_dtype=None):
+        """A caller-supplied HF `past_key_values` -> KVCache (reference models/ullava_core.py:279-292 takes `past_key_values:
+        Optional[List[torch.FloatTensor]]`): the legacy tuple of per-layer (key, value) pairs, each [B, H, S, hd] with post-RoPE keys, or a
+        transformers Cache object exposing `key_cache` / `value_cache` lists (or `.layers[i].keys / .values`).  Keys are copied into the
+        K buffers, values go through `ull_transpose_v` into the permuted V^T layout; `last_hidden` starts empty (hidden states of the
+        cached positions are not part of an HF cache).  kv_dtype="fp8_e4m3": the keys and values are quantized into an fp8 cache."""
+        if hasattr(past, "key_cache") and hasattr(past, "value_cache"):
+            pairs = list(zip(past.key_cache, past.value_cache))
+        elif hasattr(past, "layers"):
+            pairs = [(l.keys, l.values) for l in past.layers]
+        else:
+            pairs = [(kv[0], kv[1]) for kv in past]
+        if not pairs:
+            raise ValueError("empty past_key_values")
+        k0 = pairs[0][0]
+        if k0.dim() != 4:
+            raise ValueError("past_key_values entries must be [batch, heads, seq, head_dim] tensors")
+        B, H, S, hd = k0.shape
+        c = cls(len(pairs), B, H, hd, S + headroom, k0.device, k0.dtype, kv_dtype=kv_dtype)
+        for li, (k, v) in enumerate(pairs):
+            if k.shape != (B, H, S, hd) or v.shape != (B, H, S, hd):
+                raise ValueError("past_key_values layers disagree in shape")
+            if kv_dtype is not None:
+                k, v = k.contiguous(), v.contiguous()
+                ops.quantize_kv(k, k.stride()[:3], v, v.stride()[:3], *c.kv8_layer(li), 0, S)
+                continue
+            c.k[li][:, :, :S].copy_(k)
+            vr = v.permute(0, 2, 1, 3).contiguous()                              # [B, S, H, hd]: heads contiguous per token (data movement)
+            ops.transpose_v(vr, S * H * hd, H * hd, B, S, H, hd, pitch=c.smax, out=c.vt[li])
+        c.length = S
+        return c
+
+    @staticmethod
+    def vt_slot(pos: int) -> int:
+        """column of key `pos` inside V^T (32-key blocks stored as slot 8g+4a+r <- key 16a+4g+r, see transpose_v)."""
+        w = pos & 31
+        return (pos & ~31) + 8 * ((w >> 2) & 3) + 4 * (w >> 4) + (w & 3)

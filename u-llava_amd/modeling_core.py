@@ -15,8 +15,6 @@ MI355X-specific host design:
 """
 from typing import List, Optional
 
-import weakref
-
 import torch
 import torch.nn as nn
 
@@ -24,6 +22,10 @@ from . import _lib
 from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaCoreConfig
+# (imported by name: the cache and the decoding helpers stay importable from this module)
+from .generation import (Decoding, GenerateOutput, check_generate_args, check_prompt_lookup, check_sampler, fused_loop, host_loop,
+                         no_repeat_ngram_banned_tokens, prompt_lookup_candidates, prompt_lookup_loop, sampling_probs)
+from .kv_cache import DEFAULT_HEADROOM, KV_CACHE_DTYPES, KVCache, _check_kv_dtype
 
 BF16 = torch.bfloat16
 
@@ -173,203 +175,9 @@ class CausalLMOutputWithPast(dict):
         return dict.__getitem__(self, k)
 
 
-class GenerateOutput(dict):
-    __getattr__ = dict.__getitem__
-
-
 class ScoreOutput(dict):
     """What score() returns: token_logprobs, sequence_logprob, num_tokens."""
     __getattr__ = dict.__getitem__
-
-
-KV_CACHE_DTYPES = ("fp8_e4m3",)
-
-
-def _check_kv_dtype(kv_dtype, dtype):
-    """the cache formats there are: None (the model dtype) or "fp8_e4m3" (bf16 models only)."""
-    if kv_dtype is None:
-        return
-    if not isinstance(kv_dtype, str) or kv_dtype not in KV_CACHE_DTYPES:
-        raise ValueError(f"unknown KV cache dtype {kv_dtype!r} (supported: None, {', '.join(repr(d) for d in KV_CACHE_DTYPES)})")
-    if dtype != BF16:
-        raise NotImplementedError(f"an fp8 KV cache needs a bf16 model, not {dtype}: the dequantized values of a position with a small amax "
-                                  "can fall below the fp16 range, and the fp32 build has no fp8 kernels")
-
-
-class KVCache:
-    """Per-layer K [B,H,Smax,hd] (post-RoPE) and V^T [B,H,hd,Smax] in the attention kernel's key-permuted layout, plus the
-    last-layer hidden states of every position seen so far (what `evaluate()` reads for [SEG]/[LOC] rows).  Truthy once a
-    prefill has been stored, like a non-empty HF past_key_values tuple."""
-
-    kv_dtype = None                        # "fp8_e4m3": see below
-
-    def __init__(self, n_layers, B, H, hd, smax, device, dtype=BF16, kv_dtype=None):
-        """kv_dtype="fp8_e4m3" (bf16 models only): the cache holds e4m3fn codes in the same two layouts (k8 [B,H,Smax,hd], vt8 [B,H,hd,Smax])
-        plus one fp32 power-of-two scale per (batch, head, position) for the K row (k_scale, by key) and the V column (vt_scale, by V^T slot),
-        with the fp8-weight rule (DESIGN f2).  Attention reads the K / V of its own forward call at full bf16 precision and the earlier
-        positions dequantized; the new positions are quantized into the cache.  So the model equals, bit for bit, the same model with a bf16
-        cache holding the dequantized positions (`dequantized()`).  A decode step's new keys pass through a bf16 staging window (k_stage /
-        vt_stage: 128 positions, one window shared by all layers) on their way into the cache."""
-        _check_kv_dtype(kv_dtype, dtype)
-        self.smax = ((smax + 63) // 64) * 64
-        self.length = 0
-        self.last_hidden = []
-        if kv_dtype is None:
-            self.k = [torch.empty(B, H, self.smax, hd, device=device, dtype=dtype) for _ in range(n_layers)]
-            self.vt = [torch.zeros(B, H, hd, self.smax, device=device, dtype=dtype) for _ in range(n_layers)]
-            return
-        self.kv_dtype = kv_dtype
-        self.k = self.vt = None
-        u8, f32 = torch.uint8, torch.float32
-        self.k8 = [torch.zeros(B, H, self.smax, hd, device=device, dtype=u8) for _ in range(n_layers)]
-        self.vt8 = [torch.zeros(B, H, hd, self.smax, device=device, dtype=u8) for _ in range(n_layers)]
-        self.k_scale = [torch.zeros(B, H, self.smax, device=device, dtype=f32) for _ in range(n_layers)]
-        self.vt_scale = [torch.zeros(B, H, self.smax, device=device, dtype=f32) for _ in range(n_layers)]
-        self.k_stage = torch.zeros(B, H, 128, hd, device=device, dtype=dtype)
-        self.vt_stage = torch.zeros(B, H, hd, 128, device=device, dtype=dtype)
-        self._kv8_ptrs = None              # (data_ptr key, ctypes arrays) of c_ptrs()
-
-    def kv8_layer(self, li):
-        """(k8, vt8, k_scale, vt_scale) of layer li of an fp8 cache."""
-        return self.k8[li], self.vt8[li], self.k_scale[li], self.vt_scale[li]
-
-    def bf16_scratch(self):
-        """(fp8 cache) a bf16 K [B,H,Smax,hd] / V^T [B,H,hd,Smax] pair (V^T zero-filled) for the calls the fp8 decode attention does not take
-        (<= 64 keys, > 16 new tokens): each layer is dequantized into it, runs the bf16 path, and its new positions are quantized back.
-        Made per forward call and shared by its layers; the cache itself keeps no bf16 buffer but the staging window."""
-        B, H, smax, hd = self.k8[0].shape
-        dev = self.k8[0].device
-        return torch.empty(B, H, smax, hd, device=dev, dtype=BF16), torch.zeros(B, H, hd, smax, device=dev, dtype=BF16)
-
-    def nbytes(self) -> int:
-        """bytes of every device buffer the cache keeps (fp8: codes, scales and the staging window; bf16: K and V^T)."""
-        ts = (self.k + self.vt) if self.kv_dtype is None else (self.k8 + self.vt8 + self.k_scale + self.vt_scale + [self.k_stage, self.vt_stage])
-        return sum(t.numel() * t.element_size() for t in ts)
-
-    def dequantized(self) -> "KVCache":
-        """The bf16 twin of an fp8 cache: a bf16 KVCache whose positions < length hold dequant(codes) = float(code) * 2^s (same length,
-        same last_hidden).  A bf16 cache returns itself."""
-        if self.kv_dtype is None:
-            return self
-        B, H, smax, hd = self.k8[0].shape
-        c = KVCache(len(self), B, H, hd, smax, self.k8[0].device, BF16)
-        if self.length:
-            for li in range(len(self)):
-                ops.dequantize_kv(*self.kv8_layer(li), self.length, k_out=c.k[li], vt_out=c.vt[li])
-        c.length = self.length
-        c.last_hidden = list(self.last_hidden)
-        return c
-
-    def __bool__(self):
-        return self.length > 0
-
-    def truncate(self, n: int) -> None:
-        """Give back the positions >= n (speculative decoding: the rejected drafts of a verify step): `length` becomes n and `last_hidden`
-        holds exactly the first n positions (the last call's tensor is sliced).  bf16 and fp8 caches alike: the buffers keep the rejected
-        positions' K rows, V^T columns, codes and scales as stale finite data, which no kernel reads -- attention, append and quantization
-        address keys below `length` plus the call's own new positions, and the next call overwrites them."""
-        n = int(n)
-        if n < 0 or n > self.length:
-            raise ValueError(f"KVCache.truncate({n}): the cache holds {self.length} positions")
-        self.length = n
-        have = sum(h.shape[1] for h in self.last_hidden)
-        while self.last_hidden and have > n:
-            last = self.last_hidden[-1]
-            if have - last.shape[1] >= n:
-                self.last_hidden.pop()
-                have -= last.shape[1]
-            else:
-                self.last_hidden[-1] = last[:, :last.shape[1] - (have - n)]
-                have = n
-
-    def c_ptrs(self):
-        """(void* array of the K buffers, void* array of the V^T buffers) for the coarse decode entry; built once per cache.
-        fp8 cache: (k8, vt8, k_scale, vt_scale void* arrays, k_stage, vt_stage) for the *_kv8 entries, rebuilt whenever a list entry has
-        been rebound since (the arrays hold raw pointers)."""
-        if self.kv_dtype is not None:
-            import ctypes
-            lists = (self.k8, self.vt8, self.k_scale, self.vt_scale)
-            key = tuple(t.data_ptr() for l in lists for t in l)
-            if self._kv8_ptrs is None or self._kv8_ptrs[0] != key:
-                arrs = tuple((ctypes.c_void_p * len(l))(*[t.data_ptr() for t in l]) for l in lists)
-                self._kv8_ptrs = (key, arrs + (self.k_stage, self.vt_stage))
-            return self._kv8_ptrs[1]
-        if getattr(self, "_c_ptrs", None) is None:
-            import ctypes
-            self._c_ptrs = ((ctypes.c_void_p * len(self.k))(*[t.data_ptr() for t in self.k]), (ctypes.c_void_p * len(self.vt))(*[t.data_ptr() for t in self.vt]))
-        return self._c_ptrs
-
-    def __len__(self):
-        return len(self.k) if self.kv_dtype is None else len(self.k8)
-
-    def to_legacy_cache(self):
-        """The HF view of this cache (what `outputs.past_key_values` is in the reference under transformers 4.29.1, models/ullava_core.py:349-355):
-        a tuple of per-layer (key, value) pairs, each [B, H, length, hd] with post-RoPE keys.  Pure data movement (a slice of the K buffer;
-        the key-permuted V^T image gathered back into natural key order and transposed); `KVCache.from_hf` is the inverse.  An fp8 cache
-        hands out its dequantized positions: it builds its bf16 twin (`dequantized()`, every layer at once) first, a transient allocation of
-        about twice the fp8 cache's size; `__getitem__` dequantizes one layer only."""
-        if self.kv_dtype is not None:
-            return self.dequantized().to_legacy_cache()
-        n = self.length
-        idx = ops.vt_unpermute_index(self.smax).to(self.k[0].device)[:n]
-        return tuple((k[:, :, :n].contiguous(), vt[..., idx].transpose(-1, -2).contiguous()) for k, vt in zip(self.k, self.vt))
-
-    def __iter__(self):
-        return iter(self.to_legacy_cache())
-
-    def __getitem__(self, i):
-        """layer i's (key, value) pair -- so that code written against a tuple of pairs (`past_key_values[0][0].shape[2]`, the idiom of
-        4.29-era callers) reads this object too.  An fp8 cache dequantizes the layer."""
-        if self.kv_dtype is not None:
-            B, H, smax, hd = self.k8[i].shape
-            k = torch.empty(B, H, max(self.length, 1), hd, device=self.k8[i].device, dtype=BF16)
-            vt = torch.zeros(B, H, hd, smax, device=self.k8[i].device, dtype=BF16)
-            if self.length:
-                ops.dequantize_kv(*self.kv8_layer(i), self.length, k_out=k, vt_out=vt)
-            idx = ops.vt_unpermute_index(smax).to(vt.device)[:self.length]
-            return k[:, :, :self.length], vt[..., idx].transpose(-1, -2)
-        n = self.length
-        idx = ops.vt_unpermute_index(self.smax).to(self.k[i].device)[:n]
-        return self.k[i][:, :, :n], self.vt[i][..., idx].transpose(-1, -2)
-
-    @classmethod
-    def from_hf(cls, past, headroom: int = 512, kv_dtype=None):
-        """A caller-supplied HF `past_key_values` -> KVCache (reference models/ullava_core.py:279-292 takes `past_key_values:
-        Optional[List[torch.FloatTensor]]`): the legacy tuple of per-layer (key, value) pairs, each [B, H, S, hd] with post-RoPE keys, or a
-        transformers Cache object exposing `key_cache` / `value_cache` lists (or `.layers[i].keys / .values`).  Keys are copied into the
-        K buffers, values go through `ull_transpose_v` into the permuted V^T layout; `last_hidden` starts empty (hidden states of the
-        cached positions are not part of an HF cache).  kv_dtype="fp8_e4m3": the keys and values are quantized into an fp8 cache."""
-        if hasattr(past, "key_cache") and hasattr(past, "value_cache"):
-            pairs = list(zip(past.key_cache, past.value_cache))
-        elif hasattr(past, "layers"):
-            pairs = [(l.keys, l.values) for l in past.layers]
-        else:
-            pairs = [(kv[0], kv[1]) for kv in past]
-        if not pairs:
-            raise ValueError("empty past_key_values")
-        k0 = pairs[0][0]
-        if k0.dim() != 4:
-            raise ValueError("past_key_values entries must be [batch, heads, seq, head_dim] tensors")
-        B, H, S, hd = k0.shape
-        c = cls(len(pairs), B, H, hd, S + headroom, k0.device, k0.dtype, kv_dtype=kv_dtype)
-        for li, (k, v) in enumerate(pairs):
-            if k.shape != (B, H, S, hd) or v.shape != (B, H, S, hd):
-                raise ValueError("past_key_values layers disagree in shape")
-            if kv_dtype is not None:
-                k, v = k.contiguous(), v.contiguous()
-                ops.quantize_kv(k, k.stride()[:3], v, v.stride()[:3], *c.kv8_layer(li), 0, S)
-                continue
-            c.k[li][:, :, :S].copy_(k)
-            vr = v.permute(0, 2, 1, 3).contiguous()                              # [B, S, H, hd]: heads contiguous per token (data movement)
-            ops.transpose_v(vr, S * H * hd, H * hd, B, S, H, hd, pitch=c.smax, out=c.vt[li])
-        c.length = S
-        return c
-
-    @staticmethod
-    def vt_slot(pos: int) -> int:
-        """column of key `pos` inside V^T (32-key blocks stored as slot 8g+4a+r <- key 16a+4g+r, see transpose_v)."""
-        w = pos & 31
-        return (pos & ~31) + 8 * ((w >> 2) & 3) + 4 * (w >> 4) + (w & 3)
 
 
 def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
@@ -377,95 +185,6 @@ def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     I, K = gate.shape
     assert I % 16 == 0
     return torch.stack((gate.view(I // 16, 16, K), up.view(I // 16, 16, K)), dim=1).reshape(2 * I, K).contiguous()
-
-
-def no_repeat_ngram_banned_tokens(rows, ngram_size: int):
-    """transformers' NoRepeatNGramLogitsProcessor rule (generation/logits_process.py `_calc_banned_ngram_tokens`; reference
-    models/ullava.py:360 forwards `no_repeat_ngram_size` to HF generate): for every row (list of ids so far, prompt included), the tokens
-    that followed an earlier occurrence of the row's last ngram_size - 1 tokens.  Host-side integer bookkeeping, like HF's."""
-    out = []
-    for toks in rows:
-        cur = len(toks)
-        if ngram_size <= 0 or cur + 1 < ngram_size:
-            out.append([])
-            continue
-        prefix = tuple(toks[cur + 1 - ngram_size:cur])
-        banned = []
-        for i in range(cur - ngram_size + 1):
-            if tuple(toks[i:i + ngram_size - 1]) == prefix:
-                banned.append(toks[i + ngram_size - 1])
-        out.append(banned)
-    return out
-
-
-def prompt_lookup_candidates(row, num_tokens: int, max_ngram: int, eos_ids, limit: int):
-    """The draft of prompt-lookup decoding (transformers generation/candidate_generator.py, PromptLookupCandidateGenerator: what HF
-    `generate(prompt_lookup_num_tokens=, max_matching_ngram_size=)` proposes), restated on a plain list; the reference of the device lookup in
-    ops.spec_step.  row: the ids so far, prompt included.  For n = min(max_ngram, len(row) - 1) down to 1: the earliest window equal to the
-    row's trailing n ids whose continuation is non-empty wins; the continuation is the next min(num_tokens, limit) ids, cut at the end of the
-    row and before the first id in eos_ids (what is left may be empty, and is the draft all the same).  No window at any n: no draft.
-    limit = max_new_tokens - tokens generated so far - 1: a step never proposes more than it may emit."""
-    row = list(row)
-    L = len(row)
-    want = min(int(num_tokens), int(limit))
-    if want <= 0:
-        return []
-    eos = set() if eos_ids is None else {int(e) for e in eos_ids}
-    for n in range(min(int(max_ngram), L - 1), 0, -1):
-        tail = row[L - n:]
-        for s in range(L - n):                                   # s + n < L: the continuation has at least one id
-            if row[s:s + n] == tail:
-                out = []
-                for tok in row[s + n:min(s + n + want, L)]:
-                    if tok in eos:
-                        break
-                    out.append(tok)
-                return out
-    return []
-
-
-def check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size):
-    """generate()'s `prompt_lookup_num_tokens` / `max_matching_ngram_size` -> (k, n-gram size), or None when the feature is off."""
-    if prompt_lookup_num_tokens is None:
-        if max_matching_ngram_size is not None:
-            raise ValueError("`max_matching_ngram_size` is an option of prompt-lookup decoding: it needs `prompt_lookup_num_tokens`")
-        return None
-    k = int(prompt_lookup_num_tokens)
-    if k != prompt_lookup_num_tokens or not 1 <= k <= ops.SPEC_MAX_DRAFT:
-        raise ValueError(f"`prompt_lookup_num_tokens` has to be an integer in 1..{ops.SPEC_MAX_DRAFT} (a verify step takes at most "
-                         f"{ops.SPEC_MAX_DRAFT + 1} new tokens), but is {prompt_lookup_num_tokens}")
-    g = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
-    if (max_matching_ngram_size is not None and g != max_matching_ngram_size) or g < 1:
-        raise ValueError(f"`max_matching_ngram_size` has to be an integer >= 1, but is {max_matching_ngram_size}")
-    return k, g
-
-
-def sampling_probs(logits: torch.Tensor, temperature: float, top_k: Optional[int] = 50, top_p: Optional[float] = None) -> torch.Tensor:
-    """The distribution HF `GenerationMixin._sample` draws from, in its own arithmetic and order (transformers generation/logits_process.py:
-    TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper on fp32 scores, then softmax): the reference's callers pass `temperature`
-    (and optionally `top_p`) and inherit `top_k = 50` from GenerationConfig's defaults (models/ullava.py:350-361, inference_ullava_core.py:73-80).
-    One `torch.multinomial(probs, 1)` per step on these probabilities consumes the RNG exactly as HF does, so a seeded run draws HF's tokens
-    from the same logits.  Integer / fp32 bookkeeping on [B, V] scores (the logits themselves come from the HIP lm_head)."""
-    scores = logits.float()
-    if temperature is not None and temperature != 1.0:
-        scores = scores / temperature
-    if top_k is not None and top_k > 0:
-        k = min(int(top_k), scores.size(-1))
-        scores = scores.masked_fill(scores < torch.topk(scores, k)[0][..., -1, None], float("-inf"))
-    if top_p is not None and top_p < 1.0:
-        sorted_logits, sorted_indices = torch.sort(scores, descending=False)
-        cumulative = sorted_logits.softmax(dim=-1).cumsum(dim=-1)
-        remove = cumulative <= (1 - top_p)
-        remove[..., -1:] = 0                                     # min_tokens_to_keep = 1
-        scores = scores.masked_fill(remove.scatter(1, sorted_indices, remove), float("-inf"))
-    return torch.softmax(scores, dim=-1)
-
-
-def check_sampler(sampler) -> bool:
-    """generate()'s `sampler`: None / "host" = torch's sampling path, "device" = ops.sample_step in the fused loop (True)."""
-    if sampler not in (None, "host", "device"):
-        raise ValueError(f'unknown sampler {sampler!r} (None / "host": the torch path; "device": one HIP launch per token)')
-    return sampler == "device"
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -1289,7 +1008,7 @@ class UllavaCoreForCausalLM(nn.Module):
                 all_h.append(x.view(B, S, D))
             decode = cache is not None and past > 0
             if kv8 and decode:
-                kc, vtc, smax_, past_ = self._kv8_decode_buffers(cache, li, past, kv8_fewq, kv8_scr)
+                kc, vtc, smax_, past_ = cache._kv8_decode_buffers(li, past, kv8_fewq, kv8_scr)
             elif decode:
                 kc, vtc, smax_, past_ = cache.k[li], cache.vt[li], cache.smax, past
             if fuse_append:
@@ -1297,7 +1016,7 @@ class UllavaCoreForCausalLM(nn.Module):
                                                rms_eps=cfg.rms_norm_eps)
                 att = torch.empty(T, D, device=dev, dtype=x.dtype)
                 if kv8:
-                    self._kv8_attention(q, (S * D, hd, D), cache, li, att, B, H, S, past, hd, key_mask, kv8_fewq, kv8_scr)
+                    cache._kv8_attention(q, (S * D, hd, D), li, att, B, H, S, past, hd, key_mask, kv8_fewq, kv8_scr)
                 else:
                     ops.attention(q, kc, vtc, att, B, H, S, past + S, hd, (S * D, hd, D), (H * cache.smax * hd, cache.smax * hd, hd),
                                   (S * D, hd, D), key_mask, causal=True, scale_mode=1, scale=hd ** -0.5)
@@ -1314,7 +1033,7 @@ class UllavaCoreForCausalLM(nn.Module):
                 # generation step: RoPE + cache append in one launch, then the split-key attention over the cache
                 ops.rope_append(qkv, 3 * D, pos, inv_freq, B, S, H, hd, kc, vtc, smax_, past_)
                 if kv8:
-                    self._kv8_attention(qkv, (S * 3 * D, hd, 3 * D), cache, li, att, B, H, S, past, hd, key_mask, kv8_fewq, kv8_scr)
+                    cache._kv8_attention(qkv, (S * 3 * D, hd, 3 * D), li, att, B, H, S, past, hd, key_mask, kv8_fewq, kv8_scr)
                 else:
                     ops.attention(qkv, kc, vtc, att, B, H, S, past + S, hd, (S * 3 * D, hd, 3 * D), (H * cache.smax * hd, cache.smax * hd, hd),
                                   (S * D, hd, D), key_mask, causal=True, scale_mode=1, scale=hd ** -0.5)
@@ -1349,33 +1068,6 @@ class UllavaCoreForCausalLM(nn.Module):
             all_h.append(last)
         return last, (tuple(all_h) if output_hidden_states else None)
 
-    @staticmethod
-    def _kv8_decode_buffers(cache: KVCache, li: int, past: int, fewq: bool, scr: list):
-        """(K, V^T, pitch, position of the first new key) the decode appenders of layer li write into, on an fp8 cache: the staging window
-        (first new key at past mod 64) where the fp8 decode attention takes the call (fewq), else the call's bf16 scratch (scr, made on first
-        use) with positions < past dequantized."""
-        if fewq:
-            return cache.k_stage, cache.vt_stage, 128, past & 63
-        if not scr:
-            scr.append(cache.bf16_scratch())
-        kc, vtc = scr[0]
-        ops.dequantize_kv(*cache.kv8_layer(li), past, k_out=kc, vt_out=vtc)
-        return kc, vtc, cache.smax, past
-
-    @staticmethod
-    def _kv8_attention(q, q_strides, cache: KVCache, li: int, att, B: int, H: int, S: int, past: int, hd: int, key_mask, fewq: bool, scr: list):
-        """the decode attention of layer li over an fp8 cache, after _kv8_decode_buffers' appenders; the new positions end in the cache."""
-        if fewq:
-            ops.attention_kv8(q, q_strides, cache.k_stage, cache.vt_stage, *cache.kv8_layer(li), att, (S * H * hd, hd, H * hd), B, H, S, past + S,
-                              hd, key_mask, hd ** -0.5)
-            return
-        kc, vtc = scr[0]
-        smax = cache.smax
-        ops.attention(q, kc, vtc, att, B, H, S, past + S, hd, q_strides, (H * smax * hd, smax * hd, hd), (S * H * hd, hd, H * hd), key_mask,
-                      causal=True, scale_mode=1, scale=hd ** -0.5)
-        ops.quantize_kv(kc, (H * smax * hd, smax * hd, hd), vtc, (H * hd * smax, hd * smax, smax), *cache.kv8_layer(li), past, S, src_p0=past,
-                        v_image=True)
-
     def forward(self, input_ids: torch.LongTensor = None, attention_mask: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.LongTensor] = None, past_key_values: Optional[List[torch.FloatTensor]] = None,
                 inputs_embeds: Optional[torch.FloatTensor] = None, labels: Optional[torch.LongTensor] = None,
@@ -1387,12 +1079,10 @@ class UllavaCoreForCausalLM(nn.Module):
             raise NotImplementedError("attention probabilities never leave LDS on this path")
         if self.weight_quantization is not None and self._training_graph():
             self._refuse_quantized("building a training graph (gradients enabled with trainable parameters; use torch.no_grad())")
-        cache = None
-        if past_key_values is not None or use_cache:
-            if past_key_values is not None and not isinstance(past_key_values, KVCache):
-                # an HF-style cache handed in by the caller (legacy tuple of (key, value) per layer, or a transformers Cache object)
-                past_key_values = KVCache.from_hf(past_key_values, headroom=getattr(self, "_cache_headroom", 512))
-            cache = past_key_values
+        cache = past_key_values
+        if cache is not None and not isinstance(cache, KVCache):
+            # an HF-style cache handed in by the caller (legacy tuple of (key, value) per layer, or a transformers Cache object)
+            cache = KVCache.from_hf(cache, headroom=DEFAULT_HEADROOM)
         output_hidden_states = output_hidden_states if output_hidden_states is not None else self.config.output_hidden_states
         return_dict = return_dict if return_dict is not None else self.config.use_return_dict
         if inputs_embeds is None:
@@ -1403,8 +1093,7 @@ class UllavaCoreForCausalLM(nn.Module):
             B_, S_ = inputs_embeds.shape[:2]
             cache = KVCache(self.config.num_hidden_layers, B_, self.config.num_attention_heads,
                             self.config.hidden_size // self.config.num_attention_heads,
-                            max(S_ + getattr(self, "_cache_headroom", 512), 64), inputs_embeds.device, inputs_embeds.dtype,
-                            kv_dtype=getattr(self, "_new_cache_kv_dtype", None))
+                            max(S_ + DEFAULT_HEADROOM, 64), inputs_embeds.device, inputs_embeds.dtype)
         if self._training_graph():
             if cache is not None:
                 raise NotImplementedError("use_cache / past_key_values are inference features (the training scripts set use_cache=False)")
@@ -1467,58 +1156,6 @@ class UllavaCoreForCausalLM(nn.Module):
             scored = scored & keep.bool()
         return ScoreOutput(token_logprobs=lp, sequence_logprob=lp.sum(-1), num_tokens=scored.sum(-1))
 
-    def _generate_prompt_lookup(self, seq, images, videos, max_new_tokens, lookup, sampling, temperature, top_k, top_p, eos_ids, crit,
-                                kv_cache_dtype, output_hidden_states, return_dict_in_generate, output_logprobs=False):
-        """generate()'s loop under prompt_lookup_num_tokens (batch 1, KV cache, arguments already checked).  The ids live in one device
-        buffer: n valid ids, then the d drafts of the next step.  A step is one forward over buf[n-1 : n+d] and ops.spec_step, which emits,
-        drafts again and leaves (emitted, finished, d') for the one host read of the step -- the next forward's length depends on it.
-        output_logprobs: after the step, its 1 + d verify rows are scored against buf[0, n : n+1+d] into columns n-L0 ... of a buffer with
-        buf's k columns of slack; only the first `emitted` are valid, the next step overwrites the rest, and the result is cut at n."""
-        k, max_ngram = lookup
-        L0 = seq.shape[1]
-        n_max = L0 + max_new_tokens
-        dev = seq.device
-        buf = torch.empty(1, n_max + k, dtype=torch.int64, device=dev)
-        buf[:, :L0] = seq
-        picks = torch.empty(16, dtype=torch.int32, device=dev)
-        record = torch.empty(3, dtype=torch.int32, device=dev)
-        lp = torch.zeros(max_new_tokens + k, dtype=torch.float32, device=dev) if output_logprobs else None
-        self._cache_headroom = max_new_tokens + k + 1            # (the cache forward() creates for the prefill)
-        cache = None
-        n, d = L0, 0
-        while n < n_max:
-            if cache is None:
-                self._new_cache_kv_dtype = kv_cache_dtype
-                try:
-                    out = self.forward(input_ids=buf[:, :L0], images=images, videos=videos, use_cache=True)
-                finally:
-                    self._new_cache_kv_dtype = None
-                cache = out.past_key_values
-            else:
-                out = self.forward(input_ids=buf[:, n - 1:n + d], past_key_values=cache, use_cache=True)
-            logits = out.logits[0, -(1 + d):]
-            # torch's noise, one row per verified position, drawn in one call per step
-            noise = torch.empty(logits.shape, dtype=torch.float32, device=dev).exponential_() if sampling else None
-            ops.spec_step(logits, noise, temperature, top_k, top_p, buf, n, d, n_max, eos_ids, k, max_ngram, picks, record)
-            if lp is not None:
-                # rows 0 .. emitted-1 hold the emitted tokens (a row past them is scored against whatever id sits there: never returned)
-                ops.token_logprobs(logits, buf[0, n:n + 1 + d], out=lp[n - L0:n - L0 + 1 + d])
-            emitted, finished, d = record.tolist()               # the step's device -> host read
-            n += emitted
-            cache.truncate(n - 1)                                # the rejected drafts' positions (and the states of the token not yet fed)
-            if finished or (crit and any(bool(torch.as_tensor(c(buf[:, :n], None)).all()) for c in crit)):
-                break
-        seq = buf[:, :n].contiguous()
-        if not return_dict_in_generate:
-            return seq
-        hidden = None
-        if output_hidden_states:
-            hidden = ((torch.cat(cache.last_hidden, dim=1),),) if cache is not None else ()
-        res = GenerateOutput(sequences=seq, hidden_states=hidden)
-        if lp is not None:
-            res["logprobs"] = lp[:n - L0].unsqueeze(0).clone()
-        return res
-
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, videos=None, attention_mask=None, max_new_tokens=32, do_sample=False,
                  temperature=1.0, top_p=None, top_k=50, num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, eos_token_id=None,
@@ -1557,190 +1194,35 @@ class UllavaCoreForCausalLM(nn.Module):
         top-p and the n-gram ban, so it says how likely the model itself held the token, whatever the sampling settings (HF's
         `output_logits`, not `output_scores`).  A row that had finished before the step holds a pad-fill token there and gets exactly 0.0;
         a row's EOS token itself gets its real log-probability.  One launch per step (ops.token_logprobs) in every loop; GPU tensors only."""
-        if num_beams != 1:
-            raise NotImplementedError("beam search is not used by the reference callers (num_beams=1)")
-        if kwargs:
-            # HF generate() validates its model kwargs and raises on unknown ones; options this loop does not implement must not be
-            # swallowed (a silently ignored `repetition_penalty` changes the ids)
-            raise TypeError(f"generate() got unsupported keyword arguments {sorted(kwargs)} (supported: greedy / sampling with temperature, "
-                            "top_k, top_p, no_repeat_ngram_size, stopping_criteria, eos_token_id, pad_token_id, max_new_tokens)")
-        if output_logprobs and not return_dict_in_generate:
-            raise ValueError("`output_logprobs=True` needs `return_dict_in_generate=True`: the log-probabilities travel in the returned dict")
-        ngram = int(no_repeat_ngram_size) if no_repeat_ngram_size else 0
-        if ngram < 0:
-            raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer, but is {no_repeat_ngram_size}")
-        sampling = bool(do_sample and temperature and temperature > 0)
-        device_sampler = check_sampler(sampler)
-        if device_sampler and ngram:
-            raise ValueError('sampler="device" does not combine with `no_repeat_ngram_size`: the n-gram ban is host-side list work '
-                             '(use sampler=None)')
-        if device_sampler and sampling and self.config.vocab_size > ops.SAMPLE_MAX_V:
-            raise ValueError(f'sampler="device" stages a row of logits in LDS: vocab_size {self.config.vocab_size} is above its limit of '
-                             f"{ops.SAMPLE_MAX_V} (use sampler=None)")
-        use_cache = self.config.use_cache if use_cache is None else use_cache
-        lookup = check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size)
-        if lookup is not None:
-            if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
-                raise ValueError("prompt-lookup decoding takes a batch of one row (as HF's assisted decoding does), got "
-                                 f"{None if input_ids is None else tuple(input_ids.shape)}")
-            if not use_cache:
-                raise ValueError("prompt-lookup decoding needs use_cache=True: a verify step runs over a filled KV cache")
-            if ngram:
-                raise ValueError("prompt-lookup decoding does not combine with `no_repeat_ngram_size`: the n-gram ban is host-side list work")
-            if attention_mask is not None and not bool(attention_mask.ne(0).all()):
-                raise ValueError("prompt-lookup decoding does not take a padded attention mask (one unpadded row)")
-            if sampling and not device_sampler:
-                raise ValueError('prompt-lookup decoding with do_sample=True needs sampler="device": its loop picks the tokens on the device')
-        if kv_cache_dtype is not None:
-            _check_kv_dtype(kv_cache_dtype, self.dtype)
-            if not use_cache:
-                raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r} needs use_cache=True: without a KV cache there is nothing to quantize")
+        cfg = self.config
+        ngram, sampling, device_sampler, use_cache, lookup = check_generate_args(
+            input_ids, attention_mask, do_sample=do_sample, temperature=temperature, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size,
+            use_cache=use_cache, kv_cache_dtype=kv_cache_dtype, sampler=sampler, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+            max_matching_ngram_size=max_matching_ngram_size, output_logprobs=output_logprobs, return_dict_in_generate=return_dict_in_generate,
+            unknown=kwargs, dtype=self.dtype, vocab_size=cfg.vocab_size, config_use_cache=cfg.use_cache)
         seq = input_ids
-        B = seq.shape[0]
-        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
-        eos_ids = None
-        if eos is not None:
-            eos_ids = torch.as_tensor([eos] if isinstance(eos, int) else list(eos), device=seq.device, dtype=seq.dtype)
-        pad = pad_token_id if pad_token_id is not None else getattr(self.config, "pad_token_id", None)
+        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
+        eos_ids = None if eos is None else torch.as_tensor([eos] if isinstance(eos, int) else list(eos), device=seq.device, dtype=seq.dtype)
+        pad = pad_token_id if pad_token_id is not None else getattr(cfg, "pad_token_id", None)
         if pad is None and eos_ids is not None:
             pad = int(eos_ids[0])
-        steps_hidden = []
-        cache = None
-        self._cache_headroom = max_new_tokens + 1
         # No padding anywhere (no mask given, or a mask of ones -- one host read, here): the steps run without a key mask.  The results
         # are the same (position_ids = cumsum(ones) - 1 = arange; every key attended) and the attention kernels skip their per-key
         # mask loads, which sit on the latency chain of every decode step.
         no_pad = attention_mask is None or bool(attention_mask.ne(0).all())
         crit = [] if stopping_criteria is None else (list(stopping_criteria) if isinstance(stopping_criteria, (list, tuple)) else [stopping_criteria])
+        cache = None
+        if use_cache:
+            # the prefill fills it; room for every token fed (the last one emitted never is), and for a verify step's drafts
+            H, room = cfg.num_attention_heads, max_new_tokens + 1 + (lookup[0] if lookup is not None else 0)
+            cache = KVCache(cfg.num_hidden_layers, seq.shape[0], H, cfg.hidden_size // H, max(seq.shape[1] + room, 64), seq.device, self.dtype,
+                            kv_dtype=kv_cache_dtype)
+        d = Decoding(self, images, videos, attention_mask, no_pad, cache, max_new_tokens, sampling, temperature, top_k, top_p, eos_ids, pad, crit,
+                     output_hidden_states, keep_last_step_only, output_logprobs)
         if lookup is not None:
-            if not seq.is_cuda:
-                raise RuntimeError("prompt-lookup decoding needs GPU tensors (no CPU path exists)")
-            return self._generate_prompt_lookup(seq, images, videos, max_new_tokens, lookup, sampling, temperature, top_k, top_p, eos_ids, crit,
-                                                kv_cache_dtype, output_hidden_states, return_dict_in_generate, output_logprobs)
-        # Greedy decoding keeps the whole step on the device: the tokens land in a pre-sized [B, L0 + max_new_tokens] buffer, the
-        # argmax / pad-fill / EOS bookkeeping is ONE kernel (ops.greedy_step), and the host looks at the "rows still unfinished"
-        # counters only every CHECK steps (every step when a stopping criterion needs the ids on the host anyway).  Steps that run past
-        # the point where every row had finished only produce pad tokens; the result is trimmed to what a per-step check returns.
-        # sampler="device": the same loop with ops.sample_step in place of ops.greedy_step.
-        if device_sampler and sampling and not seq.is_cuda:
-            raise RuntimeError('sampler="device" needs GPU tensors (no CPU path exists)')
-        if output_logprobs and not seq.is_cuda:
-            raise RuntimeError("output_logprobs needs GPU tensors (no CPU path exists)")
-        fused = (not sampling or device_sampler) and ngram == 0 and seq.is_cuda
-        L0 = seq.shape[1]
-        CHECK = 1 if crit else 8
-        if fused:
-            buf = torch.empty(B, L0 + max_new_tokens, dtype=torch.int64, device=seq.device)
-            buf[:, :L0] = seq
-            live = torch.ones(B, dtype=torch.int32, device=seq.device)
-            alive = torch.zeros(max_new_tokens, dtype=torch.int32, device=seq.device)
-            if output_logprobs:
-                # the step kernels update `live` in place and the score needs it as it stood BEFORE the step: a snapshot per step
-                lp = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=seq.device)
-                live_before = torch.empty_like(live)
+            seq, logprobs = prompt_lookup_loop(d, seq, lookup)
+        elif (not sampling or device_sampler) and ngram == 0 and seq.is_cuda:
+            seq, logprobs = fused_loop(d, seq)
         else:
-            unfinished = torch.ones(B, dtype=torch.bool, device=seq.device)
-            lp_cols = []
-        n_done = 0                                              # tokens appended so far
-        stop_at = None                                          # fused: number of tokens after which every row had finished
-        for step in range(max_new_tokens):
-            if fused:
-                seq = buf[:, :L0 + step]
-            mask = None if no_pad else torch.cat(
-                [attention_mask, attention_mask.new_ones(B, seq.shape[1] - attention_mask.shape[1])], dim=1)
-            inputs = self.prepare_inputs_for_generation(input_ids=seq, attention_mask=mask, images=images, videos=videos,
-                                                        past_key_values=cache if use_cache else None, use_cache=use_cache)
-            if use_cache:
-                # KV-cached decoding (SURVEY 8(f) row 1): prefill once, then one token per step; vision runs once
-                if step > 0:
-                    inputs["images"] = inputs["videos"] = None
-                if step == 0 and kv_cache_dtype is not None:
-                    self._new_cache_kv_dtype = kv_cache_dtype        # the cache forward() creates for the prefill
-                    try:
-                        out = self.forward(**inputs)
-                    finally:
-                        self._new_cache_kv_dtype = None
-                else:
-                    out = self.forward(**inputs)
-                cache = out.past_key_values
-            else:
-                # the reference's released checkpoints run with use_cache=False: every step re-runs the multimodal prefill
-                out = self.forward(**inputs, output_hidden_states=output_hidden_states)
-                if output_hidden_states:
-                    if keep_last_step_only:
-                        steps_hidden = [out.hidden_states]      # evaluate() only reads hidden_states[-1] (the last step)
-                    else:
-                        steps_hidden.append(out.hidden_states)
-            if fused:
-                if output_logprobs:
-                    live_before.copy_(live)
-                if sampling:
-                    last = out.logits[:, -1]
-                    # torch's noise, drawn as torch.multinomial draws it: the generator moves as it does on the host path
-                    noise = torch.empty(last.shape, dtype=torch.float32, device=last.device).exponential_()
-                    ops.sample_step(last, noise, temperature, top_k, top_p, live, eos_ids, pad, buf, L0 + step, alive[step:step + 1])
-                else:
-                    ops.greedy_step(out.logits[:, -1], live, eos_ids, pad, buf, L0 + step, alive[step:step + 1])
-                if output_logprobs:
-                    ops.token_logprobs(out.logits[:, -1], buf[:, L0 + step], live_before, out=lp[:, step])
-                n_done = step + 1
-                if crit:
-                    if any(bool(torch.as_tensor(c(buf[:, :L0 + n_done], None)).all()) for c in crit):
-                        break
-                if eos_ids is not None and (n_done % CHECK == 0 or n_done == max_new_tokens):
-                    a_host = alive[:n_done].cpu()               # the only device -> host read: every CHECK steps
-                    dead = (a_host == 0).nonzero()
-                    if dead.numel():
-                        stop_at = int(dead[0]) + 1
-                        break
-                continue
-            logits = out.logits[:, -1].float()
-            if output_logprobs and ngram > 0 and logits.dtype == out.logits.dtype:
-                logits = logits.clone()                         # an fp32 model: .float() is a view, and the ban must not reach the scored logits
-            if ngram > 0:
-                # HF NoRepeatNGramLogitsProcessor (logits processors run before the sampling warpers): tokens that would complete an
-                # n-gram already present in the row (prompt included) get -inf
-                for b_, banned in enumerate(no_repeat_ngram_banned_tokens(seq.tolist(), ngram)):
-                    if banned:
-                        logits[b_, torch.as_tensor(banned, device=logits.device)] = float("-inf")
-            if sampling:
-                nxt = torch.multinomial(sampling_probs(logits, temperature, top_k, top_p), 1)
-            else:
-                nxt = logits.argmax(-1, keepdim=True)
-            if pad is not None:
-                nxt = torch.where(unfinished.unsqueeze(1), nxt, torch.full_like(nxt, pad))      # finished rows: pad fill
-            seq = torch.cat([seq, nxt], dim=1)
-            if output_logprobs:
-                # the raw logits (before the n-gram ban and the warpers), masked by `unfinished` as it stood before this step
-                lp_cols.append(ops.token_logprobs(out.logits[:, -1], nxt.squeeze(1), unfinished.to(torch.int32)))
-            if eos_ids is not None:
-                unfinished = unfinished & ~torch.isin(nxt.squeeze(1), eos_ids)
-                if not bool(unfinished.any()):
-                    break
-            if crit:
-                if any(bool(torch.as_tensor(c(seq, None)).all()) for c in crit):
-                    break
-        if fused:
-            n_tok = n_done if stop_at is None else stop_at
-            seq = buf[:, :L0 + n_tok].contiguous()
-            if stop_at is not None and stop_at < n_done:
-                # steps that ran after every row had finished (at most CHECK - 1): drop their states so that the outputs equal a per-step check's
-                if cache is not None:
-                    del cache.last_hidden[n_tok:]
-                    cache.length = L0 + n_tok - 1
-                if steps_hidden and not keep_last_step_only:
-                    del steps_hidden[n_tok:]
-                elif steps_hidden and keep_last_step_only and not use_cache:
-                    # the kept step saw L0 + n_done - 1 positions; the reference's last step L0 + n_tok - 1
-                    steps_hidden = [tuple(h[:, :L0 + n_tok - 1] for h in steps_hidden[0])]
-        if output_hidden_states and use_cache and cache is not None:
-            # same tensor the no-cache path returns at its last step: last-layer states of ALL positions fed so far, joined once
-            steps_hidden = [(torch.cat(cache.last_hidden, dim=1),)]
-        if return_dict_in_generate:
-            res = GenerateOutput(sequences=seq, hidden_states=tuple(steps_hidden) if output_hidden_states else None)
-            if output_logprobs:
-                # fused: the columns of the steps that ran past the end go as their ids went
-                res["logprobs"] = lp[:, :n_tok].clone() if fused else (
-                    torch.stack(lp_cols, dim=1) if lp_cols else torch.zeros(B, 0, dtype=torch.float32, device=seq.device))
-            return res
-        return seq
+            seq, logprobs = host_loop(d, seq, ngram, sampling_probs)
+        return d.result(seq, logprobs, return_dict_in_generate)

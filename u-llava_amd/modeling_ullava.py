@@ -15,7 +15,8 @@ import torch.nn as nn
 from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaConfig
-from .modeling_core import BF16, Linear, UllavaCoreForCausalLM, _Holder, _check_kv_dtype, check_prompt_lookup, check_sampler
+from .generation import check_generate_args
+from .modeling_core import BF16, Linear, UllavaCoreForCausalLM, _Holder
 from .sam import SamEngine, build_sam_holder
 
 
@@ -326,32 +327,19 @@ class UllavaForCausalLM(nn.Module):
         read from the hidden states of the accepted positions.  output_logprobs=True: the return grows to (output_ids, pred_masks, pred_boxes,
         logprobs), logprobs fp32 [B, n_new] as generate(output_logprobs=True) gives them (raw distribution; 0.0 after a row's EOS) -- the
         number to drop an unsure [SEG] / [LOC] by."""
-        if kv_cache_dtype is not None:
-            _check_kv_dtype(kv_cache_dtype, self.llm.dtype)
-        if check_sampler(sampler) and no_repeat_ngram_size:
-            raise ValueError('sampler="device" does not combine with `no_repeat_ngram_size` (use sampler=None)')
-        lookup = check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size)
-        if lookup is not None:
-            if no_repeat_ngram_size:
-                raise ValueError("prompt-lookup decoding does not combine with `no_repeat_ngram_size`")
-            if temperature > 0 and not check_sampler(sampler):
-                raise ValueError('prompt-lookup decoding with temperature > 0 needs sampler="device": its loop picks the tokens on the device')
-            if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
-                raise ValueError("prompt-lookup decoding takes a batch of one row")
+        # generate()'s refusals, before the SAM encoder starts (the model's dtype is asked for only where kv_cache_dtype needs it)
+        gen = dict(do_sample=temperature > 0, temperature=temperature, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size,
+                   sampler=sampler, return_dict_in_generate=True, output_logprobs=output_logprobs, kv_cache_dtype=kv_cache_dtype,
+                   prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
+                   use_cache=True if kv_cache_dtype is not None or prompt_lookup_num_tokens is not None else None)
+        check_generate_args(input_ids, dtype=None if kv_cache_dtype is None else self.llm.dtype, **gen)
         main = torch.cuda.current_stream()                          # SAM image encoder on the second stream, under the generation loop
         side = self._side_stream()
         side.wait_stream(main)
         with torch.cuda.stream(side):
             image_embeddings = self._visual_embs_tm(images_sam)     # its GEMMs use the side stream's own stream-K workspace
-        outputs = self.llm.generate(input_ids=input_ids, images=images, max_new_tokens=max_new_tokens, num_beams=num_beams, top_p=top_p,
-                                    do_sample=True if temperature > 0 else False, temperature=temperature, output_hidden_states=True,
-                                    return_dict_in_generate=True, no_repeat_ngram_size=no_repeat_ngram_size,
-                                    stopping_criteria=stopping_criteria, keep_last_step_only=True, sampler=sampler,
-                                    **(dict(output_logprobs=True) if output_logprobs else {}),
-                                    **({} if kv_cache_dtype is None and lookup is None else dict(use_cache=True)),
-                                    **({} if kv_cache_dtype is None else dict(kv_cache_dtype=kv_cache_dtype)),
-                                    **({} if lookup is None else dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens,
-                                                                      max_matching_ngram_size=max_matching_ngram_size)))
+        outputs = self.llm.generate(input_ids=input_ids, images=images, max_new_tokens=max_new_tokens, top_p=top_p, output_hidden_states=True,
+                                    stopping_criteria=stopping_criteria, keep_last_step_only=True, **gen)
         output_ids = outputs.sequences
         last = outputs.hidden_states[-1][-1]                          # last step, last layer: [B, L-1, D]
         seg_token_mask = output_ids[:, 1:] == self.config.seg_token_idx

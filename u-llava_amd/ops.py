@@ -1189,7 +1189,7 @@ def spec_step(logits: torch.Tensor, noise: Optional[torch.Tensor], temperature: 
     """One step of prompt-lookup speculative decoding at batch 1 in two launches (see ull_spec_step): logits [1 + d, V] of the forward over
     buf[0, n-1 : n+d] (buf int64 [1, L]: n valid ids, then the d drafts); noise None picks every row's token as greedy_step does, else as
     sample_step does from noise fp32 [1 + d, V].  The accepted drafts' tokens and the bonus token are written to buf[0, n:], cut at n_max
-    valid ids and after the first EOS id; the next step's drafts (`modeling_core.prompt_lookup_candidates` over the new valid ids, at most
+    valid ids and after the first EOS id; the next step's drafts (`generation.prompt_lookup_candidates` over the new valid ids, at most
     num_tokens) follow them; record int32 [3] = (emitted, finished, next d).  picks: int32 [16] scratch."""
     _chk(logits, "logits"); _chk(buf, "buf", torch.int64); _chk(picks, "picks", torch.int32); _chk(record, "record", torch.int32)
     R, V = logits.shape
