@@ -381,6 +381,19 @@ int ull_spec_step(const void* logits, int logits_dtype, int64_t row_stride, int6
 int ull_token_logprobs(const void* logits, int logits_dtype, int64_t row_stride, int64_t R, int64_t V, const void* ids, int64_t ids_stride,
                        const void* row_mask, void* out, int64_t out_stride, void* stream);
 
+/* HF's NoRepeatNGramLogitsProcessor (what `no_repeat_ngram_size` of the reference's evaluate(), models/ullava.py:346,360, turns on) in one
+ * launch, compiled once (logits_dtype ULL_DT_F32 0 / BF16 1 / F16 2).  logits: R rows of V entries, row_stride elements apart, any element
+ * alignment; ids int64, rows ids_ld elements apart, the first cur_len entries of a row are its ids so far (prompt, pads and placeholders
+ * included; nothing behind them is read, and cur_len == 0 reads nothing: ids may be NULL then); out: R rows of V entries of the same dtype, out_ld >= V elements apart, not overlapping logits.
+ * Per row r: out[r][0..V) = logits[r][0..V) bit for bit (NaN payloads and infinities included), except out[r][t] = -inf for every
+ * t = ids_r[i + ngram - 1] with 0 <= i <= cur_len - ngram and ids_r[i .. i+ngram-2] == ids_r[cur_len-ngram+1 .. cur_len-1]: ngram == 1 bans
+ * every id of the row, cur_len + 1 < ngram bans nothing, a window may overlap the trailing n-gram.  A t outside [0, V) is skipped: no
+ * address is formed from an unchecked id.  Any R >= 0 (the blocks stride over the rows; R == 0: nothing is launched), any V >= 1 (no LDS
+ * staging).  Null pointer, ngram < 1, cur_len < 0, V < 1, a negative stride or an unknown dtype: ULL_ERR_ARG; out_ld < V: ULL_ERR_SHAPE;
+ * nothing is launched in either case. */
+int ull_ngram_ban(const void* logits, int logits_dtype, int64_t row_stride, int64_t R, int64_t V, const void* ids, int64_t ids_ld,
+                  int64_t cur_len, int64_t ngram, void* out, int64_t out_ld, void* stream);
+
 /* models/ullava_core.py:191,243-245,266-268: token-embedding lookup with the projected visual tokens spliced in after
  * the first start token (the torch.cat of the reference, done as one gather).  Image i's n_img_tok feature rows start
  * at row i*img_pitch + img_off of img_feat (pitch = patches + 1, off = 1 skips the CLS row without a copy).

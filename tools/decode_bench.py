@@ -7,7 +7,11 @@ step).
 --rounds N (the table of profiles/logprobs_decode.txt): one process times every arm -- greedy and sampler="device", each with
 output_logprobs off and on where this tree's generate() has the flag -- interleaved per round, N timed rounds after a warm-up round, for
 every batch of --batches, with eos_token_id=-1 so that no row ends early.  --tree DIR imports bench.py and the package from another built
-checkout (the parent commit, for an A/B by the same method); run the two trees' processes alternately."""
+checkout (the parent commit, for an A/B by the same method); run the two trees' processes alternately.
+--ngram N with --rounds (the table of profiles/ngram_ban_decode.txt): the arms are instead, for greedy decoding and for sampling at temperature
+0.2 / top_k 50, "plain" (no ban: the fused loop; sampling with sampler="device"), "host-ban" (no_repeat_ngram_size=N with the list rule on
+the host: the per-step host loop, and for sampling the host sampler, the only sampler that rule combines with) and, where this tree's
+generate() has `ngram_ban`, "dev-ban" (the same N with ngram_ban="device": the fused loop, sampling with sampler="device")."""
 import argparse, importlib, inspect, os, statistics, sys, time
 import torch
 
@@ -17,6 +21,7 @@ ap.add_argument("--new", type=int, default=33)
 ap.add_argument("--sample", action="store_true")
 ap.add_argument("--logprobs", action="store_true")
 ap.add_argument("--rounds", type=int, default=0)
+ap.add_argument("--ngram", type=int, default=0)
 ap.add_argument("--batches", type=str, default="1,16")
 ap.add_argument("--tree", type=str, default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 a = ap.parse_args()
@@ -43,7 +48,14 @@ def timed(ids, images, n, kw):
 if a.rounds > 0:
     gen = importlib.import_module("u-llava_amd.modeling_core").UllavaCoreForCausalLM.generate
     arms = [("greedy", dict(do_sample=False)), ("device", SAMPLE)]
-    if "output_logprobs" in inspect.signature(gen).parameters:
+    if a.ngram > 0:
+        ban = dict(no_repeat_ngram_size=a.ngram)
+        arms = [("greedy/plain", dict(do_sample=False)), ("greedy/host-ban", dict(do_sample=False, **ban)),
+                ("sample/plain", SAMPLE), ("sample/host-ban", dict(SAMPLE, sampler=None, **ban))]
+        if "ngram_ban" in inspect.signature(gen).parameters:
+            arms[2:2] = [("greedy/dev-ban", dict(do_sample=False, ngram_ban="device", **ban))]
+            arms.append(("sample/dev-ban", dict(SAMPLE, ngram_ban="device", **ban)))
+    elif "output_logprobs" in inspect.signature(gen).parameters:
         arms = [(name + sfx, dict(kw, **extra)) for name, kw in arms for sfx, extra in (("/off", {}), ("/on", LOGPROBS))]
     with torch.no_grad():
         for batch in (int(b) for b in a.batches.split(",")):
@@ -56,7 +68,7 @@ if a.rounds > 0:
                     if rnd:
                         res[name].append(t)
             for name, _ in arms:
-                print(f"batch {batch:2d} {name:11s}: " + " ".join(f"{x:.3f}" for x in res[name]) +
+                print(f"batch {batch:2d} {name:15s}: " + " ".join(f"{x:.3f}" for x in res[name]) +
                       f"  median {statistics.median(res[name]):.3f} ms/token", flush=True)
     sys.exit(0)
 

@@ -102,14 +102,23 @@ def check_sampler(sampler) -> bool:
     return sampler == "device"
 
 
+def check_ngram_ban(ngram_ban) -> bool:
+    """generate()'s `ngram_ban`: None / "host" = the Python rule on seq.tolist() in the host loop, "device" = ops.ngram_ban (True)."""
+    if ngram_ban not in (None, "host", "device"):
+        raise ValueError(f'unknown ngram_ban {ngram_ban!r} (None / "host": the list rule on the host; "device": one HIP launch per step)')
+    return ngram_ban == "device"
+
+
 def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temperature=1.0, num_beams=1, no_repeat_ngram_size=None,
                         use_cache=None, kv_cache_dtype=None, sampler=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None,
-                        output_logprobs=False, return_dict_in_generate=False, unknown=None, dtype=None, vocab_size=None, config_use_cache=None):
+                        output_logprobs=False, return_dict_in_generate=False, unknown=None, dtype=None, vocab_size=None, config_use_cache=None,
+                        ngram_ban=None):
     """Every refusal of generate()'s arguments that needs no device work, in generate()'s order; evaluate() calls it too, before it starts
     the SAM encoder on the side stream.  No model is needed: what the model decides comes in as plain values, each read only when the
     option it belongs to is set -- `dtype` with kv_cache_dtype, `vocab_size` with sampler="device" (None: the caller does not know it
     and leaves that one refusal to generate(), which always passes it), `config_use_cache` where use_cache is None.  `unknown`: generate()'s
-    **kwargs.  -> (n-gram size or 0, tokens are sampled, on the device, use_cache with the config's default filled in, (k, n-gram size) or None)"""
+    **kwargs.  -> (n-gram size or 0, tokens are sampled, on the device, use_cache with the config's default filled in, (k, n-gram size) or None);
+    whether the ban runs on the device is check_ngram_ban(ngram_ban), checked here against the other options."""
     if num_beams != 1:
         raise NotImplementedError("beam search is not used by the reference callers (num_beams=1)")
     if unknown:
@@ -124,9 +133,12 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
         raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer, but is {no_repeat_ngram_size}")
     sampling = bool(do_sample and temperature and temperature > 0)
     device_sampler = check_sampler(sampler)
-    if device_sampler and ngram:
-        raise ValueError('sampler="device" does not combine with `no_repeat_ngram_size`: the n-gram ban is host-side list work '
-                         '(use sampler=None)')
+    device_ban = check_ngram_ban(ngram_ban)
+    if device_ban and not ngram:
+        raise ValueError('ngram_ban="device" is an option of the n-gram ban: it needs `no_repeat_ngram_size` >= 1')
+    if device_sampler and ngram and not device_ban:
+        raise ValueError('sampler="device" does not combine with `no_repeat_ngram_size` while the n-gram ban is host-side list work '
+                         '(use sampler=None, or ngram_ban="device": the ban in one launch, inside the device loop)')
     if device_sampler and sampling and vocab_size is not None and vocab_size > ops.SAMPLE_MAX_V:
         raise ValueError(f'sampler="device" stages a row of logits in LDS: vocab_size {vocab_size} is above its limit of '
                          f"{ops.SAMPLE_MAX_V} (use sampler=None)")
@@ -139,7 +151,10 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
         if not use_cache:
             raise ValueError("prompt-lookup decoding needs use_cache=True: a verify step runs over a filled KV cache")
         if ngram:
-            raise ValueError("prompt-lookup decoding does not combine with `no_repeat_ngram_size`: the n-gram ban is host-side list work")
+            # (on the host or on the device alike)
+            raise ValueError("prompt-lookup decoding does not combine with `no_repeat_ngram_size`: a draft is the continuation of a repeated "
+                             "n-gram, so its first token is what the ban forbids (max_matching_ngram_size >= no_repeat_ngram_size - 1) and "
+                             "the pair could only reject drafts")
         if attention_mask is not None and not bool(attention_mask.ne(0).all()):
             raise ValueError("prompt-lookup decoding does not take a padded attention mask (one unpadded row)")
         if sampling and not device_sampler:
@@ -148,7 +163,8 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
         _check_kv_dtype(kv_cache_dtype, dtype)
         if not use_cache:
             raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r} needs use_cache=True: without a KV cache there is nothing to quantize")
-    for on, what in ((lookup is not None, "prompt-lookup decoding"), (device_sampler and sampling, 'sampler="device"'), (output_logprobs, "output_logprobs")):
+    for on, what in ((lookup is not None, "prompt-lookup decoding"), (device_sampler and sampling, 'sampler="device"'), (output_logprobs, "output_logprobs"),
+                     (device_ban, 'ngram_ban="device"')):
         if on and input_ids is not None and not input_ids.is_cuda:
             raise RuntimeError(f"{what} needs GPU tensors (no CPU path exists)")
     return ngram, sampling, device_sampler, use_cache, lookup
@@ -200,24 +216,30 @@ class Decoding:
         return GenerateOutput(sequences=seq, hidden_states=hidden, **({} if logprobs is None else dict(logprobs=logprobs)))
 
 
-def host_loop(d: Decoding, seq, ngram: int, probs=sampling_probs):
+def host_loop(d: Decoding, seq, ngram: int, probs=sampling_probs, device_ban: bool = False):
     """One token per step, picked by torch on the host's schedule: the n-gram ban, torch.multinomial on sampling_probs (or argmax), pad fill
     and EOS bookkeeping per row, one host read per step.  probs: generate() hands in the `sampling_probs` of its own module, so that a
-    wrapper installed there (the tests record the logits that way) is the one that runs.  -> (ids, logprobs or None)"""
+    wrapper installed there (the tests record the logits that way) is the one that runs.  device_ban: the ban is ops.ngram_ban on the
+    model-dtype logits (-inf where the list rule puts it, the same fp32 values after .float()) instead of tolist() + the Python rule + one
+    indexed store per row.  -> (ids, logprobs or None)"""
     B = seq.shape[0]
     unfinished = torch.ones(B, dtype=torch.bool, device=seq.device)
     lp_cols = []
     for step in range(d.max_new_tokens):
         out = d.forward(seq, step)
-        logits = out.logits[:, -1].float()
-        if d.output_logprobs and ngram > 0 and logits.dtype == out.logits.dtype:
-            logits = logits.clone()                              # an fp32 model: .float() is a view, and the ban must not reach the scored logits
-        if ngram > 0:
-            # HF NoRepeatNGramLogitsProcessor (logits processors run before the sampling warpers): tokens that would complete an
-            # n-gram already present in the row (prompt included) get -inf
-            for b_, banned in enumerate(no_repeat_ngram_banned_tokens(seq.tolist(), ngram)):
-                if banned:
-                    logits[b_, torch.as_tensor(banned, device=logits.device)] = float("-inf")
+        if ngram > 0 and device_ban:
+            # the processor below in one launch, into a new tensor: the scored logits stay raw
+            logits = ops.ngram_ban(out.logits[:, -1], seq, seq.shape[1], ngram).float()
+        else:
+            logits = out.logits[:, -1].float()
+            if d.output_logprobs and ngram > 0 and logits.dtype == out.logits.dtype:
+                logits = logits.clone()                          # an fp32 model: .float() is a view, and the ban must not reach the scored logits
+            if ngram > 0:
+                # HF NoRepeatNGramLogitsProcessor (logits processors run before the sampling warpers): tokens that would complete an
+                # n-gram already present in the row (prompt included) get -inf
+                for b_, banned in enumerate(no_repeat_ngram_banned_tokens(seq.tolist(), ngram)):
+                    if banned:
+                        logits[b_, torch.as_tensor(banned, device=logits.device)] = float("-inf")
         nxt = torch.multinomial(probs(logits, d.temperature, d.top_k, d.top_p), 1) if d.sampling else logits.argmax(-1, keepdim=True)
         if d.pad is not None:
             nxt = torch.where(unfinished.unsqueeze(1), nxt, torch.full_like(nxt, d.pad))      # finished rows: pad fill
@@ -236,12 +258,14 @@ def host_loop(d: Decoding, seq, ngram: int, probs=sampling_probs):
     return seq, torch.stack(lp_cols, dim=1) if lp_cols else torch.zeros(B, 0, dtype=torch.float32, device=seq.device)
 
 
-def fused_loop(d: Decoding, seq):
+def fused_loop(d: Decoding, seq, ngram: int = 0):
     """Greedy decoding, or sampler="device", with the whole step on the device: the tokens land in a pre-sized [B, L0 + max_new_tokens]
     buffer, the pick / pad-fill / EOS bookkeeping is ONE kernel (ops.greedy_step / ops.sample_step), and the host looks at the "rows still
     unfinished" counters only every `check` steps (every step when a stopping criterion needs the ids on the host anyway).  Steps that run
     past the point where every row had finished only produce pad tokens; ids, cache and hidden states are trimmed to what a per-step check
-    returns.  -> (ids, logprobs or None)"""
+    returns.  ngram > 0 (ngram_ban="device"): one more launch per step, ops.ngram_ban, copies the last-position logits into a [B, V] scratch
+    with the banned tokens at -inf -- it reads the ids in `buf`, pad fill included, as HF's processor does -- and the pick runs on the
+    scratch; the log-probabilities keep scoring the raw logits.  -> (ids, logprobs or None)"""
     B, L0 = seq.shape
     n_max, dev = d.max_new_tokens, seq.device
     buf = torch.empty(B, L0 + n_max, dtype=torch.int64, device=dev)
@@ -253,18 +277,24 @@ def fused_loop(d: Decoding, seq):
         # the step kernels update `live` in place and the score needs it as it stood BEFORE the step: a snapshot per step
         lp = torch.zeros(B, n_max, dtype=torch.float32, device=dev)
         live_before = torch.empty_like(live)
+    banned = None                                                # the step's logits under the n-gram ban: allocated once, at the first step
     check = 1 if d.crit else 8
     n_done = n_tok = 0                                           # tokens appended so far; tokens after which every row had finished
     for step in range(n_max):
         last = d.forward(buf[:, :L0 + step], step).logits[:, -1]
         if lp is not None:
             live_before.copy_(live)
+        pick = last
+        if ngram > 0:
+            if banned is None:
+                banned = torch.empty(last.shape, dtype=last.dtype, device=dev)
+            pick = ops.ngram_ban(last, buf, L0 + step, ngram, out=banned)
         if d.sampling:
             # torch's noise, drawn as torch.multinomial draws it: the generator moves as it does on the host path
             noise = torch.empty(last.shape, dtype=torch.float32, device=last.device).exponential_()
-            ops.sample_step(last, noise, d.temperature, d.top_k, d.top_p, live, d.eos_ids, d.pad, buf, L0 + step, alive[step:step + 1])
+            ops.sample_step(pick, noise, d.temperature, d.top_k, d.top_p, live, d.eos_ids, d.pad, buf, L0 + step, alive[step:step + 1])
         else:
-            ops.greedy_step(last, live, d.eos_ids, d.pad, buf, L0 + step, alive[step:step + 1])
+            ops.greedy_step(pick, live, d.eos_ids, d.pad, buf, L0 + step, alive[step:step + 1])
         if lp is not None:
             ops.token_logprobs(last, buf[:, L0 + step], live_before, out=lp[:, step])
         n_done = n_tok = step + 1

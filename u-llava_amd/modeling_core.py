@@ -23,8 +23,8 @@ from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaCoreConfig
 # (imported by name: the cache and the decoding helpers stay importable from this module)
-from .generation import (Decoding, GenerateOutput, check_generate_args, check_prompt_lookup, check_sampler, fused_loop, host_loop,
-                         no_repeat_ngram_banned_tokens, prompt_lookup_candidates, prompt_lookup_loop, sampling_probs)
+from .generation import (Decoding, GenerateOutput, check_generate_args, check_ngram_ban, check_prompt_lookup, check_sampler, fused_loop,
+                         host_loop, no_repeat_ngram_banned_tokens, prompt_lookup_candidates, prompt_lookup_loop, sampling_probs)
 from .kv_cache import DEFAULT_HEADROOM, KV_CACHE_DTYPES, KVCache, _check_kv_dtype
 
 BF16 = torch.bfloat16
@@ -1160,8 +1160,8 @@ class UllavaCoreForCausalLM(nn.Module):
     def generate(self, input_ids=None, images=None, videos=None, attention_mask=None, max_new_tokens=32, do_sample=False,
                  temperature=1.0, top_p=None, top_k=50, num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, eos_token_id=None,
                  pad_token_id=None, output_hidden_states=False, return_dict_in_generate=False, use_cache=None,
-                 keep_last_step_only=False, kv_cache_dtype=None, sampler=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None,
-                 output_logprobs=False, **kwargs):
+                 keep_last_step_only=False, kv_cache_dtype=None, sampler=None, ngram_ban=None, prompt_lookup_num_tokens=None,
+                 max_matching_ngram_size=None, output_logprobs=False, **kwargs):
         """Token-by-token decoding with HF GenerationMixin's greedy / sampling semantics (the reference inherits `generate`):
         every step goes through `prepare_inputs_for_generation` (position_ids = cumsum(attention_mask) - 1, so left-padded batches
         get the reference's RoPE positions); `eos_token_id` defaults to `config.eos_token_id` (int or list); rows that have emitted
@@ -1177,7 +1177,13 @@ class UllavaCoreForCausalLM(nn.Module):
         same distribution, the same torch noise, so a seeded run draws the host path's tokens) inside the device-resident loop greedy
         decoding uses.  That loop looks at the host every 8 steps, so it may run up to 7 steps past the point where every row had
         finished: the returned ids are trimmed and equal, but the global generator has advanced further than on the host path.
-        It does not combine with `no_repeat_ngram_size` (host-side list work).
+        It does not combine with `no_repeat_ngram_size` (host-side list work) unless ngram_ban="device".
+        ngram_ban="device" (opt-in, needs no_repeat_ngram_size >= 1; None and "host" are the list rule on the host, which sends every
+        decoding to the per-step host loop): the ban is one launch per step (ops.ngram_ban: a copy of the last-position logits with -inf
+        at the tokens `no_repeat_ngram_banned_tokens` names, read from the ids on the device).  Greedy decoding and sampler="device" then
+        stay in the device-resident loop and pick from that copy; the host sampler keeps its loop and only skips the tolist() and the
+        Python rule.  The ids are the host ban's, bit for bit, from the same logits; `logprobs` still score the raw logits.  GPU tensors
+        only.  Prompt-lookup stays refused with either ban: a draft is the continuation of a repeated n-gram, what the ban forbids.
         prompt_lookup_num_tokens=k (opt-in, 1..15; HF's option of the same name, with max_matching_ngram_size, default 2): prompt-lookup
         speculative decoding.  Each step drafts up to k tokens by copying what followed an earlier occurrence of the row's trailing n-gram
         (`prompt_lookup_candidates`), runs ONE forward over the last token and the drafts, and emits the accepted drafts plus one more token
@@ -1199,7 +1205,8 @@ class UllavaCoreForCausalLM(nn.Module):
             input_ids, attention_mask, do_sample=do_sample, temperature=temperature, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size,
             use_cache=use_cache, kv_cache_dtype=kv_cache_dtype, sampler=sampler, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
             max_matching_ngram_size=max_matching_ngram_size, output_logprobs=output_logprobs, return_dict_in_generate=return_dict_in_generate,
-            unknown=kwargs, dtype=self.dtype, vocab_size=cfg.vocab_size, config_use_cache=cfg.use_cache)
+            unknown=kwargs, dtype=self.dtype, vocab_size=cfg.vocab_size, config_use_cache=cfg.use_cache, ngram_ban=ngram_ban)
+        device_ban = check_ngram_ban(ngram_ban)
         seq = input_ids
         eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
         eos_ids = None if eos is None else torch.as_tensor([eos] if isinstance(eos, int) else list(eos), device=seq.device, dtype=seq.dtype)
@@ -1221,8 +1228,8 @@ class UllavaCoreForCausalLM(nn.Module):
                      output_hidden_states, keep_last_step_only, output_logprobs)
         if lookup is not None:
             seq, logprobs = prompt_lookup_loop(d, seq, lookup)
-        elif (not sampling or device_sampler) and ngram == 0 and seq.is_cuda:
-            seq, logprobs = fused_loop(d, seq)
+        elif (not sampling or device_sampler) and (ngram == 0 or device_ban) and seq.is_cuda:
+            seq, logprobs = fused_loop(d, seq, ngram)
         else:
-            seq, logprobs = host_loop(d, seq, ngram, sampling_probs)
+            seq, logprobs = host_loop(d, seq, ngram, sampling_probs, device_ban)
         return d.result(seq, logprobs, return_dict_in_generate)

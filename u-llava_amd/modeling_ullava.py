@@ -318,11 +318,13 @@ class UllavaForCausalLM(nn.Module):
 
     @torch.no_grad()
     def evaluate(self, images_sam, images, input_ids, raw_size_list, resize_list, max_new_tokens=32, temperature=0.2, top_p=None,
-                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None,
-                 max_matching_ngram_size=None, output_logprobs=False, sampler=None):
+                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None, ngram_ban=None,
+                 prompt_lookup_num_tokens=None, max_matching_ngram_size=None, output_logprobs=False, sampler=None):
         """reference ullava.py:335-434 -> (output_ids, pred_masks, pred_boxes).  kv_cache_dtype="fp8_e4m3": generate with an fp8 KV cache
         (which implies use_cache=True; see UllavaCoreForCausalLM.generate).  sampler="device": draw the tokens with the on-device sampler
-        (same ids under the same seed; see generate).  prompt_lookup_num_tokens / max_matching_ngram_size: prompt-lookup speculative decoding
+        (same ids under the same seed; see generate).  ngram_ban="device" (with no_repeat_ngram_size): the n-gram ban in one launch per step, so
+        that greedy decoding and sampler="device" keep the device-resident loop (the host ban's ids; see generate).
+        prompt_lookup_num_tokens / max_matching_ngram_size: prompt-lookup speculative decoding
         (which implies use_cache=True; batch 1; with temperature > 0 it needs sampler="device"; see generate) -- the [SEG] / [LOC] rows are
         read from the hidden states of the accepted positions.  output_logprobs=True: the return grows to (output_ids, pred_masks, pred_boxes,
         logprobs), logprobs fp32 [B, n_new] as generate(output_logprobs=True) gives them (raw distribution; 0.0 after a row's EOS) -- the
@@ -330,7 +332,7 @@ class UllavaForCausalLM(nn.Module):
         # generate()'s refusals, before the SAM encoder starts (the model's dtype is asked for only where kv_cache_dtype needs it)
         gen = dict(do_sample=temperature > 0, temperature=temperature, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size,
                    sampler=sampler, return_dict_in_generate=True, output_logprobs=output_logprobs, kv_cache_dtype=kv_cache_dtype,
-                   prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
+                   prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size, ngram_ban=ngram_ban,
                    use_cache=True if kv_cache_dtype is not None or prompt_lookup_num_tokens is not None else None)
         check_generate_args(input_ids, dtype=None if kv_cache_dtype is None else self.llm.dtype, **gen)
         main = torch.cuda.current_stream()                          # SAM image encoder on the second stream, under the generation loop

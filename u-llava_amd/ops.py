@@ -1243,6 +1243,39 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, row_mask: Optional[t
     return out
 
 
+def ngram_ban(logits: torch.Tensor, ids: torch.Tensor, cur_len: int, ngram: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """HF's NoRepeatNGramLogitsProcessor in one launch (see ull_ngram_ban): out = logits bit for bit, with -inf at the tokens
+    `generation.no_repeat_ngram_banned_tokens(ids[:, :cur_len], ngram)` names (those outside [0, V) skipped).  logits [R, V] bf16 / fp16 /
+    fp32, rows may be strided (`out.logits[:, -1]`); ids int64 [R, >= cur_len] with contiguous rows of any pitch (the generate buffer);
+    out: [R, V] of the logits' dtype with contiguous rows, not overlapping logits; allocated when None, returned."""
+    _chk(logits, "logits")
+    if logits.dim() != 2:
+        raise RuntimeError(f"u-llava_amd.ngram_ban: logits must be [R, V], got {tuple(logits.shape)}")
+    R, V = logits.shape
+    _chk(ids, "ids", torch.int64)
+    cur_len, ngram = int(cur_len), int(ngram)
+    if ngram < 1 or cur_len < 0:
+        raise ValueError(f"u-llava_amd.ngram_ban: ngram must be >= 1 and cur_len >= 0, got ngram = {ngram}, cur_len = {cur_len}")
+    if ids.dim() != 2 or ids.shape[0] != R or ids.shape[1] < cur_len:
+        raise RuntimeError(f"u-llava_amd.ngram_ban: ids must be torch.int64 [{R}, >= {cur_len}], got {tuple(ids.shape)}")
+    if out is None:
+        out = torch.empty(R, V, device=logits.device, dtype=logits.dtype)
+    else:
+        _chk(out, "out", logits.dtype)
+        if tuple(out.shape) != (R, V):
+            raise RuntimeError(f"u-llava_amd.ngram_ban: out must be [{R}, {V}], got {tuple(out.shape)}")
+    if V == 0 or any(t.stride(0) < 0 for t in (logits, ids, out)) or (R > 1 and out.stride(0) < V):
+        raise RuntimeError("u-llava_amd.ngram_ban: empty rows / negative strides / overlapping rows of `out` are not supported")
+    if R:
+        esz = logits.element_size()
+        lo, oo = logits.data_ptr(), out.data_ptr()
+        if lo < oo + ((R - 1) * out.stride(0) + V) * esz and oo < lo + ((R - 1) * logits.stride(0) + V) * esz:
+            raise RuntimeError("u-llava_amd.ngram_ban: `out` must not overlap `logits` (the ban is not applied in place)")
+        _lib.call("ull_ngram_ban", _p(logits), DT_CODE[logits.dtype], logits.stride(0), R, V, _p(ids), ids.stride(0), cur_len, ngram, _p(out),
+                  max(out.stride(0), V), _stream())
+    return out
+
+
 def video_pool(f: torch.Tensor, B: int, T: int, N: int, tok_pitch: Optional[int] = None, tok_off: int = 0) -> torch.Tensor:
     """f [B*T, tok_pitch, D]; patches are tokens tok_off..tok_off+N of every frame."""
     _chk(f, "f")
