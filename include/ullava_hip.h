@@ -394,6 +394,39 @@ int ull_token_logprobs(const void* logits, int logits_dtype, int64_t row_stride,
 int ull_ngram_ban(const void* logits, int logits_dtype, int64_t row_stride, int64_t R, int64_t V, const void* ids, int64_t ids_ld,
                   int64_t cur_len, int64_t ngram, void* out, int64_t out_ld, void* stream);
 
+/* One step of HF `GenerationMixin._beam_search` with do_sample=False (hf: generation/utils.py; the `num_beams` the reference's evaluate(),
+ * models/ullava.py:346,360, forwards) for the whole batch, in two launches, compiled once (logits_dtype ULL_DT_F32 0 / BF16 1 / F16 2).  The
+ * rule is `generation.beam_search_reference`, steps 1-7.  logits: B * Kin rows of V entries, row_stride elements apart, Kin == K, or
+ * Kin == 1: only beam 0 of every item exists (the prefill step) and the result is what K identical rows give.  pick (or NULL: the logits
+ * themselves): the same rows as ull_ngram_ban wrote them, pick_stride elements apart; a candidate's log-probability is
+ * float(pick[j]) - max_r - logf(sum_r) with max_r / sum_r of the raw row exactly as ull_token_logprobs takes them (the same bits), plus
+ * the beam's running score.  KK = max(2, 1 + n_eos) * K candidates per item are kept, by (score descending, k * V + j ascending).
+ * State of an item (K beams; ids int64 rows of Lmax entries, `cur` of them valid, the pad id behind): run_in -> run_out and pool_in -> pool_out
+ * (the running and the finished ids; in and out must differ), run_sc / pool_sc fp32 [B*K], pool_len / fin int32 [B*K], open int32 [B], all
+ * updated in place.  pow_fin = fp32((cur + 1 - L0) ** length_penalty) and pow_hyp = fp32(hyp ** length_penalty) divide the finished and the
+ * best running score (IEEE fp32 division); early_stopping 0 False / 1 True / 2 "never".  parent int32 [B*K]: the row of run_in (batch offset
+ * included) each row of run_out continues; go int32 [1]: whether the loop goes on after this step.  cand_v fp32 / cand_t int32
+ * [B * K * ULL_BEAM_MAX_CAND]: scratch between the two launches.  K in 1..ULL_BEAM_MAX_K, L0 <= cur < Lmax (ULL_ERR_ARG otherwise);
+ * (1 + n_eos) * K > ULL_BEAM_MAX_CAND or K * V < KK: ULL_ERR_SHAPE.  A NaN logit gives unspecified candidates, with tokens in [0, V) and
+ * parents inside their item.  Fixed-order reductions, no floating-point atomics: the same inputs give the same bits. */
+#define ULL_BEAM_MAX_K 16
+#define ULL_BEAM_MAX_CAND 64
+int ull_beam_step(const void* logits, int logits_dtype, int64_t row_stride, const void* pick, int64_t pick_stride, int64_t B, int64_t Kin,
+                  int64_t K, int64_t V, const void* run_in, void* run_out, const void* pool_in, void* pool_out, void* run_sc, void* pool_sc,
+                  void* pool_len, void* fin, void* open, const void* eos, int64_t n_eos, int64_t pad, int64_t Lmax, int64_t L0, int64_t cur,
+                  float pow_fin, float pow_hyp, int early_stopping, void* cand_v, void* cand_t, void* parent, void* go, void* stream);
+
+/* Rows of a KV cache copied between two sets of per-layer buffers (K [rows, H, smax, hd], V^T [rows, H, hd, smax] in ull_transpose_v's
+ * 32-key block permutation; elem_size 2 or 4 bytes) in one launch per 64 layers: for every layer and every destination row r with
+ * skip[r] != r, positions [dst_p0, dst_p0 + n) of row r become positions [src_p0, src_p0 + n) of source row row_map[r] (int32, device;
+ * NULL: r itself; a row outside [0, src_rows) is left alone).  skip: int32 [dst_rows] or NULL.  V^T is copied in the whole 32-key blocks
+ * the range touches, so src_p0 and dst_p0 must agree mod 32.  src_k / src_vt / dst_k / dst_vt: HOST arrays of n_layers device pointers.
+ * Source and destination buffers must not overlap where rows move (a reorder in place goes through a scratch: two calls).  smax not a
+ * multiple of 32, a range past smax, hd * elem_size not a multiple of 16, a base not 16-byte aligned, dst_rows * H > 65535: ULL_ERR_SHAPE. */
+int ull_kv_gather_rows(const void* const* src_k, const void* const* src_vt, void* const* dst_k, void* const* dst_vt, int64_t n_layers,
+                       int64_t src_rows, int64_t dst_rows, int64_t H, int64_t hd, int64_t elem_size, int64_t src_smax, int64_t dst_smax,
+                       int64_t src_p0, int64_t dst_p0, int64_t n, const void* row_map, const void* skip, void* stream);
+
 /* models/ullava_core.py:191,243-245,266-268: token-embedding lookup with the projected visual tokens spliced in after
  * the first start token (the torch.cat of the reference, done as one gather).  Image i's n_img_tok feature rows start
  * at row i*img_pitch + img_off of img_feat (pitch = patches + 1, off = 1 skips the CLS row without a copy).

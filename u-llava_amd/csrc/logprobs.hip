@@ -14,43 +14,18 @@
 // floating-point atomics): the same inputs give the same bits on every run.
 #include "ull_common.h"
 #include "select.h"
+#include "logsumexp.h"
 
 namespace {
 
-constexpr int LP_THREADS = 1024;
 constexpr int LP_MAX_GRID = 1 << 16;
-
-struct LpScratch {
-    float f[16];
-};
-
-ULL_DEV float lp_block_max(float v, LpScratch& sc) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sc.f[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = sc.f[0];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) t = fmaxf(t, sc.f[w]);
-    return t;
-}
-ULL_DEV float lp_block_sum(float v, LpScratch& sc) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sc.f[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) t += sc.f[w];
-    return t;
-}
 
 template <int DT>
 __global__ __launch_bounds__(LP_THREADS) void token_logprobs_kernel(const void* __restrict__ logits, long row_stride, long R, int V,
                                                                     const int64_t* __restrict__ ids, long ids_stride,
                                                                     const int32_t* __restrict__ row_mask, float* __restrict__ out, long out_stride) {
     __shared__ LpScratch sc;
-    constexpr int ESZ = DT == ULL_DT_F32 ? 4 : 2, EPC = 16 / ESZ;
+    constexpr int ESZ = DT == ULL_DT_F32 ? 4 : 2;
     const int tid = threadIdx.x;
     for (long r = blockIdx.x; r < R; r += gridDim.x) {             // (every branch below is uniform over the block)
         const int64_t id = ids[r * ids_stride];
@@ -59,59 +34,8 @@ __global__ __launch_bounds__(LP_THREADS) void token_logprobs_kernel(const void* 
             continue;
         }
         const char* row = (const char*)logits + r * row_stride * ESZ;
-        // The sum gives every element to the same thread on either load path -- element i of the nfull whole chunks to thread (i / EPC) % 1024,
-        // element i of the tail behind them to thread (i - nfull * EPC) % 1024 -- and every thread adds its elements in increasing order, chunks
-        // before tail: the sum's bits depend on the row's values alone, not on where the row lies (a verify step's odd rows against the plain
-        // loop's aligned ones).  The maximum needs no such care.  The element-wise loops count in long: V + 1023 may pass 2^31.
-        const bool vec = ((uintptr_t)row & 15) == 0;
-        const int nfull = V / EPC, nchunk = vec ? nfull : 0;
-
-        // ---- 1. the maximum; q0 keeps the first round of chunks for step 2
-        uint4 q0[4] = {};
-        float m = -INFINITY;
-        for (int c0 = tid; c0 < nchunk; c0 += 4 * LP_THREADS) {
-            uint4 q[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) q[u] = c0 + u * LP_THREADS < nchunk ? *(const uint4*)(row + (long)(c0 + u * LP_THREADS) * 16) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (c0 == tid) q0[u] = q[u];
-                if (c0 + u * LP_THREADS < nchunk) {
-                    float f[EPC];
-                    unpack_chunk<DT>(q[u], f);
-#pragma unroll
-                    for (int j = 0; j < EPC; ++j) m = fmaxf(m, f[j]);
-                }
-            }
-        }
-        for (long c = (vec ? (long)nfull * EPC : 0) + tid; c < V; c += LP_THREADS) m = fmaxf(m, load_dt<DT>(row, c));
-        m = lp_block_max(m, sc);
-
-        // ---- 2. the sum of exp(x - max)
-        float s = 0.f;
-        for (int c0 = tid; c0 < nchunk; c0 += 4 * LP_THREADS) {
-            uint4 q[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (c0 == tid) q[u] = q0[u];
-                else q[u] = c0 + u * LP_THREADS < nchunk ? *(const uint4*)(row + (long)(c0 + u * LP_THREADS) * 16) : make_uint4(0, 0, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (c0 + u * LP_THREADS < nchunk) {
-                    float f[EPC];
-                    unpack_chunk<DT>(q[u], f);
-#pragma unroll
-                    for (int j = 0; j < EPC; ++j) s += expf(f[j] - m);
-                }
-            }
-        }
-        if (!vec)
-            for (int c = tid; c < nfull; c += LP_THREADS)
-#pragma unroll
-                for (int j = 0; j < EPC; ++j) s += expf(load_dt<DT>(row, (long)c * EPC + j) - m);
-        for (long c = (long)nfull * EPC + tid; c < V; c += LP_THREADS) s += expf(load_dt<DT>(row, c) - m);
-        s = lp_block_sum(s, sc);
+        float m, s;
+        lp_row_max_sum<DT>(row, V, sc, m, s);              // (logsumexp.h: the beam step takes the same two numbers)
 
         // ---- 3. the chosen token's entry (id was checked against [0, V) above)
         if (tid == 0) out[r * out_stride] = load_dt<DT>(row, (long)id) - m - logf(s);      // (the next row's reductions start with a barrier)

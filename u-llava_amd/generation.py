@@ -109,18 +109,40 @@ def check_ngram_ban(ngram_ban) -> bool:
     return ngram_ban == "device"
 
 
+def check_num_beams(num_beams, length_penalty=1.0, early_stopping=False, num_return_sequences=1) -> int:
+    """generate()'s `num_beams` and the three options that belong to it -> the number of beams (1: no beam search)."""
+    if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= ops.BEAM_MAX_K:
+        raise ValueError(f"`num_beams` has to be an integer in 1..{ops.BEAM_MAX_K}, but is {num_beams!r}")
+    if not (early_stopping is False or early_stopping is True or early_stopping == "never"):
+        raise ValueError(f'`early_stopping` has to be False, True or "never", but is {early_stopping!r}')
+    if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or num_return_sequences < 1:
+        raise ValueError(f"`num_return_sequences` has to be a positive integer, but is {num_return_sequences!r}")
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)):
+        raise ValueError(f"`length_penalty` has to be a number, but is {length_penalty!r}")
+    if num_beams == 1:
+        for name, value, default in (("length_penalty", length_penalty, 1.0), ("early_stopping", early_stopping, False),
+                                     ("num_return_sequences", num_return_sequences, 1)):
+            if value is not default and value != default or isinstance(value, str):
+                raise ValueError(f"`{name}={value!r}` is an option of beam search: it needs `num_beams` > 1")
+    elif num_return_sequences > num_beams:
+        raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be at most `num_beams` ({num_beams})")
+    return num_beams
+
+
 def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temperature=1.0, num_beams=1, no_repeat_ngram_size=None,
                         use_cache=None, kv_cache_dtype=None, sampler=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None,
                         output_logprobs=False, return_dict_in_generate=False, unknown=None, dtype=None, vocab_size=None, config_use_cache=None,
-                        ngram_ban=None):
+                        ngram_ban=None, length_penalty=1.0, early_stopping=False, num_return_sequences=1, stopping_criteria=None,
+                        output_hidden_states=False, n_eos=None):
     """Every refusal of generate()'s arguments that needs no device work, in generate()'s order; evaluate() calls it too, before it starts
     the SAM encoder on the side stream.  No model is needed: what the model decides comes in as plain values, each read only when the
     option it belongs to is set -- `dtype` with kv_cache_dtype, `vocab_size` with sampler="device" (None: the caller does not know it
     and leaves that one refusal to generate(), which always passes it), `config_use_cache` where use_cache is None.  `unknown`: generate()'s
     **kwargs.  -> (n-gram size or 0, tokens are sampled, on the device, use_cache with the config's default filled in, (k, n-gram size) or None);
-    whether the ban runs on the device is check_ngram_ban(ngram_ban), checked here against the other options."""
-    if num_beams != 1:
-        raise NotImplementedError("beam search is not used by the reference callers (num_beams=1)")
+    whether the ban runs on the device is check_ngram_ban(ngram_ban), checked here against the other options.  Beam search (num_beams > 1;
+    check_num_beams for the option values) is refused with everything its loop does not define -- stopping_criteria, output_hidden_states and
+    the number of EOS ids `n_eos` (None: not known) come in for that alone -- and on tensors that are not on the GPU."""
+    beams = check_num_beams(num_beams, length_penalty, early_stopping, num_return_sequences)
     if unknown:
         # HF generate() validates its model kwargs and raises on unknown ones; options this loop does not implement must not be
         # swallowed (a silently ignored `repetition_penalty` changes the ids)
@@ -163,6 +185,30 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
         _check_kv_dtype(kv_cache_dtype, dtype)
         if not use_cache:
             raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r} needs use_cache=True: without a KV cache there is nothing to quantize")
+    if beams > 1:
+        # beam search (beam_loop): deterministic, in its own device loop; what it does not define is refused, with the way out
+        for on, what in ((sampling, "do_sample=True with temperature > 0 (beam sampling is not implemented: use do_sample=False)"),
+                         (device_sampler, 'sampler="device" (beam search picks by score: leave `sampler` unset)'),
+                         (lookup is not None, "prompt-lookup decoding (drop `prompt_lookup_num_tokens`: the beams already share one forward)"),
+                         (bool(stopping_criteria), "`stopping_criteria` (HF calls them per candidate row and the reference's criterion answers "
+                                                   "with one bool: use `eos_token_id`)"),
+                         (output_logprobs, "output_logprobs=True (read `sequences_scores`, or score the result with score())"),
+                         (kv_cache_dtype is not None, f"kv_cache_dtype={kv_cache_dtype!r} (the fp8 cache is not reordered: leave it unset)"),
+                         (bool(ngram) and not device_ban, '`no_repeat_ngram_size` with the host ban (pass ngram_ban="device")')):
+            if on:
+                raise ValueError(f"num_beams={beams} does not combine with {what}")
+        if output_hidden_states:
+            raise NotImplementedError(f"num_beams={beams} does not return hidden states (the rows of a step are reordered by the next one; "
+                                      "evaluate() therefore decodes with num_beams=1)")
+        kk = ops.beam_candidates(beams, 1 if n_eos is None else n_eos)
+        if n_eos is not None and (1 + n_eos) * beams > ops.BEAM_MAX_CAND:
+            raise ValueError(f"num_beams={beams} with {n_eos} EOS ids: a step keeps (1 + EOS ids) * num_beams <= {ops.BEAM_MAX_CAND} candidates "
+                             "(pass fewer EOS ids or fewer beams)")
+        if vocab_size is not None and vocab_size * beams < kk:
+            raise ValueError(f"num_beams={beams} needs {kk} candidates per step and vocab_size * num_beams = {vocab_size * beams} is fewer "
+                             "(use fewer beams)")
+        if input_ids is None or not input_ids.is_cuda:
+            raise NotImplementedError("beam search needs GPU tensors (no CPU path exists)")
     for on, what in ((lookup is not None, "prompt-lookup decoding"), (device_sampler and sampling, 'sampler="device"'), (output_logprobs, "output_logprobs"),
                      (device_ban, 'ngram_ban="device"')):
         if on and input_ids is not None and not input_ids.is_cuda:
@@ -349,3 +395,194 @@ def prompt_lookup_loop(d: Decoding, seq, lookup):
         if finished or d.stopped(buf[:, :n]):
             break
     return buf[:, :n].contiguous(), None if lp is None else lp[:n - L0].unsqueeze(0).clone()
+
+
+# ------------------------------------------------------------------------------------------------------------------ beam search
+BEAM_NEG = -1.0e9
+
+
+class BeamState:
+    """The state of deterministic beam search (HF `GenerationMixin._beam_search`, do_sample=False) for B items of K beams, as tensors on
+    `device`: the running ids run [B, K, Lmax] (Lmax = L0 + max_new_tokens, the pad id behind the prompt) with scores run_sc [B, K] =
+    [0, -1e9, ...]; the pool of finished hypotheses pool [B, K, Lmax] (copies of the padded prompt), pool_sc = -1e9, pool_len = 0, fin = 0
+    (int32); open [B] = 1 (int32): the item's best running beam can still beat its worst finished one."""
+
+    def __init__(self, input_ids, num_beams: int, max_new_tokens: int, pad: int, device=None):
+        dev = input_ids.device if device is None else device
+        B, L0 = input_ids.shape
+        K = num_beams
+        self.B, self.K, self.L0, self.Lmax, self.pad = B, K, L0, L0 + max_new_tokens, int(pad)
+        self.run = torch.full((B, K, self.Lmax), int(pad), dtype=torch.int64, device=dev)
+        self.run[:, :, :L0] = input_ids.to(dev).unsqueeze(1)
+        self.pool = self.run.clone()
+        self.run_sc = torch.full((B, K), BEAM_NEG, dtype=torch.float32, device=dev)
+        self.run_sc[:, 0] = 0.0
+        self.pool_sc = torch.full((B, K), BEAM_NEG, dtype=torch.float32, device=dev)
+        self.pool_len = torch.zeros(B, K, dtype=torch.int32, device=dev)
+        self.fin = torch.zeros(B, K, dtype=torch.int32, device=dev)
+        self.open = torch.ones(B, dtype=torch.int32, device=dev)
+
+    def result(self, num_return_sequences: int):
+        """(sequences [B * n, L0 + longest returned hypothesis], sequences_scores fp32 [B * n]): the first n pool rows of every item."""
+        n = num_return_sequences
+        longest = int(self.pool_len[:, :n].max()) if self.pool_len.numel() else 0
+        return (self.pool[:, :n, :self.L0 + longest].reshape(self.B * n, -1).contiguous(), self.pool_sc[:, :n].reshape(-1).clone())
+
+
+def beam_powers(cur: int, L0: int, Lmax: int, length_penalty, early_stopping):
+    """The two powers of the length penalty at a step that starts with `cur` valid ids, computed in Python double (the step's kernels and
+    the host rule round each to fp32 once and divide by it): the one a hypothesis finished at this step is divided by, and the one the
+    best running beam is divided by after the step."""
+    hyp = Lmax - L0 if (early_stopping == "never" and length_penalty > 0) else cur + 1 - L0
+    return float((cur + 1 - L0) ** length_penalty), float(hyp ** length_penalty)
+
+
+def _first_k(values, k: int):
+    """indices of the k largest entries of a 1-D CPU tensor, descending, the lowest index first among equals (torch.topk leaves that open)."""
+    return torch.sort(values, descending=True, stable=True).indices[:k]
+
+
+def beam_step_reference(st: BeamState, lp, cur: int, eos_ids, length_penalty=1.0, early_stopping=False) -> tuple:
+    """One step of the beam-search rule on a BeamState of CPU tensors, in fp32 -- the written form of what ops.beam_step does.
+    lp: fp32 [B, K, V], log_softmax of the step's logits per beam row with the n-gram ban's -inf already on it; cur: valid ids per row.
+    With n_eos EOS ids, KK = max(2, 1 + n_eos) * K.
+      1. acc[k, j] = lp[k, j] + run_sc[k].
+      2. The KK largest acc over the flat index k * V + j, ties to the lowest flat index -> (tv, parent, tok), descending; a candidate
+         is run[parent] with tok at `cur`.
+      3. hit = tok in eos or cur + 1 == Lmax.
+      4. rv = tv + (-1e9 where hit); the K largest rv (same tie rule) become run / run_sc.
+      5. fv = tv / fp32((cur + 1 - L0) ** length_penalty), plus -1e9 where (early_stopping is True and all of fin) or not open or the
+         candidate is not (hit and among the first K); [pool ; candidates], pool first, keep the K largest; a finished candidate's
+         length is cur + 1 - L0.
+      6. best = run_sc[0] / fp32(hyp ** length_penalty), hyp = Lmax - L0 if early_stopping == "never" and length_penalty > 0 else
+         cur + 1 - L0; worst_k = min(pool_sc) if fin[k] else -1e9; open &= any_k(best > worst_k).
+      7. The loop goes on while any item is open, not (early_stopping is True and every fin of every item), and not every candidate hit.
+    Both divisions are IEEE fp32 divisions on CPU tensors.  -> (parent int32 [B * K] with the batch offset, as HF's beam_idx; goes on)."""
+    B, K, L0, Lmax = st.B, st.K, st.L0, st.Lmax
+    V = lp.shape[-1]
+    f32 = torch.float32
+    eos = torch.as_tensor([] if eos_ids is None else [int(e) for e in eos_ids], dtype=torch.int64)
+    KK = ops.beam_candidates(K, eos.numel())
+    neg = torch.tensor(BEAM_NEG, dtype=f32)
+    p_fin, p_hyp = (torch.tensor(p, dtype=f32) for p in beam_powers(cur, L0, Lmax, length_penalty, early_stopping))
+    parents = torch.empty(B * K, dtype=torch.int32)
+    every_hit = True
+    for b in range(B):
+        acc = (lp[b].to(f32) + st.run_sc[b].unsqueeze(1)).reshape(-1)
+        idx = _first_k(acc, KK)
+        tv, parent, tok = acc[idx], idx // V, idx % V
+        hit = torch.isin(tok, eos) | (cur + 1 == Lmax)
+        cand = st.run[b, parent].clone()
+        cand[:, cur] = tok
+        every_hit = every_hit and bool(hit.all())
+        rv = torch.where(hit, tv + neg, tv)
+        sel = _first_k(rv, K)
+        fv = tv / p_fin
+        first_k = torch.arange(KK) < K
+        pen = (early_stopping is True and bool(st.fin[b].all())) or not bool(st.open[b])
+        fv = torch.where(~(hit & first_k) | pen, fv + neg, fv)
+        e = _first_k(torch.cat([st.pool_sc[b], fv]), K)
+        st.pool[b] = torch.cat([st.pool[b], cand])[e]
+        st.pool_sc[b] = torch.cat([st.pool_sc[b], fv])[e]
+        st.pool_len[b] = torch.cat([st.pool_len[b], torch.full((KK,), cur + 1 - L0, dtype=torch.int32)])[e]
+        st.fin[b] = torch.cat([st.fin[b], (hit & first_k).to(torch.int32)])[e]
+        st.run[b], st.run_sc[b] = cand[sel], rv[sel]
+        parents[b * K:(b + 1) * K] = (b * K + parent[sel]).to(torch.int32)
+        best = st.run_sc[b, 0] / p_hyp
+        worst = torch.where(st.fin[b].bool(), st.pool_sc[b].min(), neg)
+        st.open[b] = int(bool(st.open[b]) and bool((best > worst).any()))
+    go = bool(st.open.any()) and not (early_stopping is True and bool(st.fin.all())) and not every_hit
+    return parents, go
+
+
+def beam_search_reference(logits_fn, input_ids, num_beams: int, max_new_tokens: int, eos_ids=None, pad: int = 0, length_penalty=1.0,
+                          early_stopping=False, num_return_sequences: int = 1, no_repeat_ngram_size: int = 0, log_probs=None,
+                          extra_steps: int = 0, trace=None):
+    """generate(num_beams=K)'s rule on the host: HF `GenerationMixin._beam_search` with do_sample=False, restated step by step
+    (beam_step_reference) with the one thing HF leaves open fixed -- ties go to the lowest flat index.  The reference of the device loop.
+    logits_fn(ids int64 [R, cur]) -> the last-position logits [R, V] of those rows: the first step hands it the B prompts (only beam 0
+    of an item exists: the K rows would be equal), every later one the B * K running rows.  log_probs(logits [R, V]) -> fp32 [R, V]:
+    the log-softmax (default: torch's on the fp32 logits; the GPU tests hand in ops.token_logprobs' bits).  The n-gram ban puts -inf on the
+    log-probabilities, after the softmax (HF's processor order).  extra_steps: steps to run on after the rule has stopped (they must
+    change nothing).  trace: a list that receives one dict per step (logits, lp, parent, goes on, the running rows and scores before the step, the rows after).
+    -> GenerateOutput(sequences [B * n, <= Lmax], sequences_scores fp32 [B * n], steps = the forwards up to the stop)."""
+    if log_probs is None:
+        log_probs = lambda x: torch.log_softmax(x.float(), dim=-1)                                      # noqa: E731
+    ids = input_ids.cpu()
+    B, K = ids.shape[0], num_beams
+    st = BeamState(ids, K, max_new_tokens, pad, device="cpu")
+    steps, extra = None, 0
+    for step in range(max_new_tokens):
+        cur = st.L0 + step
+        rows = st.run[:, 0, :cur] if step == 0 else st.run[:, :, :cur].reshape(B * K, cur)
+        logits = logits_fn(rows.to(input_ids.device))
+        lp = log_probs(logits).float().cpu().view(B, -1, logits.shape[-1]).expand(B, K, -1).clone()
+        if no_repeat_ngram_size:
+            for r, banned in enumerate(no_repeat_ngram_banned_tokens(st.run[:, :, :cur].reshape(B * K, cur).tolist(), no_repeat_ngram_size)):
+                lp[r // K, r % K, [t for t in banned if 0 <= t < lp.shape[-1]]] = float("-inf")
+        before = (st.run.clone(), st.run_sc.clone()) if trace is not None else None
+        parent, go = beam_step_reference(st, lp, cur, eos_ids, length_penalty, early_stopping)
+        if trace is not None:
+            trace.append(dict(cur=cur, logits=logits, lp=lp, parent=parent, go=go, run_before=before[0], run_sc_before=before[1], run_after=st.run.clone(),
+                              stopped=steps is not None))
+        if steps is not None:
+            extra += 1
+        elif not go:
+            steps = step + 1
+        if steps is not None and extra >= extra_steps:
+            break
+    seqs, scores = st.result(num_return_sequences)
+    return GenerateOutput(sequences=seqs, sequences_scores=scores, steps=max_new_tokens if steps is None else steps)
+
+
+def beam_loop(d: Decoding, seq, num_beams: int, ngram: int = 0, length_penalty=1.0, early_stopping=False, num_return_sequences: int = 1):
+    """generate(num_beams=K): deterministic beam search (`beam_search_reference` is the rule) with the state on the device, after the
+    pattern of fused_loop.  The prefill runs once per item (B rows, vision tower included); its cache is replicated to B * K rows and every
+    later forward takes the B * K running rows.  A step is the forward, ops.ngram_ban if asked (a copy of the rows with -inf at the banned
+    tokens; the normalizer keeps reading the raw rows), ops.beam_step (two launches: the new state, `parent`, and the step's "the loop goes
+    on" word) and, with a cache, KVCache.gather_rows by `parent` over the generated positions only (the beams of an item share the prompt's
+    K / V).  The host reads the go-on words every 8 steps; steps past the stop change neither the pool nor its scores, so nothing is trimmed.
+    Without a cache every step re-runs the rows and nothing is gathered.  -> (ids [B * n, <= Lmax], sequences_scores fp32 [B * n])"""
+    B, L0 = seq.shape
+    K, n_max, dev = num_beams, d.max_new_tokens, seq.device
+    st = BeamState(seq, K, n_max, 0 if d.pad is None else d.pad)
+    run = [st.run, torch.empty_like(st.run)]
+    pool = [st.pool, torch.empty_like(st.pool)]
+    cand_v = torch.empty(B * K * ops.BEAM_MAX_CAND, dtype=torch.float32, device=dev)
+    cand_t = torch.empty(B * K * ops.BEAM_MAX_CAND, dtype=torch.int32, device=dev)
+    parent = torch.empty(B * K, dtype=torch.int32, device=dev)
+    go = torch.zeros(max(n_max, 1), dtype=torch.int32, device=dev)
+    banned = None
+    n_done = 0
+    for step in range(n_max):
+        cur, a, b_ = L0 + step, step & 1, (step + 1) & 1
+        if step == 0:
+            last = d.forward(seq, 0).logits[:, -1]                                   # [B, V]: the prefill
+            rows = run[a][:, 0]                                                      # beam 0 of every item (a view: rows K * Lmax apart)
+            # from here on the rows are the beams: cache, mask and vision inputs K times, item by item
+            if d.cache is not None:
+                d.cache = d.cache.replicated(K)
+            if d.attention_mask is not None:
+                d.attention_mask = d.attention_mask.repeat_interleave(K, 0)
+            if d.cache is None:
+                d.images, d.videos = (None if t is None else t.repeat_interleave(K, 0) if torch.is_tensor(t) else [x for x in t for _ in range(K)]
+                                      for t in (d.images, d.videos))
+        else:
+            rows = run[a].view(B * K, -1)
+            last = d.forward(rows[:, :cur], step).logits[:, -1]                      # [B * K, V]
+        pick = None
+        if ngram > 0:
+            if banned is None or banned.shape != last.shape:
+                banned = torch.empty(last.shape, dtype=last.dtype, device=dev)
+            pick = ops.ngram_ban(last, rows, cur, ngram, out=banned)
+        p_fin, p_hyp = beam_powers(cur, L0, st.Lmax, length_penalty, early_stopping)
+        ops.beam_step(last.view(B, -1, last.shape[-1]) if step else last.unsqueeze(1), pick, run[a], run[b_], pool[a], pool[b_], st.run_sc, st.pool_sc,
+                      st.pool_len, st.fin, st.open, d.eos_ids, st.pad, L0, cur, p_fin, p_hyp, early_stopping, cand_v, cand_t, parent, go[step:step + 1])
+        if d.cache is not None and step > 0 and step + 1 < n_max:
+            d.cache.gather_rows(parent, L0, cur)                                     # (step 0: every row continues beam 0's prefill)
+        n_done = step + 1
+        if n_done % 8 == 0 or n_done == n_max:
+            if bool((go[:n_done] == 0).any()):                                       # the only device -> host read: every 8 steps
+                break
+    st.run, st.pool = run[n_done & 1], pool[n_done & 1]                              # (step s wrote the buffers (s + 1) & 1)
+    return st.result(num_return_sequences)

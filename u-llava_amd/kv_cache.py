@@ -152,6 +152,49 @@ class KVCache:
             self._c_ptrs = ((ctypes.c_void_p * len(self.k))(*[t.data_ptr() for t in self.k]), (ctypes.c_void_p * len(self.vt))(*[t.data_ptr() for t in self.vt]))
         return self._c_ptrs
 
+    def _shape(self):
+        return tuple(self.k[0].shape) + (self.k[0].element_size(),)     # B, H, smax, hd, bytes per element
+
+    def gather_rows(self, parent, p0: int, p1: int) -> None:
+        """Beam search's reorder: for every layer, positions [p0, p1) of row r of K and V^T become those of row parent[r] (int32 [B], device;
+        HF's `beam_idx`).  The beams of an item share everything below the first generated position, so only that tail moves.  V^T moves in
+        the whole 32-key blocks the range touches (`vt_slot`): what lies below p0 in the first block has to be equal in r and parent[r].
+        A reorder in place would read rows it has overwritten under a swap, so the tail goes through a scratch the cache keeps (sized once,
+        for every position from p0's block to the end): two launches for all layers (ops.kv_gather_rows), and a row with parent[r] == r
+        moves no bytes.  The model-dtype caches only."""
+        if self.kv_dtype is not None:
+            raise NotImplementedError("KVCache.gather_rows: an fp8 cache is not reordered (its staging window would need its own treatment)")
+        B, H, smax, hd, esz = self._shape()
+        p0, p1 = int(p0), int(p1)
+        if not 0 <= p0 <= p1 <= smax:
+            raise ValueError(f"KVCache.gather_rows: [{p0}, {p1}) is not a range of positions of a cache of {smax}")
+        if p1 == p0:
+            return
+        q0 = p0 & ~31
+        sc = getattr(self, "_gather_scratch", None)
+        if sc is None or sc[0] > q0:
+            W, dev, dt, n = smax - q0, self.k[0].device, self.k[0].dtype, len(self.k)
+            ks, vs = torch.empty(n, B, H, W, hd, device=dev, dtype=dt), torch.empty(n, B, H, hd, W, device=dev, dtype=dt)
+            sc = self._gather_scratch = (q0, W, ks, vs, ops._ptr_array(list(ks)), ops._ptr_array(list(vs)))
+        s0, W, _, _, sk, sv = sc
+        ck, cv = self.c_ptrs()
+        n = len(self.k)
+        ops.kv_gather_rows(ck, cv, sk, sv, n, B, B, H, hd, esz, smax, W, p0, p0 - s0, p1 - p0, parent, parent)
+        ops.kv_gather_rows(sk, sv, ck, cv, n, B, B, H, hd, esz, W, smax, p0 - s0, p0, p1 - p0, None, parent)
+
+    def replicated(self, times: int, smax: int = None) -> "KVCache":
+        """A cache of B * times rows whose rows r * times ... (r + 1) * times - 1 hold row r's positions (beam search: the prefill, vision
+        tower included, runs once per item, not once per beam).  One launch for all layers; `last_hidden` is not carried."""
+        if self.kv_dtype is not None:
+            raise NotImplementedError("KVCache.replicated: an fp8 cache is not replicated")
+        B, H, smax0, hd, esz = self._shape()
+        c = KVCache(len(self.k), B * times, H, hd, smax0 if smax is None else smax, self.k[0].device, self.k[0].dtype)
+        if self.length:
+            row_map = torch.arange(B, device=self.k[0].device, dtype=torch.int32).repeat_interleave(times)
+            ops.kv_gather_rows(*self.c_ptrs(), *c.c_ptrs(), len(self.k), B, B * times, H, hd, esz, smax0, c.smax, 0, 0, self.length, row_map, None)
+        c.length = self.length
+        return c
+
     def __len__(self):
         return len(self.k) if self.kv_dtype is None else len(self.k8)
 

@@ -23,7 +23,7 @@ from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaCoreConfig
 # (imported by name: the cache and the decoding helpers stay importable from this module)
-from .generation import (Decoding, GenerateOutput, check_generate_args, check_ngram_ban, check_prompt_lookup, check_sampler, fused_loop,
+from .generation import (Decoding, GenerateOutput, beam_loop, beam_search_reference, check_generate_args, check_ngram_ban, check_prompt_lookup, check_sampler, fused_loop,
                          host_loop, no_repeat_ngram_banned_tokens, prompt_lookup_candidates, prompt_lookup_loop, sampling_probs)
 from .kv_cache import DEFAULT_HEADROOM, KV_CACHE_DTYPES, KVCache, _check_kv_dtype
 
@@ -1160,8 +1160,8 @@ class UllavaCoreForCausalLM(nn.Module):
     def generate(self, input_ids=None, images=None, videos=None, attention_mask=None, max_new_tokens=32, do_sample=False,
                  temperature=1.0, top_p=None, top_k=50, num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, eos_token_id=None,
                  pad_token_id=None, output_hidden_states=False, return_dict_in_generate=False, use_cache=None,
-                 keep_last_step_only=False, kv_cache_dtype=None, sampler=None, ngram_ban=None, prompt_lookup_num_tokens=None,
-                 max_matching_ngram_size=None, output_logprobs=False, **kwargs):
+                 keep_last_step_only=False, kv_cache_dtype=None, sampler=None, ngram_ban=None, length_penalty=1.0, early_stopping=False,
+                 num_return_sequences=1, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, output_logprobs=False, **kwargs):
         """Token-by-token decoding with HF GenerationMixin's greedy / sampling semantics (the reference inherits `generate`):
         every step goes through `prepare_inputs_for_generation` (position_ids = cumsum(attention_mask) - 1, so left-padded batches
         get the reference's RoPE positions); `eos_token_id` defaults to `config.eos_token_id` (int or list); rows that have emitted
@@ -1199,17 +1199,31 @@ class UllavaCoreForCausalLM(nn.Module):
         token sequences[b, L0 + j] under softmax of the RAW last-position logits of the step that produced it: before temperature, top-k,
         top-p and the n-gram ban, so it says how likely the model itself held the token, whatever the sampling settings (HF's
         `output_logits`, not `output_scores`).  A row that had finished before the step holds a pad-fill token there and gets exactly 0.0;
-        a row's EOS token itself gets its real log-probability.  One launch per step (ops.token_logprobs) in every loop; GPU tensors only."""
+        a row's EOS token itself gets its real log-probability.  One launch per step (ops.token_logprobs) in every loop; GPU tensors only.
+        num_beams=K (2..16; HF's option, with HF's length_penalty=1.0, early_stopping=False / True / "never" and num_return_sequences=1..K):
+        deterministic beam search, HF `_beam_search` with do_sample=False -- `generation.beam_search_reference` is the rule, with ties
+        between equal scores going to the lowest (beam, token), which HF leaves open.  The state lives on the device (`beam_loop`): per
+        step the forward over the B * K running rows, ops.beam_step (two launches) and, with use_cache=True, a reorder of the generated
+        positions of the KV cache by the step's parents (KVCache.gather_rows; the prompt's K / V is equal in an item's beams and stays).
+        The prefill runs once per item, not once per beam.  Returns the best num_return_sequences finished hypotheses per item, [B * n, L]
+        with pad fill behind each row's end; with return_dict_in_generate=True the result also carries `sequences_scores`, fp32 [B * n]
+        (the sum of log-probabilities divided by length ** length_penalty).  The host reads one word per step every 8 steps, so up to 7
+        forwards may run past the stop; they change nothing.  GPU tensors only.  Not with: sampling, sampler="device", prompt lookup,
+        stopping_criteria, output_hidden_states (so not through evaluate()), output_logprobs, kv_cache_dtype, or `no_repeat_ngram_size`
+        without ngram_ban="device".  num_beams=1 is the decoding above, unchanged, and refuses the three beam options."""
         cfg = self.config
+        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
+        eos_list = [] if eos is None else [eos] if isinstance(eos, int) else list(eos)
         ngram, sampling, device_sampler, use_cache, lookup = check_generate_args(
             input_ids, attention_mask, do_sample=do_sample, temperature=temperature, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size,
             use_cache=use_cache, kv_cache_dtype=kv_cache_dtype, sampler=sampler, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
             max_matching_ngram_size=max_matching_ngram_size, output_logprobs=output_logprobs, return_dict_in_generate=return_dict_in_generate,
-            unknown=kwargs, dtype=self.dtype, vocab_size=cfg.vocab_size, config_use_cache=cfg.use_cache, ngram_ban=ngram_ban)
+            unknown=kwargs, dtype=self.dtype, vocab_size=cfg.vocab_size, config_use_cache=cfg.use_cache, ngram_ban=ngram_ban,
+            length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,
+            stopping_criteria=stopping_criteria, output_hidden_states=output_hidden_states, n_eos=len(eos_list))
         device_ban = check_ngram_ban(ngram_ban)
         seq = input_ids
-        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
-        eos_ids = None if eos is None else torch.as_tensor([eos] if isinstance(eos, int) else list(eos), device=seq.device, dtype=seq.dtype)
+        eos_ids = None if eos is None else torch.as_tensor(eos_list, device=seq.device, dtype=seq.dtype)
         pad = pad_token_id if pad_token_id is not None else getattr(cfg, "pad_token_id", None)
         if pad is None and eos_ids is not None:
             pad = int(eos_ids[0])
@@ -1226,6 +1240,9 @@ class UllavaCoreForCausalLM(nn.Module):
                             kv_dtype=kv_cache_dtype)
         d = Decoding(self, images, videos, attention_mask, no_pad, cache, max_new_tokens, sampling, temperature, top_k, top_p, eos_ids, pad, crit,
                      output_hidden_states, keep_last_step_only, output_logprobs)
+        if num_beams > 1:
+            seq, scores = beam_loop(d, seq, num_beams, ngram, length_penalty, early_stopping, num_return_sequences)
+            return GenerateOutput(sequences=seq, hidden_states=None, sequences_scores=scores) if return_dict_in_generate else seq
         if lookup is not None:
             seq, logprobs = prompt_lookup_loop(d, seq, lookup)
         elif (not sampling or device_sampler) and (ngram == 0 or device_ban) and seq.is_cuda:

@@ -334,7 +334,7 @@ class UllavaForCausalLM(nn.Module):
                    sampler=sampler, return_dict_in_generate=True, output_logprobs=output_logprobs, kv_cache_dtype=kv_cache_dtype,
                    prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size, ngram_ban=ngram_ban,
                    use_cache=True if kv_cache_dtype is not None or prompt_lookup_num_tokens is not None else None)
-        check_generate_args(input_ids, dtype=None if kv_cache_dtype is None else self.llm.dtype, **gen)
+        check_generate_args(input_ids, dtype=None if kv_cache_dtype is None else self.llm.dtype, output_hidden_states=True, **gen)
         main = torch.cuda.current_stream()                          # SAM image encoder on the second stream, under the generation loop
         side = self._side_stream()
         side.wait_stream(main)

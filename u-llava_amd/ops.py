@@ -1276,6 +1276,76 @@ def ngram_ban(logits: torch.Tensor, ids: torch.Tensor, cur_len: int, ngram: int,
     return out
 
 
+BEAM_MAX_K, BEAM_MAX_CAND = _D["ULL_BEAM_MAX_K"], _D["ULL_BEAM_MAX_CAND"]
+BEAM_EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+
+
+def beam_candidates(num_beams: int, n_eos: int) -> int:
+    """KK: how many candidates a beam step keeps per item (HF: max(2, 1 + n_eos) * num_beams)."""
+    return max(2, 1 + n_eos) * num_beams
+
+
+def beam_step(logits: torch.Tensor, pick: Optional[torch.Tensor], run_in: torch.Tensor, run_out: torch.Tensor, pool_in: torch.Tensor,
+              pool_out: torch.Tensor, run_sc: torch.Tensor, pool_sc: torch.Tensor, pool_len: torch.Tensor, fin: torch.Tensor, open_: torch.Tensor,
+              eos_ids: Optional[torch.Tensor], pad: int, L0: int, cur: int, pow_fin: float, pow_hyp: float, early_stopping, cand_v: torch.Tensor,
+              cand_t: torch.Tensor, parent: torch.Tensor, go: torch.Tensor) -> None:
+    """One step of beam search for the whole batch in two launches (see ull_beam_step; the rule is generation.beam_search_reference).
+    logits [B, Kin, V] bf16 / fp16 / fp32 with Kin in (1, K), rows of one pitch; pick: the same rows after ops.ngram_ban, or None.
+    run_in / run_out / pool_in / pool_out int64 [B, K, Lmax] contiguous (in != out), run_sc / pool_sc fp32 [B, K], pool_len / fin int32
+    [B, K], open_ int32 [B]: the state, updated; parent int32 [B * K] and go int32 [1]: written; cand_v fp32 / cand_t int32
+    [B * K * BEAM_MAX_CAND]: scratch.  pow_fin / pow_hyp: the two powers of the length penalty, rounded to fp32 here."""
+    _chk(logits, "logits")
+    if logits.dim() != 3:
+        raise RuntimeError(f"u-llava_amd.beam_step: logits must be [B, Kin, V], got {tuple(logits.shape)}")
+    B, Kin, V = logits.shape
+    if run_in.dim() != 3 or run_in.shape[0] != B:
+        raise RuntimeError(f"u-llava_amd.beam_step: run_in must be int64 [{B}, K, Lmax], got {tuple(run_in.shape)}")
+    K, Lmax = run_in.shape[1:]
+    rows, ld = _rows(logits[:, 0] if Kin == 1 else logits)          # (Kin == 1: the rows are the items', whatever the middle stride says)
+    pick_ld = 0
+    if pick is not None:
+        _chk(pick, "pick", logits.dtype)
+        if pick.numel() != rows * V or pick.shape[-1] != V:
+            raise RuntimeError(f"u-llava_amd.beam_step: pick must hold the logits' {rows} rows of {V}, got {tuple(pick.shape)}")
+        pick_ld = _rows(pick.reshape(rows, V) if pick.is_contiguous() else pick[:, 0] if Kin == 1 and pick.dim() == 3 else pick)[1]
+    for t, name in ((run_in, "run_in"), (run_out, "run_out"), (pool_in, "pool_in"), (pool_out, "pool_out")):
+        _chk(t, name, torch.int64)
+        if tuple(t.shape) != (B, K, Lmax) or not t.is_contiguous():
+            raise RuntimeError(f"u-llava_amd.beam_step: {name} must be a contiguous int64 [{B}, {K}, {Lmax}], got {tuple(t.shape)}")
+    for t, name, dt, n in ((run_sc, "run_sc", F32, B * K), (pool_sc, "pool_sc", F32, B * K), (pool_len, "pool_len", torch.int32, B * K),
+                           (fin, "fin", torch.int32, B * K), (open_, "open", torch.int32, B), (parent, "parent", torch.int32, B * K),
+                           (go, "go", torch.int32, 1), (cand_v, "cand_v", F32, B * K * BEAM_MAX_CAND), (cand_t, "cand_t", torch.int32, B * K * BEAM_MAX_CAND)):
+        _chk(t, name, dt)
+        if t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"u-llava_amd.beam_step: {name} must be a contiguous {dt} tensor of {n} entries, got {tuple(t.shape)}")
+    if run_in.data_ptr() == run_out.data_ptr() or pool_in.data_ptr() == pool_out.data_ptr():
+        raise RuntimeError("u-llava_amd.beam_step: the ids are double-buffered: run_in / run_out and pool_in / pool_out must differ")
+    if Kin not in (1, K) or not 1 <= K <= BEAM_MAX_K or not L0 <= cur < Lmax:
+        raise ValueError(f"u-llava_amd.beam_step: Kin must be 1 or K = {K} <= {BEAM_MAX_K} and L0 <= cur < Lmax, got Kin = {Kin}, L0 = {L0}, cur = {cur}, "
+                         f"Lmax = {Lmax}")
+    n_eos = 0
+    if eos_ids is not None:
+        _chk(eos_ids, "eos_ids", torch.int64)
+        n_eos = eos_ids.numel()
+    _lib.call("ull_beam_step", _p(logits), DT_CODE[logits.dtype], ld, _p(pick), pick_ld, B, Kin, K, V, _p(run_in), _p(run_out), _p(pool_in),
+              _p(pool_out), _p(run_sc), _p(pool_sc), _p(pool_len), _p(fin), _p(open_), _p(eos_ids), n_eos, int(pad), Lmax, int(L0), int(cur),
+              float(pow_fin), float(pow_hyp), BEAM_EARLY_STOPPING[early_stopping], _p(cand_v), _p(cand_t), _p(parent), _p(go), _stream())
+
+
+def kv_gather_rows(src_k, src_vt, dst_k, dst_vt, n_layers: int, src_rows: int, dst_rows: int, H: int, hd: int, elem_size: int, src_smax: int,
+                   dst_smax: int, src_p0: int, dst_p0: int, n: int, row_map: Optional[torch.Tensor], skip: Optional[torch.Tensor]) -> None:
+    """Rows of a KV cache copied into another set of buffers in one launch (see ull_kv_gather_rows): positions [dst_p0, dst_p0 + n) of row r
+    <- positions [src_p0, src_p0 + n) of source row row_map[r], for every layer, K and V^T, except rows with skip[r] == r.  src_* / dst_*:
+    ctypes void* arrays of the per-layer buffers (KVCache.c_ptrs); row_map / skip: int32 [dst_rows] on the device, or None."""
+    for t, name in ((row_map, "row_map"), (skip, "skip")):
+        if t is not None:
+            _chk(t, name, torch.int32)
+            if tuple(t.shape) != (dst_rows,) or not t.is_contiguous():
+                raise RuntimeError(f"u-llava_amd.kv_gather_rows: {name} must be a contiguous int32 [{dst_rows}], got {tuple(t.shape)}")
+    _lib.call("ull_kv_gather_rows", src_k, src_vt, dst_k, dst_vt, n_layers, src_rows, dst_rows, H, hd, elem_size, src_smax, dst_smax, int(src_p0),
+              int(dst_p0), int(n), _p(row_map), _p(skip), _stream())
+
+
 def video_pool(f: torch.Tensor, B: int, T: int, N: int, tok_pitch: Optional[int] = None, tok_off: int = 0) -> torch.Tensor:
     """f [B*T, tok_pitch, D]; patches are tokens tok_off..tok_off+N of every frame."""
     _chk(f, "f")
