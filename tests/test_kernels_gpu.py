@@ -870,9 +870,15 @@ def test_direct_activation_epilogue_matches_the_staged_one_over_the_value_range(
         xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
         y4 = ops.linear(xd, wd, bd, act=act, tune=ops.GEMM_TUNE_WAVES4)
         y8 = ops.linear(xd, wd, bd, act=act, tune=ops.GEMM_TUNE_WAVES8)
-        same = (y4.view(torch.int16) == y8.view(torch.int16)) | (torch.isnan(y4) & torch.isnan(y8))
+        # NaN == NaN only where the pre-activation (the same call without activation) is itself not finite; at a finite one both forms
+        # must give a number (the activation's own NaN used to pass here as agreement)
+        pre = torch.isfinite(ops.linear(xd, wd, bd, act=None, tune=ops.GEMM_TUNE_WAVES4))
+        assert not bool((torch.isnan(y4) | torch.isnan(y8))[pre].any()), (act, scale, "NaN at a finite pre-activation")
+        same = (y4.view(torch.int16) == y8.view(torch.int16)) | (torch.isnan(y4) & torch.isnan(y8) & ~pre)
         assert bool(same.all()), (act, scale, int((~same).sum()))
         y4n = ops.linear(xd, wd, None, act=act, tune=ops.GEMM_TUNE_WAVES4)
         y8n = ops.linear(xd, wd, None, act=act, tune=ops.GEMM_TUNE_WAVES8)
-        samen = (y4n.view(torch.int16) == y8n.view(torch.int16)) | (torch.isnan(y4n) & torch.isnan(y8n))
+        pren = torch.isfinite(ops.linear(xd, wd, None, act=None, tune=ops.GEMM_TUNE_WAVES4))
+        assert not bool((torch.isnan(y4n) | torch.isnan(y8n))[pren].any()), (act, scale, "no bias", "NaN at a finite pre-activation")
+        samen = (y4n.view(torch.int16) == y8n.view(torch.int16)) | (torch.isnan(y4n) & torch.isnan(y8n) & ~pren)
         assert bool(samen.all()), (act, scale, "no bias")

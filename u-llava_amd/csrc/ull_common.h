@@ -287,12 +287,19 @@ ULL_DEV f32x2_t act_gelu_erf2(f32x2_t x) {
     return (x * 0.5f) * (f32x2_t{1.0f, 1.0f} + erf);
 }
 
-// 1 / d for d in [1, inf): the hardware reciprocal (1 ulp) plus one Newton step, three instructions where the IEEE division sequence
-// (v_div_scale / v_rcp / 4 FMAs / v_div_fmas / v_div_fixup) is ten -- the SwiGLU and QuickGELU epilogues are VALU-bound.  The results
-// go through a 16-bit rounding right away; the fixtures and the exhaustive activation tests pin that they do not move.
+// 1 / d for d in [1, inf]: the hardware reciprocal (1 ulp) plus one Newton step, three instructions where the IEEE division sequence
+// (v_div_scale / v_rcp / 4 FMAs / v_div_fmas / v_div_fixup) is ten -- the SwiGLU and QuickGELU epilogues are VALU-bound.
+// d = +inf is a real input: 1 + __expf(-x) overflows from x <= -88.73 on (QuickGELU: t <= -52.1).  There r = 0 and the step's residual
+// 1 - d r is 1 - inf * 0 = NaN, where the reference has 1 / inf = 0.  The result lies in [0, 1] for every d >= 1, so the median with 0
+// and 1 leaves every number as it is (same bits) and turns that NaN into 0: v_med3_f32 takes the minimum of the other two when an
+// operand is NaN, and so does the form the compiler folds it into, the clamp modifier of the second FMA (kernels run with DX10_CLAMP
+// set) -- no instruction is added (a v_min_f32 on d cost 0.2 % of the C4 forward, docs/experiments.md).  A NaN that comes IN (d = NaN)
+// becomes 0 as well; the callers multiply by x or pass x on beside it, so a NaN pre-activation still gives NaN out.
+// The results go through a 16-bit rounding right away; tests/test_activation_sweep_gpu.py holds SiLU and QuickGELU against a float64
+// reference over every finite 16-bit input on each kernel path that evaluates them (the sites are listed in that file).
 ULL_DEV float rcp_newton(float d) {
     const float r = __builtin_amdgcn_rcpf(d);
-    return fmaf(fmaf(-d, r, 1.0f), r, r);
+    return __builtin_amdgcn_fmed3f(fmaf(fmaf(-d, r, 1.0f), r, r), 0.0f, 1.0f);
 }
 ULL_DEV float act_sigmoid(float x) { return rcp_newton(1.0f + __expf(-x)); }
 ULL_DEV float act_silu(float x) { return x * rcp_newton(1.0f + __expf(-x)); }
