@@ -1,7 +1,8 @@
 """GPU: the HIP backward kernels (csrc/backward.hip + Linear backward as transposed-operand GEMMs) against torch autograd of the
 oracle's ops on the CPU, and the full training path of UllavaCoreForCausalLM against the reference's gradients (G12 fixtures,
 tests/golden/gen_golden.py::gen_core_grads).  Tolerance: gradients are compared in relative L2 norm; for the model-level test the
-HIP bf16 gradients must be as close to the reference's fp32 gradients as the reference's own bf16 backward is (x1.5)."""
+HIP bf16 gradients must be as close to the reference's fp32 gradients as the reference's own bf16 backward is (x1.5).
+The norm and cross-entropy kernels are held row by row and column by column, in bf16 and fp16, by tests/test_row_backward_gpu.py."""
 import math
 import os
 

@@ -1454,12 +1454,19 @@ def bilinear(x: torch.Tensor, in_h: int, in_w: int, out_h: int, out_w: int) -> t
     return out
 
 
+def _ce_rows(logits: torch.Tensor, labels: torch.Tensor):
+    """The one layout rule of the three shifted-CE wrappers -> (B, S, V, ld).  The kernels index row (b, t) as (b * S + t) * ld, so the
+    [B, S, V] logits must fold onto rows of ONE pitch (_rows: contiguous, or a [..., :V] view of wider rows); anything else is refused."""
+    _chk(logits, "logits"); _chk(labels, "labels", torch.int64)
+    if logits.dim() != 3 or tuple(labels.shape) != tuple(logits.shape[:2]):
+        raise RuntimeError("u-llava_amd.shifted_cross_entropy: logits [B, S, V] and labels [B, S] required")
+    B, S, V = logits.shape
+    return B, S, V, _rows(logits)[1]
+
+
 def shifted_cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     """mean CE of logits[:, :-1] against labels[:, 1:] (ignore_index -100) -> 0-dim tensor of the logits' dtype like the reference's loss."""
-    _chk(logits, "logits"); _chk(labels, "labels", torch.int64)
-    B, S, V = logits.shape
-    acc = torch.zeros(2, device=logits.device, dtype=torch.float32)
-    _lib.call("ull_shifted_cross_entropy_" + _SFX[logits.dtype], _p(logits), logits.stride(1), _p(labels.contiguous()), B, S, V, _p(acc), _stream())
+    acc = shifted_cross_entropy_stats(logits, labels)
     return (acc[0] / acc[1]).to(logits.dtype)
 
 
@@ -1565,18 +1572,19 @@ def attention_bwd(q, k, v, o, do, dq, dk, dv, strides, key_mask, B: int, H: int,
 
 def shifted_cross_entropy_stats(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     """float32 [2] = {sum of token losses, counted tokens} of the shifted CE (the loss is stats[0] / stats[1])."""
-    _chk(logits, "logits"); _chk(labels, "labels", torch.int64)
-    B, S, V = logits.shape
+    B, S, V, ld = _ce_rows(logits, labels)
     acc = torch.zeros(2, device=logits.device, dtype=torch.float32)
-    _lib.call("ull_shifted_cross_entropy_" + _SFX[logits.dtype], _p(logits), logits.stride(1), _p(labels.contiguous()), B, S, V, _p(acc), _stream())
+    _lib.call("ull_shifted_cross_entropy_" + _SFX[logits.dtype], _p(logits), ld, _p(labels.contiguous()), B, S, V, _p(acc), _stream())
     return acc
 
 
 def shifted_cross_entropy_bwd(logits: torch.Tensor, labels: torch.Tensor, stats: torch.Tensor, gout: torch.Tensor) -> torch.Tensor:
-    _chk(logits, "logits"); _chk(labels, "labels", torch.int64); _chk(stats, "stats", torch.float32); _chk(gout, "gout", torch.float32)
-    B, S, V = logits.shape
-    dl = torch.empty_like(logits)
-    _lib.call("ull_shifted_cross_entropy_bwd_" + _SFX[logits.dtype], _p(logits), logits.stride(1), _p(labels.contiguous()), B, S, V, _p(stats),
+    """dlogits [B, S, V] at the row pitch of `logits` (the kernel takes ONE pitch for both: a [..., :V] view of padded rows gets a gradient
+    with the same padded rows, whose pad columns are never written)."""
+    _chk(stats, "stats", torch.float32); _chk(gout, "gout", torch.float32)
+    B, S, V, ld = _ce_rows(logits, labels)
+    dl = torch.empty_strided((B, S, V), (S * ld, ld, 1), device=logits.device, dtype=logits.dtype)
+    _lib.call("ull_shifted_cross_entropy_bwd_" + _SFX[logits.dtype], _p(logits), ld, _p(labels.contiguous()), B, S, V, _p(stats),
               _p(gout), _p(dl), _stream())
     return dl
 
