@@ -427,6 +427,23 @@ int ull_kv_gather_rows(const void* const* src_k, const void* const* src_vt, void
                        int64_t src_rows, int64_t dst_rows, int64_t H, int64_t hd, int64_t elem_size, int64_t src_smax, int64_t dst_smax,
                        int64_t src_p0, int64_t dst_p0, int64_t n, const void* row_map, const void* skip, void* stream);
 
+/* The prefix check of a continued generate() call (HF: the caller hands in the whole conversation and a cache of its first positions), one
+ * launch, compiled once: out[r] (int32, device) = the length of the common prefix of the int64 rows ids_a + r * lda and ids_b + r * ldb,
+ * at most n: the first i < n with a[i] != b[i], or n.  n == 0 gives 0 and reads nothing (the id pointers may be NULL then).  Any R >= 0
+ * (the blocks stride over the rows; R == 0: nothing is launched).  The ids are compared only: no address is formed from one.
+ * A negative size or pitch, n > 2^31 - 1, a null pointer that would be read or written: ULL_ERR_ARG; R > 1 with a pitch < n: ULL_ERR_SHAPE. */
+int ull_ids_common_prefix(const void* ids_a, int64_t lda, const void* ids_b, int64_t ldb, int64_t R, int64_t n, void* out, void* stream);
+
+/* Positions [0, n) of an fp8 KV cache (ull_attention_kv8_bf16's layouts: K codes [B, H, smax, hd], V^T codes [B, H, hd, smax] in the permuted
+ * slot order, K scales [B, H, smax] by key, V scales [B, H, smax] by V^T slot) copied into another set of buffers, whose pitch dst_smax may
+ * differ from src_smax, in one launch per 32 layers.  The eight arguments are HOST arrays of n_layers device pointers.  Nothing at or beyond
+ * position n is written in any destination array (the keys of a last partial 32-key block go to their slots one by one), and nothing of the
+ * bf16 staging window travels: each forward call rewrites it before it reads it.  A pitch that is not a multiple of 32, n above either
+ * pitch, a base not 16-byte aligned, B * H > 65535: ULL_ERR_SHAPE; a null pointer, a source that is its own destination: ULL_ERR_ARG. */
+int ull_kv8_copy_positions(const void* const* src_k8, const void* const* src_vt8, const void* const* src_k_scale, const void* const* src_vt_scale,
+                           void* const* dst_k8, void* const* dst_vt8, void* const* dst_k_scale, void* const* dst_vt_scale, int64_t n_layers,
+                           int64_t B, int64_t H, int64_t hd, int64_t src_smax, int64_t dst_smax, int64_t n, void* stream);
+
 /* models/ullava_core.py:191,243-245,266-268: token-embedding lookup with the projected visual tokens spliced in after
  * the first start token (the torch.cat of the reference, done as one gather).  Image i's n_img_tok feature rows start
  * at row i*img_pitch + img_off of img_feat (pitch = patches + 1, off = 1 skips the CLS row without a copy).

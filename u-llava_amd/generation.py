@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .kv_cache import _check_kv_dtype
+from .kv_cache import KVCache, _check_kv_dtype
 
 
 class GenerateOutput(dict):
@@ -129,11 +129,91 @@ def check_num_beams(num_beams, length_penalty=1.0, early_stopping=False, num_ret
     return num_beams
 
 
+def _past_geometry(past):
+    """(layers, batch, heads, head_dim, kv_dtype, on the GPU, holds the hidden states of its positions) of generate()'s `past_key_values`:
+    a KVCache, or what KVCache.from_hf takes (kv_dtype then None: it is converted to whatever the call asks for).  Host-side reads only."""
+    if isinstance(past, KVCache):
+        n_layers, B, H, hd, dev, _ = past._geom
+        return n_layers, B, H, hd, past.kv_dtype, dev.type == "cuda", sum(h.shape[1] for h in past.last_hidden) == past.length
+    if hasattr(past, "key_cache") and hasattr(past, "value_cache"):
+        keys = list(past.key_cache)
+    elif hasattr(past, "layers"):
+        keys = [l.keys for l in past.layers]
+    else:
+        try:
+            keys = [kv[0] for kv in past]
+        except TypeError:
+            raise TypeError(f"`past_key_values` has to be a KVCache, an HF legacy tuple of (key, value) pairs or a Cache object, not {type(past).__name__}")
+    if not keys or not torch.is_tensor(keys[0]) or keys[0].dim() != 4:
+        raise ValueError("`past_key_values` entries must be [batch, heads, seq, head_dim] tensors (an empty HF cache: pass an empty KVCache)")
+    B, H, _, hd = keys[0].shape
+    return len(keys), B, H, hd, None, keys[0].is_cuda, False
+
+
+def check_past_key_values(past, input_ids, cache_shape=None, kv_cache_dtype=None, output_hidden_states=False, num_beams=1):
+    """The refusals of generate(past_key_values=) after `use_cache=False`, in check_generate_args' documented order; no device work."""
+    n_layers, B, H, hd, kv_dtype, on_gpu, has_hidden = _past_geometry(past)
+    if input_ids is None or input_ids.dim() != 2:
+        raise ValueError("`past_key_values` needs `input_ids` [batch, length]: the whole conversation so far, the cached positions included")
+    if input_ids.shape[0] != B:
+        raise ValueError(f"`past_key_values` holds {B} rows and `input_ids` has {input_ids.shape[0]}")
+    if cache_shape is not None and tuple(cache_shape) != (n_layers, H, hd):
+        raise ValueError(f"`past_key_values` has (layers, heads, head_dim) = {(n_layers, H, hd)}, the model {tuple(cache_shape)}")
+    if isinstance(past, KVCache) and kv_cache_dtype is not None and kv_cache_dtype != kv_dtype:
+        raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r} contradicts the cache handed in, which is "
+                         f"{'in the model dtype' if kv_dtype is None else repr(kv_dtype)} (leave `kv_cache_dtype` unset)")
+    if output_hidden_states and not has_hidden and not (isinstance(past, KVCache) and past.length == 0):
+        raise ValueError("output_hidden_states=True needs a cache that holds the last-layer states of its positions; one built from an HF "
+                         "cache (KVCache.from_hf) does not")
+    if num_beams > 1:
+        raise NotImplementedError(f"num_beams={num_beams} does not continue a cache (`past_key_values`): beam search replicates and reorders its own")
+    if not input_ids.is_cuda or not on_gpu:
+        raise RuntimeError("`past_key_values` needs GPU tensors (no CPU path exists)")
+
+
+def enter_cache(cache: KVCache, seq, attention_mask, no_pad: bool, need: int, mm_ids=None) -> None:
+    """generate()'s entry with a cache handed in (HF's rule: `seq` [B, L] is the whole conversation, the cache covers its first positions):
+    the cache is cut to the longest prefix it shares with every row of `seq` (ops.ids_common_prefix against `cache.ids`, one launch and one
+    int32 per row read by the host; ids unknown: the caller is trusted), and to L - 1 at most, so that at least one token is fed; the mask
+    is held against the one the cache was filled under (one more flag read by the host, only where either mask has a zero); the ids to
+    feed must not hold image / video placeholders (one flag, only on models with placeholder ids); and the cache is grown to `need`
+    positions.  Up to three small host reads, then; the cache is touched only after the last refusal.  The images are not looked at."""
+    B, L = seq.shape
+    P = cache.length
+    if P:
+        ids = cache.ids
+        if ids is not None:
+            keep = min(ops.ids_common_prefix(seq, ids, min(P, L)).tolist())
+        elif P > L:
+            raise ValueError(f"`past_key_values` covers {P} positions and `input_ids` has {L} (pass the whole conversation)")
+        else:
+            keep = P
+        keep = min(keep, L - 1)
+        if keep > 0 and not (no_pad and cache.mask is None):
+            # the kept positions' keys carry the RoPE positions of the mask they were filled under.  A new mask may only clear positions
+            # behind a row's last visible kept one (the pad fill behind its EOS): cumsum(mask) - 1 of every key still visible is unchanged
+            new = seq.new_ones(B, keep, dtype=torch.bool) if attention_mask is None else attention_mask[:, :keep].ne(0)
+            rec = new.new_ones(B, keep) if cache.mask is None else cache.mask[:, :keep].ne(0)
+            tail = new.flip(1).cumsum(1).flip(1) == 0
+            if bool(((new != rec) & ~tail).any()):
+                raise ValueError("`attention_mask` differs from the mask the cache was filled under at a cached position that stays visible "
+                                 "(only the pad fill behind a row's last visible cached position may be cleared)")
+        if keep and mm_ids:
+            mm = torch.as_tensor(sorted(set(int(v) for v in mm_ids)), dtype=seq.dtype, device=seq.device)
+            if bool(torch.isin(seq[:, keep:], mm).any()):
+                raise NotImplementedError("the ids to feed behind the cached positions hold image / video placeholder ids: images and videos "
+                                          "inside a continuation are not implemented (start a new cache)")
+        if keep < P:
+            cache.truncate(keep)                                 # (behind every refusal: a refused call leaves the cache as it was)
+    if need > cache.smax:
+        cache.grow(need)
+
+
 def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temperature=1.0, num_beams=1, no_repeat_ngram_size=None,
                         use_cache=None, kv_cache_dtype=None, sampler=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None,
                         output_logprobs=False, return_dict_in_generate=False, unknown=None, dtype=None, vocab_size=None, config_use_cache=None,
                         ngram_ban=None, length_penalty=1.0, early_stopping=False, num_return_sequences=1, stopping_criteria=None,
-                        output_hidden_states=False, n_eos=None):
+                        output_hidden_states=False, n_eos=None, past_key_values=None, cache_shape=None):
     """Every refusal of generate()'s arguments that needs no device work, in generate()'s order; evaluate() calls it too, before it starts
     the SAM encoder on the side stream.  No model is needed: what the model decides comes in as plain values, each read only when the
     option it belongs to is set -- `dtype` with kv_cache_dtype, `vocab_size` with sampler="device" (None: the caller does not know it
@@ -141,7 +221,11 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
     **kwargs.  -> (n-gram size or 0, tokens are sampled, on the device, use_cache with the config's default filled in, (k, n-gram size) or None);
     whether the ban runs on the device is check_ngram_ban(ngram_ban), checked here against the other options.  Beam search (num_beams > 1;
     check_num_beams for the option values) is refused with everything its loop does not define -- stopping_criteria, output_hidden_states and
-    the number of EOS ids `n_eos` (None: not known) come in for that alone -- and on tensors that are not on the GPU."""
+    the number of EOS ids `n_eos` (None: not known) come in for that alone -- and on tensors that are not on the GPU.
+    past_key_values (a KVCache, or an HF legacy tuple / Cache object): the call continues an earlier one's cache, which implies use_cache=True;
+    refused, in this order: use_cache=False; a cache whose batch is not input_ids', or whose (layers, heads, head_dim) are not the model's
+    `cache_shape` (None: not known, left to generate()); a kv_cache_dtype other than the cache's own; output_hidden_states=True on a cache
+    that does not hold the hidden states of its positions (from_hf); num_beams > 1; tensors that are not on the GPU."""
     beams = check_num_beams(num_beams, length_penalty, early_stopping, num_return_sequences)
     if unknown:
         # HF generate() validates its model kwargs and raises on unknown ones; options this loop does not implement must not be
@@ -164,6 +248,11 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
     if device_sampler and sampling and vocab_size is not None and vocab_size > ops.SAMPLE_MAX_V:
         raise ValueError(f'sampler="device" stages a row of logits in LDS: vocab_size {vocab_size} is above its limit of '
                          f"{ops.SAMPLE_MAX_V} (use sampler=None)")
+    if past_key_values is not None:
+        if use_cache is not None and not use_cache:
+            raise ValueError("`past_key_values` needs use_cache=True: the call continues a KV cache (leave `use_cache` unset)")
+        use_cache = True                                         # (whatever the config's default is)
+        check_past_key_values(past_key_values, input_ids, cache_shape, kv_cache_dtype, output_hidden_states, beams)
     use_cache = config_use_cache if use_cache is None else use_cache
     lookup = check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size)
     if lookup is not None:
@@ -227,6 +316,8 @@ class Decoding:
         self.max_new_tokens, self.eos_ids, self.pad, self.crit = max_new_tokens, eos_ids, pad, crit
         self.output_hidden_states, self.keep_last_step_only, self.output_logprobs = output_hidden_states, keep_last_step_only, output_logprobs
         self.steps_hidden = []
+        self.return_cache = False                                # the cache came from the caller (past_key_values): the result names it
+        self.continued = bool(cache)                             # ... and held positions at entry: step 0 feeds what lies behind them
 
     def forward(self, seq, step: int):
         """The forward of decode step `step` over the ids so far, through prepare_inputs_for_generation.  With a cache:
@@ -234,6 +325,16 @@ class Decoding:
         released checkpoints: use_cache=False) every step re-runs the multimodal prefill, and its hidden states are kept when asked for."""
         m = self.attention_mask
         mask = None if self.no_pad else torch.cat([m, m.new_ones(seq.shape[0], seq.shape[1] - m.shape[1])], dim=1)
+        if step == 0 and self.continued:
+            # a cache handed in with P positions: the ids behind them in one call, many new tokens over a filled cache (no `[:, -1:]` cut,
+            # no vision inputs, as in the later steps); the positions come from the full mask, as prepare_inputs_for_generation takes them
+            P = self.cache.length
+            pos = None
+            if mask is not None:
+                pos = mask.long().cumsum(-1) - 1
+                pos.masked_fill_(mask == 0, 1)
+                pos = pos[:, P:]
+            return self.model.forward(input_ids=seq[:, P:], attention_mask=mask, position_ids=pos, past_key_values=self.cache, use_cache=True)
         inputs = self.model.prepare_inputs_for_generation(input_ids=seq, attention_mask=mask, images=self.images, videos=self.videos,
                                                           past_key_values=self.cache, use_cache=self.cache is not None)
         if self.cache is not None:
@@ -259,7 +360,8 @@ class Decoding:
         hidden = None
         if self.output_hidden_states:
             hidden = tuple(self.steps_hidden) if self.cache is None else ((torch.cat(self.cache.last_hidden, dim=1),),) if self.cache else ()
-        return GenerateOutput(sequences=seq, hidden_states=hidden, **({} if logprobs is None else dict(logprobs=logprobs)))
+        return GenerateOutput(sequences=seq, hidden_states=hidden, **({} if logprobs is None else dict(logprobs=logprobs)),
+                              **(dict(past_key_values=self.cache) if self.return_cache else {}))
 
 
 def host_loop(d: Decoding, seq, ngram: int, probs=sampling_probs, device_ban: bool = False):
@@ -379,9 +481,12 @@ def prompt_lookup_loop(d: Decoding, seq, lookup):
     record = torch.empty(3, dtype=torch.int32, device=dev)
     lp = torch.zeros(d.max_new_tokens + k, dtype=torch.float32, device=dev) if d.output_logprobs else None
     n, dn = L0, 0
+    first = True
     while n < n_max:
-        # the prefill through the step forward every loop shares; then the last valid id and the drafts over the filled cache
-        out = d.forward(buf[:, :L0], 0) if not d.cache else d.model.forward(input_ids=buf[:, n - 1:n + dn], past_key_values=d.cache, use_cache=True)
+        # the prefill (or, on a cache handed in, the ids behind its positions) through the step forward every loop shares; then the last
+        # valid id and the drafts over the filled cache
+        out = d.forward(buf[:, :L0], 0) if first else d.model.forward(input_ids=buf[:, n - 1:n + dn], past_key_values=d.cache, use_cache=True)
+        first = False
         logits = out.logits[0, -(1 + dn):]
         # torch's noise, one row per verified position, drawn in one call per step
         noise = torch.empty(logits.shape, dtype=torch.float32, device=dev).exponential_() if d.sampling else None

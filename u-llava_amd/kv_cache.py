@@ -30,6 +30,9 @@ class KVCache:
     prefill has been stored, like a non-empty HF past_key_values tuple."""
 
     kv_dtype = None                        # "fp8_e4m3": see below
+    _id_chunks = None                      # (a cache made without __init__: ids unknown, no mask recorded)
+    mask = None
+    borrow_ids = False                     # generate() sets it for the length of a call: see note_fed
 
     def __init__(self, n_layers, B, H, hd, smax, device, dtype=BF16, kv_dtype=None):
         """kv_dtype="fp8_e4m3" (bf16 models only): the cache holds e4m3fn codes in the same two layouts (k8 [B,H,Smax,hd], vt8 [B,H,hd,Smax])
@@ -42,6 +45,10 @@ class KVCache:
         self.smax = ((smax + 63) // 64) * 64
         self.length = 0
         self.last_hidden = []
+        self._geom = (n_layers, B, H, hd, torch.device(device), dtype)
+        self._id_chunks = []               # the ids the positions were filled with (see `ids`); None: unknown
+        self.mask = None                   # the attention mask the positions were filled under ([B, length]); None: all ones
+        self.side = {}                     # what a caller keeps beside the keys (evaluate(): the SAM image embeddings)
         if kv_dtype is None:
             self.k = [torch.empty(B, H, self.smax, hd, device=device, dtype=dtype) for _ in range(n_layers)]
             self.vt = [torch.zeros(B, H, hd, self.smax, device=device, dtype=dtype) for _ in range(n_layers)]
@@ -111,14 +118,60 @@ class KVCache:
                 ops.dequantize_kv(*self.kv8_layer(li), self.length, k_out=c.k[li], vt_out=c.vt[li])
         c.length = self.length
         c.last_hidden = list(self.last_hidden)
+        c._id_chunks, c.mask = self._ids_carried(), self.mask
         return c
 
     def __bool__(self):
         return self.length > 0
 
+    @property
+    def ids(self):
+        """int64 [B, length] on the device: the ids the cache was filled with, which forward() appends to when it is handed `input_ids`
+        (placeholder ids of image / video patches included); None once a position was fed as `inputs_embeds` or came from `from_hf`.
+        The calls' id tensors are kept as they come and joined -- into a tensor of the cache's own -- when this is read."""
+        if self._id_chunks is None or sum(c.shape[1] for c, _ in self._id_chunks) != self.length:
+            return None                                           # (positions that did not come through forward(): a replicated cache)
+        if len(self._id_chunks) != 1 or not self._id_chunks[0][1]:
+            B, dev = self._geom[1], self._geom[4]
+            ids = torch.cat([c for c, _ in self._id_chunks], dim=1) if self._id_chunks else torch.empty(B, 0, dtype=torch.int64, device=dev)
+            self._id_chunks = [(ids, True)]                       # (True: the cache's own copy, no view of a caller's tensor)
+        return self._id_chunks[0][0]
+
+    def _ids_carried(self):
+        """`_id_chunks` of a copy of this cache (the joined tensor is never written in place: shared)."""
+        ids = self.ids
+        return None if ids is None else [(ids, True)]
+
+    def own_ids(self) -> None:
+        """join what was noted into tensors of the cache's own (ids and mask): no view of a caller's tensor is left behind."""
+        self.ids
+        if self.mask is not None and not getattr(self, "_mask_own", False):
+            self.mask, self._mask_own = self.mask.clone(), True
+
+    def note_fed(self, input_ids, n: int, attention_mask=None) -> None:
+        """forward()'s bookkeeping after it has stored n new positions: their ids (None: fed as embeddings, the ids become unknown) and the
+        mask the cache now stands under ([B, length] or None).  The cache keeps COPIES: a caller may reuse or overwrite its id buffer and
+        its mask after the call (a one-token step copies 8 bytes per row; every 32 calls the copies are joined).  Only inside generate()
+        (`borrow_ids`), whose loops own their buffers and which joins them into the cache's own tensor before it returns, the tensors are
+        noted as they come, so that a decode step launches nothing for it."""
+        own = not self.borrow_ids
+        if input_ids is None or tuple(input_ids.shape) != (self._geom[1], n) or input_ids.dtype != torch.int64:
+            self._id_chunks = None
+        elif self._id_chunks is not None:
+            self._id_chunks.append((input_ids.clone() if own else input_ids, own))
+            if own and len(self._id_chunks) >= 32:
+                self.ids
+        self._mask_own = own or attention_mask is None
+        if attention_mask is not None and attention_mask.shape[-1] == self.length:
+            self.mask = attention_mask.clone() if own else attention_mask
+        elif attention_mask is None and self.mask is not None:
+            self.mask = torch.cat([self.mask, self.mask.new_ones(self.mask.shape[0], self.length - self.mask.shape[1])], dim=1)
+        elif attention_mask is not None:
+            self.mask = None                                      # (a mask of another width: what the cache stands under is not known)
+
     def truncate(self, n: int) -> None:
-        """Give back the positions >= n (speculative decoding: the rejected drafts of a verify step): `length` becomes n and `last_hidden`
-        holds exactly the first n positions (the last call's tensor is sliced).  bf16 and fp8 caches alike: the buffers keep the rejected
+        """Give back the positions >= n (speculative decoding: the rejected drafts of a verify step): `length` becomes n, `last_hidden`
+        holds exactly the first n positions (the last call's tensor is sliced) and so do `ids` and the recorded mask.  bf16 and fp8 caches alike: the buffers keep the rejected
         positions' K rows, V^T columns, codes and scales as stale finite data, which no kernel reads -- attention, append and quantization
         address keys below `length` plus the call's own new positions, and the next call overwrites them."""
         n = int(n)
@@ -134,6 +187,20 @@ class KVCache:
             else:
                 self.last_hidden[-1] = last[:, :last.shape[1] - (have - n)]
                 have = n
+        if self._id_chunks is not None:
+            have = sum(c.shape[1] for c, _ in self._id_chunks)
+            while self._id_chunks and have > n:
+                c, own = self._id_chunks[-1]
+                if have - c.shape[1] >= n:
+                    self._id_chunks.pop()
+                    have -= c.shape[1]
+                else:
+                    self._id_chunks[-1] = (c[:, :c.shape[1] - (have - n)], own)
+                    have = n
+        if self.mask is not None:
+            self.mask = self.mask[:, :n] if n else None
+        if n == 0:
+            self._id_chunks = []                                   # an empty cache knows its ids again
 
     def c_ptrs(self):
         """(void* array of the K buffers, void* array of the V^T buffers) for the coarse decode entry; built once per cache.
@@ -154,6 +221,61 @@ class KVCache:
 
     def _shape(self):
         return tuple(self.k[0].shape) + (self.k[0].element_size(),)     # B, H, smax, hd, bytes per element
+
+    def _copy_into(self, c: "KVCache") -> None:
+        """positions < length of every layer into the (fresh, zero-filled where a fresh cache is) buffers of c: the model-dtype caches
+        through ops.kv_gather_rows with the identity row map, the fp8 cache through ops.kv8_copy_positions.  gather_rows moves V^T in whole
+        32-key blocks, so the slots of the keys length .. of the last block are zeroed again afterwards (a truncated cache holds stale
+        values there): beyond the sequence the V^T columns of c are zero, as a fresh cache has them."""
+        n = self.length
+        if n == 0:
+            return
+        if self.kv_dtype is not None:
+            ops.kv8_copy_positions((self.k8, self.vt8, self.k_scale, self.vt_scale), (c.k8, c.vt8, c.k_scale, c.vt_scale), n)
+            return
+        B, H, smax, hd, esz = self._shape()
+        ops.kv_gather_rows(*self.c_ptrs(), *c.c_ptrs(), len(self.k), B, B, H, hd, esz, smax, c.smax, 0, 0, n, None, None)
+        if n & 31:
+            slots = torch.tensor([self.vt_slot(p) for p in range(n, (n + 31) & ~31)], dtype=torch.int64, device=self.k[0].device)
+            for vt in c.vt:
+                vt.index_fill_(3, slots, 0)
+
+    def _carry(self, c: "KVCache") -> "KVCache":
+        c.length = self.length
+        c.last_hidden = list(self.last_hidden)
+        c._id_chunks = self._ids_carried()
+        c.mask = self.mask
+        c.side = dict(self.side)
+        return c
+
+    def fork(self) -> "KVCache":
+        """An independent copy of the same capacity, with the same `ids`, `last_hidden`, mask and `side` entries (the tensors behind
+        those are shared: nothing writes them in place): several continuations of one prefilled prefix, each on its own fork."""
+        n_layers, B, H, hd, dev, dtype = self._geom
+        c = KVCache(n_layers, B, H, hd, self.smax, dev, dtype, kv_dtype=self.kv_dtype)
+        self._copy_into(c)
+        return self._carry(c)
+
+    def grow(self, smax: int) -> None:
+        """Make room for `smax` positions (rounded up to 64) in place: new buffers, positions < length copied (one launch for all layers;
+        V^T columns beyond the sequence zero, as in a fresh cache), the lists rebound, the pointer arrays and the reorder scratch dropped.
+        smax below `length` is refused; a capacity the cache already has changes nothing."""
+        smax = int(smax)
+        if smax < self.length:
+            raise ValueError(f"KVCache.grow({smax}): the cache holds {self.length} positions")
+        if ((smax + 63) // 64) * 64 <= self.smax:
+            return
+        n_layers, B, H, hd, dev, dtype = self._geom
+        c = KVCache(n_layers, B, H, hd, smax, dev, dtype, kv_dtype=self.kv_dtype)
+        self._copy_into(c)
+        self.smax = c.smax
+        if self.kv_dtype is None:
+            self.k, self.vt = c.k, c.vt
+        else:
+            self.k8, self.vt8, self.k_scale, self.vt_scale = c.k8, c.vt8, c.k_scale, c.vt_scale      # (the staging window has no pitch: kept)
+            self._kv8_ptrs = None
+        self._c_ptrs = None
+        self._gather_scratch = None
 
     def gather_rows(self, parent, p0: int, p1: int) -> None:
         """Beam search's reorder: for every layer, positions [p0, p1) of row r of K and V^T become those of row parent[r] (int32 [B], device;
@@ -259,6 +381,7 @@ class KVCache:
             vr = v.permute(0, 2, 1, 3).contiguous()                              # [B, S, H, hd]: heads contiguous per token (data movement)
             ops.transpose_v(vr, S * H * hd, H * hd, B, S, H, hd, pitch=c.smax, out=c.vt[li])
         c.length = S
+        c._id_chunks = None                                        # an HF cache does not say what it was filled with
         return c
 
     @staticmethod

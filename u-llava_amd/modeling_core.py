@@ -23,8 +23,8 @@ from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaCoreConfig
 # (imported by name: the cache and the decoding helpers stay importable from this module)
-from .generation import (Decoding, GenerateOutput, beam_loop, beam_search_reference, check_generate_args, check_ngram_ban, check_prompt_lookup, check_sampler, fused_loop,
-                         host_loop, no_repeat_ngram_banned_tokens, prompt_lookup_candidates, prompt_lookup_loop, sampling_probs)
+from .generation import (Decoding, GenerateOutput, beam_loop, beam_search_reference, check_generate_args, check_ngram_ban, check_prompt_lookup, check_sampler, enter_cache,
+                         fused_loop, host_loop, no_repeat_ngram_banned_tokens, prompt_lookup_candidates, prompt_lookup_loop, sampling_probs)
 from .kv_cache import DEFAULT_HEADROOM, KV_CACHE_DTYPES, KVCache, _check_kv_dtype
 
 BF16 = torch.bfloat16
@@ -1085,6 +1085,7 @@ class UllavaCoreForCausalLM(nn.Module):
             cache = KVCache.from_hf(cache, headroom=DEFAULT_HEADROOM)
         output_hidden_states = output_hidden_states if output_hidden_states is not None else self.config.output_hidden_states
         return_dict = return_dict if return_dict is not None else self.config.use_return_dict
+        fed_ids = input_ids if inputs_embeds is None else None       # (what a cache remembers it was filled with)
         if inputs_embeds is None:
             ids, inputs_embeds = self.embed_images_videos(input_ids, images, videos)
             if inputs_embeds is None:
@@ -1102,6 +1103,8 @@ class UllavaCoreForCausalLM(nn.Module):
             loss = A.shifted_cross_entropy(logits, labels) if labels is not None else None
         else:
             last, all_h = self._llama(inputs_embeds, attention_mask, position_ids, output_hidden_states, cache)
+            if cache is not None:
+                cache.note_fed(fed_ids, inputs_embeds.shape[1], attention_mask)
             logits = ops.linear(last, self._packed["lm_head"] if self.weight_quantization is not None else self.lm_head.weight)
             loss = ops.shifted_cross_entropy(logits, labels) if labels is not None else None
         if not return_dict:
@@ -1125,6 +1128,14 @@ class UllavaCoreForCausalLM(nn.Module):
         model_inputs.update({"position_ids": position_ids, "past_key_values": past_key_values, "use_cache": kwargs.get("use_cache"),
                              "attention_mask": attention_mask, "images": images, "videos": videos})
         return model_inputs
+
+    def new_kv_cache(self, batch_size: int, capacity: int, kv_cache_dtype=None) -> KVCache:
+        """An empty KVCache of this model's geometry on its device, with room for `capacity` positions (generate() grows it when a call
+        needs more): what a first generate(past_key_values=) / evaluate(past_key_values=) call fills and later calls continue."""
+        cfg = self.config
+        H = cfg.num_attention_heads
+        return KVCache(cfg.num_hidden_layers, int(batch_size), H, cfg.hidden_size // H, max(int(capacity), 64), self.device, self.dtype,
+                       kv_dtype=kv_cache_dtype)
 
     @torch.no_grad()
     def score(self, input_ids, attention_mask=None, images=None, videos=None, labels=None):
@@ -1210,8 +1221,26 @@ class UllavaCoreForCausalLM(nn.Module):
         (the sum of log-probabilities divided by length ** length_penalty).  The host reads one word per step every 8 steps, so up to 7
         forwards may run past the stop; they change nothing.  GPU tensors only.  Not with: sampling, sampler="device", prompt lookup,
         stopping_criteria, output_hidden_states (so not through evaluate()), output_logprobs, kv_cache_dtype, or `no_repeat_ngram_size`
-        without ngram_ban="device".  num_beams=1 is the decoding above, unchanged, and refuses the three beam options."""
+        without ngram_ban="device".  num_beams=1 is the decoding above, unchanged, and refuses the three beam options.
+        past_key_values (opt-in, default None; taken by keyword from **kwargs, the one keyword read there -- `output_logprobs` stays the last
+        named parameter, which callers and tests rely on -- and every other unknown keyword keeps raising TypeError; a KVCache -- `new_kv_cache()` makes an empty one -- or an HF legacy tuple / Cache object, converted by
+        KVCache.from_hf): continue an earlier call's KV cache, with HF's semantics: `input_ids` [B, L] is the WHOLE conversation so far and
+        the cache covers its first `cache.length` positions.  It implies use_cache=True.  A KVCache remembers the ids it was filled with
+        (`cache.ids`): one launch (ops.ids_common_prefix) compares them with `input_ids` and the cache is cut to the prefix all rows share
+        (an edited last turn, another question about the same image), and to L - 1 at most, so that at least one token is fed (HF's rule);
+        the ids of an HF cache are unknown and the caller is trusted.  ONLY THE IDS ARE COMPARED, NOT THE IMAGES: a caller who changes the
+        image under equal ids gets the old image's keys, as in HF.  Step 0 then feeds the ids behind the kept positions in one forward
+        (`images` / `videos` are ignored for a non-empty cache, as the later steps ignore them; placeholder ids among the ids to feed raise
+        NotImplementedError).  `attention_mask` is [B, L] over the whole conversation; in the cached columns it may differ from the mask the
+        cache was filled under only by clearing the pad fill behind a row's last visible cached position (ValueError otherwise), so every
+        visible key keeps the RoPE position a one-shot run gives it.  The cache is advanced IN PLACE (and grown in place when it is too
+        small, KVCache.grow): after the call it covers every position that was fed, sequences.shape[1] - 1 of them.  An EMPTY KVCache is
+        filled by the call: how a first turn obtains a cache to keep.  With return_dict_in_generate=True the result carries
+        `past_key_values` (the same object), and `hidden_states` holds the last-layer states of ALL positions, the earlier calls' included.
+        Every loop but beam search, both cache dtypes (the cache's own decides; a contradicting `kv_cache_dtype` is refused).
+        `KVCache.fork()` gives an independent copy for several continuations of one prefix."""
         cfg = self.config
+        past_key_values = kwargs.pop("past_key_values", None)
         eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
         eos_list = [] if eos is None else [eos] if isinstance(eos, int) else list(eos)
         ngram, sampling, device_sampler, use_cache, lookup = check_generate_args(
@@ -1220,7 +1249,8 @@ class UllavaCoreForCausalLM(nn.Module):
             max_matching_ngram_size=max_matching_ngram_size, output_logprobs=output_logprobs, return_dict_in_generate=return_dict_in_generate,
             unknown=kwargs, dtype=self.dtype, vocab_size=cfg.vocab_size, config_use_cache=cfg.use_cache, ngram_ban=ngram_ban,
             length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,
-            stopping_criteria=stopping_criteria, output_hidden_states=output_hidden_states, n_eos=len(eos_list))
+            stopping_criteria=stopping_criteria, output_hidden_states=output_hidden_states, n_eos=len(eos_list), past_key_values=past_key_values,
+            cache_shape=(cfg.num_hidden_layers, cfg.num_attention_heads, cfg.hidden_size // cfg.num_attention_heads))
         device_ban = check_ngram_ban(ngram_ban)
         seq = input_ids
         eos_ids = None if eos is None else torch.as_tensor(eos_list, device=seq.device, dtype=seq.dtype)
@@ -1236,17 +1266,34 @@ class UllavaCoreForCausalLM(nn.Module):
         if use_cache:
             # the prefill fills it; room for every token fed (the last one emitted never is), and for a verify step's drafts
             H, room = cfg.num_attention_heads, max_new_tokens + 1 + (lookup[0] if lookup is not None else 0)
-            cache = KVCache(cfg.num_hidden_layers, seq.shape[0], H, cfg.hidden_size // H, max(seq.shape[1] + room, 64), seq.device, self.dtype,
-                            kv_dtype=kv_cache_dtype)
+            if past_key_values is None:
+                cache = KVCache(cfg.num_hidden_layers, seq.shape[0], H, cfg.hidden_size // H, max(seq.shape[1] + room, 64), seq.device, self.dtype,
+                                kv_dtype=kv_cache_dtype)
+                cache._id_chunks, cache.borrow_ids = None, True  # the call's own cache goes with the call: no ids remembered, no mask copied
+            else:
+                cache = past_key_values
+                if not isinstance(cache, KVCache):
+                    cache = KVCache.from_hf(cache, headroom=room, kv_dtype=kv_cache_dtype)
+                enter_cache(cache, seq, attention_mask, no_pad, seq.shape[1] + room, None if self.mm_token_ids is None else self.mm_token_ids.values())
         d = Decoding(self, images, videos, attention_mask, no_pad, cache, max_new_tokens, sampling, temperature, top_k, top_p, eos_ids, pad, crit,
                      output_hidden_states, keep_last_step_only, output_logprobs)
+        d.return_cache = past_key_values is not None
         if num_beams > 1:
             seq, scores = beam_loop(d, seq, num_beams, ngram, length_penalty, early_stopping, num_return_sequences)
             return GenerateOutput(sequences=seq, hidden_states=None, sequences_scores=scores) if return_dict_in_generate else seq
-        if lookup is not None:
-            seq, logprobs = prompt_lookup_loop(d, seq, lookup)
-        elif (not sampling or device_sampler) and (ngram == 0 or device_ban) and seq.is_cuda:
-            seq, logprobs = fused_loop(d, seq, ngram)
-        else:
-            seq, logprobs = host_loop(d, seq, ngram, sampling_probs, device_ban)
+        if d.return_cache:
+            # inside this call the cache notes the loops' id tensors as they come, without a copy per step: they are the loops' own buffers
+            # and are joined into a tensor of the cache's own before the call returns or raises
+            cache.borrow_ids = True
+        try:
+            if lookup is not None:
+                seq, logprobs = prompt_lookup_loop(d, seq, lookup)
+            elif (not sampling or device_sampler) and (ngram == 0 or device_ban) and seq.is_cuda:
+                seq, logprobs = fused_loop(d, seq, ngram)
+            else:
+                seq, logprobs = host_loop(d, seq, ngram, sampling_probs, device_ban)
+        finally:
+            if d.return_cache:
+                cache.borrow_ids = False
+                cache.own_ids()
         return d.result(seq, logprobs, return_dict_in_generate)

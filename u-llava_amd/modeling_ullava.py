@@ -16,6 +16,7 @@ from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaConfig
 from .generation import check_generate_args
+from .kv_cache import KVCache
 from .modeling_core import BF16, Linear, UllavaCoreForCausalLM, _Holder
 from .sam import SamEngine, build_sam_holder
 
@@ -319,7 +320,7 @@ class UllavaForCausalLM(nn.Module):
     @torch.no_grad()
     def evaluate(self, images_sam, images, input_ids, raw_size_list, resize_list, max_new_tokens=32, temperature=0.2, top_p=None,
                  num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None, ngram_ban=None,
-                 prompt_lookup_num_tokens=None, max_matching_ngram_size=None, output_logprobs=False, sampler=None):
+                 past_key_values=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, output_logprobs=False, sampler=None):
         """reference ullava.py:335-434 -> (output_ids, pred_masks, pred_boxes).  kv_cache_dtype="fp8_e4m3": generate with an fp8 KV cache
         (which implies use_cache=True; see UllavaCoreForCausalLM.generate).  sampler="device": draw the tokens with the on-device sampler
         (same ids under the same seed; see generate).  ngram_ban="device" (with no_repeat_ngram_size): the n-gram ban in one launch per step, so
@@ -328,18 +329,33 @@ class UllavaForCausalLM(nn.Module):
         (which implies use_cache=True; batch 1; with temperature > 0 it needs sampler="device"; see generate) -- the [SEG] / [LOC] rows are
         read from the hidden states of the accepted positions.  output_logprobs=True: the return grows to (output_ids, pred_masks, pred_boxes,
         logprobs), logprobs fp32 [B, n_new] as generate(output_logprobs=True) gives them (raw distribution; 0.0 after a row's EOS) -- the
-        number to drop an unsure [SEG] / [LOC] by."""
+        number to drop an unsure [SEG] / [LOC] by.
+        past_key_values (a KVCache; `new_kv_cache()` makes an empty one for the first turn): continue an earlier call's cache, as
+        generate(past_key_values=) does (which implies use_cache=True; `input_ids` is the whole conversation; only the ids are compared with
+        what the cache holds, NOT the images -- a changed image under equal ids gets the old image's keys, as in HF).  The cache is advanced
+        in place and also keeps the SAM image embeddings of the call that computed them (`cache.side["sam_image_embeddings"]`, keyed to
+        nothing else): while they are there the SAM encoder does not run.  Masks and boxes are computed from the hidden states of all
+        positions, the earlier calls' included: what the reference yields when it is fed the whole conversation."""
         # generate()'s refusals, before the SAM encoder starts (the model's dtype is asked for only where kv_cache_dtype needs it)
         gen = dict(do_sample=temperature > 0, temperature=temperature, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size,
                    sampler=sampler, return_dict_in_generate=True, output_logprobs=output_logprobs, kv_cache_dtype=kv_cache_dtype,
                    prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size, ngram_ban=ngram_ban,
-                   use_cache=True if kv_cache_dtype is not None or prompt_lookup_num_tokens is not None else None)
-        check_generate_args(input_ids, dtype=None if kv_cache_dtype is None else self.llm.dtype, output_hidden_states=True, **gen)
-        main = torch.cuda.current_stream()                          # SAM image encoder on the second stream, under the generation loop
-        side = self._side_stream()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            image_embeddings = self._visual_embs_tm(images_sam)     # its GEMMs use the side stream's own stream-K workspace
+                   use_cache=True if kv_cache_dtype is not None or prompt_lookup_num_tokens is not None or past_key_values is not None else None)
+        gen_shape = None
+        if past_key_values is not None:
+            gen["past_key_values"] = past_key_values                # (a call without one hands generate() exactly the keywords it always did)
+            lc = self.llm.config                                    # (the model's geometry is asked for only where a cache is held against it)
+            gen_shape = (lc.num_hidden_layers, lc.num_attention_heads, lc.hidden_size // lc.num_attention_heads)
+        check_generate_args(input_ids, dtype=None if kv_cache_dtype is None else self.llm.dtype, output_hidden_states=True,
+                            cache_shape=gen_shape, **gen)
+        kept = past_key_values.side if isinstance(past_key_values, KVCache) else None
+        image_embeddings = None if kept is None else kept.get("sam_image_embeddings")
+        main = side = torch.cuda.current_stream()
+        if image_embeddings is None:
+            side = self._side_stream()                              # SAM image encoder on the second stream, under the generation loop
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                image_embeddings = self._visual_embs_tm(images_sam)     # its GEMMs use the side stream's own stream-K workspace
         outputs = self.llm.generate(input_ids=input_ids, images=images, max_new_tokens=max_new_tokens, top_p=top_p, output_hidden_states=True,
                                     stopping_criteria=stopping_criteria, keep_last_step_only=True, **gen)
         output_ids = outputs.sequences
@@ -349,13 +365,22 @@ class UllavaForCausalLM(nn.Module):
         L1 = last.shape[1]
         pred_embeddings = self._select(last, seg_token_mask[:, :L1], self.seg_projector)
         pred_loc_embeddings = self._select(last, loc_token_mask[:, :L1], self.det_projector)
-        main.wait_stream(side)
-        image_embeddings.record_stream(main)
+        if side is not main:
+            main.wait_stream(side)
+            image_embeddings.record_stream(main)
+        if kept is not None:
+            # kept only now, behind the wait: a later call reads them on the main stream, ordered after the encoder; a call that raised
+            # before this line has kept nothing
+            kept["sam_image_embeddings"] = image_embeddings
         pred_masks = self._decode(image_embeddings, pred_embeddings, resize_list, raw_size_list)
         pred_boxes = [self._run_mlp(self.det_decoder, e) if e.shape[0] else e.new_empty(0, 4) for e in pred_loc_embeddings]
         if output_logprobs:
             return output_ids, pred_masks, pred_boxes, outputs.logprobs
         return output_ids, pred_masks, pred_boxes
+
+    def new_kv_cache(self, batch_size: int, capacity: int, kv_cache_dtype=None):
+        """UllavaCoreForCausalLM.new_kv_cache of the language model: an empty KVCache for evaluate(past_key_values=) to fill."""
+        return self.llm.new_kv_cache(batch_size, capacity, kv_cache_dtype)
 
     def score(self, input_ids, attention_mask=None, images=None, videos=None, labels=None):
         """UllavaCoreForCausalLM.score of the language model (see there)."""

@@ -1346,6 +1346,51 @@ def kv_gather_rows(src_k, src_vt, dst_k, dst_vt, n_layers: int, src_rows: int, d
               int(dst_p0), int(n), _p(row_map), _p(skip), _stream())
 
 
+def ids_common_prefix(ids_a: torch.Tensor, ids_b: torch.Tensor, n: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [R]: per row, the length of the common prefix of ids_a[r, :n] and ids_b[r, :n] (see ull_ids_common_prefix), in one launch.
+    ids_a / ids_b: int64 [R, >= n] with contiguous rows of any pitch (a slice of the columns of the generate buffer will do)."""
+    _chk(ids_a, "ids_a", torch.int64); _chk(ids_b, "ids_b", torch.int64)
+    n = int(n)
+    if ids_a.dim() != 2 or ids_b.dim() != 2 or ids_a.shape[0] != ids_b.shape[0] or n < 0 or ids_a.shape[1] < n or ids_b.shape[1] < n:
+        raise RuntimeError(f"u-llava_amd.ids_common_prefix: need two int64 [R, >= {n}] tensors, got {tuple(ids_a.shape)} and {tuple(ids_b.shape)}")
+    R = ids_a.shape[0]
+    for t in (ids_a, ids_b):
+        if n > 1 and t.stride(1) != 1 or (R > 1 and n > 0 and t.stride(0) < n):
+            raise RuntimeError("u-llava_amd.ids_common_prefix: the rows must be contiguous and must not overlap")
+    if out is None:
+        out = torch.empty(R, dtype=torch.int32, device=ids_a.device)
+    else:
+        _chk(out, "out", torch.int32)
+        if tuple(out.shape) != (R,) or not out.is_contiguous():
+            raise RuntimeError(f"u-llava_amd.ids_common_prefix: out must be a contiguous int32 [{R}], got {tuple(out.shape)}")
+    _lib.call("ull_ids_common_prefix", _p(ids_a), ids_a.stride(0), _p(ids_b), ids_b.stride(0), R, n, _p(out), _stream())
+    return out
+
+
+def kv8_copy_positions(src, dst, n: int) -> None:
+    """Positions [0, n) of every layer of an fp8 KV cache into another set of buffers, in one launch per 32 layers (see
+    ull_kv8_copy_positions).  src / dst: (k8 list, vt8 list, k_scale list, vt_scale list) of per-layer tensors -- codes uint8
+    [B, H, smax, hd] / [B, H, hd, smax], scales fp32 [B, H, smax]; the two pitches may differ.  Nothing at or beyond position n is written."""
+    n = int(n)
+    n_layers = len(src[0])
+    if len(src) != 4 or len(dst) != 4 or any(len(l) != n_layers for l in tuple(src) + tuple(dst)):
+        raise RuntimeError("u-llava_amd.kv8_copy_positions: src and dst are four lists of one tensor per layer each")
+    if n_layers == 0:
+        return
+    B, H, s_smax, hd = src[0][0].shape
+    d_smax = dst[0][0].shape[2]
+    for lists, smax, side in ((src, s_smax, "src"), (dst, d_smax, "dst")):
+        shapes = ((B, H, smax, hd), (B, H, hd, smax), (B, H, smax), (B, H, smax))
+        for l, shp, dt in zip(lists, shapes, (torch.uint8, torch.uint8, F32, F32)):
+            for t in l:
+                _chk(t, side, dt)
+                if tuple(t.shape) != shp or not t.is_contiguous():
+                    raise RuntimeError(f"u-llava_amd.kv8_copy_positions: a {side} buffer is {tuple(t.shape)}, not a contiguous {shp}")
+    if not 0 <= n <= min(s_smax, d_smax):
+        raise ValueError(f"u-llava_amd.kv8_copy_positions: {n} positions do not fit caches of {s_smax} and {d_smax}")
+    _lib.call("ull_kv8_copy_positions", *[_ptr_array(l) for l in src], *[_ptr_array(l) for l in dst], n_layers, B, H, hd, s_smax, d_smax, n, _stream())
+
+
 def video_pool(f: torch.Tensor, B: int, T: int, N: int, tok_pitch: Optional[int] = None, tok_off: int = 0) -> torch.Tensor:
     """f [B*T, tok_pitch, D]; patches are tokens tok_off..tok_off+N of every frame."""
     _chk(f, "f")
