@@ -61,6 +61,56 @@ struct GemmArgs {
     int rope_cols;
 };
 
+// ---- block -> tile ----------------------------------------------------------------------------------------------------------------
+// Every kernel below but patchify_strip_kernel: the hardware deals block ids round-robin over the 8 XCDs, so block b becomes the
+// (b >> 3)-th of XCD b % 8's contiguous chunk of the tile space; that chunk is walked in groups of `group_m` M-tiles per N-tile, so
+// that co-resident blocks share X / W panels in their L2.
+// bid: the block's place in the raster (a stream-K tile's slab index is bid - t_full); slice: its K slice.
+struct TileRaster { int bid, slice, bm, bn; bool split; };
+
+// 128x128 family (GROUP_M).  SLICED (gemm128_kernel's split-K): slice s = blockIdx / tiles, and every slice walks the same raster.
+template <bool SLICED = false>
+ULL_DEV TileRaster raster128(const GemmArgs& p) {
+    const int nwg = p.nbm * p.nbn;
+    const int slice = SLICED ? blockIdx.x / nwg : 0;
+    int bid = blockIdx.x - slice * nwg;
+    {
+        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;   // bijective for any nwg
+    }
+    const int per_group = GROUP_M * p.nbn;
+    const int gid = bid / per_group;
+    const int first_m = gid * GROUP_M;
+    const int gsz = min(p.nbm - first_m, GROUP_M);
+    const int bm = first_m + (bid % per_group) % gsz;
+    const int bn = (bid % per_group) / gsz;
+    return TileRaster{bid, slice, bm, bn, false};
+}
+
+// 256x256 family (p.group_m).  Blocks [0, t_full) own one whole tile each (t_full is a multiple of the CU count, so those rounds are
+// full); the remaining tiles -- which would otherwise occupy a few CUs for one more whole round -- are split `sk` ways along K.
+ULL_DEV TileRaster raster256(const GemmArgs& p) {
+    int bid = blockIdx.x;
+    int slice = 0;
+    const bool split = bid >= p.t_full;
+    if (!split) {
+        const int nwg = p.t_full;
+        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;   // bijective for any nwg
+    } else {
+        const int r = bid - p.t_full;
+        bid = p.t_full + r / p.sk;
+        slice = r % p.sk;
+    }
+    const int per_group = p.group_m * p.nbn;
+    const int gid = bid / per_group;
+    const int first_m = gid * p.group_m;
+    const int gsz = min(p.nbm - first_m, p.group_m);
+    const int bm = first_m + (bid % per_group) % gsz;
+    const int bn = (bid % per_group) / gsz;
+    return TileRaster{bid, slice, bm, bn, split};
+}
+
 // LDS-DMA: 64 lanes x 16 B from per-lane global addresses to LDS[m0 .. m0+1024) (lane-linear).
 // Issued through inline asm on purpose: hipcc models the builtin form as a pending LDS write and
 // drains it with `s_waitcnt vmcnt(0)` in front of the next ds_read, which would serialise the DMA of
@@ -423,6 +473,30 @@ ULL_DEV void staged_epilogue(const GemmArgs& p, f32x4_t (&acc)[4][JT], char* reg
     }
 }
 
+// ---- shared by the 128x128 kernels whose K-tile is a 128-byte LDS row of T: elem_t (64 per row) or fp8 codes (128 per row) --------------
+// (Only what compiles to the same instructions as each kernel's own copy did is shared.  The source-pointer setup, the K-step skeleton
+// and the MFMA block came out reordered when they moved into functions of their own -- a device function is optimized on its own before
+// it is inlined -- and stay written out in the kernels: profiles/gemm_refactor_isa.txt.)
+// Request K-tile kt of both operands into buffer `buf`: this wave's four 1-KiB pieces of each.
+template <class T>
+ULL_DEV void tile128_stage(const T* const (&xsrc)[4], const T* const (&wsrc)[4], uint32_t lds_base, int wave, int buf, int kt) {
+    const int stage_off = wave * 4 * 8 * 128;        // byte offset of this wave's first 1-KiB piece
+    const uint32_t bx = lds_base + buf * BUF_BYTES + stage_off;
+    const uint32_t bw = bx + TILE_BYTES;
+    const long ko = (long)kt * (128 / (int)sizeof(T));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        glds16(xsrc[i] + ko, bx + i * 1024);
+        glds16(wsrc[i] + ko, bw + i * 1024);
+    }
+}
+ULL_DEV void tile128_clear(f32x4_t (&acc)[4][4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+}
+
 template <bool SWIGLU, bool ROPE = false>
 __global__ __launch_bounds__(256, 2) void gemm128_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -431,23 +505,11 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(GemmArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave & 1, wm = wave >> 1;
 
-    // ---- block -> (tile, K slice): XCD-contiguous chunks, grouped raster inside --------------
     // split-K (p.sk > 1: few tiles and a long K -- the o_proj / down_proj of a single-image prefill are 96 tiles of 64 / 172 K-steps on a
     // chip that holds 512 blocks): slice s = blockIdx / tiles works on K-steps [s nk / sk, (s + 1) nk / sk) and leaves its raw fp32
     // accumulators in p.ws [tile][slice][128][128]; gemm128_splitk_finalize sums the slices in order and applies the epilogue.
-    const int nwg = p.nbm * p.nbn;
-    const int slice = blockIdx.x / nwg;
-    int bid = blockIdx.x - slice * nwg;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;   // bijective for any nwg
-    }
-    const int per_group = GROUP_M * p.nbn;
-    const int gid = bid / per_group;
-    const int first_m = gid * GROUP_M;
-    const int gsz = min(p.nbm - first_m, GROUP_M);
-    const int bm = first_m + (bid % per_group) % gsz;
-    const int bn = (bid % per_group) / gsz;
+    const TileRaster t = raster128<true>(p);
+    const int slice = t.slice, bm = t.bm, bn = t.bn;
     const int m0 = bm * BM, n0 = bn * BN;
 
     // ---- DMA source pointers (loop invariant apart from the K offset) --------------------------
@@ -463,20 +525,8 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(GemmArgs p) {
         xsrc[i] = p.X + (long)min(m0 + r, p.M - 1) * p.ldx + schunk * 8;
         wsrc[i] = p.W + (long)min(n0 + r, p.N - 1) * p.ldw + schunk * 8;
     }
-    const int stage_off = wave * 4 * 8 * (BK * 2);   // byte offset of this wave's first 1-KiB piece
-
     const uint32_t lds_base = __builtin_amdgcn_readfirstlane(
         (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-    auto stage = [&](int buf, int kt) {
-        const uint32_t bx = lds_base + buf * BUF_BYTES + stage_off;
-        const uint32_t bw = bx + TILE_BYTES;
-        const long ko = (long)kt * BK;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            glds16(xsrc[i] + ko, bx + i * 1024);
-            glds16(wsrc[i] + ko, bw + i * 1024);
-        }
-    };
 
     // ---- fragment read offsets ------------------------------------------------------------
     const int frow = lane & 15, fgrp = lane >> 4;
@@ -487,14 +537,11 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(GemmArgs p) {
     const int wrow_off = TILE_BYTES + (wn * 64 + frow) * (BK * 2);
 
     f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
+    tile128_clear(acc);
     const int nk_all = p.K / BK;
     const int k_first = p.sk > 1 ? (int)((long)nk_all * slice / p.sk) : 0;
     const int nk = p.sk > 1 ? (int)((long)nk_all * (slice + 1) / p.sk) : nk_all;
+    auto stage = [&](int buf, int kt) { tile128_stage(xsrc, wsrc, lds_base, wave, buf, kt); };
     stage(k_first & 1, k_first);
     for (int kt = k_first; kt < nk; ++kt) {
         const int cur = kt & 1;
@@ -561,19 +608,8 @@ __global__ __launch_bounds__(256, 2) void gemm128_a8w8_kernel(GemmArgs p, A8Args
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave & 1, wm = wave >> 1;
 
-    int bid = blockIdx.x;                              // XCD-contiguous chunks, grouped raster inside (as gemm128_kernel)
-    {
-        const int nwg = p.nbm * p.nbn;
-        const int qq = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + k;
-    }
-    const int per_group = GROUP_M * p.nbn;
-    const int gid = bid / per_group;
-    const int first_m = gid * GROUP_M;
-    const int gsz = min(p.nbm - first_m, GROUP_M);
-    const int bm = first_m + (bid % per_group) % gsz;
-    const int bn = (bid % per_group) / gsz;
-    const int m0 = bm * BM, n0 = bn * BN;
+    const TileRaster t = raster128(p);
+    const int m0 = t.bm * BM, n0 = t.bn * BN;
 
     // wave w, step i stages rows (w*4+i)*8 .. +8 of each tile; lane -> (row l>>3, physical chunk l&7) fetches LOGICAL chunk (l&7) ^ (row&7);
     // rows past M / N re-read the last row (their outputs are never stored)
@@ -587,18 +623,7 @@ __global__ __launch_bounds__(256, 2) void gemm128_a8w8_kernel(GemmArgs p, A8Args
         xsrc[i] = q.Xq + (long)min(m0 + r, p.M - 1) * q.ldxq + schunk * 16;
         wsrc[i] = q.Wq + (long)min(n0 + r, p.N - 1) * q.ldq + schunk * 16;
     }
-    const int stage_off = wave * 4 * 8 * BK8;
     const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-    auto stage = [&](int buf, int kt) {
-        const uint32_t bx = lds_base + buf * BUF_BYTES + stage_off;
-        const uint32_t bw = bx + TILE_BYTES;
-        const long ko = (long)kt * BK8;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            glds16(xsrc[i] + ko, bx + i * 1024);
-            glds16(wsrc[i] + ko, bw + i * 1024);
-        }
-    };
 
     // fragment: row (l & 15) of a 16-row group, logical chunks 2 (l >> 4) and 2 (l >> 4) + 1
     const int frow = lane & 15, fgrp = lane >> 4;
@@ -607,11 +632,8 @@ __global__ __launch_bounds__(256, 2) void gemm128_a8w8_kernel(GemmArgs p, A8Args
     const int wrow_off = TILE_BYTES + (wn * 64 + frow) * BK8;
 
     f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
+    tile128_clear(acc);
+    auto stage = [&](int buf, int kt) { tile128_stage(xsrc, wsrc, lds_base, wave, buf, kt); };
     const int nk = p.K / BK8;
     stage(0, 0);
     for (int kt = 0; kt < nk; ++kt) {
@@ -728,19 +750,8 @@ __global__ __launch_bounds__(256, 2) void gemm128_w4a8_kernel(GemmArgs p, W4A8Ar
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave & 1, wm = wave >> 1;
 
-    int bid = blockIdx.x;                              // XCD-contiguous chunks, grouped raster inside (as gemm128_kernel)
-    {
-        const int nwg = p.nbm * p.nbn;
-        const int qq = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + k;
-    }
-    const int per_group = GROUP_M * p.nbn;
-    const int gid = bid / per_group;
-    const int first_m = gid * GROUP_M;
-    const int gsz = min(p.nbm - first_m, GROUP_M);
-    const int bm = first_m + (bid % per_group) % gsz;
-    const int bn = (bid % per_group) / gsz;
-    const int m0 = bm * BM, n0 = bn * BN;
+    const TileRaster t = raster128(p);
+    const int m0 = t.bm * BM, n0 = t.bn * BN;
 
     // LDS: two activation K-tile buffers of 16 KiB (as gemm128_a8w8_kernel's: rows past M re-read the last row), then the 32 KiB weight image
     constexpr int WOFF = 2 * TILE_BYTES;
@@ -795,10 +806,7 @@ __global__ __launch_bounds__(256, 2) void gemm128_w4a8_kernel(GemmArgs p, W4A8Ar
     }
 
     f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    tile128_clear(acc);
 
     const int nk = p.K / BK8;
     const int nsup = (p.K >> 11) * 4;                  // super tiles; steps [0, 4 nsup) walk them, steps [4 nsup, nk) the standard-order tail
@@ -939,20 +947,11 @@ __global__ __launch_bounds__(256, 2) void patchify_gemm_kernel(GemmArgs p, Patch
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave & 1, wm = wave >> 1;
-    const int nwg = p.nbm * p.nbn;
-    int bid = blockIdx.x;
-    {
-        const int qq = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + k;
-    }
-    const int per_group = GROUP_M * p.nbn;
-    const int gid = bid / per_group;
-    const int first_m = gid * GROUP_M;
-    const int gsz = min(p.nbm - first_m, GROUP_M);
-    const int bm = first_m + (bid % per_group) % gsz;
-    const int bn = (bid % per_group) / gsz;
-    const int m0 = bm * BM, n0 = bn * BN;
+    const TileRaster t = raster128(p);
+    const int m0 = t.bm * BM, n0 = t.bn * BN;
 
+    // the W tile is staged as in gemm128_kernel; the X tile's rows are patches
+    // (this kernel keeps its own accumulator clear as well: with tile128_clear its fragment offsets were computed in another order)
     const int srow = lane >> 3;
     const int schunk = (lane & 7) ^ srow;                 // logical 16-byte chunk of the 128-byte K-tile row this lane fetches
     const int seg = schunk >> 1, half = schunk & 1;       // (c, ky) segment within the K-tile, first / second 8 kx
@@ -1005,7 +1004,6 @@ __global__ __launch_bounds__(256, 2) void patchify_gemm_kernel(GemmArgs p, Patch
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
     const int nk = p.K / BK;
     stage(0, 0);
     for (int kt = 0; kt < nk; ++kt) {
@@ -1032,8 +1030,9 @@ __global__ __launch_bounds__(256, 2) void patchify_gemm_kernel(GemmArgs p, Patch
 }
 
 // =============================================================================================================
-// Large-shape kernel: 256x256 block tile, BK = 64, two 64-KiB LDS slots (128 KiB), 512 threads = 8 waves (2 x 4),
-// 128(m) x 64(n) per wave = 32 accumulators (128 VGPR).  Measured motivation (profiles/r01_gemm_notes.md): ablating the
+// Large-shape kernels: 256x256 block tile, BK = 64, two 64-KiB LDS slots (128 KiB).  First form: 512 threads = 8 waves (2 x 4),
+// 128(m) x 64(n) per wave = 32 accumulators (128 VGPR) -- gemm256_kernel / gemm256d_kernel, which stand behind the 4-wave form and
+// the w4_* helpers they share with it ("the 8-wave kernels" below).  Measured motivation (profiles/r01_gemm_notes.md): ablating the
 // MFMAs out of either kernel leaves the run time almost unchanged -- the GEMM is bound by the HBM/L2 -> LDS staging path
 // (~85 GB/s per CU peak through the vector L1, ~0.2 us L2-hit and ~1-2 us first-touch latency), so this kernel doubles
 // the FLOPs per staged byte (128 vs 64 FLOP/B) and keeps a whole K-step of DMA in flight behind the MFMAs.
@@ -1042,7 +1041,6 @@ __global__ __launch_bounds__(256, 2) void patchify_gemm_kernel(GemmArgs p, Patch
 //     being read from one LDS slot and tile k+2 is being DMA'd into the other: two slots give a prefetch distance of 2.
 //   * two barriers per BK=64 step and a hand-dealt slot schedule (at the loop): one MFMA per slot, the fragment reads and the DMA
 //     pieces of tile k+2 spread between them so that the memory pipe sees an even stream and is never drained.
-#define ULL_STAMP(slot) ((void)0)
 
 namespace big {
 
@@ -1051,169 +1049,6 @@ constexpr int OP_BYTES = BM * BK * 2;             // 32 KiB per operand per slot
 constexpr int SLOT_BYTES = 2 * OP_BYTES;          // 64 KiB
 constexpr int LDS_BYTES = 8 * 128 * (64 * 2 + 16);   // 144 KiB: two 64-KiB K-tile slots, re-used by the 8 x 18-KiB epilogue regions
 constexpr int LDS_BYTES_W4 = LDS_BYTES + 16 * 1024;   // + the dump of the last two steps' prefetches: all 160 KiB of the CU
-
-struct Frags { uint4 w[4]; uint4 x[8]; };
-
-template <bool SWIGLU, bool ROPE = false>
-__global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wn = wave & 3, wm = wave >> 2;
-    // Blocks [0, t_full) own one whole tile each (t_full is a multiple of the CU count, so those rounds are full); the
-    // remaining tiles -- which would otherwise occupy a few CUs for one more whole round -- are split `sk` ways along K.
-    int bid = blockIdx.x;
-    int slice = 0;
-    const bool split = bid >= p.t_full;
-    if (!split) {
-        const int nwg = p.t_full;
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;   // bijective for any nwg
-    } else {
-        const int r = bid - p.t_full;
-        bid = p.t_full + r / p.sk;
-        slice = r % p.sk;
-    }
-    const int per_group = p.group_m * p.nbn;
-    const int gid = bid / per_group;
-    const int first_m = gid * p.group_m;
-    const int gsz = min(p.nbm - first_m, p.group_m);
-    const int bm = first_m + (bid % per_group) % gsz;
-    const int bn = (bid % per_group) / gsz;
-    const int m0 = bm * BM, n0 = bn * BN;
-    const int nk_total = p.K / BK;
-    const bool w_tiled = p.flags & EPI_W_TILED, x_tiled = p.flags & EPI_X_TILED;
-
-    // DMA: a 1-KiB piece = 8 rows x 128 B; wave w stages pieces 4w..4w+3 of X and of W.
-    const int srow = lane >> 3;
-    const int schunk = (lane & 7) ^ srow;
-    const elem_t* xsrc[4];
-    const elem_t* wsrc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = (wave * 4 + i) * 8 + srow;
-        xsrc[i] = x_tiled ? p.X + (((long)bm * nk_total) * BM + r) * BK + schunk * 8
-                          : p.X + (long)min(m0 + r, p.M - 1) * p.ldx + schunk * 8;
-        wsrc[i] = w_tiled ? p.W + (((long)bn * nk_total) * BN + r) * BK + schunk * 8
-                          : p.W + (long)min(n0 + r, p.N - 1) * p.ldw + schunk * 8;
-    }
-    const long xstep = x_tiled ? BM * BK : BK, wstep = w_tiled ? BN * BK : BK;    // elements between consecutive K-tiles
-    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-    const uint32_t piece_off = wave * 4 * 1024;
-    auto stage = [&](int kt) {
-        const uint32_t bx = lds_base + (kt & 1) * SLOT_BYTES + piece_off;
-        const long kox = (long)kt * xstep, kow = (long)kt * wstep;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            glds16(xsrc[i] + kox, bx + i * 1024);
-            glds16(wsrc[i] + kow, bx + OP_BYTES + i * 1024);
-        }
-    };
-
-    const int fr = lane & 15, fg = lane >> 4;
-    int swz[2];
-    swz[0] = ((0 + fg) ^ (lane & 7)) << 4;
-    swz[1] = ((4 + fg) ^ (lane & 7)) << 4;
-    const int xoff = (wm * 128 + fr) * (BK * 2);
-    const int woff = OP_BYTES + (wn * 64 + fr) * (BK * 2);
-    auto read_frags = [&](int kt, int kk, Frags& f) {
-        const char* base = smem + (kt & 1) * SLOT_BYTES + swz[kk];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f.w[i] = *(const uint4*)(base + woff + i * 16 * (BK * 2));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f.x[j] = *(const uint4*)(base + xoff + j * 16 * (BK * 2));
-    };
-
-    f32x4_t acc[4][8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    int nk = p.K / BK;                                // >= 2 (host dispatch, also per K-slice)
-    if (split) {
-        const int kt0 = (int)((long)nk * slice / p.sk), kt1 = (int)((long)nk * (slice + 1) / p.sk);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { xsrc[i] += (long)kt0 * xstep; wsrc[i] += (long)kt0 * wstep; }
-        nk = kt1 - kt0;
-    }
-    // Same step schedule as the 4-wave kernel (see there), 64 MFMA slots per wave and step: the 12 fragment reads of the tile's second
-    // half first, barrier A, the 8 DMA pieces of tile kt+2 dealt out one per 6 slots (a burst of all 64 pieces of a CU right behind
-    // the barrier measured 3-7 % slower end to end: the memory pipe wants an even stream), barrier B with the newest pieces still in
-    // flight, then the first-half fragments of tile kt+1.  The last two steps re-fetch the last tile into a 16-KiB dump.
-constexpr int ULL_W8_BAR_A = 14;
-constexpr int ULL_W8_DMA_STRIDE = 6;
-constexpr int ULL_W8_BAR_B = 40;
-constexpr int ULL_W8_FA_STRIDE = 2;
-    constexpr int W8_BAR_A = ULL_W8_BAR_A, W8_DMA_STRIDE = ULL_W8_DMA_STRIDE, W8_BAR_B = ULL_W8_BAR_B, W8_FA_STRIDE = ULL_W8_FA_STRIDE;
-    constexpr int W8_ISSUED = (W8_BAR_B - W8_BAR_A + W8_DMA_STRIDE - 1) / W8_DMA_STRIDE;
-    constexpr int W8_INFLIGHT = W8_ISSUED > 8 ? 8 : W8_ISSUED;
-    static_assert(W8_BAR_A >= 12 && W8_BAR_B >= W8_BAR_A && W8_BAR_A + 7 * W8_DMA_STRIDE < 64 && W8_BAR_B + 11 * W8_FA_STRIDE < 64, "schedule");
-    constexpr int USE_ORDER[12] = {0, 4, 1, 2, 3, 5, 6, 7, 8, 9, 10, 11};    // w0, x0, w1..w3, x1..x7
-    auto read1 = [&](int kt, int kk, Frags& f, int r) {
-        const char* base = smem + (kt & 1) * SLOT_BYTES + swz[kk];
-        if (r < 4) f.w[r] = *(const uint4*)(base + woff + r * 16 * (BK * 2));
-        else f.x[r - 4] = *(const uint4*)(base + xoff + (r - 4) * 16 * (BK * 2));
-    };
-    auto mma1 = [&](const Frags& f, int s) {
-        const int j = s >> 2, i = s & 3;
-        acc[i][j] = mfma16(f.w[i], f.x[j], acc[i][j]);
-    };
-    stage(0);
-    stage(1);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // tile 0 landed, tile 1 in flight
-    __builtin_amdgcn_s_barrier();
-    Frags fa, fb;                                     // fa: half 0 of the current tile, fb: half 1
-    read_frags(0, 0, fa);
-    const uint32_t dump = lds_base + LDS_BYTES;
-#pragma clang loop unroll(disable)
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool with_dma = kt + 2 < nk;
-        const int ktd = with_dma ? kt + 2 : nk - 1;
-        const long kox = (long)ktd * xstep, kow = (long)ktd * wstep;
-        const uint32_t bx = with_dma ? lds_base + (kt & 1) * SLOT_BYTES + piece_off : dump;
-        const uint32_t bw = with_dma ? bx + OP_BYTES : dump + 4096;
-#pragma clang loop unroll(full)
-        for (int s = 0; s < 64; ++s) {
-            if (s == W8_BAR_A) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-            if (s == W8_BAR_B) {
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(W8_INFLIGHT) : "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-            if (s < 12) read1(kt, 1, fb, s);
-            if (s >= W8_BAR_B && (s - W8_BAR_B) % W8_FA_STRIDE == 0 && (s - W8_BAR_B) / W8_FA_STRIDE < 12)
-                read1(kt + 1, 0, fa, USE_ORDER[(s - W8_BAR_B) / W8_FA_STRIDE]);
-            if (s >= W8_BAR_A && (s - W8_BAR_A) % W8_DMA_STRIDE == 0 && (s - W8_BAR_A) / W8_DMA_STRIDE < 8) {
-                const int pc = (s - W8_BAR_A) / W8_DMA_STRIDE;
-                if (pc < 4) glds16(xsrc[pc] + kox, bx + pc * 1024);
-                else glds16(wsrc[pc - 4] + kow, bw + (pc - 4) * 1024);
-            }
-            mma1(s < 32 ? fa : fb, s & 31);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    // (the dump's pieces may still be landing: they touch nothing the epilogue uses, and s_endpgm waits for them)
-
-    // ---- epilogue: acc[i][j][r] = D[n = n0 + wn*64 + i*16 + 4*fg + r][m = m0 + wm*128 + j*16 + fr] ----------
-    if (split) {
-        float* slab = p.ws + ((long)(bid - p.t_full) * p.sk + slice) * (BM * BN);
-#pragma clang loop unroll(full)
-        for (int j = 0; j < 8; ++j)
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 4; ++i)
-                *(f32x4_t*)(slab + (wm * 128 + j * 16 + fr) * BN + wn * 64 + i * 16 + fg * 4) = acc[i][j];
-        return;
-    }
-    __builtin_amdgcn_s_barrier();                          // every wave has consumed the last K-tile: LDS is free
-    staged_epilogue<SWIGLU, 8, ROPE>(p, acc, smem + wave * (128 * 144), lane, m0 + wm * 128, n0 + wn * 64, smem + (wave ^ 1) * (128 * 144));
-}
-
-// (A persistent form of this kernel -- one workgroup per CU walking its tiles, K-tile 0 of the next tile prefetched by step nk-2, the
-// epilogue staged through the slot the last step frees, K-tile 1 issued behind it -- was built and measured twice, rounds 1 and 2:
-// bit-identical results, 5-8 % SLOWER on every shape from K = 1024 to K = 11008.  The hardware's block hand-over plus a cold
-// prologue costs less than an in-kernel tile turn-around with its extra barrier and branchy DMA slots; profiles/r02_gemm_notes.md.)
 
 // ---- 4-wave form of the same tile ---------------------------------------------------------------------------------------------
 // Same 256x256x64 block tile, LDS layout, raster and stream-K tail, but 256 threads = 4 waves (2 x 2), 128(m) x 128(n) per wave:
@@ -1454,28 +1289,12 @@ ULL_DEV void w4_direct_epilogue(const GemmArgs& p, f32x4_t (&acc)[NH][4][8], int
 template <bool SWIGLU, bool ROPE = false>
 __global__ __launch_bounds__(256) void gemm256w4_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    ULL_STAMP(0); ULL_STAMP(7);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave & 1, wm = wave >> 1;
-    int bid = blockIdx.x;
-    int slice = 0;
-    const bool split = bid >= p.t_full;
-    if (!split) {
-        const int nwg = p.t_full;
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;   // bijective for any nwg
-    } else {
-        const int r = bid - p.t_full;
-        bid = p.t_full + r / p.sk;
-        slice = r % p.sk;
-    }
-    const int per_group = p.group_m * p.nbn;
-    const int gid = bid / per_group;
-    const int first_m = gid * p.group_m;
-    const int gsz = min(p.nbm - first_m, p.group_m);
-    const int bm = first_m + (bid % per_group) % gsz;
-    const int bn = (bid % per_group) / gsz;
+    const TileRaster t = raster256(p);
+    const int bid = t.bid, slice = t.slice, bm = t.bm, bn = t.bn;
+    const bool split = t.split;
     const int m0 = bm * BM, n0 = bn * BN;
     const int nk_total = p.K / BK;
     const bool w_tiled = p.flags & EPI_W_TILED, x_tiled = p.flags & EPI_X_TILED;
@@ -1545,12 +1364,10 @@ __global__ __launch_bounds__(256) void gemm256w4_kernel(GemmArgs p) {
         xbase += (long)kt0 * xstep; wbase += (long)kt0 * wstep;
         nk = kt1 - kt0;
     }
-    ULL_STAMP(1);                                     // index arithmetic done
     stage_all(0);
     stage_all(1);
     asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); // tile 0 landed, tile 1 in flight
     __builtin_amdgcn_s_barrier();
-    ULL_STAMP(2);                                     // first K-tile in LDS
     Frags4 fa, fb;                                    // fa: half 0 of the current tile, fb: half 1
 #pragma unroll
     for (int c = 0; c < 16; ++c) read_one(0, 0, fa, c);
@@ -1631,7 +1448,6 @@ constexpr int ULL_W4_DMA_STRIDE = 7;
         }
         if (kt == nk - 1) asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
     }
-    ULL_STAMP(3);                                     // K-loop done
     asm volatile("s_mov_b32 m0, %0" :: "s"(m0_keep) : "memory");   // (the dump's pieces may still be landing: they touch nothing
                                                                     // the epilogue uses, and s_endpgm waits for them)
 
@@ -1655,9 +1471,7 @@ constexpr int ULL_W4_DMA_STRIDE = 7;
                                      ((SWIGLU ? p.N / 2 : p.N) & 7) == 0 && (!(fl & EPI_RESID) || (p.ldr & 7) == 0) && !(fl & ULL_W4_FORCE_STAGED));
         if (direct) {
             w4_direct_epilogue<SWIGLU, ROPE>(p, acc, lane, mrow0, nw0);
-            ULL_STAMP(4);                             // stores issued
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            ULL_STAMP(5);                             // stores retired (this wave's)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // stores retired (this wave's)
             return;
         }
     }
@@ -1856,180 +1670,37 @@ __global__ __launch_bounds__(512) void patchify_strip_kernel(GemmArgs p, PatchAr
     }
 }
 
-// ---- 8 waves, permuted W rows, register-direct epilogue ----------------------------------------------------------------------------
-// The 8-wave K-loop with the 4-wave kernel's W-row permutation and direct epilogue (one 64-column half per wave).  For launches whose
-// epilogue is VALU-heavy -- QuickGELU / erf-GELU -- two waves per SIMD issue the activation at the full VALU rate (one wave per SIMD gets
-// every other issue slot), which outweighs this form's 4 % slower K-loop at K = 1024 / 1280.
+// ---- the 8-wave kernels: one body, two W layouts ---------------------------------------------------------------------------------
+// 512 threads = 8 waves (2 x 4), 128(m) x 64(n) per wave = 32 accumulators (128 VGPR); see the head of this section.  The two kernels
+// are one text, gemm256_w8_body.inc (why a text and not a function: there), compiled for the two layouts of the W tile:
+//   gemm256_kernel   W rows in order, swizzled by row & 7 like X; the LDS-staged epilogue.
+//   gemm256d_kernel  the 4-wave kernel's W-row permutation (w4_* above) and its register-direct epilogue, one 64-column half per wave,
+//                    the staged one (PERM = 1) where the direct form does not apply.  For launches whose epilogue is VALU-heavy --
+//                    QuickGELU / erf-GELU -- two waves per SIMD issue the activation at the full VALU rate (one wave per SIMD gets every
+//                    other issue slot), which outweighs this form's 4 % slower K-loop at K = 1024 / 1280.
+// Step schedule of the body: barrier A before slot W8_BAR_A, one DMA piece every W8_DMA_STRIDE slots from there, barrier B before slot
+// W8_BAR_B, one first-half fragment of the next tile every W8_FA_STRIDE slots from there.
+constexpr int W8_BAR_A = 14, W8_DMA_STRIDE = 6, W8_BAR_B = 40, W8_FA_STRIDE = 2;
+constexpr int W8_ISSUED = (W8_BAR_B - W8_BAR_A + W8_DMA_STRIDE - 1) / W8_DMA_STRIDE;      // pieces of tile kt+2 issued before barrier B
+constexpr int W8_INFLIGHT = W8_ISSUED > 8 ? 8 : W8_ISSUED;
+static_assert(W8_BAR_A >= 12 && W8_BAR_B >= W8_BAR_A && W8_BAR_A + 7 * W8_DMA_STRIDE < 64 && W8_BAR_B + 11 * W8_FA_STRIDE < 64, "schedule");
+
+struct Frags { uint4 w[4]; uint4 x[8]; };
+
+template <bool SWIGLU, bool ROPE = false>
+__global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
+    constexpr bool PERMUTED_W = false;
+#include "gemm256_w8_body.inc"
+}
 __global__ __launch_bounds__(512) void gemm256d_kernel(GemmArgs p) {
-    constexpr bool SWIGLU = false, ROPE = false;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wn = wave & 3, wm = wave >> 2;
-    // Blocks [0, t_full) own one whole tile each (t_full is a multiple of the CU count, so those rounds are full); the
-    // remaining tiles -- which would otherwise occupy a few CUs for one more whole round -- are split `sk` ways along K.
-    int bid = blockIdx.x;
-    int slice = 0;
-    const bool split = bid >= p.t_full;
-    if (!split) {
-        const int nwg = p.t_full;
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;   // bijective for any nwg
-    } else {
-        const int r = bid - p.t_full;
-        bid = p.t_full + r / p.sk;
-        slice = r % p.sk;
-    }
-    const int per_group = p.group_m * p.nbn;
-    const int gid = bid / per_group;
-    const int first_m = gid * p.group_m;
-    const int gsz = min(p.nbm - first_m, p.group_m);
-    const int bm = first_m + (bid % per_group) % gsz;
-    const int bn = (bid % per_group) / gsz;
-    const int m0 = bm * BM, n0 = bn * BN;
-    const int nk_total = p.K / BK;
-    const bool w_tiled = p.flags & EPI_W_TILED, x_tiled = p.flags & EPI_X_TILED;
-
-    // DMA: a 1-KiB piece = 8 rows x 128 B; wave w stages pieces 4w..4w+3 of X and of W.
-    const int srow = lane >> 3;
-    const int schunk = (lane & 7) ^ srow;
-    const elem_t* xsrc[4];
-    const elem_t* wsrc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = (wave * 4 + i) * 8 + srow;
-        xsrc[i] = x_tiled ? p.X + (((long)bm * nk_total) * BM + r) * BK + schunk * 8
-                          : p.X + (long)min(m0 + r, p.M - 1) * p.ldx + schunk * 8;
-        const int wchunk = (lane & 7) ^ w4_row_swizzle<false>(r);           // permuted W rows: the W tile's own swizzle
-        wsrc[i] = w_tiled ? p.W + (((long)bn * nk_total) * BN + r) * BK + wchunk * 8
-                          : p.W + (long)min(n0 + r, p.N - 1) * p.ldw + wchunk * 8;
-    }
-    const long xstep = x_tiled ? BM * BK : BK, wstep = w_tiled ? BN * BK : BK;    // elements between consecutive K-tiles
-    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-    const uint32_t piece_off = wave * 4 * 1024;
-    auto stage = [&](int kt) {
-        const uint32_t bx = lds_base + (kt & 1) * SLOT_BYTES + piece_off;
-        const long kox = (long)kt * xstep, kow = (long)kt * wstep;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            glds16(xsrc[i] + kox, bx + i * 1024);
-            glds16(wsrc[i] + kow, bx + OP_BYTES + i * 1024);
-        }
-    };
-
-    const int fr = lane & 15, fg = lane >> 4;
-    int swz[2];
-    swz[0] = ((0 + fg) ^ (lane & 7)) << 4;
-    swz[1] = ((4 + fg) ^ (lane & 7)) << 4;
-    int wswz[2];
-    wswz[0] = ((0 + fg) ^ (fr >> 1)) << 4;
-    wswz[1] = ((4 + fg) ^ (fr >> 1)) << 4;
-    const int xoff = (wm * 128 + fr) * (BK * 2);
-    const int woff = OP_BYTES + (wn * 64 + w4_lane_row<false>(fr)) * (BK * 2);
-    auto read_frags = [&](int kt, int kk, Frags& f) {
-        const char* base = smem + (kt & 1) * SLOT_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f.w[i] = *(const uint4*)(base + wswz[kk] + woff + w4_frag_row<false>(i) * (BK * 2));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f.x[j] = *(const uint4*)(base + swz[kk] + xoff + j * 16 * (BK * 2));
-    };
-
-    f32x4_t acc[1][4][8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[0][i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    int nk = p.K / BK;                                // >= 2 (host dispatch, also per K-slice)
-    if (split) {
-        const int kt0 = (int)((long)nk * slice / p.sk), kt1 = (int)((long)nk * (slice + 1) / p.sk);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { xsrc[i] += (long)kt0 * xstep; wsrc[i] += (long)kt0 * wstep; }
-        nk = kt1 - kt0;
-    }
-    // Same step schedule as the 4-wave kernel (see there), 64 MFMA slots per wave and step: the 12 fragment reads of the tile's second
-    // half first, barrier A, the 8 DMA pieces of tile kt+2 dealt out one per 6 slots (a burst of all 64 pieces of a CU right behind
-    // the barrier measured 3-7 % slower end to end: the memory pipe wants an even stream), barrier B with the newest pieces still in
-    // flight, then the first-half fragments of tile kt+1.  The last two steps re-fetch the last tile into a 16-KiB dump.
-constexpr int ULL_W8_BAR_A = 14;
-constexpr int ULL_W8_DMA_STRIDE = 6;
-constexpr int ULL_W8_BAR_B = 40;
-constexpr int ULL_W8_FA_STRIDE = 2;
-    constexpr int W8_BAR_A = ULL_W8_BAR_A, W8_DMA_STRIDE = ULL_W8_DMA_STRIDE, W8_BAR_B = ULL_W8_BAR_B, W8_FA_STRIDE = ULL_W8_FA_STRIDE;
-    constexpr int W8_ISSUED = (W8_BAR_B - W8_BAR_A + W8_DMA_STRIDE - 1) / W8_DMA_STRIDE;
-    constexpr int W8_INFLIGHT = W8_ISSUED > 8 ? 8 : W8_ISSUED;
-    static_assert(W8_BAR_A >= 12 && W8_BAR_B >= W8_BAR_A && W8_BAR_A + 7 * W8_DMA_STRIDE < 64 && W8_BAR_B + 11 * W8_FA_STRIDE < 64, "schedule");
-    constexpr int USE_ORDER[12] = {0, 4, 1, 2, 3, 5, 6, 7, 8, 9, 10, 11};    // w0, x0, w1..w3, x1..x7
-    auto read1 = [&](int kt, int kk, Frags& f, int r) {
-        const char* base = smem + (kt & 1) * SLOT_BYTES;
-        if (r < 4) f.w[r] = *(const uint4*)(base + wswz[kk] + woff + w4_frag_row<false>(r) * (BK * 2));
-        else f.x[r - 4] = *(const uint4*)(base + swz[kk] + xoff + (r - 4) * 16 * (BK * 2));
-    };
-    auto mma1 = [&](const Frags& f, int s) {
-        const int j = s >> 2, i = s & 3;
-        acc[0][i][j] = mfma16(f.w[i], f.x[j], acc[0][i][j]);
-    };
-    stage(0);
-    stage(1);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // tile 0 landed, tile 1 in flight
-    __builtin_amdgcn_s_barrier();
-    Frags fa, fb;                                     // fa: half 0 of the current tile, fb: half 1
-    read_frags(0, 0, fa);
-    const uint32_t dump = lds_base + LDS_BYTES;
-#pragma clang loop unroll(disable)
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool with_dma = kt + 2 < nk;
-        const int ktd = with_dma ? kt + 2 : nk - 1;
-        const long kox = (long)ktd * xstep, kow = (long)ktd * wstep;
-        const uint32_t bx = with_dma ? lds_base + (kt & 1) * SLOT_BYTES + piece_off : dump;
-        const uint32_t bw = with_dma ? bx + OP_BYTES : dump + 4096;
-#pragma clang loop unroll(full)
-        for (int s = 0; s < 64; ++s) {
-            if (s == W8_BAR_A) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-            if (s == W8_BAR_B) {
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(W8_INFLIGHT) : "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-            if (s < 12) read1(kt, 1, fb, s);
-            if (s >= W8_BAR_B && (s - W8_BAR_B) % W8_FA_STRIDE == 0 && (s - W8_BAR_B) / W8_FA_STRIDE < 12)
-                read1(kt + 1, 0, fa, USE_ORDER[(s - W8_BAR_B) / W8_FA_STRIDE]);
-            if (s >= W8_BAR_A && (s - W8_BAR_A) % W8_DMA_STRIDE == 0 && (s - W8_BAR_A) / W8_DMA_STRIDE < 8) {
-                const int pc = (s - W8_BAR_A) / W8_DMA_STRIDE;
-                if (pc < 4) glds16(xsrc[pc] + kox, bx + pc * 1024);
-                else glds16(wsrc[pc - 4] + kow, bw + (pc - 4) * 1024);
-            }
-            mma1(s < 32 ? fa : fb, s & 31);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    // (the dump's pieces may still be landing: they touch nothing the epilogue uses, and s_endpgm waits for them)
-
-    // ---- epilogue: acc[i][j][r] = D[n = n0 + wn*64 + i*16 + 4*fg + r][m = m0 + wm*128 + j*16 + fr] ----------
-    if (split) {
-        float* slab = p.ws + ((long)(bid - p.t_full) * p.sk + slice) * (BM * BN);
-#pragma clang loop unroll(full)
-        for (int j = 0; j < 8; ++j)
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 4; ++i)
-                *(f32x4_t*)(slab + (wm * 128 + j * 16 + fr) * BN + wn * 64 + w4_acc_row<false>(0, i, fg)) = acc[0][i][j];
-        return;
-    }
-    {
-        const int fl = p.flags;
-        const bool direct = !(fl & (EPI_OUT_F32 | EPI_BIAS_ROUNDED)) && (!(fl & EPI_ACT_MASK) || !(fl & EPI_RESID)) && (p.ldc & 7) == 0 && (p.N & 7) == 0 &&
-                            (!(fl & EPI_RESID) || (p.ldr & 7) == 0) && !(fl & ULL_W4_FORCE_STAGED);
-        if (direct) {
-            w4_direct_epilogue<false, false, 1>(p, acc, lane, m0 + wm * 128, n0 + wn * 64);
-            return;
-        }
-    }
-    __builtin_amdgcn_s_barrier();                          // every wave has consumed the last K-tile: LDS is free
-    staged_epilogue<false, 8, false, 0, false, 2, false, 1>(p, acc[0], smem + wave * (128 * 144), lane, m0 + wm * 128, n0 + wn * 64);
+    constexpr bool SWIGLU = false, ROPE = false, PERMUTED_W = true;
+#include "gemm256_w8_body.inc"
 }
 
-
+// (A persistent form of the 8-wave kernel -- one workgroup per CU walking its tiles, K-tile 0 of the next tile prefetched by step nk-2, the
+// epilogue staged through the slot the last step frees, K-tile 1 issued behind it -- was built and measured twice, rounds 1 and 2:
+// bit-identical results, 5-8 % SLOWER on every shape from K = 1024 to K = 11008.  The hardware's block hand-over plus a cold
+// prologue costs less than an in-kernel tile turn-around with its extra barrier and branchy DMA slots; profiles/r02_gemm_notes.md.)
 
 // (A v_mfma_f32_32x32x16_bf16 variant of this kernel measured 6-11 % slower in this structure and was removed;
 // numbers in profiles/r01_gemm_notes.md.)
@@ -2130,10 +1801,36 @@ __global__ __launch_bounds__(256) void splitk_finalize_any_kernel(GemmArgs p) {
 
 }  // namespace
 
+// A kernel family's three epilogue instantiations (plain, SwiGLU, fused RoPE) and its launch shape.
+using GemmKernel = void (*)(GemmArgs);
+struct GemmFamily { GemmKernel plain, swiglu, rope; int threads, lds; };
+static const GemmFamily FAMILY_128 = {gemm128_kernel<false>, gemm128_kernel<true>, gemm128_kernel<false, true>, 256, GEMM_LDS};
+static const GemmFamily FAMILY_256_W8 = {big::gemm256_kernel<false>, big::gemm256_kernel<true>, big::gemm256_kernel<false, true>, 512, big::LDS_BYTES_W4};
+static const GemmFamily FAMILY_256_W4 = {big::gemm256w4_kernel<false>, big::gemm256w4_kernel<true>, big::gemm256w4_kernel<false, true>, 256, big::LDS_BYTES_W4};
+static void gemm_launch(const GemmFamily& f, bool swiglu, bool rope, int grid, void* stream, const GemmArgs& a) {
+    hipLaunchKernelGGL(swiglu ? f.swiglu : rope ? f.rope : f.plain, dim3(grid), dim3(f.threads), f.lds, (hipStream_t)stream, a);
+}
+
 // Per-device launch state (function attributes are per device; the CU count sizes the stream-K tail).  No allocation, no stream
 // state: the only scratch the GEMM needs -- the fp32 slabs of the stream-K tail -- is the caller's (`ws`), so two streams
 // never share anything.
 static int gemm_device_state(int* n_cu_out) {
+    // every kernel that asks for more dynamic LDS than the default limit, with the most it is launched with
+    struct LdsNeed { const void* kernel; int bytes; };
+    static const LdsNeed LDS_NEEDS[] = {
+        {(const void*)FAMILY_256_W8.plain, big::LDS_BYTES_W4}, {(const void*)FAMILY_256_W8.swiglu, big::LDS_BYTES_W4},
+        {(const void*)FAMILY_256_W8.rope, big::LDS_BYTES_W4},  {(const void*)big::gemm256d_kernel, big::LDS_BYTES_W4},
+        {(const void*)FAMILY_256_W4.plain, big::LDS_BYTES_W4}, {(const void*)FAMILY_256_W4.swiglu, big::LDS_BYTES_W4},
+        {(const void*)FAMILY_256_W4.rope, big::LDS_BYTES_W4},
+        {(const void*)FAMILY_128.plain, GEMM_LDS}, {(const void*)FAMILY_128.swiglu, GEMM_LDS}, {(const void*)FAMILY_128.rope, GEMM_LDS},
+        {(const void*)patchify_gemm_kernel<0>, GEMM_LDS},
+#ifndef ULL_ELEM_F16
+        {(const void*)gemm128_a8w8_kernel<false>, GEMM_LDS}, {(const void*)gemm128_a8w8_kernel<true>, GEMM_LDS},
+        {(const void*)gemm128_w4a8_kernel<false>, GEMM_LDS}, {(const void*)gemm128_w4a8_kernel<true>, GEMM_LDS},
+#endif
+        {(const void*)big::patchify_strip_kernel<9>, 2 * (288 + 256) * 128 + 256},
+        {(const void*)big::patchify_strip_kernel<4>, 2 * (128 + 256) * 128 + 256},
+    };
     constexpr int MAX_DEV = 64;
     static int n_cu[MAX_DEV];            // 0 = not yet initialised
     int dev = 0;
@@ -2141,25 +1838,7 @@ static int gemm_device_state(int* n_cu_out) {
     if (!n_cu[dev]) {
         hipDeviceProp_t prop;
         const int n = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        (void)hipFuncSetAttribute((const void*)big::gemm256_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, big::LDS_BYTES_W4);
-        (void)hipFuncSetAttribute((const void*)big::gemm256_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, big::LDS_BYTES_W4);
-        (void)hipFuncSetAttribute((const void*)big::gemm256_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big::LDS_BYTES_W4);
-        (void)hipFuncSetAttribute((const void*)big::gemm256d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, big::LDS_BYTES_W4);
-        (void)hipFuncSetAttribute((const void*)big::gemm256w4_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, big::LDS_BYTES_W4);
-        (void)hipFuncSetAttribute((const void*)big::gemm256w4_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, big::LDS_BYTES_W4);
-        (void)hipFuncSetAttribute((const void*)big::gemm256w4_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big::LDS_BYTES_W4);
-        (void)hipFuncSetAttribute((const void*)gemm128_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-        (void)hipFuncSetAttribute((const void*)gemm128_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-        (void)hipFuncSetAttribute((const void*)gemm128_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-        (void)hipFuncSetAttribute((const void*)patchify_gemm_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-#ifndef ULL_ELEM_F16
-        (void)hipFuncSetAttribute((const void*)gemm128_a8w8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-        (void)hipFuncSetAttribute((const void*)gemm128_a8w8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-        (void)hipFuncSetAttribute((const void*)gemm128_w4a8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-        (void)hipFuncSetAttribute((const void*)gemm128_w4a8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-#endif
-        (void)hipFuncSetAttribute((const void*)big::patchify_strip_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (288 + 256) * 128 + 256);
-        (void)hipFuncSetAttribute((const void*)big::patchify_strip_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 256) * 128 + 256);
+        for (const LdsNeed& k : LDS_NEEDS) (void)hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes);
         n_cu[dev] = n;                   // last: a racing first call on another thread repeats the (idempotent) attribute calls
     }
     *n_cu_out = n_cu[dev];
@@ -2244,19 +1923,9 @@ static int gemm_dispatch(const void* X, int64_t ldx, const void* W, int64_t ldw,
                                    ((flags & EPI_ACT_MASK) >> EPI_ACT_SHIFT) != 3 && K < 3072;
         if (waves8_direct) {
             hipLaunchKernelGGL(big::gemm256d_kernel, dim3(grid), dim3(512), big::LDS_BYTES_W4, (hipStream_t)stream, a);
-        } else if (waves4) {
-            if (flags & EPI_SWIGLU)
-                hipLaunchKernelGGL(big::gemm256w4_kernel<true>, dim3(grid), dim3(256), big::LDS_BYTES_W4, (hipStream_t)stream, a);
-            else if (rope)
-                hipLaunchKernelGGL((big::gemm256w4_kernel<false, true>), dim3(grid), dim3(256), big::LDS_BYTES_W4, (hipStream_t)stream, a);
-            else
-                hipLaunchKernelGGL(big::gemm256w4_kernel<false>, dim3(grid), dim3(256), big::LDS_BYTES_W4, (hipStream_t)stream, a);
-        } else if (flags & EPI_SWIGLU)
-            hipLaunchKernelGGL(big::gemm256_kernel<true>, dim3(grid), dim3(512), big::LDS_BYTES_W4, (hipStream_t)stream, a);
-        else if (rope)
-            hipLaunchKernelGGL((big::gemm256_kernel<false, true>), dim3(grid), dim3(512), big::LDS_BYTES_W4, (hipStream_t)stream, a);
-        else
-            hipLaunchKernelGGL(big::gemm256_kernel<false>, dim3(grid), dim3(512), big::LDS_BYTES_W4, (hipStream_t)stream, a);
+        } else {
+            gemm_launch(waves4 ? FAMILY_256_W4 : FAMILY_256_W8, flags & EPI_SWIGLU, rope, grid, stream, a);
+        }
         if (a.sk > 1) hipLaunchKernelGGL((big::splitk_finalize_any_kernel<big::BM, big::BN, false>), dim3(32, rem), dim3(256), 0, (hipStream_t)stream, a);
         return ull_check_launch();
     }
@@ -2276,12 +1945,7 @@ static int gemm_dispatch(const void* X, int64_t ldx, const void* W, int64_t ldw,
         if (sk > 1) { a.sk = sk; a.ws = (float*)ws; }
     }
     const int grid = T * a.sk;
-    if (flags & EPI_SWIGLU)
-        hipLaunchKernelGGL(gemm128_kernel<true>, dim3(grid), dim3(256), GEMM_LDS, (hipStream_t)stream, a);
-    else if (rope)
-        hipLaunchKernelGGL((gemm128_kernel<false, true>), dim3(grid), dim3(256), GEMM_LDS, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(gemm128_kernel<false>, dim3(grid), dim3(256), GEMM_LDS, (hipStream_t)stream, a);
+    gemm_launch(FAMILY_128, flags & EPI_SWIGLU, rope, grid, stream, a);
     if (a.sk > 1) hipLaunchKernelGGL((big::splitk_finalize_any_kernel<BM, BN, true>), dim3(16, T), dim3(256), 0, (hipStream_t)stream, a);
     return ull_check_launch();
 }
