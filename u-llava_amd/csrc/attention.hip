@@ -1307,179 +1307,16 @@ __global__ __launch_bounds__(512, 4) void attn_stream_kernel(AttnArgs p) {
 constexpr int ULL_SAMG_VA = 5;
 constexpr int ULL_SAMG_VB = 8;
 __global__ __launch_bounds__(256, 2) void sam_global_kernel(AttnArgs p) {
-    extern __shared__ __attribute__((aligned(256))) char smem[];
-    constexpr int NWV = 4, NG = 2, BQ = 16 * NG * NWV, HDP = 128, hd = 80;
-    constexpr int KROW = HDP * 2, NKS = 3 /* 96 = 3 x 32 >= hd */, NDS = 5 /* 80 = 5 x 16 */;
-    constexpr int TILE = 64 * KROW;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 15, fg = lane >> 4;
-    const int nq = p.Sq / BQ;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int head = (slot / nq) * 8 + xcd;
-    if (head >= p.B * p.H) return;
-    const int qt = slot % nq;
-    const int b = head / p.H, h = head % p.H;
-    const int q0 = qt * BQ + wave * 16 * NG;                   // this wave's first query; its 32 queries share the grid row qy
-    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-    elem_t* ghl = (elem_t*)(smem + 4 * TILE) + wave * (64 * 16 * NG);     // [64 key rows][32 queries]: rel_h, 16-bit (a tile's read = 64 B)
-
-    uint4 qf[NG][NKS];
+#include "sam_global_prologue.inc"
+    // the one-pass form's row sum: an accumulator of its own, fed by one more "V^T row" of ones
+    f32x4_t lacc[NG];
 #pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        const elem_t* qp = p.Q + (long)b * p.q_bs + (long)h * p.q_hs + (long)(q0 + g * 16 + fr) * p.q_ss;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const int d = ks * 32 + fg * 8;
-            qf[g][ks] = d < hd ? *(const uint4*)(qp + d) : make_uint4(0, 0, 0, 0);
-        }
-    }
-    // G[q][t] = 16-bit(q . rel_pos[t]) on the MFMA (A = table rows, B = the UNSCALED query fragments): rel_w[q][kw] = Gw[q][qx - kw + 63],
-    // rel_h[q][kh] = Gh[q][qy - kh + 63].  Gw: all 127 rows -> this wave's pad (aliases the tile slots, not in use yet) -> 16 registers per
-    // group; Gh: the 64 rows qy - kh + 63 -> the wave's LDS table.
-    float rw[NG][16];
-    {
-        elem_t* gw = (elem_t*)(smem + wave * (NG * 4096));      // [group][16 queries][128]
-        const int qy = q0 >> 6;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-#pragma unroll 2
-            for (int st = 0; st < 8; ++st) {
-                f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-                const elem_t* tr = p.rel_w + (long)min(st * 16 + fr, 126) * hd + fg * 8;
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) {
-                    const uint4 a = (ks * 32 + fg * 8 < hd) ? *(const uint4*)(tr + ks * 32) : make_uint4(0, 0, 0, 0);
-                    acc = mfma16(a, qf[g][ks], acc);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gw[g * 2048 + fr * 128 + st * 16 + fg * 4 + r] = f2e(acc[r]);   // G[t = st*16 + 4*fg + r][query fr]
-            }
-#pragma unroll 2
-            for (int st = 0; st < 4; ++st) {
-                f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-                const elem_t* tr = p.rel_h + (long)(qy - (st * 16 + fr) + 63) * hd + fg * 8;               // row of key-grid row kh = st*16 + fr
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) {
-                    const uint4 a = (ks * 32 + fg * 8 < hd) ? *(const uint4*)(tr + ks * 32) : make_uint4(0, 0, 0, 0);
-                    acc = mfma16(a, qf[g][ks], acc);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ghl[(st * 16 + fg * 4 + r) * (16 * NG) + g * 16 + fr] = f2e(acc[r]);  // Gh[kh = st*16 + 4*fg + r][query fr]
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // own pad only
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int qx = (q0 + g * 16 + fr) & 63;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) rw[g][i] = e2f(gw[g * 2048 + fr * 128 + qx - ((i >> 2) * 16 + fg * 4 + (i & 3)) + 63]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-    if (p.q_scale != 1.0f) {
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) qf[g][ks] = scale_q8(qf[g][ks], p.q_scale);
-    }
-    __builtin_amdgcn_s_barrier();                              // every wave is done with its pad before tile 0 is DMA'd over it
-
-    // LDS: K ring [2][64 x 256 B] at 0, V ring [2][64 x 256 B] at 2 TILE, rel_h tables behind.  DMA: a tile is 16 pieces of 1 KiB (4 key rows x
-    // 16 chunks); a wave issues 4 K + 4 V pieces per step.  The per-lane byte offset of every piece is the same for all 64 tiles; the six
-    // chunks of a row that are head-dim padding are not transferred: chunks 10 / 11 of every K row (dims 80..95, read by the last QK k-step)
-    // are zeroed once per buffer, the rest is never read.
-    const elem_t* kbase = p.K + (long)b * p.k_bs + (long)h * p.k_hs;
-    const elem_t* vbase = p.Vt + (long)b * p.vt_bs + (long)h * p.vt_hs;
-    uint32_t dko[4], dvo[4];
-    bool dk_real[4], dv_real[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int i = wave + j * NWV, row = i * 4 + (lane >> 4), cpos = lane & 15;
-        const int ck = cpos ^ (row & 15), cv = ((((cpos >> 1) ^ (row & 7)) << 1) | (cpos & 1));
-        dko[j] = (uint32_t)(((long)row * p.k_ss + ck * 8) * 2);
-        dvo[j] = (uint32_t)(((long)row * p.vt_ds + cv * 8) * 2);
-        dk_real[j] = ck * 8 < hd;
-        dv_real[j] = cv * 8 < hd;
-    }
-    for (int t = tid; t < 2 * 64 * 2; t += 64 * NWV) {
-        const int sl = t >> 7, row = (t & 127) >> 1, c = 10 + (t & 1);
-        *(uint4*)(smem + sl * TILE + row * KROW + ((c ^ (row & 15)) << 4)) = make_uint4(0, 0, 0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // (the first barrier below orders these writes before every read)
-    auto issue_k = [&](int kt) {
-        if (kt >= 64) return;
-        const uint32_t dst = lds_base + (kt & 1) * TILE;
-        const elem_t* tk = kbase + (long)kt * KT * p.k_ss;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (dk_real[j]) glds16s(tk, dko[j], dst + (wave + j * NWV) * 1024);
-    };
-    auto issue_v = [&](int kt) {
-        if (kt >= 64) return;
-        const uint32_t dst = lds_base + (2 + (kt & 1)) * TILE;
-        const elem_t* tv = vbase + (long)kt * KT * p.vt_ds;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (dv_real[j]) glds16s(tv, dvo[j], dst + (wave + j * NWV) * 1024);
-    };
-    // LDS fragment addresses, per lane and once: K fragment of k-step ks in rows fr, fr + 16, ... (the swizzle term of row 16 ns + fr is fr);
-    // V fragment base of the transposing reads (see attn_reg_kernel)
-    uint32_t kfo[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) kfo[ks] = fr * KROW + (((ks * 4 + fg) ^ fr) << 4);
-    const int swr = 4 * (fg & 1) + (fr >> 2);
-    const uint32_t vfo = 2 * TILE + (4 * fg + (fr >> 2)) * KROW + ((fr & 2) << 3) + ((fr & 1) << 3);
-
-    f32x4_t oacc[NG][NDS], lacc[NG];
-    float m[NG], mn[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        m[g] = -INFINITY;
-        lacc[g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ds = 0; ds < NDS; ++ds) oacc[g][ds] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
+    for (int g = 0; g < NG; ++g) lacc[g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #ifdef ULL_ELEM_F16
     const uint4 ones = make_uint4(0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u);
 #else
     const uint4 ones = make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);
 #endif
-    // S tile kt on the matrix pipe: 4 x 3 K fragments, each into both groups' chains (24 MFMAs)
-    auto qk = [&](int kt, f32x4_t (&acc)[NG][4]) {
-        const char* tb = smem + (kt & 1) * TILE;
-#pragma unroll
-        for (int ns = 0; ns < 4; ++ns) {
-#pragma unroll
-            for (int g = 0; g < NG; ++g) acc[g][ns] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                const uint4 kf = *(const uint4*)(tb + ns * 16 * KROW + kfo[ks]);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g][ns] = mfma16(kf, qf[g][ks], acc[g][ns]);
-            }
-        }
-    };
-    // score epilogue of tile kt: rnd(rnd(rnd(acc) + rel_h) + rel_w) as 16-bit pairs sq[g][2 ns + half] (keys 16 ns + 4 fg + {0,1 | 2,3}), the
-    // tile maximum folded into mn[g] = the row maximum including tile kt; returns whether some query of the wave saw a new maximum
-    auto scores = [&](int kt, const f32x4_t (&acc)[NG][4], uint32_t (&sq)[NG][8]) -> bool {
-        bool grew = false;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const float rh = e2f(ghl[kt * (16 * NG) + g * 16 + fr]);
-            float tm = -INFINITY;
-#pragma unroll
-            for (int ns = 0; ns < 4; ++ns)
-                score_quad_win(acc[g][ns], rh, f32x2_t{rw[g][ns * 4], rw[g][ns * 4 + 1]}, f32x2_t{rw[g][ns * 4 + 2], rw[g][ns * 4 + 3]}, sq[g][ns * 2],
-                               sq[g][ns * 2 + 1], tm);
-            tm = rnd(tm);
-            tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-            tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-            mn[g] = fmaxf(m[g], tm);                           // finite from tile 0 on
-            grew = grew || mn[g] > m[g];
-        }
-        return __builtin_amdgcn_ballot_w64(grew) != 0;
-    };
     // The tile loop is software-pipelined by hand: while the matrix pipe computes S of tile kt + 1 the vector pipe turns the scores of tile
     // kt into probabilities, and while it multiplies P(kt) into V(kt) the vector pipe does the score epilogue of tile kt + 1 -- the two
     // halves of a step are independent instruction streams inside one wave (the 16-query form left that overlap to chance between waves,
@@ -1599,177 +1436,12 @@ __global__ __launch_bounds__(256, 2) void sam_global_kernel(AttnArgs p) {
 //                  form has two row-sum MFMAs and the rescaling)
 // so ~ 1.8 x the one-pass form by the count; measured 1.63 - 1.74 x (2.2 - 2.3 ms against 1.3 - 1.4 ms per layer at B = 8, H = 16; the generic
 // exact route, attn_long_kernel, 8.5 - 8.9 ms: profiles/sam_global_exact.txt).  216 (bf16) / 232 (fp16) VGPRs, no scratch, 80 KB of LDS.
-// Everything up to the tile loops (fragments, bias tables, DMA pieces, the S tile and its score epilogue) is sam_global_kernel's text, and
-// pass 2's P V is its second half: kept as a sibling, because moving the one-pass kernel's body into a shared template changed its
-// register allocation (tools/kernel_isa_diff.py), and that kernel's code is what every default run is measured on.
+// Everything up to the tile loops (fragments, bias tables, DMA pieces, the S tile and its score epilogue) is the text sam_global_kernel
+// is compiled from as well, sam_global_prologue.inc.  Pass 2's P V (pv) is the second half of the one-pass step, written out in both:
+// called from that step as a lambda it changed sam_global_kernel's instructions (profiles/attention_refactor_isa.txt), and that kernel's
+// code is what every default run is measured on.
 __global__ __launch_bounds__(256, 2) void sam_global_exact_kernel(AttnArgs p) {
-    extern __shared__ __attribute__((aligned(256))) char smem[];
-    constexpr int NWV = 4, NG = 2, BQ = 16 * NG * NWV, HDP = 128, hd = 80;
-    constexpr int KROW = HDP * 2, NKS = 3 /* 96 = 3 x 32 >= hd */, NDS = 5 /* 80 = 5 x 16 */;
-    constexpr int TILE = 64 * KROW;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 15, fg = lane >> 4;
-    const int nq = p.Sq / BQ;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int head = (slot / nq) * 8 + xcd;
-    if (head >= p.B * p.H) return;
-    const int qt = slot % nq;
-    const int b = head / p.H, h = head % p.H;
-    const int q0 = qt * BQ + wave * 16 * NG;                   // this wave's first query; its 32 queries share the grid row qy
-    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-    elem_t* ghl = (elem_t*)(smem + 4 * TILE) + wave * (64 * 16 * NG);     // [64 key rows][32 queries]: rel_h, 16-bit (a tile's read = 64 B)
-
-    uint4 qf[NG][NKS];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        const elem_t* qp = p.Q + (long)b * p.q_bs + (long)h * p.q_hs + (long)(q0 + g * 16 + fr) * p.q_ss;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const int d = ks * 32 + fg * 8;
-            qf[g][ks] = d < hd ? *(const uint4*)(qp + d) : make_uint4(0, 0, 0, 0);
-        }
-    }
-    // G[q][t] = 16-bit(q . rel_pos[t]) on the MFMA (A = table rows, B = the UNSCALED query fragments): rel_w[q][kw] = Gw[q][qx - kw + 63],
-    // rel_h[q][kh] = Gh[q][qy - kh + 63].  Gw: all 127 rows -> this wave's pad (aliases the tile slots, not in use yet) -> 16 registers per
-    // group; Gh: the 64 rows qy - kh + 63 -> the wave's LDS table.
-    float rw[NG][16];
-    {
-        elem_t* gw = (elem_t*)(smem + wave * (NG * 4096));      // [group][16 queries][128]
-        const int qy = q0 >> 6;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-#pragma unroll 2
-            for (int st = 0; st < 8; ++st) {
-                f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-                const elem_t* tr = p.rel_w + (long)min(st * 16 + fr, 126) * hd + fg * 8;
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) {
-                    const uint4 a = (ks * 32 + fg * 8 < hd) ? *(const uint4*)(tr + ks * 32) : make_uint4(0, 0, 0, 0);
-                    acc = mfma16(a, qf[g][ks], acc);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gw[g * 2048 + fr * 128 + st * 16 + fg * 4 + r] = f2e(acc[r]);   // G[t = st*16 + 4*fg + r][query fr]
-            }
-#pragma unroll 2
-            for (int st = 0; st < 4; ++st) {
-                f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-                const elem_t* tr = p.rel_h + (long)(qy - (st * 16 + fr) + 63) * hd + fg * 8;               // row of key-grid row kh = st*16 + fr
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) {
-                    const uint4 a = (ks * 32 + fg * 8 < hd) ? *(const uint4*)(tr + ks * 32) : make_uint4(0, 0, 0, 0);
-                    acc = mfma16(a, qf[g][ks], acc);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ghl[(st * 16 + fg * 4 + r) * (16 * NG) + g * 16 + fr] = f2e(acc[r]);  // Gh[kh = st*16 + 4*fg + r][query fr]
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // own pad only
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int qx = (q0 + g * 16 + fr) & 63;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) rw[g][i] = e2f(gw[g * 2048 + fr * 128 + qx - ((i >> 2) * 16 + fg * 4 + (i & 3)) + 63]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-    if (p.q_scale != 1.0f) {
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) qf[g][ks] = scale_q8(qf[g][ks], p.q_scale);
-    }
-    __builtin_amdgcn_s_barrier();                              // every wave is done with its pad before tile 0 is DMA'd over it
-
-    // LDS: K ring [2][64 x 256 B] at 0, V ring [2][64 x 256 B] at 2 TILE, rel_h tables behind.  DMA: a tile is 16 pieces of 1 KiB (4 key rows x
-    // 16 chunks); a wave issues 4 K + 4 V pieces per step.  The per-lane byte offset of every piece is the same for all 64 tiles; the six
-    // chunks of a row that are head-dim padding are not transferred: chunks 10 / 11 of every K row (dims 80..95, read by the last QK k-step)
-    // are zeroed once per buffer, the rest is never read.
-    const elem_t* kbase = p.K + (long)b * p.k_bs + (long)h * p.k_hs;
-    const elem_t* vbase = p.Vt + (long)b * p.vt_bs + (long)h * p.vt_hs;
-    uint32_t dko[4], dvo[4];
-    bool dk_real[4], dv_real[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int i = wave + j * NWV, row = i * 4 + (lane >> 4), cpos = lane & 15;
-        const int ck = cpos ^ (row & 15), cv = ((((cpos >> 1) ^ (row & 7)) << 1) | (cpos & 1));
-        dko[j] = (uint32_t)(((long)row * p.k_ss + ck * 8) * 2);
-        dvo[j] = (uint32_t)(((long)row * p.vt_ds + cv * 8) * 2);
-        dk_real[j] = ck * 8 < hd;
-        dv_real[j] = cv * 8 < hd;
-    }
-    for (int t = tid; t < 2 * 64 * 2; t += 64 * NWV) {
-        const int sl = t >> 7, row = (t & 127) >> 1, c = 10 + (t & 1);
-        *(uint4*)(smem + sl * TILE + row * KROW + ((c ^ (row & 15)) << 4)) = make_uint4(0, 0, 0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // (the first barrier below orders these writes before every read)
-    auto issue_k = [&](int kt) {
-        if (kt >= 64) return;
-        const uint32_t dst = lds_base + (kt & 1) * TILE;
-        const elem_t* tk = kbase + (long)kt * KT * p.k_ss;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (dk_real[j]) glds16s(tk, dko[j], dst + (wave + j * NWV) * 1024);
-    };
-    auto issue_v = [&](int kt) {
-        if (kt >= 64) return;
-        const uint32_t dst = lds_base + (2 + (kt & 1)) * TILE;
-        const elem_t* tv = vbase + (long)kt * KT * p.vt_ds;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (dv_real[j]) glds16s(tv, dvo[j], dst + (wave + j * NWV) * 1024);
-    };
-    // LDS fragment addresses, per lane and once: K fragment of k-step ks in rows fr, fr + 16, ... (the swizzle term of row 16 ns + fr is fr);
-    // V fragment base of the transposing reads (see attn_reg_kernel)
-    uint32_t kfo[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) kfo[ks] = fr * KROW + (((ks * 4 + fg) ^ fr) << 4);
-    const int swr = 4 * (fg & 1) + (fr >> 2);
-    const uint32_t vfo = 2 * TILE + (4 * fg + (fr >> 2)) * KROW + ((fr & 2) << 3) + ((fr & 1) << 3);
-
-    f32x4_t oacc[NG][NDS];
-    float m[NG], mn[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        m[g] = -INFINITY;
-#pragma unroll
-        for (int ds = 0; ds < NDS; ++ds) oacc[g][ds] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
-    // S tile kt on the matrix pipe: 4 x 3 K fragments, each into both groups' chains (24 MFMAs)
-    auto qk = [&](int kt, f32x4_t (&acc)[NG][4]) {
-        const char* tb = smem + (kt & 1) * TILE;
-#pragma unroll
-        for (int ns = 0; ns < 4; ++ns) {
-#pragma unroll
-            for (int g = 0; g < NG; ++g) acc[g][ns] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                const uint4 kf = *(const uint4*)(tb + ns * 16 * KROW + kfo[ks]);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g][ns] = mfma16(kf, qf[g][ks], acc[g][ns]);
-            }
-        }
-    };
-    // score epilogue of tile kt: rnd(rnd(rnd(acc) + rel_h) + rel_w) as 16-bit pairs sq[g][2 ns + half] (keys 16 ns + 4 fg + {0,1 | 2,3}), the
-    // tile maximum folded into mn[g] = the row maximum including tile kt; returns whether some query of the wave saw a new maximum
-    auto scores = [&](int kt, const f32x4_t (&acc)[NG][4], uint32_t (&sq)[NG][8]) -> bool {
-        bool grew = false;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const float rh = e2f(ghl[kt * (16 * NG) + g * 16 + fr]);
-            float tm = -INFINITY;
-#pragma unroll
-            for (int ns = 0; ns < 4; ++ns)
-                score_quad_win(acc[g][ns], rh, f32x2_t{rw[g][ns * 4], rw[g][ns * 4 + 1]}, f32x2_t{rw[g][ns * 4 + 2], rw[g][ns * 4 + 3]}, sq[g][ns * 2],
-                               sq[g][ns * 2 + 1], tm);
-            tm = rnd(tm);
-            tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-            tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-            mn[g] = fmaxf(m[g], tm);                           // finite from tile 0 on
-            grew = grew || mn[g] > m[g];
-        }
-        return __builtin_amdgcn_ballot_w64(grew) != 0;
-    };
+#include "sam_global_prologue.inc"
     // O += V(kt)^T P(kt) on the matrix pipe: 2 x 5 V fragments (two transposing reads each), each into both groups' chains (20 MFMAs)
     auto pv = [&](int kt, const uint32_t (&pk)[NG][8]) {
         const uint32_t vb = lds_base + (kt & 1) * TILE + vfo;
@@ -1929,153 +1601,10 @@ __global__ __launch_bounds__(256, 2) void sam_global_exact_kernel(AttnArgs p) {
 // P*V partials differs.
 //   TPW = tiles per wave held in registers: 1 for <= 1024 keys (decode; the wave's V^T fragments are then requested together
 //   with its K fragments, ahead of the softmax barriers), 4 for up to 4096 keys.
+// The body is attn_fewq_body.inc, which kv8.hip compiles a second time with the fp8 cache's fragment fetches (attn_fewq_kv8_kernel).
 template <int HDP, int FL, int TPW>
 __global__ __launch_bounds__(1024) void attn_fewq_kernel(AttnArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NKS = HDP / 32, NDS = HDP / 16;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int hd = head_dim_of<HDP, FL>(p);
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nwv = blockDim.x >> 6;
-    const int fr = lane & 15, fg = lane >> 4;
-    const int head = blockIdx.x;
-    const int b = head / p.H, h = head % p.H;
-    const int koff = p.Sk - p.Sq;
-    const int nkt = (p.Sk + KT - 1) / KT;
-    float* red = (float*)smem;                                  // [2][16 waves][16 queries]
-    float* obuf = red + 2 * 16 * 16;                            // [nwv][NDS * 4][64 lanes]
-
-    uint4 qf[NKS];
-    const int qi = fr;
-    {
-        const elem_t* qp = p.Q + (long)b * p.q_bs + (long)h * p.q_hs + (long)qi * p.q_ss;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const int d = ks * 32 + fg * 8;
-            qf[ks] = (qi < p.Sq && d < hd) ? *(const uint4*)(qp + d) : make_uint4(0, 0, 0, 0);
-        }
-        if (p.q_scale != 1.0f) {
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) qf[ks] = scale_q8(qf[ks], p.q_scale);
-        }
-    }
-    const elem_t* kbase = p.K + (long)b * p.k_bs + (long)h * p.k_hs;
-    const elem_t* vbase = p.Vt + (long)b * p.vt_bs + (long)h * p.vt_hs;
-
-    // ---- scores of this wave's tiles -> registers (packed bf16), running max -------------------------------
-    uint32_t sp[TPW][8];
-    float m = -INFINITY;
-#pragma clang loop unroll(full)
-    for (int t = 0; t < TPW; ++t) {
-        const int kt = wave + t * nwv;
-        if (kt < nkt) {
-#pragma unroll
-            for (int ns = 0; ns < 4; ++ns) {
-                const int key = min(kt * KT + ns * 16 + fr, p.Sk - 1);
-                const elem_t* kp = kbase + (long)key * p.k_ss + fg * 8;
-                f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) {
-                    if (ks * 32 < hd) {
-                        const uint4 kf = (ks * 32 + fg * 8 < hd) ? *(const uint4*)(kp + ks * 32) : make_uint4(0, 0, 0, 0);
-                        acc = mfma16(kf, qf[ks], acc);
-                    }
-                }
-                const int j0 = kt * KT + ns * 16 + fg * 4;
-                uint32_t mk = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = j0 + r;
-                    uint32_t mb = 2;
-                    if (j < p.Sk) mb = (p.key_mask == nullptr || p.key_mask[(long)b * p.Sk + j] != 0) ? 1 : 0;
-                    mk |= mb << (8 * r);
-                }
-                score_quad<FL>(p, acc, j0, mk, qi, koff, nullptr, 0, 0, sp[t][ns * 2], sp[t][ns * 2 + 1]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                m = fmaxf(m, pk_lo(sp[t][i]));
-                m = fmaxf(m, pk_hi(sp[t][i]));
-            }
-        }
-    }
-    uint4 vpre[2][NDS];                                         // TPW == 1: this wave's V^T fragments, in flight across the barriers
-    if constexpr (TPW == 1) {
-        if (wave < nkt) {
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int ds = 0; ds < NDS; ++ds)
-                    if (ds * 16 < hd) vpre[kk][ds] = *(const uint4*)(vbase + (long)(ds * 16 + fr) * p.vt_ds + wave * KT + (kk * 4 + fg) * 8);
-        }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    if (fg == 0) red[wave * 16 + fr] = m;
-    __syncthreads();
-    for (int w = 0; w < nwv; ++w) m = fmaxf(m, red[w * 16 + fr]);
-
-    // ---- exact fp32 softmax over the bf16 scores of ALL waves ----------------------------------------------
-    float sum = 0.f;
-#pragma clang loop unroll(full)
-    for (int t = 0; t < TPW; ++t)
-        if (wave + t * nwv < nkt) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                sum += __expf(pk_lo(sp[t][i]) - m);
-                sum += __expf(pk_hi(sp[t][i]) - m);
-            }
-        }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    if (fg == 0) red[256 + wave * 16 + fr] = sum;
-    __syncthreads();
-    sum = 0.f;
-    for (int w = 0; w < nwv; ++w) sum += red[256 + w * 16 + fr];
-    const float inv = 1.0f / sum;
-
-    // ---- partial O^T = V^T P^T over this wave's tiles --------------------------------------------------------
-    f32x4_t oacc[NDS];
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) oacc[ds] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma clang loop unroll(full)
-    for (int t = 0; t < TPW; ++t) {
-        const int kt = wave + t * nwv;
-        if (kt < nkt) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float lo = __expf(pk_lo(sp[t][i]) - m) * inv;
-                const float hi = __expf(pk_hi(sp[t][i]) - m) * inv;
-                sp[t][i] = pack2e(lo, hi);
-            }
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const uint4 pf = make_uint4(sp[t][4 * kk], sp[t][4 * kk + 1], sp[t][4 * kk + 2], sp[t][4 * kk + 3]);
-#pragma unroll
-                for (int ds = 0; ds < NDS; ++ds) {
-                    if (ds * 16 < hd) {
-                        uint4 vf;
-                        if constexpr (TPW == 1) vf = vpre[kk][ds];
-                        else vf = *(const uint4*)(vbase + (long)(ds * 16 + fr) * p.vt_ds + kt * KT + (kk * 4 + fg) * 8);
-                        oacc[ds] = mfma16(vf, pf, oacc[ds]);
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) obuf[(wave * NDS * 4 + ds * 4 + r) * 64 + lane] = oacc[ds][r];
-    __syncthreads();
-    // element e = (ds*4 + r)*64 + lane  <->  O[query lane & 15][d = ds*16 + 4*(lane >> 4) + r]
-    for (int e = tid; e < NDS * 4 * 64; e += blockDim.x) {
-        float acc = 0.f;
-        for (int w = 0; w < nwv; ++w) acc += obuf[w * NDS * 4 * 64 + e];
-        const int reg = e >> 6, ln = e & 63;
-        const int q = ln & 15, d = (reg >> 2) * 16 + (ln >> 4) * 4 + (reg & 3);
-        if (q < p.Sq && d < hd) p.O[(long)b * p.o_bs + (long)h * p.o_hs + (long)q * p.o_ss + d] = f2e(acc);
-    }
+#include "attn_fewq_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2219,8 +1748,7 @@ __global__ __launch_bounds__(256) void transpose_v_kernel(const elem_t* __restri
 template <int HDP, int NT, int FL, int NWV = 8, bool EXACT = false, bool VROW = false>
 int launch_attn(const AttnArgs& a, hipStream_t st) {
     constexpr int TILE = 64 * HDP * 2 > HDP * 128 ? 64 * HDP * 2 : HDP * 128;
-    const int lds = attn_reg_nbuf<HDP, NT, NWV, EXACT, VROW>() * TILE + NT * KT +
-                    (a.rel_h ? NWV * 16 * (((a.rel_mode == 2 ? 2 * (a.KH + a.KW) - 2 : a.KH + a.KW) | 1)) * 2 + 16 : 0);
+    const int lds = attn_reg_nbuf<HDP, NT, NWV, EXACT, VROW>() * TILE + NT * KT + rel_bias_lds_bytes(a, NWV);
     if (lds > 160 * 1024) return ULL_ERR_LDS;
     static UllOncePerDevice once;
     if (lds > 64 * 1024 && once.first())
@@ -2236,7 +1764,7 @@ template <int HDP, int FL>
 int launch_long(const AttnArgs& a, hipStream_t st) {
     constexpr int TILE = 64 * HDP * 2;
     const int nt = (a.Sk + KT - 1) / KT;
-    const int lds = 4 * TILE + ((nt * KT + 15) & ~15) + (a.rel_h ? 8 * 16 * (((a.rel_mode == 2 ? 2 * (a.KH + a.KW) - 2 : a.KH + a.KW) | 1)) * 2 + 16 : 0);
+    const int lds = 4 * TILE + ((nt * KT + 15) & ~15) + rel_bias_lds_bytes(a, 8);
     if (lds > 160 * 1024) return ULL_ERR_LDS;
     static UllOncePerDevice once;
     if (once.first()) (void)hipFuncSetAttribute((const void*)attn_long_kernel<HDP, FL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -2252,7 +1780,7 @@ int launch_stream(const AttnArgs& a, hipStream_t st) {
     static_assert(!VROW || HOIST == 2, "row-major V: the SAM global-attention form");
     const int nt = (a.Sk + KT - 1) / KT;
     int lds = 4 * TILE;
-    if (HOIST == 0) lds += ((nt * KT + 15) & ~15) + (a.rel_h ? 8 * 16 * (((a.rel_mode == 2 ? 2 * (a.KH + a.KW) - 2 : a.KH + a.KW) | 1)) * 2 + 16 : 0);
+    if (HOIST == 0) lds += ((nt * KT + 15) & ~15) + rel_bias_lds_bytes(a, 8);
     if (lds > 160 * 1024) return ULL_ERR_LDS;
     static UllOncePerDevice once;
     if (once.first()) (void)hipFuncSetAttribute((const void*)attn_stream_kernel<HDP, FL, HOIST, VROW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -2262,40 +1790,20 @@ int launch_stream(const AttnArgs& a, hipStream_t st) {
     return ull_check_launch();
 }
 
+template <auto KERNEL>                  // sam_global_kernel or sam_global_exact_kernel
 int launch_sam_global(const AttnArgs& a, hipStream_t st) {
     constexpr int LDS = 4 * 64 * 256 + 4 * 32 * 64 * 2;        // K ring + V ring + the rel_h tables = 80 KB: two blocks per CU
-    static UllOncePerDevice once;
-    if (once.first()) (void)hipFuncSetAttribute((const void*)sam_global_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    static UllOncePerDevice once;                              // (one per kernel)
+    if (once.first()) (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     const int nq = a.Sq / 128;
     const dim3 grid(((a.B * a.H + 7) / 8) * 8 * nq);
-    hipLaunchKernelGGL(sam_global_kernel, grid, dim3(256), LDS, st, a);
-    return ull_check_launch();
-}
-
-int launch_sam_global_exact(const AttnArgs& a, hipStream_t st) {
-    constexpr int LDS = 4 * 64 * 256 + 4 * 32 * 64 * 2;        // as launch_sam_global
-    static UllOncePerDevice once;
-    if (once.first()) (void)hipFuncSetAttribute((const void*)sam_global_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    const int nq = a.Sq / 128;
-    const dim3 grid(((a.B * a.H + 7) / 8) * 8 * nq);
-    hipLaunchKernelGGL(sam_global_exact_kernel, grid, dim3(256), LDS, st, a);
-    return ull_check_launch();
-}
-
-template <int HDP, int FL, int TPW>
-int launch_fewq_t(const AttnArgs& a, int nwv, hipStream_t st) {
-    const int lds = 2 * 16 * 16 * 4 + nwv * HDP * 16 * 4;
-    static UllOncePerDevice once;
-    if (once.first()) (void)hipFuncSetAttribute((const void*)attn_fewq_kernel<HDP, FL, TPW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((attn_fewq_kernel<HDP, FL, TPW>), dim3(a.B * a.H), dim3(nwv * 64), lds, st, a);
+    hipLaunchKernelGGL(KERNEL, grid, dim3(256), LDS, st, a);
     return ull_check_launch();
 }
 
 template <int HDP, int FL>
 int launch_fewq(const AttnArgs& a, hipStream_t st) {
-    const int nt = (a.Sk + KT - 1) / KT;
-    const int nwv = nt < 16 ? nt : 16;
-    return nt <= 16 ? launch_fewq_t<HDP, FL, 1>(a, nwv, st) : launch_fewq_t<HDP, FL, 4>(a, nwv, st);
+    return launch_fewq_as<attn_fewq_kernel<HDP, FL, 1>, attn_fewq_kernel<HDP, FL, 4>, HDP>(a, st);
 }
 
 // Which straight-line flavor (if any) the arguments correspond to.
@@ -2321,7 +1829,7 @@ int dispatch_nt(const AttnArgs& a, hipStream_t st) {
             if (fl == FL_LLAMA && a.Sq > 16 && nt <= 16) return launch_attn<128, 16, FL_LLAMA, 8, false, true>(a, st);
             if (fl == FL_SAM_ENC && a.rel_mode == 2 && a.KW == 64 && a.KH == 64 && a.Sk == 4096 && (a.Sq & 15) == 0 && a.Sq > 16 &&
                 64 * a.k_ss * 2 < (1L << 31) && 64 * a.vt_ds * 2 < (1L << 31)) {       // (32-bit per-lane DMA offsets inside a tile)
-                if ((a.Sq & 127) == 0 && a.Sq == a.Sk && a.hd == 80 && !a.key_mask && !a.causal) return launch_sam_global(a, st);   // (queries = the key grid)
+                if ((a.Sq & 127) == 0 && a.Sq == a.Sk && a.hd == 80 && !a.key_mask && !a.causal) return launch_sam_global<sam_global_kernel>(a, st);   // (queries = the key grid)
                 return launch_stream<128, FL_SAM_ENC, 2, true>(a, st);
             }
         }
@@ -2399,20 +1907,15 @@ extern "C" int ULL_FN(ull_attention_)(const void* Q, int64_t q_bs, int64_t q_hs,
     // 8-element strides and a 16-byte base, not only the 8 bytes of the register-direct epilogue (no kernel of that form otherwise: -2, and
     // the host falls back to the V^T path)
     if (vt_len == 0 && (((o_ss | o_hs | o_bs) & 7) || ((uintptr_t)O & 15))) return ULL_ERR_SHAPE;
-    AttnArgs a;
-    a.Q = (const elem_t*)Q; a.K = (const elem_t*)K; a.Vt = (const elem_t*)Vt; a.O = (elem_t*)O;
+    AttnArgs a = attn_args({Q, q_bs, q_hs, q_ss}, {K, k_bs, k_hs, k_ss}, {Vt, vt_bs, vt_hs, vt_ds}, {O, o_bs, o_hs, o_ss}, B, H, Sq, Sk, hd);
     a.key_mask = (const int32_t*)key_mask;
-    a.q_bs = q_bs; a.q_hs = q_hs; a.q_ss = q_ss; a.k_bs = k_bs; a.k_hs = k_hs; a.k_ss = k_ss;
-    a.vt_bs = vt_bs; a.vt_hs = vt_hs; a.vt_ds = vt_ds; a.o_bs = o_bs; a.o_hs = o_hs; a.o_ss = o_ss;
-    a.B = (int)B; a.H = (int)H; a.Sq = (int)Sq; a.Sk = (int)Sk; a.hd = (int)hd; a.vt_len = (int)vt_len;
-    a.causal = causal; a.scale_mode = scale_mode; a.scale = scale;
+    a.vt_len = (int)vt_len;
+    a.causal = causal; a.scale_mode = scale_mode; a.scale = scale; a.q_scale = q_scale;
     a.zeros = (const elem_t*)zeros;
-    a.rel_h = (const elem_t*)rel_h; a.rel_w = (const elem_t*)rel_w; a.KH = (int)rel_kh; a.KW = (int)rel_kw; a.q_scale = q_scale;
+    a.rel_h = (const elem_t*)rel_h; a.rel_w = (const elem_t*)rel_w; a.KH = (int)rel_kh; a.KW = (int)rel_kw;
     a.inv_kw = rel_kw > 0 ? 1.0f / (float)rel_kw : 0.f;
     a.rel_mode = rel_h ? rel_mode : 0;
-    a.win16 = 0; a.mg_h = a.mg_nwx = a.mg_nwy = a.mg_nw = 0;
     a.v_rows = vt_len == 0;
-    a.img_h = a.img_w = a.nwy = a.nwx = 0; a.k_pad = a.v_pad = nullptr;
     if (rel_h && rel_mode != 1 && rel_mode != 2) return ULL_ERR_ARG;
     if ((rel_h == nullptr) != (rel_w == nullptr)) return ULL_ERR_ARG;
     if (rel_h && (rel_kh <= 0 || rel_kw <= 0 || rel_kh + rel_kw > 256 || rel_kh * rel_kw < Sk)) return ULL_ERR_SHAPE;
@@ -2437,20 +1940,14 @@ extern "C" int ULL_FN(ull_sam_global_attention_exact_)(const void* Q, int64_t q_
         return ULL_ERR_SHAPE;
     // rows do not overlap; 32-bit per-lane DMA offsets inside a 64-key tile
     if (q_ss < hd || k_ss < hd || v_ss < hd || o_ss < hd || 64 * k_ss * 2 >= (1L << 31) || 64 * v_ss * 2 >= (1L << 31)) return ULL_ERR_SHAPE;
-    AttnArgs a;
-    a.Q = (const elem_t*)Q; a.K = (const elem_t*)K; a.Vt = (const elem_t*)V; a.O = (elem_t*)O;
-    a.key_mask = nullptr;
-    a.q_bs = q_bs; a.q_hs = q_hs; a.q_ss = q_ss; a.k_bs = k_bs; a.k_hs = k_hs; a.k_ss = k_ss;
-    a.vt_bs = v_bs; a.vt_hs = v_hs; a.vt_ds = v_ss; a.o_bs = o_bs; a.o_hs = o_hs; a.o_ss = o_ss;
-    a.B = (int)B; a.H = (int)H; a.Sq = a.Sk = (int)(side * side); a.hd = (int)hd; a.vt_len = 0;
-    a.causal = 0; a.scale_mode = 0; a.scale = 1.0f;
-    a.zeros = nullptr;
-    a.rel_h = (const elem_t*)rel_pos_h; a.rel_w = (const elem_t*)rel_pos_w; a.KH = a.KW = (int)side; a.q_scale = q_scale;
+    AttnArgs a = attn_args({Q, q_bs, q_hs, q_ss}, {K, k_bs, k_hs, k_ss}, {V, v_bs, v_hs, v_ss}, {O, o_bs, o_hs, o_ss}, B, H, side * side,
+                           side * side, hd);
+    a.q_scale = q_scale;
+    a.rel_h = (const elem_t*)rel_pos_h; a.rel_w = (const elem_t*)rel_pos_w; a.KH = a.KW = (int)side;
     a.inv_kw = 1.0f / (float)side;
-    a.rel_mode = 2; a.win16 = 0; a.mg_h = a.mg_nwx = a.mg_nwy = a.mg_nw = 0;
-    a.v_rows = 1;
-    a.img_h = a.img_w = a.nwy = a.nwx = 0; a.k_pad = a.v_pad = nullptr;
-    return launch_sam_global_exact(a, (hipStream_t)stream);
+    a.rel_mode = 2;
+    a.v_rows = 1;                        // (zeros stays null: this kernel has no head-dim padding chunks to source)
+    return launch_sam_global<sam_global_exact_kernel>(a, (hipStream_t)stream);
 }
 
 // x: first of `n_heads` consecutive heads (q heads then k heads of a fused QKV row); positions int64 [tokens];
@@ -2522,17 +2019,12 @@ extern "C" int ULL_FN(ull_sam_window_attention_)(const void* qkv, int64_t ld, co
     const int nwy = (int)((Hh + ws - 1) / ws), nwx = (int)((Ww + ws - 1) / ws);
     const int C = (int)(nH * hd), S = (int)(ws * ws);
     const elem_t* base = (const elem_t*)qkv;
-    AttnArgs a;
-    a.Q = base; a.K = base + C; a.Vt = base + 2 * C; a.O = (elem_t*)out;
-    a.key_mask = nullptr;
-    a.q_bs = 0; a.q_hs = hd; a.q_ss = ld; a.k_bs = 0; a.k_hs = hd; a.k_ss = ld;
-    a.vt_bs = 0; a.vt_hs = 0; a.vt_ds = 0; a.o_bs = 0; a.o_hs = hd; a.o_ss = ldo;
-    a.B = (int)(B * nwy * nwx); a.H = (int)nH; a.Sq = S; a.Sk = S; a.hd = (int)hd; a.vt_len = 0;
-    a.causal = 0; a.scale_mode = 0; a.scale = 1.0f;
+    AttnArgs a = attn_args({base, 0, hd, ld}, {base + C, 0, hd, ld}, {base + 2 * C, 0, 0, 0}, {out, 0, hd, ldo}, B * nwy * nwx, nH, S, S, hd);
+    a.q_scale = q_scale;
     a.zeros = (const elem_t*)zeros;
-    a.rel_h = (const elem_t*)rel_pos_h; a.rel_w = (const elem_t*)rel_pos_w; a.KH = (int)ws; a.KW = (int)ws; a.q_scale = q_scale;
+    a.rel_h = (const elem_t*)rel_pos_h; a.rel_w = (const elem_t*)rel_pos_w; a.KH = (int)ws; a.KW = (int)ws;
     a.inv_kw = 1.0f / (float)ws;
-    a.rel_mode = 2; a.win16 = 1; a.v_rows = 0;
+    a.rel_mode = 2; a.win16 = 1;
     a.img_h = (int)Hh; a.img_w = (int)Ww; a.nwy = nwy; a.nwx = nwx;
     // the kernel's index arithmetic: (window, head) -> window -> image by multiply-high, row offsets inside a window in 32 bits
     const int64_t items = (int64_t)a.B * nH, dmax = nH > (int64_t)nwy * nwx ? nH : (int64_t)nwy * nwx;

@@ -36,6 +36,20 @@ struct AttnArgs {
 };
 #define ULL_ATT_ACC(slot, t0) ((void)0)
 
+// The argument block of a C entry point: the four tensors with their (batch, head, row) strides in elements and the shape; every other
+// field zero / null (no mask, not causal, scale_mode 0, no rel-pos bias, V^T form with vt_len 0, no windows) except scale = q_scale = 1.
+// The entry sets what it uses on top.
+struct AttnTensor { const void* ptr; int64_t bs, hs, ss; };
+inline AttnArgs attn_args(AttnTensor q, AttnTensor k, AttnTensor vt, AttnTensor o, int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t hd) {
+    AttnArgs a{};
+    a.Q = (const elem_t*)q.ptr; a.K = (const elem_t*)k.ptr; a.Vt = (const elem_t*)vt.ptr; a.O = (elem_t*)o.ptr;
+    a.q_bs = q.bs; a.q_hs = q.hs; a.q_ss = q.ss; a.k_bs = k.bs; a.k_hs = k.hs; a.k_ss = k.ss;
+    a.vt_bs = vt.bs; a.vt_hs = vt.hs; a.vt_ds = vt.ss; a.o_bs = o.bs; a.o_hs = o.hs; a.o_ss = o.ss;
+    a.B = (int)B; a.H = (int)H; a.Sq = (int)Sq; a.Sk = (int)Sk; a.hd = (int)hd;
+    a.scale = a.q_scale = 1.0f;
+    return a;
+}
+
 // ull_sam_window_attention: window b = (img * nwy + wy) * nwx + wx -> (image, first token row, first token column).  The divisors are
 // run-time values; a / d goes through the host-computed m = ceil(2^32 / d): exact while a * d < 2^32 (the dispatcher checks), m = 0
 // encodes d = 1.  (As three integer divisions, ~30 scalar instructions each and repeated per DMA piece, this was ~1200 scalar
@@ -250,9 +264,29 @@ ULL_DEV void stage_rel_bias(const AttnArgs& p, elem_t* dst, int bp, const uint4 
     }
 }
 
-ULL_DEV int bias_pitch(const AttnArgs& p) {       // elements; odd so the 16 query rows start in different LDS banks
+__host__ ULL_DEV int bias_pitch(const AttnArgs& p) {       // elements; odd so the 16 query rows start in different LDS banks
     const int n = p.rel_mode == 2 ? (2 * p.KH - 1) + (2 * p.KW - 1) : p.KH + p.KW;
     return n | 1;
+}
+// ... and the LDS bytes the launcher adds for them: 16 rows per wave (+ 16: the rows start at the next 16-byte boundary)
+inline int rel_bias_lds_bytes(const AttnArgs& a, int nwv) { return a.rel_h ? nwv * 16 * bias_pitch(a) * 2 + 16 : 0; }
+
+// Launch of the few-query kernels (attn_fewq_kernel; attn_fewq_kv8_kernel with extra = its Kv8Args), one block per (batch, head): one
+// wave per key tile up to 16 waves, which then hold TPW = 1 tile each in registers (KERNEL_TPW1); beyond 16 tiles 16 waves with TPW = 4
+// (KERNEL_TPW4, <= 64 tiles).  LDS: the two reductions' [16 waves][16 queries] floats and one partial O per wave.
+template <auto KERNEL, int HDP, typename... Extra>
+int launch_fewq_block(const AttnArgs& a, int nwv, hipStream_t st, const Extra&... extra) {
+    const int lds = 2 * 16 * 16 * 4 + nwv * HDP * 16 * 4;
+    static UllOncePerDevice once;                               // (one per kernel: KERNEL is a template argument)
+    if (once.first()) (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(KERNEL, dim3(a.B * a.H), dim3(nwv * 64), lds, st, a, extra...);
+    return ull_check_launch();
+}
+template <auto KERNEL_TPW1, auto KERNEL_TPW4, int HDP, typename... Extra>
+int launch_fewq_as(const AttnArgs& a, hipStream_t st, const Extra&... extra) {
+    const int nt = (a.Sk + KT - 1) / KT;
+    const int nwv = nt < 16 ? nt : 16;
+    return nt <= 16 ? launch_fewq_block<KERNEL_TPW1, HDP>(a, nwv, st, extra...) : launch_fewq_block<KERNEL_TPW4, HDP>(a, nwv, st, extra...);
 }
 
 ULL_DEV uint4 scale_q8(const uint4& v, float sc) {

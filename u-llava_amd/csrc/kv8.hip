@@ -1,11 +1,12 @@
 // FP8 (e4m3) KV cache for KV-cached LLaMA decoding, bf16 build only (compiled once): the decode attention that reads the cache's codes,
 // and the kernels that quantize positions into it and dequantize them out of it.
 //
-// attn_fewq_kv8_kernel is attention.hip's attn_fewq_kernel (<= 16 queries, the keys split over the waves of one block per head) with the
-// cached keys' K / V^T fragments built from codes: each lane turns its 8 codes into exactly the bf16 operand the 16-bit kernel loads from
-// the dequantized cache.  The Sq new keys come from a bf16 staging window.  Same MFMAs, lane mapping, rounding points and reduction order,
-// so the result equals attn_fewq_kernel's on the dequantized cache bit for bit.  After the attention the block quantizes the new keys'
-// K rows and V columns (staging -> codes and scales): a block owns its (batch, head) and never reads the cache at the positions it writes.
+// attn_fewq_kv8_kernel is compiled from the same text as attention.hip's attn_fewq_kernel, attn_fewq_body.inc (<= 16 queries, the keys
+// split over the waves of one block per head); the text's fp8 arms build the cached keys' K / V^T fragments from codes: each lane turns
+// its 8 codes into exactly the bf16 operand the 16-bit kernel loads from the dequantized cache.  The Sq new keys come from a bf16 staging
+// window.  MFMAs, lane mapping, rounding points and reduction order exist once, so the result equals attn_fewq_kernel's on the
+// dequantized cache bit for bit.  After the attention the block quantizes the new keys' K rows and V columns (staging -> codes and
+// scales): a block owns its (batch, head) and never reads the cache at the positions it writes.
 #ifdef ULL_ELEM_F16
 #error "kv8.hip is bf16 only"
 #endif
@@ -76,203 +77,15 @@ ULL_DEV void kv8_quant_vec(const elem_t* src, long sstride, int hd, uint8_t* dst
 
 template <int HDP, int FL, int TPW>
 __global__ __launch_bounds__(1024) void attn_fewq_kv8_kernel(AttnArgs p, Kv8Args kv) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NKS = HDP / 32, NDS = HDP / 16;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int hd = head_dim_of<HDP, FL>(p);
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nwv = blockDim.x >> 6;
-    const int fr = lane & 15, fg = lane >> 4;
-    const int head = blockIdx.x;
-    const int b = head / p.H, h = head % p.H;
-    const int koff = p.Sk - p.Sq;
-    const int nkt = (p.Sk + KT - 1) / KT;
-    const int w0 = koff & ~(KT - 1);                            // staging row / slot of key k >= koff: k - w0
-    const long bh = head;                                       // = b * H + h
-    float* red = (float*)smem;                                  // [2][16 waves][16 queries]
-    float* obuf = red + 2 * 16 * 16;                            // [nwv][NDS * 4][64 lanes]
-
-    uint4 qf[NKS];
-    const int qi = fr;
-    {
-        const elem_t* qp = p.Q + (long)b * p.q_bs + (long)h * p.q_hs + (long)qi * p.q_ss;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const int d = ks * 32 + fg * 8;
-            qf[ks] = (qi < p.Sq && d < hd) ? *(const uint4*)(qp + d) : make_uint4(0, 0, 0, 0);
-        }
-        if (p.q_scale != 1.0f) {
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) qf[ks] = scale_q8(qf[ks], p.q_scale);
-        }
-    }
-    const elem_t* kbase = p.K + (long)b * p.k_bs + (long)h * p.k_hs;
-    const elem_t* vbase = p.Vt + (long)b * p.vt_bs + (long)h * p.vt_hs;
-
-    // ---- scores of this wave's tiles -> registers (packed bf16), running max -------------------------------
-    uint32_t sp[TPW][8];
-    float m = -INFINITY;
-#pragma clang loop unroll(full)
-    for (int t = 0; t < TPW; ++t) {
-        const int kt = wave + t * nwv;
-        if (kt < nkt) {
-#pragma unroll
-            for (int ns = 0; ns < 4; ++ns) {
-                const int key = min(kt * KT + ns * 16 + fr, p.Sk - 1);
-                f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-                const bool old = key < koff;                    // cached key: codes; new key: staging row key - w0
-                const elem_t* kp = kbase + (long)(old ? 0 : key - w0) * p.k_ss + fg * 8;
-                const uint8_t* kq = kv.k8 + (bh * kv.smax + key) * hd + fg * 8;
-                const float ksc = old ? kv.ks[bh * kv.smax + key] : 0.f;
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) {
-                    if (ks * 32 < hd) {
-                        uint4 kf = make_uint4(0, 0, 0, 0);
-                        if (ks * 32 + fg * 8 < hd) {
-                            if (old) {
-                                float f[8];
-                                unpack8_w8(*(const uint2*)(kq + ks * 32), ksc, f);
-                                kf = pack8(f);
-                            } else {
-                                kf = *(const uint4*)(kp + ks * 32);
-                            }
-                        }
-                        acc = mfma16(kf, qf[ks], acc);
-                    }
-                }
-                const int j0 = kt * KT + ns * 16 + fg * 4;
-                uint32_t mk = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = j0 + r;
-                    uint32_t mb = 2;
-                    if (j < p.Sk) mb = (p.key_mask == nullptr || p.key_mask[(long)b * p.Sk + j] != 0) ? 1 : 0;
-                    mk |= mb << (8 * r);
-                }
-                score_quad<FL>(p, acc, j0, mk, qi, koff, nullptr, 0, 0, sp[t][ns * 2], sp[t][ns * 2 + 1]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                m = fmaxf(m, pk_lo(sp[t][i]));
-                m = fmaxf(m, pk_hi(sp[t][i]));
-            }
-        }
-    }
-    uint2 vq[2][NDS];                                           // TPW == 1: this wave's V^T codes and the 8 slots' scales, in flight across
-                                                                // the barriers (converted at use)
-    float vsc[2][8];
-    if constexpr (TPW == 1) {
-        if (wave < nkt) {
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const int slot0 = wave * KT + (kk * 4 + fg) * 8;
-                kv8_load_vsc(kv, bh, slot0, koff, vsc[kk]);
-#pragma unroll
-                for (int ds = 0; ds < NDS; ++ds)
-                    if (ds * 16 < hd) vq[kk][ds] = kv8_load_vcode(kv, bh, hd, ds * 16 + fr, slot0, koff);
-            }
-        }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    if (fg == 0) red[wave * 16 + fr] = m;
-    __syncthreads();
-    for (int w = 0; w < nwv; ++w) m = fmaxf(m, red[w * 16 + fr]);
-
-    // ---- exact fp32 softmax over the bf16 scores of ALL waves ----------------------------------------------
-    float sum = 0.f;
-#pragma clang loop unroll(full)
-    for (int t = 0; t < TPW; ++t)
-        if (wave + t * nwv < nkt) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                sum += __expf(pk_lo(sp[t][i]) - m);
-                sum += __expf(pk_hi(sp[t][i]) - m);
-            }
-        }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    if (fg == 0) red[256 + wave * 16 + fr] = sum;
-    __syncthreads();
-    sum = 0.f;
-    for (int w = 0; w < nwv; ++w) sum += red[256 + w * 16 + fr];
-    const float inv = 1.0f / sum;
-
-    // ---- partial O^T = V^T P^T over this wave's tiles --------------------------------------------------------
-    f32x4_t oacc[NDS];
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) oacc[ds] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma clang loop unroll(full)
-    for (int t = 0; t < TPW; ++t) {
-        const int kt = wave + t * nwv;
-        if (kt < nkt) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float lo = __expf(pk_lo(sp[t][i]) - m) * inv;
-                const float hi = __expf(pk_hi(sp[t][i]) - m) * inv;
-                sp[t][i] = pack2e(lo, hi);
-            }
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const uint4 pf = make_uint4(sp[t][4 * kk], sp[t][4 * kk + 1], sp[t][4 * kk + 2], sp[t][4 * kk + 3]);
-#pragma unroll
-                for (int ds = 0; ds < NDS; ++ds) {
-                    if (ds * 16 < hd) {
-                        const int slot0 = kt * KT + (kk * 4 + fg) * 8;
-                        const elem_t* stg = vbase + (long)(ds * 16 + fr) * p.vt_ds + slot0 - w0;
-                        uint4 vf;
-                        if constexpr (TPW == 1) {
-                            vf = kv8_vfrag(vq[kk][ds], vsc[kk], slot0, koff, p.Sk, stg);
-                        } else {
-                            if (ds == 0) kv8_load_vsc(kv, bh, slot0, koff, vsc[0]);
-                            vf = kv8_vfrag(kv8_load_vcode(kv, bh, hd, ds * 16 + fr, slot0, koff), vsc[0], slot0, koff, p.Sk, stg);
-                        }
-                        oacc[ds] = mfma16(vf, pf, oacc[ds]);
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) obuf[(wave * NDS * 4 + ds * 4 + r) * 64 + lane] = oacc[ds][r];
-    __syncthreads();
-    // element e = (ds*4 + r)*64 + lane  <->  O[query lane & 15][d = ds*16 + 4*(lane >> 4) + r]
-    for (int e = tid; e < NDS * 4 * 64; e += blockDim.x) {
-        float acc = 0.f;
-        for (int w = 0; w < nwv; ++w) acc += obuf[w * NDS * 4 * 64 + e];
-        const int reg = e >> 6, ln = e & 63;
-        const int q = ln & 15, d = (reg >> 2) * 16 + (ln >> 4) * 4 + (reg & 3);
-        if (q < p.Sq && d < hd) p.O[(long)b * p.o_bs + (long)h * p.o_hs + (long)q * p.o_ss + d] = f2e(acc);
-    }
-    // the new keys into the cache: vector 2i = K row of key koff + i, 2i + 1 = its V column; one wave per vector
-    for (int v = wave; v < 2 * p.Sq; v += nwv) {
-        const int key = koff + (v >> 1);
-        if ((v & 1) == 0) {
-            kv8_quant_vec(kbase + (long)(key - w0) * p.k_ss, 1, hd, kv.k8 + (bh * kv.smax + key) * hd, 1, kv.ks + bh * kv.smax + key, lane);
-        } else {
-            const int slot = kv8_slot(key);
-            kv8_quant_vec(vbase + (slot - w0), p.vt_ds, hd, kv.vt8 + bh * hd * kv.smax + slot, kv.smax, kv.vs + bh * kv.smax + slot, lane);
-        }
-    }
+#define ULL_FEWQ_KV8
+#include "attn_fewq_body.inc"
+#undef ULL_FEWQ_KV8
 }
 
-template <int HDP, int FL, int TPW>
-int launch_fewq_kv8_t(const AttnArgs& a, const Kv8Args& kv, int nwv, hipStream_t st) {
-    const int lds = 2 * 16 * 16 * 4 + nwv * HDP * 16 * 4;
-    static UllOncePerDevice once;
-    if (once.first()) (void)hipFuncSetAttribute((const void*)attn_fewq_kv8_kernel<HDP, FL, TPW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((attn_fewq_kv8_kernel<HDP, FL, TPW>), dim3(a.B * a.H), dim3(nwv * 64), lds, st, a, kv);
-    return ull_check_launch();
-}
-
-// the block shape and TPW of launch_fewq, so that the fp8 form mirrors the 16-bit launch it replaces
+// the block shape and TPW of the 16-bit launch it replaces: the same rule (launch_fewq_as)
 template <int HDP, int FL>
 int launch_fewq_kv8(const AttnArgs& a, const Kv8Args& kv, hipStream_t st) {
-    const int nt = (a.Sk + KT - 1) / KT;
-    const int nwv = nt < 16 ? nt : 16;
-    return nt <= 16 ? launch_fewq_kv8_t<HDP, FL, 1>(a, kv, nwv, st) : launch_fewq_kv8_t<HDP, FL, 4>(a, kv, nwv, st);
+    return launch_fewq_as<attn_fewq_kv8_kernel<HDP, FL, 1>, attn_fewq_kv8_kernel<HDP, FL, 4>, HDP>(a, st, kv);
 }
 
 // positions p0 .. p0 + n - 1 into the cache: block (s, b * H + h), wave 0 quantizes the K row, wave 1 the V column of position p0 + s.
@@ -341,18 +154,12 @@ extern "C" int ull_attention_kv8_bf16(const void* Q, int64_t q_bs, int64_t q_hs,
     const int64_t nt = (Sk + KT - 1) / KT;
     if (Sq < 1 || Sq > 16 || Sk <= Sq || Sk > smax || nt < 2 || nt > 64) return ULL_ERR_SHAPE;
     if ((q_ss & 7) || (q_hs & 7) || (q_bs & 7) || (o_ss & 3) || (o_hs & 3) || (o_bs & 3)) return ULL_ERR_SHAPE;
-    AttnArgs a;
-    a.Q = (const elem_t*)Q; a.K = (const elem_t*)k_stage; a.Vt = (const elem_t*)vt_stage; a.O = (elem_t*)O;
+    AttnArgs a = attn_args({Q, q_bs, q_hs, q_ss}, {k_stage, H * 128 * hd, 128 * hd, hd}, {vt_stage, H * hd * 128, hd * 128, 128},
+                           {O, o_bs, o_hs, o_ss}, B, H, Sq, Sk, hd);
     a.key_mask = (const int32_t*)key_mask;
-    a.q_bs = q_bs; a.q_hs = q_hs; a.q_ss = q_ss; a.k_bs = H * 128 * hd; a.k_hs = 128 * hd; a.k_ss = hd;
-    a.vt_bs = H * hd * 128; a.vt_hs = hd * 128; a.vt_ds = 128; a.o_bs = o_bs; a.o_hs = o_hs; a.o_ss = o_ss;
-    a.B = (int)B; a.H = (int)H; a.Sq = (int)Sq; a.Sk = (int)Sk; a.hd = (int)hd; a.vt_len = 128;
-    a.causal = 1; a.scale_mode = 1; a.scale = scale; a.q_scale = 1.0f;
+    a.vt_len = 128;
+    a.causal = 1; a.scale_mode = 1; a.scale = scale;
     a.zeros = (const elem_t*)zeros;
-    a.rel_h = a.rel_w = nullptr; a.KH = a.KW = 0; a.inv_kw = 0.f; a.rel_mode = 0;
-    a.win16 = 0; a.mg_h = a.mg_nwx = a.mg_nwy = a.mg_nw = 0;
-    a.v_rows = 0;
-    a.img_h = a.img_w = a.nwy = a.nwx = 0; a.k_pad = a.v_pad = nullptr;
     Kv8Args kv;
     kv.k8 = (uint8_t*)k8; kv.vt8 = (uint8_t*)vt8; kv.ks = (float*)k_scale; kv.vs = (float*)vt_scale; kv.smax = (int)smax;
     hipStream_t st = (hipStream_t)stream;
