@@ -394,6 +394,31 @@ int ull_token_logprobs(const void* logits, int logits_dtype, int64_t row_stride,
 int ull_ngram_ban(const void* logits, int logits_dtype, int64_t row_stride, int64_t R, int64_t V, const void* ids, int64_t ids_ld,
                   int64_t cur_len, int64_t ngram, void* out, int64_t out_ld, void* stream);
 
+/* generate(stop_strings=): the per-row stop on text (HF's `stop_strings`; what the reference's callers ask of KeywordsStoppingCriteria,
+ * inference_ullava.py:90-101) in one launch per decode step, compiled once (no dtype: only ids and bytes are read).  The rule is
+ * `generation.stop_strings_reference`.  ids int64: R rows, ids_ld elements apart, cur_len valid entries each, the last one the token the
+ * step just wrote; columns before L0 (the prompt) never count.  The token table: tok_off int32 [V + 1] (device, ascending from 0) and
+ * tok_bytes uint8 [n_tok_bytes] (device): id t contributes tok_bytes[tok_off[t] .. tok_off[t+1]) to the text, an id outside [0, V)
+ * nothing -- no address is formed from an unchecked id, and any V >= 1 fits (nothing of the table is staged).  max_token_bytes: the longest
+ * entry of the table, as its builder measured it (a longer entry is read as its first ULL_STOP_MAX_TOKEN_BYTES bytes).  The stop strings:
+ * stop_off int32 [S + 1] in HOST memory (read by the call itself, ascending from 0) and stop_bytes uint8 [stop_off[S]] (device).
+ * For every row with live[r] != 0 (int32 [R], the `unfinished` of ull_greedy_step_* / ull_sample_step): if some stop string occurs in the
+ * text of ids[r, L0 .. cur_len) with its last byte inside the bytes of ids[r, cur_len-1], then live[r] = 0 and alive[0] -= 1 (int32, the
+ * step's counter those kernels have already added the live rows to; one vector atomic per stopping row, so the order of the rows does
+ * not matter).  The walk back over earlier tokens ends at column L0 or once the longest stop string is covered; zero-byte tokens are
+ * stepped over.  Rows with live[r] == 0 are not touched.
+ * Limits: S <= ULL_STOP_MAX_STRINGS strings of 1 .. ULL_STOP_MAX_BYTES bytes each, max_token_bytes <= ULL_STOP_MAX_TOKEN_BYTES; the last
+ * token and the head of the longest string are staged in an LDS window of ULL_STOP_MAX_WINDOW bytes per row.  Over a limit: ULL_ERR_SHAPE.
+ * Null pointer, S < 1, V < 1, an empty stop string, stop_off[0] != 0, cur_len <= L0, cur_len > ids_ld, a negative size: ULL_ERR_ARG.
+ * Nothing is launched and nothing is written in either case.  R == 0: ULL_OK, nothing is launched. */
+#define ULL_STOP_MAX_STRINGS 32
+#define ULL_STOP_MAX_BYTES 64
+#define ULL_STOP_MAX_TOKEN_BYTES 256
+#define ULL_STOP_MAX_WINDOW 320
+int ull_stop_strings(const void* ids, int64_t ids_ld, int64_t R, int64_t L0, int64_t cur_len, const void* tok_off, const void* tok_bytes,
+                     int64_t V, int64_t n_tok_bytes, int64_t max_token_bytes, const void* stop_off, const void* stop_bytes, int64_t S,
+                     void* live, void* alive, void* stream);
+
 /* One step of HF `GenerationMixin._beam_search` with do_sample=False (hf: generation/utils.py; the `num_beams` the reference's evaluate(),
  * models/ullava.py:346,360, forwards) for the whole batch, in two launches, compiled once (logits_dtype ULL_DT_F32 0 / BF16 1 / F16 2).  The
  * rule is `generation.beam_search_reference`, steps 1-7.  logits: B * Kin rows of V entries, row_stride elements apart, Kin == K, or

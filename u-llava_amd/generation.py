@@ -1,6 +1,7 @@
 """Decoding for UllavaCoreForCausalLM.generate(): the HF rules restated on the host (sampling warpers, n-gram ban, prompt-lookup draft), every
 refusal of generate()'s / evaluate()'s arguments in one function, and the three decode loops -- host per-step, fused on the device, prompt-lookup
 -- over what they share (`Decoding`: the step's forward, the stopping test, the result).  The loops take the model; no model class is imported."""
+import re
 from typing import Optional
 
 import torch
@@ -30,6 +31,105 @@ def no_repeat_ngram_banned_tokens(rows, ngram_size: int):
                 banned.append(toks[i + ngram_size - 1])
         out.append(banned)
     return out
+
+
+_BYTE_TOKEN = re.compile(r"<0x([0-9A-Fa-f]{2})>")
+
+
+def token_byte_table(tokenizer, vocab_size: int):
+    """The bytes every id contributes to the decoded text -> (offsets int32 [V + 1], bytes uint8 [n]), V = vocab_size: id t gives
+    bytes[offsets[t]:offsets[t + 1]].  A regular token gives the UTF-8 of its string IN CONTEXT, by the trick of transformers'
+    StopStringCriteria (generation/stopping_criteria.py, `clean_tokenizer_vocab`): convert_tokens_to_string(prefix tokens + [token]) minus
+    what the prefix alone gives, so a LLaMA piece's `▁` becomes a space and the decoder's strip of the text's first space does not reach it.
+    A byte-fallback token `<0xXX>` gives that one raw byte (two of them may form a character no single one decodes to).  A special id
+    (tokenizer.all_special_ids, and added tokens flagged special) gives nothing -- the `skip_special_tokens=True` of the reference's
+    criterion (models/tools.py:28) -- and so does an id >= len(tokenizer): the padded rows of a resized embedding."""
+    V = int(vocab_size)
+    special = {int(i) for i in tokenizer.all_special_ids}
+    special |= {int(i) for i, t in getattr(tokenizer, "added_tokens_decoder", {}).items() if getattr(t, "special", False)}
+    prefix = tokenizer.convert_ids_to_tokens(tokenizer("abcdef", add_special_tokens=False)["input_ids"])
+    head = tokenizer.convert_tokens_to_string(prefix)
+    pieces = []
+    for t, tok in enumerate(tokenizer.convert_ids_to_tokens(list(range(min(V, len(tokenizer)))))):
+        m = None if tok is None else _BYTE_TOKEN.fullmatch(tok)
+        if tok is None or t in special:
+            pieces.append(b"")
+        elif m:
+            pieces.append(bytes([int(m.group(1), 16)]))
+        else:
+            text = tokenizer.convert_tokens_to_string(prefix + [tok])
+            if not text.startswith(head):
+                raise ValueError(f"token_byte_table: token {t} ({tok!r}) changes the text in front of it: its bytes in context are not defined")
+            pieces.append(text[len(head):].encode("utf-8"))
+    pieces += [b""] * (V - len(pieces))
+    offsets = torch.zeros(V + 1, dtype=torch.int32)
+    offsets[1:] = torch.tensor([len(p) for p in pieces], dtype=torch.int64).cumsum(0).to(torch.int32)
+    return offsets, torch.frombuffer(bytearray(b"".join(pieces)), dtype=torch.uint8) if offsets[-1] else torch.zeros(0, dtype=torch.uint8)
+
+
+def stop_strings_reference(ids_row, L0: int, table, stops):
+    """generate(stop_strings=)'s rule on one row, on the host: the definition ops.stop_strings is held against.  ids_row: the row's ids,
+    prompt included; only ids_row[L0:], the generated ones, count (as in the reference's criterion and its `outputs.endswith(stop_str)`
+    clean-up).  table: token_byte_table's pair; stops: str or bytes.  The row's text is the concatenation of the table bytes of its
+    generated ids (an id outside [0, V) gives nothing).  -> n (1-based), the first generated token for which some stop string occurs in
+    the text with its LAST byte inside token n's bytes -- the token that completes the string is kept, as HF and the reference keep
+    it -- or None.  Checked from the first generated token on."""
+    offsets, data = table
+    offsets, data = offsets.tolist(), bytes(data.tolist())
+    V = len(offsets) - 1
+    stops = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in stops]
+    text = b""
+    for n, t in enumerate(list(ids_row)[L0:], 1):
+        t = int(t)
+        start = len(text)
+        if 0 <= t < V:
+            text += data[offsets[t]:offsets[t + 1]]
+        for s in stops:
+            # an occurrence that ends behind `start`: it begins at start - len(s) + 1 or later
+            if len(text) > start and text.find(s, max(0, start - len(s) + 1)) >= 0:
+                return n
+    return None
+
+
+def check_stop_strings(stop_strings, tokenizer):
+    """generate()'s `stop_strings` / `tokenizer` (HF's names and HF's errors) -> the UTF-8 of the strings, or None when the feature is off."""
+    if stop_strings is None:
+        return None
+    if tokenizer is None:
+        raise ValueError("`stop_strings` needs the `tokenizer` the ids come from: pass `tokenizer=` to generate() (a stop string is text, "
+                         "and only the tokenizer knows the text of a token)")
+    strings = [stop_strings] if isinstance(stop_strings, str) else list(stop_strings) if isinstance(stop_strings, (list, tuple)) else None
+    if not strings or not all(isinstance(s, str) for s in strings):
+        raise ValueError(f"`stop_strings` has to be a str or a non-empty list of str, but is {stop_strings!r}")
+    if any(s == "" or "\ufffd" in s for s in strings):
+        raise ValueError("`stop_strings` must not hold an empty string (it would stop every row at once) or U+FFFD (the replacement "
+                         "character stands for bytes that are not text: no token sequence spells it)")
+    stops = [s.encode("utf-8") for s in strings]
+    if len(stops) > ops.STOP_MAX_STRINGS:
+        raise ValueError(f"`stop_strings` holds {len(stops)} strings, above the limit of {ops.STOP_MAX_STRINGS} (ULL_STOP_MAX_STRINGS)")
+    if max(len(s) for s in stops) > ops.STOP_MAX_BYTES:
+        raise ValueError(f"a stop string of {max(len(s) for s in stops)} bytes (UTF-8) is above the limit of {ops.STOP_MAX_BYTES} (ULL_STOP_MAX_BYTES)")
+    return stops
+
+
+def _tokenizer_size(tokenizer):
+    """What changes whenever len(tokenizer) does.  A tokenizer grows through added tokens only, and on a fast tokenizer of 32 000 ids
+    len() itself costs 4-5 ms (measured, transformers 5.15: the backend counts the whole vocabulary), which a 64-token batch-1 call would pay
+    as 60 us per token; the base size and the number of added tokens cost microseconds."""
+    added = getattr(tokenizer, "added_tokens_decoder", None)
+    return len(tokenizer) if added is None else (tokenizer.vocab_size, len(added))
+
+
+def stop_table(model, tokenizer, device):
+    """The ops.StopTable of `tokenizer` on `device`, built on first use and kept on the model under the tokenizer's identity; rebuilt when
+    len(tokenizer) (`_tokenizer_size`) or the model's vocabulary size has changed since (the resize helpers of tools.py grow both).  One
+    plain dict."""
+    tables = model.__dict__.setdefault("_stop_tables", {})
+    key = (_tokenizer_size(tokenizer), int(model.config.vocab_size), torch.device(device))
+    held = tables.get(id(tokenizer))
+    if held is None or held[0] is not tokenizer or held[1] != key:
+        held = tables[id(tokenizer)] = (tokenizer, key, ops.StopTable(*token_byte_table(tokenizer, key[1]), device))
+    return held[2]
 
 
 def prompt_lookup_candidates(row, num_tokens: int, max_ngram: int, eos_ids, limit: int):
@@ -213,7 +313,7 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
                         use_cache=None, kv_cache_dtype=None, sampler=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None,
                         output_logprobs=False, return_dict_in_generate=False, unknown=None, dtype=None, vocab_size=None, config_use_cache=None,
                         ngram_ban=None, length_penalty=1.0, early_stopping=False, num_return_sequences=1, stopping_criteria=None,
-                        output_hidden_states=False, n_eos=None, past_key_values=None, cache_shape=None):
+                        output_hidden_states=False, n_eos=None, past_key_values=None, cache_shape=None, stop_strings=None, tokenizer=None):
     """Every refusal of generate()'s arguments that needs no device work, in generate()'s order; evaluate() calls it too, before it starts
     the SAM encoder on the side stream.  No model is needed: what the model decides comes in as plain values, each read only when the
     option it belongs to is set -- `dtype` with kv_cache_dtype, `vocab_size` with sampler="device" (None: the caller does not know it
@@ -225,7 +325,10 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
     past_key_values (a KVCache, or an HF legacy tuple / Cache object): the call continues an earlier one's cache, which implies use_cache=True;
     refused, in this order: use_cache=False; a cache whose batch is not input_ids', or whose (layers, heads, head_dim) are not the model's
     `cache_shape` (None: not known, left to generate()); a kv_cache_dtype other than the cache's own; output_hidden_states=True on a cache
-    that does not hold the hidden states of its positions (from_hf); num_beams > 1; tensors that are not on the GPU."""
+    that does not hold the hidden states of its positions (from_hf); num_beams > 1; tensors that are not on the GPU.
+    stop_strings / tokenizer (check_stop_strings: a str or a list of str with its tokenizer, no empty string, no U+FFFD, within ops.STOP_MAX_STRINGS
+    and ops.STOP_MAX_BYTES), behind the refusals of prompt lookup; then refused, in this order: with num_beams > 1; with prompt_lookup_num_tokens
+    (a verify step emits several tokens and would have to be cut in the middle); and, last of all, on tensors that are not on the GPU."""
     beams = check_num_beams(num_beams, length_penalty, early_stopping, num_return_sequences)
     if unknown:
         # HF generate() validates its model kwargs and raises on unknown ones; options this loop does not implement must not be
@@ -270,6 +373,13 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
             raise ValueError("prompt-lookup decoding does not take a padded attention mask (one unpadded row)")
         if sampling and not device_sampler:
             raise ValueError('prompt-lookup decoding with do_sample=True needs sampler="device": its loop picks the tokens on the device')
+    if check_stop_strings(stop_strings, tokenizer) is not None:
+        if beams > 1:
+            raise ValueError(f"num_beams={beams} does not combine with `stop_strings` (a beam is not a row that stops: use `eos_token_id`, or "
+                             "num_beams=1)")
+        if lookup is not None:
+            raise ValueError("`stop_strings` does not combine with prompt-lookup decoding: a verify step emits several tokens and the stop may "
+                             "fall between them (drop `prompt_lookup_num_tokens`, or pass a host `stopping_criteria`)")
     if kv_cache_dtype is not None:
         _check_kv_dtype(kv_cache_dtype, dtype)
         if not use_cache:
@@ -299,7 +409,7 @@ def check_generate_args(input_ids, attention_mask=None, *, do_sample=False, temp
         if input_ids is None or not input_ids.is_cuda:
             raise NotImplementedError("beam search needs GPU tensors (no CPU path exists)")
     for on, what in ((lookup is not None, "prompt-lookup decoding"), (device_sampler and sampling, 'sampler="device"'), (output_logprobs, "output_logprobs"),
-                     (device_ban, 'ngram_ban="device"')):
+                     (device_ban, 'ngram_ban="device"'), (stop_strings is not None, "`stop_strings`")):
         if on and input_ids is not None and not input_ids.is_cuda:
             raise RuntimeError(f"{what} needs GPU tensors (no CPU path exists)")
     return ngram, sampling, device_sampler, use_cache, lookup
@@ -318,6 +428,7 @@ class Decoding:
         self.steps_hidden = []
         self.return_cache = False                                # the cache came from the caller (past_key_values): the result names it
         self.continued = bool(cache)                             # ... and held positions at entry: step 0 feeds what lies behind them
+        self.stops = None                                        # generate(stop_strings=): (ops.StopTable, ops.StopStrings) on the ids' device
 
     def forward(self, seq, step: int):
         """The forward of decode step `step` over the ids so far, through prepare_inputs_for_generation.  With a cache:
@@ -369,9 +480,11 @@ def host_loop(d: Decoding, seq, ngram: int, probs=sampling_probs, device_ban: bo
     and EOS bookkeeping per row, one host read per step.  probs: generate() hands in the `sampling_probs` of its own module, so that a
     wrapper installed there (the tests record the logits that way) is the one that runs.  device_ban: the ban is ops.ngram_ban on the
     model-dtype logits (-inf where the list rule puts it, the same fp32 values after .float()) instead of tolist() + the Python rule + one
-    indexed store per row.  -> (ids, logprobs or None)"""
-    B = seq.shape[0]
+    indexed store per row.  d.stops (stop_strings): ops.stop_strings on the ids after the token is appended, folded into `unfinished`.
+    -> (ids, logprobs or None)"""
+    B, L0 = seq.shape
     unfinished = torch.ones(B, dtype=torch.bool, device=seq.device)
+    stop_count = torch.zeros(1, dtype=torch.int32, device=seq.device) if d.stops is not None else None      # (the kernel's counter: not read here)
     lp_cols = []
     for step in range(d.max_new_tokens):
         out = d.forward(seq, step)
@@ -397,8 +510,12 @@ def host_loop(d: Decoding, seq, ngram: int, probs=sampling_probs, device_ban: bo
             lp_cols.append(ops.token_logprobs(out.logits[:, -1], nxt.squeeze(1), unfinished.to(torch.int32)))
         if d.eos_ids is not None:
             unfinished = unfinished & ~torch.isin(nxt.squeeze(1), d.eos_ids)
-            if not bool(unfinished.any()):
-                break
+        if d.stops is not None:
+            live = unfinished.to(torch.int32)
+            ops.stop_strings(seq, L0, seq.shape[1], d.stops[0], d.stops[1], live, stop_count)
+            unfinished = live.bool()
+        if (d.eos_ids is not None or d.stops is not None) and not bool(unfinished.any()):
+            break
         if d.stopped(seq):
             break
     if not d.output_logprobs:
@@ -413,7 +530,9 @@ def fused_loop(d: Decoding, seq, ngram: int = 0):
     past the point where every row had finished only produce pad tokens; ids, cache and hidden states are trimmed to what a per-step check
     returns.  ngram > 0 (ngram_ban="device"): one more launch per step, ops.ngram_ban, copies the last-position logits into a [B, V] scratch
     with the banned tokens at -inf -- it reads the ids in `buf`, pad fill included, as HF's processor does -- and the pick runs on the
-    scratch; the log-probabilities keep scoring the raw logits.  -> (ids, logprobs or None)"""
+    scratch; the log-probabilities keep scoring the raw logits.  d.stops (stop_strings): one more launch per step behind the pick,
+    ops.stop_strings, clears `live` of the rows whose text now holds a stop string and takes them out of the step's counter; the next
+    step pad-fills them as it does a row behind its EOS.  -> (ids, logprobs or None)"""
     B, L0 = seq.shape
     n_max, dev = d.max_new_tokens, seq.device
     buf = torch.empty(B, L0 + n_max, dtype=torch.int64, device=dev)
@@ -426,7 +545,7 @@ def fused_loop(d: Decoding, seq, ngram: int = 0):
         lp = torch.zeros(B, n_max, dtype=torch.float32, device=dev)
         live_before = torch.empty_like(live)
     banned = None                                                # the step's logits under the n-gram ban: allocated once, at the first step
-    check = 1 if d.crit else 8
+    check = d.check = 1 if d.crit else 8                         # (kept on `d`: the tests read how often this call looked at the host)
     n_done = n_tok = 0                                           # tokens appended so far; tokens after which every row had finished
     for step in range(n_max):
         last = d.forward(buf[:, :L0 + step], step).logits[:, -1]
@@ -443,12 +562,14 @@ def fused_loop(d: Decoding, seq, ngram: int = 0):
             ops.sample_step(pick, noise, d.temperature, d.top_k, d.top_p, live, d.eos_ids, d.pad, buf, L0 + step, alive[step:step + 1])
         else:
             ops.greedy_step(pick, live, d.eos_ids, d.pad, buf, L0 + step, alive[step:step + 1])
+        if d.stops is not None:
+            ops.stop_strings(buf, L0, L0 + step + 1, d.stops[0], d.stops[1], live, alive[step:step + 1])
         if lp is not None:
             ops.token_logprobs(last, buf[:, L0 + step], live_before, out=lp[:, step])
         n_done = n_tok = step + 1
         if d.stopped(buf[:, :L0 + n_done]):
             break
-        if d.eos_ids is not None and (n_done % check == 0 or n_done == n_max):
+        if (d.eos_ids is not None or d.stops is not None) and (n_done % check == 0 or n_done == n_max):
             dead = (alive[:n_done].cpu() == 0).nonzero()         # the only device -> host read: every `check` steps
             if dead.numel():
                 n_tok = int(dead[0]) + 1

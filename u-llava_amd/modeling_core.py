@@ -23,8 +23,9 @@ from . import autograd_ops as A
 from . import ops
 from .configuration import UllavaCoreConfig
 # (imported by name: the cache and the decoding helpers stay importable from this module)
-from .generation import (Decoding, GenerateOutput, beam_loop, beam_search_reference, check_generate_args, check_ngram_ban, check_prompt_lookup, check_sampler, enter_cache,
-                         fused_loop, host_loop, no_repeat_ngram_banned_tokens, prompt_lookup_candidates, prompt_lookup_loop, sampling_probs)
+from .generation import (Decoding, GenerateOutput, beam_loop, beam_search_reference, check_generate_args, check_ngram_ban, check_prompt_lookup, check_sampler, check_stop_strings, enter_cache,
+                         fused_loop, host_loop, no_repeat_ngram_banned_tokens, prompt_lookup_candidates, prompt_lookup_loop, sampling_probs, stop_strings_reference,
+                         stop_table, token_byte_table)
 from .kv_cache import DEFAULT_HEADROOM, KV_CACHE_DTYPES, KVCache, _check_kv_dtype
 
 BF16 = torch.bfloat16
@@ -1238,9 +1239,29 @@ class UllavaCoreForCausalLM(nn.Module):
         filled by the call: how a first turn obtains a cache to keep.  With return_dict_in_generate=True the result carries
         `past_key_values` (the same object), and `hidden_states` holds the last-layer states of ALL positions, the earlier calls' included.
         Every loop but beam search, both cache dtypes (the cache's own decides; a contradicting `kv_cache_dtype` is refused).
-        `KVCache.fork()` gives an independent copy for several continuations of one prefix."""
+        `KVCache.fork()` gives an independent copy for several continuations of one prefix.
+        stop_strings / tokenizer (opt-in, default None; HF's names, taken by keyword from **kwargs like `past_key_values`): a str or a list
+        of str on which a ROW stops, decided on the device -- what the reference's callers ask of KeywordsStoppingCriteria, without the host
+        read and the decode of all generated tokens per step, and for every row of a batch, not row 0 alone.  `tokenizer` is required with
+        it (ValueError otherwise, as in HF); empty strings and strings holding U+FFFD are refused; at most ops.STOP_MAX_STRINGS strings of
+        ops.STOP_MAX_BYTES UTF-8 bytes each.  The rule is `generation.stop_strings_reference`: the row's text is the concatenation of the
+        bytes its GENERATED ids stand for (`generation.token_byte_table`: a piece's UTF-8 in context, the raw byte of a byte-fallback token,
+        nothing for special ids and for ids the tokenizer does not know), and the row stops after the first generated token inside whose
+        bytes a stop string ends.  That token is kept and its log-probability with it, as an EOS token's; the prompt never counts, nor does
+        the text of earlier turns under `past_key_values` (L0 is this call's input_ids.shape[1]).  One more launch per step
+        (ops.stop_strings) behind the pick in the device-resident loop -- greedy and sampler="device", with or without ngram_ban="device",
+        output_logprobs, kv_cache_dtype -- which keeps looking at the host every 8 steps; the host sampler's loop calls the same kernel on its
+        ids.  A stopped row is pad-filled from the next step on (a batch needs a pad or EOS id for that), and ids, cache, hidden states and
+        log-probabilities are trimmed to the last row's stop as they are for EOS.  The stop string is not cut from the result.  The
+        tokenizer's table is built on first use and kept on the model under the tokenizer's identity (rebuilt when len(tokenizer) or the
+        vocabulary size changes).  `stopping_criteria` may be passed beside it and forces the per-step host check as before.  GPU tensors
+        only; refused with num_beams > 1 and with prompt_lookup_num_tokens.  Differences from tools.KeywordsStoppingCriteria: that criterion
+        never checks after the FIRST generated token (a string wholly inside it stops one token earlier here); decode() strips one leading
+        space of the whole text (equal positions are claimed for stop strings that do not begin with a space); and its decoder turns a whole
+        run of byte tokens into U+FFFD when the run is not valid UTF-8 as it stands, where this rule reads each byte."""
         cfg = self.config
         past_key_values = kwargs.pop("past_key_values", None)
+        stop_strings, tokenizer = kwargs.pop("stop_strings", None), kwargs.pop("tokenizer", None)
         eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
         eos_list = [] if eos is None else [eos] if isinstance(eos, int) else list(eos)
         ngram, sampling, device_sampler, use_cache, lookup = check_generate_args(
@@ -1250,8 +1271,10 @@ class UllavaCoreForCausalLM(nn.Module):
             unknown=kwargs, dtype=self.dtype, vocab_size=cfg.vocab_size, config_use_cache=cfg.use_cache, ngram_ban=ngram_ban,
             length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,
             stopping_criteria=stopping_criteria, output_hidden_states=output_hidden_states, n_eos=len(eos_list), past_key_values=past_key_values,
-            cache_shape=(cfg.num_hidden_layers, cfg.num_attention_heads, cfg.hidden_size // cfg.num_attention_heads))
+            cache_shape=(cfg.num_hidden_layers, cfg.num_attention_heads, cfg.hidden_size // cfg.num_attention_heads), stop_strings=stop_strings,
+            tokenizer=tokenizer)
         device_ban = check_ngram_ban(ngram_ban)
+        stops = check_stop_strings(stop_strings, tokenizer)
         seq = input_ids
         eos_ids = None if eos is None else torch.as_tensor(eos_list, device=seq.device, dtype=seq.dtype)
         pad = pad_token_id if pad_token_id is not None else getattr(cfg, "pad_token_id", None)
@@ -1278,6 +1301,11 @@ class UllavaCoreForCausalLM(nn.Module):
         d = Decoding(self, images, videos, attention_mask, no_pad, cache, max_new_tokens, sampling, temperature, top_k, top_p, eos_ids, pad, crit,
                      output_hidden_states, keep_last_step_only, output_logprobs)
         d.return_cache = past_key_values is not None
+        if stops is not None:
+            if pad is None and seq.shape[0] > 1:
+                raise ValueError("`stop_strings` on a batch needs a `pad_token_id` (or an `eos_token_id`): a row that has stopped is filled with it "
+                                 "while the others go on")
+            d.stops = (stop_table(self, tokenizer, seq.device), ops.StopStrings(stops, seq.device))
         if num_beams > 1:
             seq, scores = beam_loop(d, seq, num_beams, ngram, length_penalty, early_stopping, num_return_sequences)
             return GenerateOutput(sequences=seq, hidden_states=None, sequences_scores=scores) if return_dict_in_generate else seq

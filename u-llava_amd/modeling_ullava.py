@@ -319,8 +319,9 @@ class UllavaForCausalLM(nn.Module):
 
     @torch.no_grad()
     def evaluate(self, images_sam, images, input_ids, raw_size_list, resize_list, max_new_tokens=32, temperature=0.2, top_p=None,
-                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None, ngram_ban=None,
-                 past_key_values=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, output_logprobs=False, sampler=None):
+                 num_beams=1, no_repeat_ngram_size=None, stopping_criteria=None, kv_cache_dtype=None, stop_strings=None, tokenizer=None,
+                 ngram_ban=None, past_key_values=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, output_logprobs=False,
+                 sampler=None):
         """reference ullava.py:335-434 -> (output_ids, pred_masks, pred_boxes).  kv_cache_dtype="fp8_e4m3": generate with an fp8 KV cache
         (which implies use_cache=True; see UllavaCoreForCausalLM.generate).  sampler="device": draw the tokens with the on-device sampler
         (same ids under the same seed; see generate).  ngram_ban="device" (with no_repeat_ngram_size): the n-gram ban in one launch per step, so
@@ -335,13 +336,17 @@ class UllavaForCausalLM(nn.Module):
         what the cache holds, NOT the images -- a changed image under equal ids gets the old image's keys, as in HF).  The cache is advanced
         in place and also keeps the SAM image embeddings of the call that computed them (`cache.side["sam_image_embeddings"]`, keyed to
         nothing else): while they are there the SAM encoder does not run.  Masks and boxes are computed from the hidden states of all
-        positions, the earlier calls' included: what the reference yields when it is fed the whole conversation."""
+        positions, the earlier calls' included: what the reference yields when it is fed the whole conversation.
+        stop_strings / tokenizer: stop each row on text, decided on the device (HF's names; what the reference's scripts ask of
+        KeywordsStoppingCriteria([stop_str], tokenizer, input_ids) -- see generate for the rule and its documented differences)."""
         # generate()'s refusals, before the SAM encoder starts (the model's dtype is asked for only where kv_cache_dtype needs it)
         gen = dict(do_sample=temperature > 0, temperature=temperature, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size,
                    sampler=sampler, return_dict_in_generate=True, output_logprobs=output_logprobs, kv_cache_dtype=kv_cache_dtype,
                    prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size, ngram_ban=ngram_ban,
                    use_cache=True if kv_cache_dtype is not None or prompt_lookup_num_tokens is not None or past_key_values is not None else None)
         gen_shape = None
+        if stop_strings is not None or tokenizer is not None:
+            gen["stop_strings"], gen["tokenizer"] = stop_strings, tokenizer
         if past_key_values is not None:
             gen["past_key_values"] = past_key_values                # (a call without one hands generate() exactly the keywords it always did)
             lc = self.llm.config                                    # (the model's geometry is asked for only where a cache is held against it)

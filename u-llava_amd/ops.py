@@ -1276,7 +1276,75 @@ def ngram_ban(logits: torch.Tensor, ids: torch.Tensor, cur_len: int, ngram: int,
     return out
 
 
-BEAM_MAX_K, BEAM_MAX_CAND = _D["ULL_BEAM_MAX_K"], _D["ULL_BEAM_MAX_CAND"]
+# the limits of stop_strings: how many strings, the bytes of one, the bytes of the table's longest token, the LDS window per row
+STOP_MAX_STRINGS, STOP_MAX_BYTES, STOP_MAX_TOKEN_BYTES, STOP_MAX_WINDOW = (_D["ULL_STOP_MAX_" + n] for n in ("STRINGS", "BYTES", "TOKEN_BYTES", "WINDOW"))
+
+
+class StopTable:
+    """`generation.token_byte_table`'s (offsets int32 [V + 1], bytes uint8 [n]) checked on the host and copied to `device`: what
+    stop_strings reads a token's bytes from.  A table whose longest token is above STOP_MAX_TOKEN_BYTES is refused (ValueError)."""
+
+    def __init__(self, offsets: torch.Tensor, data: torch.Tensor, device):
+        offsets, data = torch.as_tensor(offsets), torch.as_tensor(data)
+        if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2 or data.dtype != torch.uint8 or data.dim() != 1:
+            raise RuntimeError("u-llava_amd.StopTable: offsets must be torch.int32 [V + 1] and bytes torch.uint8 [n]")
+        host = offsets.cpu()
+        lens = host[1:] - host[:-1]
+        if int(host[0]) != 0 or int(host[-1]) != data.numel() or bool((lens < 0).any()):
+            raise RuntimeError("u-llava_amd.StopTable: offsets must ascend from 0 to the number of bytes")
+        self.V, self.n_bytes, self.max_token_bytes = host.numel() - 1, data.numel(), int(lens.max())
+        if self.max_token_bytes > STOP_MAX_TOKEN_BYTES:
+            raise ValueError(f"u-llava_amd.StopTable: the longest token has {self.max_token_bytes} bytes, above the limit of {STOP_MAX_TOKEN_BYTES} "
+                             "(ULL_STOP_MAX_TOKEN_BYTES)")
+        self.offsets, self.bytes = offsets.to(device).contiguous(), data.to(device).contiguous()
+
+
+class StopStrings:
+    """The stop strings of one generate() call as stop_strings takes them: `stops` is a list of non-empty byte strings (the UTF-8 of the
+    strings).  The offsets stay on the host (the entry reads and checks them before it launches), the bytes go to `device`.  More than
+    STOP_MAX_STRINGS strings, or one longer than STOP_MAX_BYTES bytes: ValueError."""
+
+    def __init__(self, stops, device):
+        stops = [bytes(s) for s in stops]
+        if not stops or any(len(s) == 0 for s in stops):
+            raise ValueError("u-llava_amd.StopStrings: at least one stop string, none of them empty")
+        if len(stops) > STOP_MAX_STRINGS:
+            raise ValueError(f"u-llava_amd.StopStrings: {len(stops)} stop strings, above the limit of {STOP_MAX_STRINGS} (ULL_STOP_MAX_STRINGS)")
+        if max(len(s) for s in stops) > STOP_MAX_BYTES:
+            raise ValueError(f"u-llava_amd.StopStrings: a stop string of {max(len(s) for s in stops)} bytes, above the limit of {STOP_MAX_BYTES} "
+                             "(ULL_STOP_MAX_BYTES)")
+        self.stops = stops
+        off = [0]
+        for s in stops:
+            off.append(off[-1] + len(s))
+        self.offsets = torch.tensor(off, dtype=torch.int32)                                   # host memory, kept alive by this object
+        self.bytes = torch.frombuffer(bytearray(b"".join(stops)), dtype=torch.uint8).to(device)
+
+
+def stop_strings(ids: torch.Tensor, L0: int, cur_len: int, table: StopTable, stops: StopStrings, live: torch.Tensor, alive: torch.Tensor) -> None:
+    """generate(stop_strings=)'s step in one launch (see ull_stop_strings; `generation.stop_strings_reference` is the rule): every row r
+    with live[r] != 0 in whose text -- the table bytes of ids[r, L0:cur_len] -- a stop string ends inside the bytes of the last token
+    ids[r, cur_len-1] gets live[r] = 0 and is taken out of alive[0].  ids int64 [R, >= cur_len] with contiguous rows of any pitch (the
+    generate buffer); live int32 [R] contiguous (greedy_step's `unfinished`); alive int32 [1] (the step's counter)."""
+    _chk(ids, "ids", torch.int64); _chk(live, "live", torch.int32); _chk(alive, "alive", torch.int32)
+    if not isinstance(table, StopTable) or not isinstance(stops, StopStrings):
+        raise RuntimeError("u-llava_amd.stop_strings: table must be an ops.StopTable and stops an ops.StopStrings")
+    _chk(table.offsets, "table.offsets", torch.int32); _chk(table.bytes, "table.bytes", torch.uint8); _chk(stops.bytes, "stops.bytes", torch.uint8)
+    L0, cur_len = int(L0), int(cur_len)
+    if ids.dim() != 2 or L0 < 0 or cur_len <= L0 or ids.shape[1] < cur_len:
+        raise RuntimeError(f"u-llava_amd.stop_strings: ids must be torch.int64 [R, >= cur_len] with 0 <= L0 < cur_len, got {tuple(ids.shape)}, "
+                           f"L0 = {L0}, cur_len = {cur_len}")
+    R = ids.shape[0]
+    if tuple(live.shape) != (R,) or not live.is_contiguous() or alive.numel() != 1:
+        raise RuntimeError(f"u-llava_amd.stop_strings: live must be a contiguous int32 [{R}] and alive int32 [1], got {tuple(live.shape)}, {tuple(alive.shape)}")
+    if R > 1 and ids.stride(0) < 0:
+        raise RuntimeError("u-llava_amd.stop_strings: negative strides are not supported")
+    if R:
+        _lib.call("ull_stop_strings", _p(ids), ids.stride(0) if R > 1 else ids.shape[1], R, L0, cur_len, _p(table.offsets), _p(table.bytes), table.V,
+                  table.n_bytes, table.max_token_bytes, stops.offsets.data_ptr(), _p(stops.bytes), len(stops.stops), _p(live), _p(alive), _stream())
+
+
+BEAM_MAX_K, BEAM_MAX_CAND =_D["ULL_BEAM_MAX_K"], _D["ULL_BEAM_MAX_CAND"]
 BEAM_EARLY_STOPPING = {False: 0, True: 1, "never": 2}
 
 
