@@ -97,7 +97,8 @@ int ull_gemv_bf16(const void* X, int64_t ldx, const void* W, int64_t ldw, void* 
 int ull_gemm_skinny_bf16(const void* X, int64_t ldx, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* R,
                          int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
 
-/* ull_gemv_bf16 with the preceding LlamaRMSNorm fused in: C = epilogue(rmsnorm(X; norm_w, eps) * W^T), M * K <= 16384.
+/* ull_gemv_bf16 with the preceding LlamaRMSNorm fused in: C = epilogue(rmsnorm(X; norm_w, eps) * W^T), where the M x K activations fit
+ * the GEMV's 32 KiB LDS staging (the shapes for which ull_linear_route answers ULL_ROUTE_GEMV with bit 8 clear).
  * Decode-step form of input_layernorm -> q/k/v_proj and post_attention_layernorm -> gate/up_proj (hf LlamaDecoderLayer.forward). */
 int ull_gemv_rmsnorm_bf16(const void* X, int64_t ldx, const void* norm_w, float eps, const void* W, int64_t ldw, void* C, int64_t ldc,
                           const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
@@ -735,6 +736,32 @@ int ull_adamw_step_f32(void* master, void* m, void* v, const void* grad, int gra
 
 /* out[0] (fp32 on the device, caller-zeroed) += sum of squares of n gradient elements: the local part of clip_grad_norm_'s total norm. */
 int ull_sumsq_f32(const void* g, int grad_dtype, int64_t n, void* out, void* stream);
+
+/* ---- the Linear dispatch rule (u-llava_amd/csrc/linear_route.h, its one definition) -------------------------------------------------------
+ * Which kernel a Linear X [M, K] * W[N, K]^T (row pitch ldw) takes is decided in one place, which the library's own callers (the GEMV / GEMM
+ * launchers, the coarse entries below) and the Python host both read.  The three queries launch nothing and touch no device; the host asks
+ * once per distinct shape and remembers the answer. */
+#define ULL_ROUTE_GEMM 0        /* ull_gemm_bf16 (a quantized weight: dequantized first) */
+#define ULL_ROUTE_GEMV 1        /* ull_gemv_bf16 / ull_gemv_rmsnorm_bf16 / their *_wq_bf16 forms */
+#define ULL_ROUTE_SKINNY 2      /* ull_gemm_skinny_bf16 / ull_gemm_skinny_wq_bf16 */
+#define ULL_ROUTE_A8W8 3        /* ull_gemm_a8w8_bf16 */
+#define ULL_ROUTE_W4A8 4        /* ull_gemm_w4a8_bf16 */
+#define ULL_ROUTE_A8W8_SKINNY 5 /* ull_gemm_skinny_a8w8_bf16 */
+/* activation quantization asked of the Linear: it takes effect only on the weight format it pairs with (fp8 + FP8, mxfp4 + MXFP8) */
+#define ULL_AF_NONE 0
+#define ULL_AF_FP8 1   /* one power-of-two scale per token (ull_quantize_rows_fp8_bf16) */
+#define ULL_AF_MXFP8 2 /* one E8M0 scale per block of 32 (ull_quantize_rows_mxfp8_bf16) */
+#define ULL_A8W8_BK 128          /* K-tile of the A8 kernels: one block-scaled matrix instruction */
+#define ULL_A8W8_SKINNY_MAX_M 32 /* ull_gemm_skinny_a8w8_bf16: two 16-row activation fragments */
+/* ULL_ROUTE_* in the low byte; bit 8: a LlamaRMSNorm asked in front of the Linear is a launch of its own (clear: the route's kernel fuses it).
+ * wfmt: ULL_WF_*; afmt: ULL_AF_*, a_decode: also at the batched decode shapes; tune: the call's ULL_GEMM_TUNE_* bits. */
+int64_t ull_linear_route(int64_t M, int64_t N, int64_t K, int64_t ldw, int wfmt, int afmt, int a_decode, int tune);
+/* How ull_gemm_bf16 is to be called at this shape.  Bit 0: "big" -- the 256 x 256 kernel, which takes the weight's ULL_EPI_W_TILED copy; bit 1:
+ * pass the workspace (the stream-K tail of a big GEMM from K >= min_k on, min_k < 0 = never; or, small_m: the caller's kernel has the split,
+ * and small_m_split_k: the opt-in latency mode is on, the split-K of a small-M GEMM). */
+int64_t ull_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t min_k, int small_m, int small_m_split_k);
+/* 1 where a decode step of T = B * S tokens at width D = H * hd takes ull_gemv_qkv_rope_append_bf16 (and ull_llama_decode_layers_bf16). */
+int64_t ull_decode_step_fused(int64_t T, int64_t D, int64_t hd);
 
 /* ---- coarse entries (round 6): ONE call enqueues a whole stack of layers on the stream --------------------------------------------------
  * Host-side composition of the per-op entries above (u-llava_amd/csrc/layers.hip holds no kernel): the same launches, the same dispatch rules

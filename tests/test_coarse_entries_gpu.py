@@ -54,15 +54,16 @@ def test_prefill_and_clip_coarse_equal_per_op(batch, image, dtype):
     assert bool(torch.isfinite(a.logits.float()).all())
 
 
-@pytest.mark.parametrize("batch,fp8", [(1, False), (2, False), (3, False), (1, True), (2, True), (3, True)],
-                         ids=["1", "2", "3", "fp8-1", "fp8-2", "fp8-3"])
-def test_decode_coarse_equal_per_op(batch, fp8):
-    """KV-cached greedy generation, 6 steps at batch 1 / 2 (GEMV) / 3 (skinny MFMA GEMM), on bf16 and on fp8 (quantize_weights) weights: token
-    ids and the last-step hidden states equal."""
+@pytest.mark.parametrize("batch,wq", [(1, None), (2, None), (3, None), (4, None), (1, "fp8_e4m3"), (2, "fp8_e4m3"), (3, "fp8_e4m3"), (4, "fp8_e4m3"),
+                                      (3, "mxfp4")],
+                         ids=["1", "2", "3", "4", "fp8-1", "fp8-2", "fp8-3", "fp8-4", "mxfp4-3"])
+def test_decode_coarse_equal_per_op(batch, wq):
+    """KV-cached greedy generation, 6 steps at batch 1 / 2 (GEMV) / 3 / 4 (skinny MFMA GEMM; 4 is the last step the fused q|k|v GEMV and the
+    coarse entry take), on bf16, fp8 and mxfp4 (quantize_weights) weights: token ids and the last-step hidden states equal."""
     ops = pkg("ops")
     model, cfg, bench = _core(224)
-    if fp8:
-        model.quantize_weights("fp8_e4m3")
+    if wq:
+        model.quantize_weights(wq)
     images, ids, mask = bench.make_inputs(cfg, batch, 32, torch.device(DEV), 9)
     kw = dict(input_ids=ids, images=images, max_new_tokens=6, do_sample=False, use_cache=True, eos_token_id=-1, output_hidden_states=True,
               return_dict_in_generate=True, keep_last_step_only=True)

@@ -76,13 +76,15 @@ def test_header_parser_refuses_a_type_it_does_not_know(bad, names):
 def test_binding_is_the_parsed_header():
     """What _lib derives from the committed header: the struct sizes are the ones the typedefs imply with 8-byte alignment (ull_linear: 3 pointers
     + 3 int64 + int (padded) + pointer + int64 = 72; a layer = its pointers and int64 + 4 x 72), a nested ull_linear is the Linear class itself
-    (ops.LayerStack tells the fields apart by it), the one int64_t query keeps its return type, and function-like macros are left out."""
+    (ops.LayerStack tells the fields apart by it), the int64_t queries -- the workspace size and the three of the Linear dispatch rule -- and
+    no other entry keep that return type, and function-like macros are left out."""
     L = pkg("_lib")
     assert [ctypes.sizeof(c) for c in (L.Linear, L.LlamaLayer, L.ClipLayer, L.SamBlock)] == [72, 304, 320, 344]
     assert L.Linear._fields_ == [("w", _P), ("w_tiled", _P), ("bias", _P), ("n", _I64), ("k", _I64), ("ldw", _I64), ("format", _I32), ("scales", _P),
                                  ("lds", _I64)]
     assert L.SamBlock._fields_[4:8] == [(n, L.Linear) for n in ("qkv", "proj", "lin1", "lin2")] and L.SamBlock._fields_[-1] == ("window", _I64)
-    assert [k for k, v in L.RESTYPES.items() if v is not _I32] == ["ull_gemm_streamk_ws_bytes"] and L.RESTYPES["ull_gemm_streamk_ws_bytes"] is _I64
+    queries = ["ull_gemm_streamk_ws_bytes", "ull_linear_route", "ull_gemm_plan", "ull_decode_step_fused"]
+    assert [k for k, v in L.RESTYPES.items() if v is not _I32] == queries and all(L.RESTYPES[k] is _I64 for k in queries)
     assert (L.DEFINES["ULL_OK"], L.DEFINES["ULL_ERR_LDS"], L.DEFINES["ULL_EPI_ACT_RELU"], L.DEFINES["ULL_GEMM_TUNE_WAVES4"]) == (0, -4, 6, 1 << 22)
     assert "ULL_GEMM_TUNE_GROUP_M" not in L.DEFINES and sorted(L.ERRORS) == [-4, -3, -2, -1]
 
@@ -846,6 +848,90 @@ def test_unified_route_table(kind, mode, shape, want):
     assert [ops.linear_route(M, w, aq) for M in ROUTE_MS] == [ops._linear_route(M, N, K, ldw, 0, wfmt, aq)[0] for M in ROUTE_MS]
     if aq is None:                                               # no mode: exactly the five-argument rule
         assert [ops._linear_route(M, N, K, ldw, 0, wfmt) for M in ROUTE_MS] == [ops._linear_route(M, N, K, ldw, 0) for M in ROUTE_MS]
+
+
+# ---- the C rule (csrc/linear_route.h, read through ull_linear_route / ull_gemm_plan / ull_decode_step_fused) against its written form ----------
+# The rule as Python stated it in the parent of the change that moved it into C: the bodies of ops._linear_route, ops._big, the split part of
+# ops._gemm_ws (its two module switches as arguments) and the shape part of modeling_core's `fuse_append`, verbatim.  Kept here as the
+# restatement the C rule is held against.
+_A8_GEMM = {("fp8", "fp8_e4m3"): "a8w8", ("mxfp4", "mxfp8_e4m3"): "w4a8"}
+A8W8_BK = 128
+A8W8_SKINNY_MAX_M = 32
+
+
+def _written_linear_route(M, N, K, ldw, tune, wfmt=None, aq=None):
+    a8 = None if aq is None else _A8_GEMM.get((wfmt, aq.fmt))
+    if a8 == "a8w8" and aq.decode and 5 <= M <= A8W8_SKINNY_MAX_M and K % A8W8_BK == 0 and N * K >= (1 << 22) and ldw % 8 == 0 and tune == 0:
+        return "a8w8_skinny", False
+    if 3 <= M <= 16 and K % 32 == 0 and N * K >= (1 << 22) and ldw % 8 == 0 and tune == 0:
+        return "skinny", True
+    if M <= 4 and K % 8 == 0:
+        return "gemv", M * K > 16384
+    return a8 or "gemm", True
+
+
+def _written_big(M, N, K):
+    return M >= 1024 and N >= 512 and K >= 128
+
+
+def _written_gemm_split(big, M, N, K, small_m, min_k, small_m_split_k):
+    if min_k is None:
+        return False
+    if big:
+        split = K >= min_k
+    else:
+        split = small_m and small_m_split_k and K >= 1024 and M >= 128 and N * K >= (1 << 22) and -(-M // 128) * -(-N // 128) <= 256
+    return bool(split)
+
+
+def _written_fuse_append(T, D, hd):
+    return T <= 4 and hd % 2 == 0 and D % 8 == 0 and T * D * 2 <= 32768
+
+
+RULE_MS = tuple(range(1, 41)) + (127, 128, 129, 1023, 1024, 1025, 20576)
+RULE_NK = [
+    (12288, 4096), (4096, 4096), (22016, 4096), (4096, 11008), (32011, 4096),          # LLaMA-7B: q|k|v, o, gate|up, down, lm_head
+    (3072, 1024), (1024, 1024), (4096, 1024), (1024, 4096),                            # CLIP ViT-L
+    (3840, 1280), (1280, 1280), (5120, 1280), (1280, 5120),                            # SAM ViT-H
+    (192, 64), (64, 64), (256, 64), (64, 128), (100, 64),                              # the tiny fixture
+    (4194303, 1), (4194304, 1), (1023, 4096), (2047, 2048), (2048, 2048),      # N * K one below / at 1 << 22, and the nearest aligned (ViT-L's fc2 is at it)
+    (4096, 4104), (8192, 4104), (4096, 4100), (4096, 4160), (8192, 4160),              # K % 32, K % 8, K % 128 (K % 32 == 0) != 0
+    (4096, 64), (65536, 64), (4096, 127), (40000, 127), (4096, 128), (32768, 128),     # K = 64, 127, 128 against a small and a large weight
+]
+
+
+def test_c_rule_equals_its_written_form():
+    """Every answer of the C rule equals the written form over the shapes, formats, modes and switches that any of its branches reads; each
+    distinct question reaches the library once and the second pass of the whole sweep asks it nothing."""
+    ops = pkg("ops")
+    modes = (None, ops.ActQuant("fp8_e4m3"), ops.ActQuant("fp8_e4m3", True), ops.ActQuant("mxfp8_e4m3"), ops.ActQuant("mxfp8_e4m3", True))
+    memo = (ops._linear_route, ops._gemm_plan, ops.decode_step_fused)
+    for f in memo:
+        f.cache_clear()
+    asked = []
+    for _ in range(2):
+        for N, K in RULE_NK:
+            for M in RULE_MS:
+                for ldw in (K, K + 8, K + 4):
+                    for wfmt in (None, "fp8", "mxfp4"):
+                        for aq in modes:
+                            for tune in (0, ops.GEMM_TUNE_WAVES8):
+                                assert ops._linear_route(M, N, K, ldw, tune, wfmt, aq) == _written_linear_route(M, N, K, ldw, tune, wfmt, aq), \
+                                    (M, N, K, ldw, tune, wfmt, aq)
+                big = _written_big(M, N, K)
+                assert ops._big(M, N, K) is big, (M, N, K)
+                for min_k in (None, 2048, 4096):
+                    for small_m in (False, True):
+                        for on in (False, True):
+                            assert ops._gemm_plan(M, N, K, min_k, small_m, on) == (big, _written_gemm_split(big, M, N, K, small_m, min_k, on)), \
+                                (M, N, K, min_k, small_m, on)
+        for T in range(1, 6):
+            for D in (64, 2048, 4096, 4104, 5120, 8192):
+                for hd in (63, 64, 128):
+                    assert ops.decode_step_fused(T, D, hd) is _written_fuse_append(T, D, hd), (T, D, hd)
+        asked.append([f.cache_info().misses for f in memo])
+    n = len(RULE_NK) * len(RULE_MS)
+    assert asked[0] == [n * 3 * 3 * 5 * 2, n * 12, 5 * 6 * 3] and asked[1] == asked[0]           # (`_big` is the (None, False, False) plan)
 
 
 # ---- the weight format travels with the weight (ULL_WF_*): refusals, all of which return before any launch --------------------------------

@@ -20,6 +20,7 @@
 //   * Fused epilogues reproduce the rounding points of the reference's bf16 graph (rnd()).
 //   * 1-D grid with XCD-aware remap (block b runs on XCD b%8; each XCD gets a contiguous chunk of the
 //     tile space, walked in GROUP_M-row groups so co-resident blocks share X / W panels in that L2).
+#include "linear_route.h"
 #include "ull_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -1877,7 +1878,7 @@ static int gemm_dispatch(const void* X, int64_t ldx, const void* W, int64_t ldw,
     // short K and fewer than two rounds of 256x256 tiles (ViT patchify: K = 640, 128 / 288 tiles): the 128x128 kernel's 4x finer
     // tiles fill the chip better (measured 61 vs 70 us at B=32, 336^2)
     const bool short_and_few = K <= 768 && ((M + 255) / 256) * ((N + 255) / 256) < 512 && !(flags & (EPI_W_TILED | EPI_X_TILED));
-    if (!force_small && !short_and_few && M >= 1024 && N >= 512 && K >= 128) {   // nk >= 2
+    if (!force_small && !short_and_few && ull_route::is_big(M, N, K)) {   // nk >= 2
         a.nbm = (int)((M + big::BM - 1) / big::BM); a.nbn = (int)((N + big::BN - 1) / big::BN);
         // stream-K tail: whole rounds of one tile per CU, the remainder split along K (needs >= 2 K-steps per slice) into fp32
         // slabs in the CALLER's workspace (ws == NULL: no split; the caller owns the policy -- see ops.py -- and one workspace per

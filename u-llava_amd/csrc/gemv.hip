@@ -8,6 +8,7 @@
 // read exactly once), X comes from L1/L2, fp32 accumulation, wave reduction, same epilogues/rounding points as the GEMM.
 #include <type_traits>
 
+#include "linear_route.h"
 #include "ull_common.h"
 
 namespace {
@@ -105,8 +106,8 @@ ULL_DEV void gemv_fma_chunk(const float* wv, const float* uv, bool swiglu, const
     }
 }
 
-constexpr int XS_MAX_BYTES = 32 * 1024;     // X (optionally RMS-normalised) is staged in LDS when M * K * 2 fits in this
-
+// X (optionally RMS-normalised) is staged in LDS when its M * K * 2 bytes fit ull_route::GEMV_STAGE_BYTES (ull_route::gemv_stages, which the
+// routing rule reads too: a Linear whose RMSNorm does not fit here gets it as a launch of its own).
 // X staged in LDS (`staged`): every block first copies -- or, with norm_w, RMS-normalises (transformers LlamaRMSNorm:
 // w * bf16(x * rsqrt(mean(x^2) + eps)), the op that precedes the q/k/v and gate/up projections) -- the M activation rows,
 // which removes one tiny latency-bound kernel per projection from the decode step.  The weight stream keeps U 16-byte loads
@@ -578,7 +579,7 @@ int launch_gemv(const void* X, int64_t ldx, const Weight& w, void* C, int64_t ld
     if ((flags & EPI_BIAS) && !bias) return ULL_ERR_ARG;
     if ((flags & EPI_RESID) && !R) return ULL_ERR_ARG;
     if ((flags & EPI_SWIGLU) && ((N & 31) || (flags & (EPI_BIAS | EPI_ACT_MASK)))) return ULL_ERR_SHAPE;
-    const int staged = M * K * 2 <= XS_MAX_BYTES;
+    const int staged = ull_route::gemv_stages(M, K);
     if (norm_w && !staged) return ULL_ERR_SHAPE;
     const int n_out = (int)((flags & (EPI_SWIGLU | EPI_ROPE_APPEND)) ? N / 2 : N);
     hipStream_t st = (hipStream_t)stream;
@@ -611,7 +612,7 @@ extern "C" int ULL_FN(ull_gemv_)(const void* X, int64_t ldx, const void* W, int6
     return launch_gemv(X, ldx, Weight{WF_ELEM, W, ldw}, C, ldc, bias, R, ldr, M, N, K, flags, nullptr, 0.f, stream);
 }
 
-// The same with the preceding LlamaRMSNorm fused in: C = epilogue(rmsnorm(X; norm_w, eps) * W^T).  M * K <= 16384.
+// The same with the preceding LlamaRMSNorm fused in: C = epilogue(rmsnorm(X; norm_w, eps) * W^T), where gemv_stages(M, K).
 extern "C" int ULL_FN(ull_gemv_rmsnorm_)(const void* X, int64_t ldx, const void* norm_w, float eps, const void* W, int64_t ldw, void* C,
                                      int64_t ldc, const void* bias, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
                                      void* stream) {

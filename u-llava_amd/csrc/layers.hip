@@ -1,7 +1,7 @@
 // Coarse C-ABI entries: ONE call enqueues a whole stack of transformer layers on the stream (round 6).
 //
-// Host code only -- no kernel lives here.  Every function below calls the per-op entry points of this library (the same kernels, the same
-// dispatch rules as u-llava_amd/ops.py applies call by call), so the results are bit-identical to the per-op path; what changes is the host
+// Host code only -- no kernel lives here.  Every function below calls the per-op entry points of this library (the same kernels, picked by the
+// same dispatch rule, linear_route.h, that u-llava_amd/ops.py reads call by call), so the results are bit-identical to the per-op path; what changes is the host
 // cost: a ctypes round trip + Python argument marshalling per LAUNCH (~15 us, profiles/r05_decode.txt) becomes one per FORWARD.  With eight
 // Python ranks sharing one host that is the margin the >= 6x target has.
 //
@@ -11,7 +11,7 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "../../include/ullava_hip.h"
+#include "linear_route.h"
 
 #ifdef ULL_ELEM_F16
 #define FN(base) base##f16
@@ -32,8 +32,8 @@ struct SK {                      // the caller's stream-K policy (ops.streamk_po
     int64_t min_k;               // < 0: never split
 };
 
-// How the tiled GEMM runs a Linear at M rows (ops._big / ops._gemm_ws): a "big" shape takes the 256 x 256 kernel, the tile-major weight where
-// there is one, and the stream-K tail from K >= min_k on.
+// How the tiled GEMM runs a Linear at M rows (ull_route::is_big / gemm_split): a "big" shape takes the tile-major weight where there is one, and
+// the workspace where the rule splits K (the small-M split-K mode is never on here: the host takes the per-op path while it is).
 struct Tiled {
     const void* w;
     int64_t ldw;
@@ -42,16 +42,17 @@ struct Tiled {
     int64_t wsb;
 };
 inline Tiled tiled(const ull_linear* L, int64_t M, const SK& sk) {
-    const bool big = M >= 1024 && L->n >= 512 && L->k >= 128;
+    const bool big = ull_route::is_big(M, L->n, L->k);
     Tiled t{L->w, L->ldw, 0, nullptr, 0};
     if (big && L->w_tiled) { t.w = L->w_tiled; t.ldw = L->k; t.flags = ULL_EPI_W_TILED; }
-    if (big && sk.min_k >= 0 && L->k >= sk.min_k) { t.ws = sk.ws; t.wsb = sk.bytes; }
+    if (ull_route::gemm_split(big, M, L->n, L->k, sk.min_k, false, false)) { t.ws = sk.ws; t.wsb = sk.bytes; }
     return t;
 }
 
-// ops.linear for M > 16, K % 64 == 0: the tiled GEMM.
+// ops.linear on a 16-bit weight where the rule says GEMM (K % 64 == 0): the tiled GEMM.  The entries below admit no other shape.
 inline int lin(const void* x, int64_t ldx, const ull_linear* L, void* out, int64_t ldc, const void* R, int64_t ldr, int64_t M, int flags,
                const SK& sk, void* stream) {
+    if (ull_route::route_of(M, L->n, L->k, L->ldw, ULL_WF_ELEM, ULL_AF_NONE, false, 0).kind != ULL_ROUTE_GEMM) return ULL_ERR_SHAPE;
     const Tiled t = tiled(L, M, sk);
     if (L->bias) flags |= ULL_EPI_BIAS;
     if (R) flags |= ULL_EPI_RESID;
@@ -60,7 +61,7 @@ inline int lin(const void* x, int64_t ldx, const ull_linear* L, void* out, int64
 
 // A decode-shape Linear in any weight format (ull_linear.format): a quantized one (bf16 build only) has no bias and goes to the *_wq_bf16 form of
 // the entry, which takes the format as an argument.  format_ok: a format this build's entries take; has_weight: its pointers are there;
-// pitch_ok: the rows are whole; ldw_of: the row pitch the routing rule (ops._linear_route) sees.
+// pitch_ok: the rows are whole; ldw_of: the row pitch the routing rule (ull_route::route_of) sees.
 inline bool quantized(const ull_linear* L) { return L->format != ULL_WF_ELEM; }
 inline bool format_ok(const ull_linear* L) {
 #ifndef ULL_ELEM_F16
@@ -110,14 +111,16 @@ inline int gemv_qkv_rope_append(const void* x, int64_t ldx, const void* rms_w, f
     return FN(ull_gemv_qkv_rope_append_)(x, ldx, rms_w, eps, L->w, L->ldw, q, ldq, cs, sn, kc, vtc, B, S, H, hd, L->k, smax, past, stream);
 }
 
-// ops.linear for M <= 4 (decode steps), ops._linear_route: the skinny MFMA GEMM from M = 3 on against LLaMA-sized weights, the weight-streaming
-// GEMV otherwise; a preceding LlamaRMSNorm is fused into the GEMV where its LDS staging allows it and is a launch of its own otherwise.
+// ops.linear at the decode steps' shapes (weight-only: these entries never quantize activations): the rule's skinny MFMA GEMM or weight-streaming
+// GEMV; a preceding LlamaRMSNorm is fused into the GEMV or a launch of its own, as the rule says.
 inline int lin_decode(const void* x, int64_t ldx, const void* rms_w, float eps, void* xn_scratch, const ull_linear* L, void* out, int64_t ldc,
                       const void* R, int64_t ldr, int64_t M, int flags, void* stream) {
-    const bool skinny = M >= 3 && L->k % 32 == 0 && L->n * L->k >= ((int64_t)1 << 22) && ldw_of(L) % 8 == 0;
+    const ull_route::Route route = ull_route::route_of(M, L->n, L->k, ldw_of(L), L->format, ULL_AF_NONE, false, 0);
+    const bool skinny = route.kind == ULL_ROUTE_SKINNY;
+    if (!skinny && route.kind != ULL_ROUTE_GEMV) return ULL_ERR_SHAPE;
     if (bias_of(L)) flags |= ULL_EPI_BIAS;
     if (R) flags |= ULL_EPI_RESID;
-    if (rms_w && (skinny || !(L->k % 8 == 0 && M * L->k <= 16384))) {
+    if (rms_w && route.rms_first) {
         TRY(FN(ull_rmsnorm_)(x, ldx, rms_w, xn_scratch, L->k, M, L->k, eps, stream));
         x = xn_scratch;
         ldx = L->k;
@@ -208,7 +211,7 @@ int llama_decode_layers(const ull_llama_layer* layers, int64_t n_layers, const v
                         int64_t hd, int64_t I, int64_t smax, int64_t past, float eps, const void* zeros, void* stream) {
     if (!layers || !x_in || !x_out || !x_mid || !xn || !q || !att || !act || !rope_cos || !rope_sin || !zeros || n_layers <= 0) return ULL_ERR_ARG;
     const int64_t D = H * hd, T = B * S;
-    if (T > 4 || T <= 0 || past <= 0 || (hd & 1) || D % 8 || I <= 0 || I % 8 || T * D * 2 > 32768 || past + S > smax) return ULL_ERR_SHAPE;
+    if (T <= 0 || past <= 0 || !ull_route::decode_step_fused(T, D, hd) || I <= 0 || I % 8 || past + S > smax) return ULL_ERR_SHAPE;
     if (!cache_shape_ok(cache, S, past)) return ULL_ERR_ARG;
     for (int64_t l = 0; l < n_layers; ++l) {
         const ull_llama_layer& w = layers[l];

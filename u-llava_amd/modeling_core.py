@@ -957,9 +957,9 @@ class UllavaCoreForCausalLM(nn.Module):
         fuse_rope = hd == 128 and T > 4 and D % 64 == 0 and not (cache is not None and past > 0) and not f32
         # generation steps of at most 4 tokens (the GEMV shapes): RoPE and the cache append run in the q|k|v GEMV's epilogue, from the
         # same per-forward table
-        # (that kernel stages the T x D activations in 32 KB of LDS: LLaMA-7B at T = 4 is exactly the limit; wider models / more rows take the
+        # (that kernel stages the T x D activations in its LDS: LLaMA-7B at T = 4 is exactly the limit; wider models / more rows take the
         # stand-alone RMSNorm + RoPE-append kernels below)
-        fuse_append = cache is not None and past > 0 and T <= 4 and hd % 2 == 0 and D % 8 == 0 and T * D * 2 <= 32768 and not f32
+        fuse_append = cache is not None and past > 0 and not f32 and ops.decode_step_fused(T, D, hd)
         wq = pk.get("fp8", False) or pk.get("mxfp4", False)      # quantize_weights(): the Linear weights are ops.Fp8Weight / ops.Mxfp4Weight
         # quantize_weights(activations=, activation_scope=): the layer Linears hand the mode to the dispatch rule (ops.linear(act_quant=))
         aq = None

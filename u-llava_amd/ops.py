@@ -4,6 +4,7 @@ torch is used for device memory and streams only; every arithmetic op on the pat
 libullava_hip.so.  Activations are 16-bit (bf16 or fp16: every kernel exists in both builds, picked by the dtype of the op's first
 operand; the other operands must match), row-major, last dim contiguous.
 """
+import functools
 import weakref
 from typing import NamedTuple, Optional
 
@@ -425,32 +426,24 @@ class ActQuant(NamedTuple):
     decode: bool = False
 
 
-_A8_GEMM = {("fp8", "fp8_e4m3"): "a8w8", ("mxfp4", "mxfp8_e4m3"): "w4a8"}      # (weight format, activation format) -> route of the pair
-A8W8_BK = 128                 # K-tile of the A8 kernels (one block-scaled matrix instruction)
-A8W8_SKINNY_MAX_M = 32        # ull_gemm_skinny_a8w8_bf16: two 16-row activation fragments
+A8W8_BK, A8W8_SKINNY_MAX_M = _D["ULL_A8W8_BK"], _D["ULL_A8W8_SKINNY_MAX_M"]
+_ROUTES = {_D["ULL_ROUTE_" + r.upper()]: r for r in ("gemm", "gemv", "skinny", "a8w8", "w4a8", "a8w8_skinny")}
+_WF = {None: _lib.WF_ELEM, "fp8": _lib.WF_FP8, "mxfp4": _lib.WF_MXFP4}
+_AF = {"fp8_e4m3": _D["ULL_AF_FP8"], "mxfp8_e4m3": _D["ULL_AF_MXFP8"]}
 
 
+# The rule itself is csrc/linear_route.h, which the library's own callers (the coarse entries among them) apply; the three functions below ask
+# the library once per distinct shape and keep the answer, so a warm path pays a dictionary hit, not a C call.
+@functools.lru_cache(maxsize=None)
 def _linear_route(M: int, N: int, K: int, ldw: int, tune: int, wfmt: Optional[str] = None, aq: Optional[ActQuant] = None):
     """(route, rms_first) of a Linear x [M, K] @ w.T, w [N, K] with row pitch ldw; wfmt: None for a 16-bit weight, else its `fmt_name`.
-    route "skinny": batched decode steps against LLaMA-sized weights put the weight stream on the matrix cores (the GEMV is FMA-bound from
-    M = 4 on and measured slower from M = 3 on (decode step at batch 3: 4.47 vs 4.24 ms; at batch 2 the GEMV wins, 4.00 vs 4.08); the tiled
-    GEMM's grid is a few dozen blocks at these M).  Small weights stay where they were.  "gemv": the weight-streaming GEMV at decode shapes
-    (no padding, no MFMA).  "gemm": the tiled GEMM.
-    aq on the weight format it pairs with (_A8_GEMM; any other pair is weight-only) quantizes the activations wherever the weight-only rule
-    says "gemm": "a8w8" (linear_a8w8) / "w4a8" (linear_w4a8), no dequantized weight.  aq.decode on fp8 weights adds "a8w8_skinny"
-    (linear_a8w8_skinny), ahead of everything else: the "skinny" size rule, starting above the 4 tokens the fused q|k|v + RoPE + cache-append
-    GEMV takes and extended to that kernel's 32 rows (so at 17 .. 32 rows it replaces "a8w8"), with K a whole number of 128-code K-tiles.
-    rms_first: a requested RMSNorm is a launch of its own ahead of the Linear; the GEMV fuses it into its prologue while the M x K
-    activations fit its LDS staging, "a8w8_skinny" into its row quantization.  csrc/layers.hip `lin_decode` mirrors the weight-only
-    "skinny" / "gemv" part of this rule for the coarse decode entries, which never take an activation-quantized route."""
-    a8 = None if aq is None else _A8_GEMM.get((wfmt, aq.fmt))
-    if a8 == "a8w8" and aq.decode and 5 <= M <= A8W8_SKINNY_MAX_M and K % A8W8_BK == 0 and N * K >= (1 << 22) and ldw % 8 == 0 and tune == 0:
-        return "a8w8_skinny", False
-    if 3 <= M <= 16 and K % 32 == 0 and N * K >= (1 << 22) and ldw % 8 == 0 and tune == 0:
-        return "skinny", True
-    if M <= 4 and K % 8 == 0:
-        return "gemv", M * K > 16384
-    return a8 or "gemm", True
+    route "gemm": the tiled GEMM; "gemv": the weight-streaming GEMV at decode shapes; "skinny": batched decode steps against LLaMA-sized
+    weights on the matrix cores; "a8w8" (linear_a8w8) / "w4a8" (linear_w4a8): quantized activations where aq pairs with the weight format and
+    the weight-only rule says "gemm"; "a8w8_skinny" (linear_a8w8_skinny): aq.decode on fp8 weights.
+    rms_first: a requested RMSNorm is a launch of its own ahead of the Linear (False: the route's kernel fuses it)."""
+    af = _D["ULL_AF_NONE"] if aq is None else _AF.get(aq.fmt, _D["ULL_AF_NONE"])
+    r = _lib.query("ull_linear_route", M, N, K, ldw, _WF[wfmt], af, bool(aq is not None and aq.decode), tune)
+    return _ROUTES[r & 255], bool(r >> 8)
 
 
 def linear_route(M: int, w, act_quant: Optional[ActQuant] = None) -> str:
@@ -465,25 +458,30 @@ w4a8_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("mxfp8_e4m3")) == "w
 a8w8_decode_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("fp8_e4m3", True)) == "a8w8_skinny"      # noqa: E731
 
 
+@functools.lru_cache(maxsize=None)
+def _gemm_plan(M: int, N: int, K: int, min_k: Optional[int], small_m: bool, small_m_split_k: bool):
+    """(big, split) of a tiled GEMM (ull_gemm_plan).  big: it takes its 256 x 256 kernel and the weight's tile-major copy; split: it gets the
+    workspace -- the stream-K tail of a big GEMM from K >= min_k on (None: never), or -- small_m: the kernel has the split, and
+    small_m_split_k is on -- the split-K of a small-M one."""
+    r = _lib.query("ull_gemm_plan", M, N, K, -1 if min_k is None else max(int(min_k), 0), small_m, small_m_split_k)
+    return bool(r & 1), bool(r & 2)
+
+
 def _big(M: int, N: int, K: int) -> bool:
-    """The tiled GEMM takes its 256 x 256 kernel, the weight's tile-major copy and (K >= streamk_min_k) the stream-K tail
-    (csrc/layers.hip `tiled` mirrors this and _gemm_ws's stream-K choice)."""
-    return M >= 1024 and N >= 512 and K >= 128
+    """`_gemm_plan`'s big, which depends on the shape alone."""
+    return _gemm_plan(M, N, K, None, False, False)[0]
+
+
+@functools.lru_cache(maxsize=None)
+def decode_step_fused(T: int, D: int, hd: int) -> bool:
+    """A generation step of T = B * S tokens at width D = H * hd runs RoPE and the cache append in the q|k|v GEMV's epilogue
+    (linear_qkv_rope_append; the shape check of the coarse decode entry)."""
+    return bool(_lib.query("ull_decode_step_fused", T, D, hd))
 
 
 def _gemm_ws(device: torch.device, stream_id: int, big: bool, M: int, N: int, K: int, small_m: bool):
-    """(pointer, bytes) of the fp32 workspace a tiled GEMM splits K into, or (None, 0): the stream-K tail of a big GEMM, or -- small_m: the
-    kernel has the split, and small_m_split_k is on -- the split-K of a small-M one."""
-    min_k = _SK_MIN_K[0]
-    if min_k is None:
-        return None, 0
-    if big:
-        split = K >= min_k
-    else:
-        # opt-in latency mode (small_m_split_k): few 128x128 tiles, a long K and a weight of at least 8 MB (single-image prefill: o_proj /
-        # down_proj, CLIP's fc2): the kernel splits K over the idle CUs (376 -> 256 us per LLaMA layer at M = 323)
-        split = small_m and _SMALL_M_SPLIT_K[0] and K >= 1024 and M >= 128 and N * K >= (1 << 22) and -(-M // 128) * -(-N // 128) <= 256
-    if not split:
+    """(pointer, bytes) of the fp32 workspace the tiled GEMM of `_gemm_plan` splits K into, or (None, 0).  big: `_big(M, N, K)`."""
+    if not _gemm_plan(M, N, K, _SK_MIN_K[0], small_m, _SMALL_M_SPLIT_K[0])[1]:
         return None, 0
     ws = _streamk_ws(device, stream_id)
     return ws.data_ptr(), ws.numel()
@@ -1950,8 +1948,8 @@ def sumsq(g: torch.Tensor, out: torch.Tensor) -> None:
 # ---- coarse entries (include/ullava_hip.h "coarse entries", csrc/layers.hip): one C call enqueues a whole stack of layers ---------------------
 # The per-op wrappers above cost a ctypes round trip + Python marshalling per LAUNCH (~15 us); a C4 step has ~400 launches, a decode step ~160.
 # A LayerStack holds the ctypes array of per-layer structs (weight / bias / norm pointers) and refreshes it when a pointer it recorded has
-# moved (a re-made tile-major copy after an optimizer step, a re-pack).  Results are bit-identical to the per-op path: same entries, same
-# dispatch rules (layers.hip `lin_decode` mirrors the weight-only decode part of `_linear_route`, `tiled` mirrors `_big` and the stream-K tail of `_gemm_ws`).
+# moved (a re-made tile-major copy after an optimizer step, a re-pack).  Results are bit-identical to the per-op path: same entries, and
+# the one dispatch rule (csrc/linear_route.h), which layers.hip applies directly and `_linear_route` / `_gemm_plan` read from the library.
 COARSE = [True]     # `with ops.per_op_layers():` = the per-op path (tests A/B the two)
 
 
