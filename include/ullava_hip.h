@@ -256,6 +256,40 @@ int ull_quantize_rows_mxfp8_bf16(const void* X, int64_t ldx, int64_t M, int64_t 
 int ull_gemm_w4a8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, int64_t ldxs, const void* Q, int64_t ldq, const void* w_scales,
                        int64_t lds, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
 
+/* ---- MXFP4 activations on MXFP4 weights: the W4A4 prefill Linear (bf16 build only: no *_f16 twins) ------------------------------------
+ * UllavaCoreForCausalLM.quantize_weights("mxfp4", activations="mxfp4_e2m1"): at prefill shapes the four LLaMA-layer Linears quantize their
+ * input rows to OCP MXFP4 and multiply them by the resident MXFP4 weight on the block-scaled matrix instruction
+ * (v_mfma_scale_f32_16x16x128_f8f6f4 cbsz:4 blgp:4: e2m1 for both operands, one E8M0 scale per operand, row and 32 K elements).
+ * For x [M, K] @ w^T, w in MXFP4 with codes wq and scales 2^s[n, j] (j = the blocks of 32 consecutive K elements):
+ *   1. xq, t = quantize_rows_mxfp4(x): the weights' own rule (the MXFP4 section above) per activation row m and block j: t[m, j] is the
+ *      smallest integer with amax|block| * 2^-t <= 6 (an all-zero block: 0), clamped to [-125, 126] and stored as the byte t + 127;
+ *      xq = e2m1(x * 2^-t), round to nearest, ties to the even code (at t = 126 saturating at the code of 3, as the weights do) -- bit for
+ *      bit what ull_quantize_rows_mxfp4_bf16 gives on the same rows.
+ *   2. y[m, n] = sum_j 2^(t[m, j] + s[n, j]) * sum_{k in block j} e2m1(xq[m, k]) * e2m1(wq[n, k]).  Every product is exact in fp32 (4
+ *      significant bits, power-of-two scales, applied by the instruction's two scale operands); the accumulation is fp32 in one fixed K
+ *      order that depends on K alone -- not on M, N, the batch or the grid -- and is W4A8's: whole 2048-element superblocks first, inside
+ *      superblock b the 128-element K-tiles in the order b * 2048 + g * 512 + t * 128 with t = 0 .. 3 outer and g = 0 .. 3 inner, then the
+ *      K-tiles after the last whole superblock ascending; K is never split.  The definition covers inputs whose scaled terms
+ *      2^(t + s) * xq * wq are normal floats or zero; what the instruction does with subnormal terms is not specified here.
+ *   3. ull_gemm_bf16's epilogue on y with its rounding points (no scaling is left to the epilogue).
+ * ull_quantize_act_rows_mxfp4_bf16: X [M, K] bf16 (row pitch ldx elements, 16-byte aligned rows), K % 32 == 0; codes: K / 2 bytes per row
+ * (row pitch ldq bytes >= K / 2 and a multiple of 4, pointer 4-byte aligned), scales: one byte per (row, block), row pitch lds >= K / 32
+ * (ULL_ERR_SHAPE otherwise).  layout 0: the standard layout (element 2i in the low nibble of byte i, scales in block order) -- the bytes of
+ * ull_quantize_rows_mxfp4_bf16 with resident = 0.  layout 1: the bytes ull_gemm_w4a4_bf16 reads, private to this pair of entries: the 64 code
+ * bytes of each 128-element K-tile stay together in standard order and the K-TILES are stored in the order the GEMM visits them -- inside
+ * whole superblock b the tile at element b * 2048 + g * 512 + t * 128 at byte b * 1024 + (4 t + g) * 64, tiles after the last whole superblock
+ * at their standard place -- and the scale byte of block j sits where the resident MXFP4 layout puts it (as ull_quantize_rows_mxfp8_bf16's).
+ * Any other layout: ULL_ERR_ARG.  Bytes of a row that belong to no block are not written.
+ * ull_gemm_w4a4_bf16: ull_gemm_w4a8_bf16's contract with (Xq, ldxq, x_scales, ldxs) from the quantizer above in layout 1 (ldxq >= K / 2):
+ * code pitches multiples of 16 bytes and base pointers 16-byte aligned, scale pitches multiples of 4 bytes >= K / 32 and scale pointers
+ * 4-byte aligned, K % 128 == 0, every operand below 2 GiB.  flags: ULL_EPI_RESID, ULL_EPI_SWIGLU (Q rows in the gate|up interleave,
+ * N % 32 == 0), ULL_EPI_OUT_F32 only -- any other bit, or a null pointer: ULL_ERR_ARG; a shape or alignment it cannot take: ULL_ERR_SHAPE;
+ * nothing is launched in either case. */
+int ull_quantize_act_rows_mxfp4_bf16(const void* X, int64_t ldx, int64_t M, int64_t K, void* codes, int64_t ldq, void* scales, int64_t lds,
+                                     int layout, void* stream);
+int ull_gemm_w4a4_bf16(const void* Xq, int64_t ldxq, const void* x_scales, int64_t ldxs, const void* Q, int64_t ldq, const void* w_scales,
+                       int64_t lds, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
+
 /* ---- FP8 (e4m3) KV cache (bf16 build only) ------------------------------------------------------------------------------------------
  * KVCache(kv_dtype="fp8_e4m3") keeps, per layer, K codes [B, H, smax, hd] and V^T codes [B, H, hd, smax] (the key-permuted slot order of
  * ull_transpose_v) plus one fp32 scale 2^s per (batch, head, position) for the K row (k_scale [B, H, smax], by key) and one for the V column
@@ -747,10 +781,12 @@ int ull_sumsq_f32(const void* g, int grad_dtype, int64_t n, void* out, void* str
 #define ULL_ROUTE_A8W8 3        /* ull_gemm_a8w8_bf16 */
 #define ULL_ROUTE_W4A8 4        /* ull_gemm_w4a8_bf16 */
 #define ULL_ROUTE_A8W8_SKINNY 5 /* ull_gemm_skinny_a8w8_bf16 */
-/* activation quantization asked of the Linear: it takes effect only on the weight format it pairs with (fp8 + FP8, mxfp4 + MXFP8) */
+#define ULL_ROUTE_W4A4 6        /* ull_gemm_w4a4_bf16 */
+/* activation quantization asked of the Linear: it takes effect only on the weight format it pairs with (fp8 + FP8, mxfp4 + MXFP8 or MXFP4) */
 #define ULL_AF_NONE 0
 #define ULL_AF_FP8 1   /* one power-of-two scale per token (ull_quantize_rows_fp8_bf16) */
 #define ULL_AF_MXFP8 2 /* one E8M0 scale per block of 32 (ull_quantize_rows_mxfp8_bf16) */
+#define ULL_AF_MXFP4 3 /* e2m1 codes, one E8M0 scale per block of 32 (ull_quantize_act_rows_mxfp4_bf16) */
 #define ULL_A8W8_BK 128          /* K-tile of the A8 kernels: one block-scaled matrix instruction */
 #define ULL_A8W8_SKINNY_MAX_M 32 /* ull_gemm_skinny_a8w8_bf16: two 16-row activation fragments */
 /* ULL_ROUTE_* in the low byte; bit 8: a LlamaRMSNorm asked in front of the Linear is a launch of its own (clear: the route's kernel fuses it).

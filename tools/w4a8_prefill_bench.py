@@ -1,23 +1,24 @@
 #!/usr/bin/env python
-"""MXFP8-activation (W4A8) prefill on MXFP4 weights against the bf16 model, the weight-only mxfp4 model (dequantize + bf16 GEMM: the yardstick)
+"""MXFP8-activation (W4A8) and MXFP4-activation (W4A4) prefill on MXFP4 weights against the bf16 model, the weight-only mxfp4 model (dequantize + bf16 GEMM: the yardstick)
 and the W8A8 Linear, in ONE process on the same random-init LLaMA-7B weights.  Arms, interleaved round by round:
 
     bf16   the bf16 model
     w4a16  quantize_weights("mxfp4"): every prefill Linear dequantizes its weight into a scratch and runs the bf16 GEMM
     w8a8   ops.linear_a8w8 on the fp8-quantized weight (layer launches only)
     w4a8   quantize_weights("mxfp4", activations="mxfp8_e4m3"): ops.linear_w4a8 (block quantization + the block-scaled matrix instruction)
+    w4a4   quantize_weights("mxfp4", activations="mxfp4_e2m1"): ops.linear_w4a4 (the same with e2m1 activations; its yardstick is w4a8)
 
 Measured: the four LLaMA-layer launches (q|k|v, o_proj + residual, gate|up + SwiGLU, down_proj + residual) and the whole 32-layer LLaMA
 prefill (`_llama` on random embeddings: no CLIP, no lm_head), at the C4 shape (batch 32, S = 643) and at batch 1, and the memory the mxfp4
 model holds.  The w4a8 launch time is given with the activation quantization included (what the model pays) and excluded (included minus
-the separately timed quantize launch).  Times are device-event medians over --reps rounds after --warmup rounds, with min and max.
+the separately timed quantize launch); the same for w4a4.  Times are device-event medians over --reps rounds after --warmup rounds, with min and max.
 Decode: ms per greedy decode step of the whole model (64-token prompt + one image, batch 1 and 16) with the mode off (the parent's mxfp4
 model) and on, interleaved; the decode launches are the same W4A16 kernels in both.
 
-    python tools/w4a8_prefill_bench.py [--reps 7] [--warmup 2] [--accuracy] > profiles/w4a8_prefill.txt
+    python tools/w4a8_prefill_bench.py [--reps 7] [--warmup 2] [--accuracy] > profiles/w4a4_prefill.txt
 
 --accuracy adds, on the committed full-depth samples (tests/golden/g15_c1_full_depth_bf16.pt), the logit error against the reference and the
-greedy-token agreement at the margin-gated positions for bf16 / w4a16 / w4a8 (builds the fixture's seeded weights on the host first: minutes).
+greedy-token agreement at the margin-gated positions for bf16 / w4a16 / w4a8 / w4a4 (builds the fixture's seeded weights on the host first: minutes).
 """
 import argparse
 import importlib
@@ -83,15 +84,20 @@ def layer_launches(M):
         with torch.no_grad():
             r = timed({"bf16": lambda: ops.linear(x, w, out=out, **args), "w4a16": lambda: ops.linear(x, q4, out=out, **args),
                        "w8a8": lambda: ops.linear_a8w8(x, q8, out=out, **args), "w4a8": lambda: ops.linear_w4a8(x, q4, out=out, **args),
-                       "quantize": lambda: ops._quantize_rows_mxfp8(x, K)}, a.reps, a.warmup)
+                       "quantize": lambda: ops._quantize_rows_mxfp8(x, K), "w4a4": lambda: ops.linear_w4a4(x, q4, out=out, **args),
+                       "quantize4": lambda: ops._quantize_rows_mxfp4(x, K, 1)}, a.reps, a.warmup)
         flop = 2.0 * M * N * K
         excl = r["w4a8"][0] - r["quantize"][0]
+        excl4 = r["w4a4"][0] - r["quantize4"][0]
         print(f"{name:22s} [{M} x {K}] @ [{N} x {K}]^T")
-        for k in ("bf16", "w4a16", "w8a8", "w4a8"):
+        for k in ("bf16", "w4a16", "w8a8", "w4a8", "w4a4"):
             print(f"    {k:6s} {fmt(r[k])}  {flop / r[k][0] / 1e9:7.1f} TFLOP/s")
         print(f"    w4a8 without the activation quantization ({r['quantize'][0]:.3f} ms): {excl:8.3f} ms  {flop / excl / 1e9:7.1f} TFLOP/s;"
               f"  w4a8 / bf16 = {r['w4a8'][0] / r['bf16'][0]:.3f} (incl.), {excl / r['bf16'][0]:.3f} (excl.);  w4a8 / w4a16 = {r['w4a8'][0] / r['w4a16'][0]:.3f};"
               f"  w4a8 / w8a8 = {r['w4a8'][0] / r['w8a8'][0]:.3f}")
+        gain = "faster, ranges apart" if r["w4a4"][2] < r["w4a8"][1] else "slower, ranges apart" if r["w4a4"][1] > r["w4a8"][2] else "ranges overlap"
+        print(f"    w4a4 without the activation quantization ({r['quantize4'][0]:.3f} ms): {excl4:8.3f} ms  {flop / excl4 / 1e9:7.1f} TFLOP/s;"
+              f"  w4a4 / w4a8 = {r['w4a4'][0] / r['w4a8'][0]:.3f} (incl.: {gain}), {excl4 / excl:.3f} (excl.);  w4a4 / bf16 = {r['w4a4'][0] / r['bf16'][0]:.3f}")
         ops.unregister_tiled(w)
         del w, q8, q4, x, out, args
 
@@ -108,16 +114,17 @@ def whole_prefill(models, B, S=643):
             with torch.no_grad():
                 m._llama(emb, mask, None, False)
         return f
-    r = timed({"bf16": arm(m16, None), "w4a16": arm(m4, None), "w4a8": arm(m4, "mxfp8_e4m3")}, a.reps, a.warmup)
+    r = timed({"bf16": arm(m16, None), "w4a16": arm(m4, None), "w4a8": arm(m4, "mxfp8_e4m3"), "w4a4": arm(m4, "mxfp4_e2m1")}, a.reps, a.warmup)
     m4.activation_quantization = None
     print(f"-- whole LLaMA prefill (32 layers + final norm), batch {B} x S = {S}  ({B * S} tokens)")
-    for k in ("bf16", "w4a16", "w4a8"):
+    for k in ("bf16", "w4a16", "w4a8", "w4a4"):
         print(f"    {k:6s} {fmt(r[k])}  {B * S / r[k][0]:9.1f} tokens/ms")
-    print(f"    w4a8 / bf16 = {r['w4a8'][0] / r['bf16'][0]:.3f};  w4a8 / w4a16 = {r['w4a8'][0] / r['w4a16'][0]:.3f}")
+    print(f"    w4a8 / bf16 = {r['w4a8'][0] / r['bf16'][0]:.3f};  w4a8 / w4a16 = {r['w4a8'][0] / r['w4a16'][0]:.3f};  "
+          f"w4a4 / w4a8 = {r['w4a4'][0] / r['w4a8'][0]:.3f};  w4a4 / bf16 = {r['w4a4'][0] / r['bf16'][0]:.3f}")
 
 
 def accuracy():
-    """bf16 / w4a16 / w4a8 on the G15 samples: max logit error / max|truth| on the committed rows, and token agreement where the fp32 margin
+    """bf16 / w4a16 / w4a8 / w4a4 on the G15 samples: max logit error / max|truth| on the committed rows, and token agreement where the fp32 margin
     clears 4 sigma of the reference's own 16-bit noise."""
     from concurrent.futures import ThreadPoolExecutor
     C, MC, W = importlib.import_module("u-llava_amd.configuration"), importlib.import_module("u-llava_amd.modeling_core"), \
@@ -161,6 +168,8 @@ def accuracy():
         report("w4a16")
         model.quantize_weights("mxfp4", activations="mxfp8_e4m3")
         report("w4a8")
+        model.quantize_weights("mxfp4", activations="mxfp4_e2m1")
+        report("w4a4")
     del model
     torch.cuda.empty_cache()
 
@@ -171,7 +180,7 @@ def decode(m4, cfg):
     for B in (1, 16):
         images, ids = bench.make_inputs(cfg, B, 64, dev, B)[:2]
         kw = dict(input_ids=ids, images=images, do_sample=False, use_cache=True, eos_token_id=-1)
-        ts = {None: [], "mxfp8_e4m3": []}
+        ts = {None: [], "mxfp8_e4m3": [], "mxfp4_e2m1": []}
         with torch.no_grad():
             for act in ts:
                 m4.activation_quantization = act

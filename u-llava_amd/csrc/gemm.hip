@@ -922,6 +922,233 @@ __global__ __launch_bounds__(256, 2) void gemm128_w4a8_kernel(GemmArgs p, W4A8Ar
     __builtin_amdgcn_s_barrier();                          // every wave has consumed the last K-tile: LDS is free
     staged_epilogue<SWIGLU, 4>(p, acc, smem + wave * (64 * 144), lane, m0 + wm * 64, n0 + wn * 64);
 }
+
+// ---- W4A4: MXFP4 activations x resident MXFP4 weights on the block-scaled matrix instruction (ull_gemm_w4a4_bf16, bf16 build only) --------
+// y[m, n] = sum_j 2^(t[m, j] + s[n, j]) * sum_{k in block j} e2m1(xq[m, k]) * e2m1(wq[n, k]) (include/ullava_hip.h).  Both operands have format
+// code 4 (cbsz:4 blgp:4): each is 16 bytes in the first 4 of its 8 registers, lane l feeding row (l & 15) and the 32 codes of block (l >> 4)
+// of the K-tile, element 2i in the low nibble of byte i, and the E8M0 byte of that (row, block) is the lane's scale (the byte select picks it
+// from the scale register) -- measured for the second operand too: tools/probes/mfma_scale_w4a4_lane_map.hip,
+// profiles/mfma_scale_w4a4_lane_map.txt.
+//
+// The activation bytes are private to ull_quantize_act_rows_mxfp4_bf16 (layout 1) and this kernel: the 64 code bytes of a 128-element K-tile
+// stay together in standard order, and the K-TILES of a row are stored in the order the kernel visits them -- inside whole superblock b the
+// tile at element b*2048 + g*512 + t*128 sits at byte b*1024 + (4t + g) * 64 (mxa_code_pos), tiles after the last whole superblock at their
+// standard place -- so step s of the K loop reads the 64 bytes at s * 64 of every row.  The scale bytes sit where the resident weight layout
+// puts them (mx_scale_pos), as W4A8's do: one rule addresses both scale operands.
+ULL_DEV long mxa_code_pos(int c, int nsb) {                // byte offset in the activation row of chunk c's 4 code bytes (c = 8 elements)
+    const int kt = c >> 4;                                 // the 128-element K-tile
+    if (kt >= nsb * 16) return (long)c * 4;
+    return (long)((kt & ~15) + ((kt & 3) << 2) + ((kt >> 2) & 3)) * 64 + (c & 15) * 4;
+}
+
+// ull_quantize_act_rows_mxfp4_bf16: the weights' own rule (mxfp4_scale_exp / mxfp4_code) per activation row and block; one row per wave, a lane
+// owns 8 consecutive elements (one 16-byte load), the four lanes of a 32-block share its amax through two xor-shuffles, and each lane writes
+// its 4 code bytes.  layout 0: standard code order, scales in block order; 1: what gemm128_w4a4_kernel reads.
+__global__ __launch_bounds__(256) void quantize_act_rows_mxfp4_kernel(const elem_t* __restrict__ X, long ldx, int M, int K, uint8_t* __restrict__ codes,
+                                                                      long ldq, uint8_t* __restrict__ scales, long lds, int layout) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const elem_t* x = X + (long)row * ldx;
+    uint8_t* q = codes + (long)row * ldq;
+    uint8_t* sc = scales + (long)row * lds;
+    const int nchunk = K >> 3, nsb = layout ? K >> 11 : 0;
+    for (int c0 = 0; c0 < nchunk; c0 += 64) {              // K % 32 == 0: the four lanes of a block are in or out together
+        const int c = c0 + lane;
+        const bool on = c < nchunk;
+        float v[8];
+        unpack8(on ? *(const uint4*)(x + c * 8) : make_uint4(0, 0, 0, 0), v);
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+        amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+        if (!on) continue;
+        const int t = mxfp4_scale_exp(amax);
+        uint32_t code = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) code |= mxfp4_code(ldexpf(v[j], -t), t == 126 ? 5u : 7u) << (4 * j);     // exact, or below a quarter of the smallest step
+        *(uint32_t*)(q + mxa_code_pos(c, nsb)) = code;
+        if ((c & 3) == 0) sc[mx_scale_pos(c >> 2, nsb)] = (uint8_t)(t + 127);
+    }
+}
+
+// gemm128_w4a4_kernel is gemm128_w4a8_kernel with a 4-bit second operand.  The weight side is that kernel's, unchanged: super tile (b, t) =
+// 256 contiguous resident bytes per row, a 128-row x 256-byte LDS image with the piece index XOR-swizzled by (row & 15), 16-byte LDS-DMA, the
+// four steps g = 0 .. 3 served by register selection, the aligned scale dword with the byte select, standard-order tail tiles after the last
+// whole superblock (global -> registers one step ahead).  The K order is W4A8's (fixed by K alone; never split): b, t, g ascending = the
+// activation K-tiles b*2048 + g*512 + t*128, then the tail ascending.
+// The activation side: a K-tile is 64 bytes per row, so a step's tile is 128 rows x 64 bytes = 8 KiB, two of them double-buffered (the 16 KiB
+// in front of the weight image; LDS in use: 48 KiB of the GEMM's 64, the epilogue staging reuses it).  One DMA instruction fills 16 rows
+// (lane -> row l >> 2, physical piece l & 3, fetching logical piece (l & 3) ^ ((row >> 2) & 3)); wave w fills rows [32 w, 32 w + 32) with 2
+// instructions.  A lane's fragment is ONE 16-byte LDS read: row 16 j + (l & 15), logical piece (l >> 4); the 16 lanes of a group read 16
+// different 16-byte slots of a 256-byte bank row ((row & 3) * 4 + (piece ^ (row >> 2))), the wave 1 KiB without a conflict.
+// Schedule and counted waits are gemm128_w4a8_kernel's: requests retire in order; every step waits for everything except step 2 of a super
+// tile that has a successor, where the 8 image requests of step 1 -- the youngest -- may stay in flight behind this step's 2 activation
+// requests (vmcnt(8)).  The image is in flight for two steps.
+template <bool SWIGLU>
+__global__ __launch_bounds__(256, 2) void gemm128_w4a4_kernel(GemmArgs p, W4A8Args q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = wave & 1, wm = wave >> 1;
+
+    const TileRaster t = raster128(p);
+    const int m0 = t.bm * BM, n0 = t.bn * BN;
+
+    constexpr int XT = BM * 64;                        // one activation K-tile: 8 KiB
+    constexpr int WOFF = 2 * XT;
+    static_assert(WOFF + BN * 256 <= GEMM_LDS, "two activation tiles and one super tile of weights fit the GEMM's LDS");
+    // every global address is a wave-uniform base plus a 32-bit lane offset (the entry refuses operands of 2 GiB and more)
+    uint32_t xsrc[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+        xsrc[i] = (uint32_t)min(m0 + wave * 32 + i * 16 + (lane >> 2), p.M - 1) * (uint32_t)q.ldxq + (((lane & 3) ^ ((lane >> 4) & 3)) << 4);
+    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
+    auto stage = [&](int buf, int step) {              // the activation K-tile of step `step`: bytes [step * 64, +64) of every row
+        const uint32_t bx = lds_base + buf * XT + wave * 2048;
+        const uint8_t* src = q.Xq + (long)step * 64;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) glds16s(src, xsrc[i], bx + i * 1024);
+    };
+    // weight image of super tile (b, t): as in gemm128_w4a8_kernel
+    auto stage_w = [&](int st) {
+        const uint8_t* src = q.Wq + ((long)(st >> 2) * 1024 + (st & 3) * 256);
+        const uint32_t bw = lds_base + WOFF + wave * 8192;
+        int l = lane;
+        asm volatile("" : "+v"(l));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int row = wave * 32 + i * 4 + (l >> 4);
+            glds16s(src, (uint32_t)min(n0 + row, p.N - 1) * (uint32_t)q.ldq + (((l & 15) ^ (row & 15)) << 4), bw + i * 1024);
+        }
+    };
+
+    const int frow = lane & 15, fgrp = lane >> 4;
+    const int xread = (wm * 64 + frow) * 64 + ((fgrp ^ (frow >> 2)) << 4);         // + j * 1024: row 16 j + frow, logical piece fgrp
+    const int wread = WOFF + (wn * 64 + frow) * 256;
+    int wpo[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) wpo[c] = ((4 * fgrp + c) ^ frow) << 4;
+    uint32_t wrow[4], wsrow[4], xsrow[4];              // the lane's weight rows (tail tiles) / scale rows (rows past N / M re-read the last row)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t n = min(n0 + wn * 64 + i * 16 + frow, p.N - 1), m = min(m0 + wm * 64 + i * 16 + frow, p.M - 1);
+        wrow[i] = n * (uint32_t)q.ldq + fgrp * 16;
+        wsrow[i] = n * (uint32_t)q.lds;
+        xsrow[i] = m * (uint32_t)q.ldxs;
+    }
+
+    f32x4_t acc[4][4];
+    tile128_clear(acc);
+
+    const int nk = p.K / BK8;
+    const int nsup = (p.K >> 11) * 4;                  // super tiles; steps [0, 4 nsup) walk them, steps [4 nsup, nk) the standard-order tail
+    auto xfrag = [&](const char* base, int j) {
+        const uint4 v = *(const uint4*)(base + xread + j * 1024);
+        return i32x8_t{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+    };
+
+    u32x4_t wc[4][4], wnx[4];                           // [i][c]: the lane's four pieces of the super tile; the next tail tile's fragments
+    uint32_t wsc[4], xsc[4], wscn[4], xscn[4];         // scale registers (four bytes: steps g = 0 .. 3), current and next
+    auto load_scales = [&](int st, uint32_t (&a)[4], uint32_t (&b)[4]) {      // the aligned dword at scale byte b*64 + (4t + fgrp) * 4
+        const long so = (long)(st >> 2) * 64 + (st & 3) * 16;
+        const uint8_t* wsb = q.ws + so;                        // wave-uniform bases, 32-bit lane offsets
+        const uint8_t* xsb = q.xs + so;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            a[i] = *(const uint32_t*)(wsb + (uint32_t)(wsrow[i] + fgrp * 4));
+            b[i] = *(const uint32_t*)(xsb + (uint32_t)(xsrow[i] + fgrp * 4));
+        }
+    };
+    auto load_tail = [&](int kt, u32x4_t (&w)[4], uint32_t (&a)[4], uint32_t (&b)[4]) {       // 16 code bytes and one scale byte per lane
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            w[i] = *(const u32x4_t*)(q.Wq + (long)kt * 64 + wrow[i]);
+            a[i] = (q.ws + kt * 4)[wsrow[i] + fgrp];
+            b[i] = (q.xs + kt * 4)[xsrow[i] + fgrp];
+        }
+    };
+
+    int s = 0;
+    if (nsup) { stage_w(0); load_scales(0, wscn, xscn); }
+    else load_tail(0, wnx, wscn, xscn);
+    stage(0, 0);
+    for (int st = 0; st < nsup; ++st) {
+        auto step = [&](auto G) {
+            constexpr int g = decltype(G)::value;
+            // step 2 of a super tile that has a successor: outstanding are this step's 2 activation requests and, younger, the 8 image
+            // requests of step 1, which may stay in flight.  Every other step waits for everything (in the last super tile nothing follows
+            // the activation requests, so a counted wait would let them through)
+            if (g == 2 && st + 1 < nsup) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                      // this step's activation tile is in LDS for every wave; the other buffer is free
+            if (s + 1 < nk) stage((s + 1) & 1, s + 1);
+            if constexpr (g == 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) wc[i][c] = *(const u32x4_t*)(smem + wread + i * 4096 + wpo[c]);
+                    wsc[i] = wscn[i]; xsc[i] = xscn[i];
+                }
+                load_scales(min(st + 1, nsup - 1), wscn, xscn);    // (the last super tile re-reads its own: one path, no copies)
+            }
+            if constexpr (g == 1) {
+                if (st + 1 < nsup) stage_w(st + 1);                // every wave has read the image: the next one, 8 requests, the youngest
+            }
+            const char* base = smem + (s & 1) * XT;
+            i32x8_t xf[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xf[j] = xfrag(base, j);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const i32x8_t wf{(int)wc[i][0][g], (int)wc[i][1][g], (int)wc[i][2][g], (int)wc[i][3][g], 0, 0, 0, 0};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)   // cbsz = blgp = 4: e2m1 A and B; scale byte g of both registers
+                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf, xf[j], acc[i][j], 4, 4, g, (int)wsc[i], g, (int)xsc[j]);
+            }
+            // keep a step's matrix instructions in the step (see gemm128_w4a8_kernel)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(acc[i][j]));
+            ++s;
+        };
+        step(std::integral_constant<int, 0>{});
+        step(std::integral_constant<int, 1>{});
+        step(std::integral_constant<int, 2>{});
+        step(std::integral_constant<int, 3>{});
+    }
+    if (nsup && s < nk) load_tail(s, wnx, wscn, xscn);         // the first tail tile after superblocks (waited for at the top of its step)
+    for (; s < nk; ++s) {                                      // standard-order tail: weights global -> registers one step ahead, scale byte 0
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        u32x4_t wt[4];
+        uint32_t a0[4], b0[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { wt[i] = wnx[i]; a0[i] = wscn[i]; b0[i] = xscn[i]; }
+        if (s + 1 < nk) {
+            stage((s + 1) & 1, s + 1);
+            load_tail(s + 1, wnx, wscn, xscn);
+        }
+        const char* base = smem + (s & 1) * XT;
+        i32x8_t xf[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xf[j] = xfrag(base, j);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const i32x8_t wf{(int)wt[i][0], (int)wt[i][1], (int)wt[i][2], (int)wt[i][3], 0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf, xf[j], acc[i][j], 4, 4, 0, (int)a0[i], 0, (int)b0[j]);
+        }
+    }
+
+    // acc[i][j][r] = D[n = n0 + wn*64 + i*16 + 4*(l>>4) + r][m = m0 + wm*64 + j*16 + (l&15)], scales already applied by the instruction
+    __builtin_amdgcn_s_barrier();                          // every wave has consumed the last K-tile: LDS is free
+    staged_epilogue<SWIGLU, 4>(p, acc, smem + wave * (64 * 144), lane, m0 + wm * 64, n0 + wn * 64);
+}
 #endif  // !ULL_ELEM_F16
 
 
@@ -1828,6 +2055,7 @@ static int gemm_device_state(int* n_cu_out) {
 #ifndef ULL_ELEM_F16
         {(const void*)gemm128_a8w8_kernel<false>, GEMM_LDS}, {(const void*)gemm128_a8w8_kernel<true>, GEMM_LDS},
         {(const void*)gemm128_w4a8_kernel<false>, GEMM_LDS}, {(const void*)gemm128_w4a8_kernel<true>, GEMM_LDS},
+        {(const void*)gemm128_w4a4_kernel<false>, GEMM_LDS}, {(const void*)gemm128_w4a4_kernel<true>, GEMM_LDS},
 #endif
         {(const void*)big::patchify_strip_kernel<9>, 2 * (288 + 256) * 128 + 256},
         {(const void*)big::patchify_strip_kernel<4>, 2 * (128 + 256) * 128 + 256},
@@ -2046,6 +2274,46 @@ extern "C" int ull_gemm_w4a8_bf16(const void* Xq, int64_t ldxq, const void* x_sc
         hipLaunchKernelGGL(gemm128_w4a8_kernel<true>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
     else
         hipLaunchKernelGGL(gemm128_w4a8_kernel<false>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
+    return ull_check_launch();
+}
+
+// MXFP4 quantization of activation rows X [M, K] (bf16, row pitch ldx elements; K % 32 == 0) with the weights' rule: e2m1 codes [M, K / 2] (row
+// pitch ldq bytes) and one E8M0 byte per row and block.  layout 0: the standard layout (what ull_quantize_rows_mxfp4_bf16 writes with
+// resident = 0); 1: what ull_gemm_w4a4_bf16 reads (K-tiles in visiting order, mxa_code_pos; scale bytes at mx_scale_pos).  Bytes of a row that
+// belong to no block are left as they are.
+extern "C" int ull_quantize_act_rows_mxfp4_bf16(const void* X, int64_t ldx, int64_t M, int64_t K, void* codes, int64_t ldq, void* scales, int64_t lds,
+                                                int layout, void* stream) {
+    if (!X || !codes || !scales || M <= 0 || K <= 0 || (layout != 0 && layout != 1)) return ULL_ERR_ARG;
+    if ((K & 31) || (ldx & 7) || ldx < K || ldq < K / 2 || (ldq & 3) || lds < K / 32 || M > (1 << 28) || K > (1 << 30) ||
+        (((uintptr_t)X & 15) | ((uintptr_t)codes & 3)))
+        return ULL_ERR_SHAPE;
+    hipLaunchKernelGGL(quantize_act_rows_mxfp4_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const elem_t*)X, (long)ldx,
+                       (int)M, (int)K, (uint8_t*)codes, (long)ldq, (uint8_t*)scales, (long)lds, layout);
+    return ull_check_launch();
+}
+
+// W4A4 Linear (bf16 build only): C[M, N] = epilogue(sum_j 2^(t[m, j] + s[n, j]) * sum_{k in block j} e2m1(Xq[m, k]) * e2m1(Q[n, k])) with
+// (Xq, x_scales) from ull_quantize_act_rows_mxfp4_bf16 (layout 1) and (Q, w_scales) a resident MXFP4 weight.  ull_gemm_w4a8_bf16's contract
+// with an activation row of K / 2 bytes.
+extern "C" int ull_gemm_w4a4_bf16(const void* Xq, int64_t ldxq, const void* x_scales, int64_t ldxs, const void* Q, int64_t ldq, const void* w_scales,
+                                  int64_t lds, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
+                                  void* stream) {
+    if (!Xq || !x_scales || !Q || !w_scales || !C || M <= 0 || N <= 0 || K <= 0) return ULL_ERR_ARG;
+    if (const int rc = ull_a8_epilogue_check(flags, R, N, ldc, ldr)) return rc;
+    if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return ULL_ERR_SHAPE;
+    if (K % BK8 != 0 || (ldxq & 15) || (ldq & 15) || ldxq < K / 2 || ldq < K / 2 || (((uintptr_t)Xq | (uintptr_t)Q) & 15)) return ULL_ERR_SHAPE;   // 16-byte pieces
+    if ((ldxs & 3) || (lds & 3) || ldxs < K / 32 || lds < K / 32 || (((uintptr_t)x_scales | (uintptr_t)w_scales) & 3)) return ULL_ERR_SHAPE;   // 4-byte scale loads
+    if ((M - 1) * ldxq + K / 2 >= (1LL << 31) || (N - 1) * ldq + K / 2 >= (1LL << 31) || M * ldxs >= (1LL << 31) || N * lds >= (1LL << 31))
+        return ULL_ERR_SHAPE;                                                                         // 32-bit lane offsets in the kernel
+    int n_cu = 0;
+    if (const int rc = gemm_device_state(&n_cu)) return rc;
+    const GemmArgs a = gemm128_a8_args(C, ldc, R, ldr, M, N, K, flags);
+    if ((long)a.nbm * a.nbn > (1L << 30)) return ULL_ERR_SHAPE;
+    const W4A8Args q{(const uint8_t*)Xq, (const uint8_t*)x_scales, (const uint8_t*)Q, (const uint8_t*)w_scales, (long)ldxq, (long)ldxs, (long)ldq, (long)lds};
+    if (flags & EPI_SWIGLU)
+        hipLaunchKernelGGL(gemm128_w4a4_kernel<true>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
+    else
+        hipLaunchKernelGGL(gemm128_w4a4_kernel<false>, dim3(a.nbm * a.nbn), dim3(256), GEMM_LDS, (hipStream_t)stream, a, q);
     return ull_check_launch();
 }
 #endif  // !ULL_ELEM_F16

@@ -192,7 +192,7 @@ def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
 class UllavaCoreForCausalLM(nn.Module):
     config_class = UllavaCoreConfig
     weight_quantization = None             # "fp8_e4m3" / "mxfp4" after quantize_weights()
-    activation_quantization = None         # "fp8_e4m3" / "mxfp8_e4m3" after quantize_weights(fmt, activations=...)
+    activation_quantization = None         # "fp8_e4m3" / "mxfp8_e4m3" / "mxfp4_e2m1" after quantize_weights(fmt, activations=...)
     activation_scope = "prefill"           # "prefill+decode" after quantize_weights(..., activation_scope="prefill+decode")
 
     def __init__(self, config: UllavaCoreConfig, device=None, dtype=BF16):
@@ -423,6 +423,14 @@ class UllavaCoreForCausalLM(nn.Module):
         for W8A16 (profiles/w4a8_prefill.txt).  May be called on a model that is already mxfp4-quantized; no weight changes.  The spelling
         differs from "fp8_e4m3" on purpose: that value means one scale per token.
 
+        activations="mxfp4_e2m1" (with fmt="mxfp4" only): MXFP4 activations in the LLaMA prefill (W4A4, DESIGN f19).  The same Linears at the
+        same shapes quantize their input rows to OCP MXFP4 by the weights' own rule (ops.quantize_rows_mxfp4: e2m1 codes, one E8M0 scale per
+        row and block of 32, round to nearest, ties to the even code) and the product runs on the block-scaled matrix instruction with e2m1
+        for both operands (ops.linear_w4a4).  Prefill scope only; decode-shape launches and lm_head stay W4A16.  Round-to-nearest 4-bit
+        activations without rotation or calibration are the crude form of the mode: the logits move far more than under "mxfp8_e4m3"
+        (profiles/w4a4_prefill.txt); task accuracy on real checkpoints is unmeasured.  May be called on a model that is already
+        mxfp4-quantized, also to switch from "mxfp8_e4m3"; no weight changes.
+
         activation_scope="prefill+decode" (with fmt="fp8_e4m3", activations="fp8_e4m3" only; default "prefill" = everything above, unchanged):
         FP8 activations in batched decode steps too (DESIGN f10).  Wherever the same dispatch rule (ops.linear_route) says "a8w8_skinny" -- 5 to
         32 rows against a LLaMA-sized weight -- the four layer Linears quantize their input rows per token (q|k|v and gate|up inside the RMSNorm launch they already pay,
@@ -433,8 +441,9 @@ class UllavaCoreForCausalLM(nn.Module):
         `model.activation_scope` reports the setting."""
         if fmt not in ("fp8_e4m3", "mxfp4"):
             raise ValueError(f"quantize_weights: unknown format {fmt!r} (supported: 'fp8_e4m3', 'mxfp4')")
-        if activations not in (None, "fp8_e4m3", "mxfp8_e4m3"):
-            raise ValueError(f"quantize_weights: unknown activation format {activations!r} (supported: None, 'fp8_e4m3', 'mxfp8_e4m3')")
+        if activations not in (None, "fp8_e4m3", "mxfp8_e4m3", "mxfp4_e2m1"):
+            raise ValueError(f"quantize_weights: unknown activation format {activations!r} (supported: None, 'fp8_e4m3', 'mxfp8_e4m3', "
+                             "'mxfp4_e2m1')")
         if activation_scope not in ("prefill", "prefill+decode"):
             raise ValueError(f"quantize_weights: unknown activation scope {activation_scope!r} (supported: 'prefill', 'prefill+decode')")
         mx = fmt == "mxfp4"
@@ -450,11 +459,14 @@ class UllavaCoreForCausalLM(nn.Module):
         if activations == "mxfp8_e4m3" and not mx:
             raise NotImplementedError("quantize_weights('fp8_e4m3', activations='mxfp8_e4m3'): block-scaled fp8 activations are implemented on "
                                       "mxfp4 weights only; fp8_e4m3 weights take activations='fp8_e4m3'")
-        if activations == "mxfp8_e4m3":      # (refused before any device work: the W4A8 kernel walks K in 128-code tiles; smaller K is padded)
+        if activations == "mxfp4_e2m1" and not mx:
+            raise NotImplementedError("quantize_weights('fp8_e4m3', activations='mxfp4_e2m1'): MXFP4 activations are implemented on mxfp4 weights "
+                                      "only; fp8_e4m3 weights take activations='fp8_e4m3'")
+        if activations in ("mxfp8_e4m3", "mxfp4_e2m1"):  # (refused before any device work: the W4A8 / W4A4 kernels walk K in 128-code tiles; smaller K is padded)
             cfg_ = self.config
             for k_ in (cfg_.hidden_size, cfg_.intermediate_size):
                 if k_ % 32 == 0 and not ops.w4a8_k_ok(k_):
-                    raise NotImplementedError(f"quantize_weights('mxfp4', activations='mxfp8_e4m3'): K = {k_} is not a multiple of 128 and cannot "
+                    raise NotImplementedError(f"quantize_weights('mxfp4', activations='{activations}'): K = {k_} is not a multiple of 128 and cannot "
                                               "be padded (the resident layout of its first 2048 elements would change)")
         if self.weight_quantization is not None:
             if self.weight_quantization == fmt:

@@ -75,7 +75,7 @@ class UllavaForCausalLM(nn.Module):
 
     def quantize_weights(self, fmt: str = "fp8_e4m3", activations=None, activation_scope: str = "prefill"):
         """FP8 ("fp8_e4m3") or MXFP4 ("mxfp4") weight-only inference for the language model (UllavaCoreForCausalLM.quantize_weights); SAM and
-        the heads keep their dtype.  activations="fp8_e4m3" (fp8 weights only) / "mxfp8_e4m3" (mxfp4 weights only): fp8 activations in the LLaMA
+        the heads keep their dtype.  activations="fp8_e4m3" (fp8 weights only) / "mxfp8_e4m3" / "mxfp4_e2m1" (mxfp4 weights only): fp8 / fp4 activations in the LLaMA
         prefill as well; activation_scope="prefill+decode" (fp8 weights and activations only): also in decode steps of 5 to 32 tokens."""
         self.llm.quantize_weights(fmt, activations=activations, activation_scope=activation_scope)
         return self

@@ -420,16 +420,16 @@ class streamk_policy:
 
 # ---- the Linear dispatch rule: every route of `linear` / `linear_qkv_rope` is decided here ------------------------------------------------
 class ActQuant(NamedTuple):
-    """quantize_weights(activations=fmt, activation_scope=): "fp8_e4m3" (one scale per token, on an Fp8Weight) or "mxfp8_e4m3" (one per block of
-    32, on an Mxfp4Weight); decode: also at the batched decode shapes ("prefill+decode").  None in its place means weight-only."""
+    """quantize_weights(activations=fmt, activation_scope=): "fp8_e4m3" (one scale per token, on an Fp8Weight) or "mxfp8_e4m3" / "mxfp4_e2m1" (one
+    per block of 32, on an Mxfp4Weight); decode: also at the batched decode shapes ("prefill+decode").  None in its place means weight-only."""
     fmt: str
     decode: bool = False
 
 
 A8W8_BK, A8W8_SKINNY_MAX_M = _D["ULL_A8W8_BK"], _D["ULL_A8W8_SKINNY_MAX_M"]
-_ROUTES = {_D["ULL_ROUTE_" + r.upper()]: r for r in ("gemm", "gemv", "skinny", "a8w8", "w4a8", "a8w8_skinny")}
+_ROUTES = {_D["ULL_ROUTE_" + r.upper()]: r for r in ("gemm", "gemv", "skinny", "a8w8", "w4a8", "a8w8_skinny", "w4a4")}
 _WF = {None: _lib.WF_ELEM, "fp8": _lib.WF_FP8, "mxfp4": _lib.WF_MXFP4}
-_AF = {"fp8_e4m3": _D["ULL_AF_FP8"], "mxfp8_e4m3": _D["ULL_AF_MXFP8"]}
+_AF = {"fp8_e4m3": _D["ULL_AF_FP8"], "mxfp8_e4m3": _D["ULL_AF_MXFP8"], "mxfp4_e2m1": _D["ULL_AF_MXFP4"]}
 
 
 # The rule itself is csrc/linear_route.h, which the library's own callers (the coarse entries among them) apply; the three functions below ask
@@ -438,7 +438,7 @@ _AF = {"fp8_e4m3": _D["ULL_AF_FP8"], "mxfp8_e4m3": _D["ULL_AF_MXFP8"]}
 def _linear_route(M: int, N: int, K: int, ldw: int, tune: int, wfmt: Optional[str] = None, aq: Optional[ActQuant] = None):
     """(route, rms_first) of a Linear x [M, K] @ w.T, w [N, K] with row pitch ldw; wfmt: None for a 16-bit weight, else its `fmt_name`.
     route "gemm": the tiled GEMM; "gemv": the weight-streaming GEMV at decode shapes; "skinny": batched decode steps against LLaMA-sized
-    weights on the matrix cores; "a8w8" (linear_a8w8) / "w4a8" (linear_w4a8): quantized activations where aq pairs with the weight format and
+    weights on the matrix cores; "a8w8" (linear_a8w8) / "w4a8" (linear_w4a8) / "w4a4" (linear_w4a4): quantized activations where aq pairs with the weight format and
     the weight-only rule says "gemm"; "a8w8_skinny" (linear_a8w8_skinny): aq.decode on fp8 weights.
     rms_first: a requested RMSNorm is a launch of its own ahead of the Linear (False: the route's kernel fuses it)."""
     af = _D["ULL_AF_NONE"] if aq is None else _AF.get(aq.fmt, _D["ULL_AF_NONE"])
@@ -455,6 +455,7 @@ def linear_route(M: int, w, act_quant: Optional[ActQuant] = None) -> str:
 # the rule read as a boolean, for callers that ask about one A8 route (N and K are w's own)
 a8w8_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("fp8_e4m3")) == "a8w8"                          # noqa: E731
 w4a8_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("mxfp8_e4m3")) == "w4a8"                        # noqa: E731
+w4a4_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("mxfp4_e2m1")) == "w4a4"                        # noqa: E731
 a8w8_decode_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("fp8_e4m3", True)) == "a8w8_skinny"      # noqa: E731
 
 
@@ -582,8 +583,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
 
 # ---- quantized activations on quantized weights (quantize_weights(activations=, activation_scope=)) ---------------------------------------
 # Which Linear takes which kernel is `_linear_route`'s decision alone; `linear(..., act_quant=)` carries it out (`_linear_a8`) through the
-# per-kernel wrappers linear_a8w8 / linear_w4a8 / linear_a8w8_skinny, each the only call site of its entry.
-A8_ROUTES = ("a8w8", "w4a8", "a8w8_skinny")
+# per-kernel wrappers linear_a8w8 / linear_w4a8 / linear_w4a4 / linear_a8w8_skinny, each the only call site of its entry.
+A8_ROUTES = ("a8w8", "w4a8", "a8w8_skinny", "w4a4")
 
 
 def _linear_a8(route: str, x, w, residual, swiglu: bool, out, out_f32: bool, rms_w, rms_eps: float) -> torch.Tensor:
@@ -595,7 +596,7 @@ def _linear_a8(route: str, x, w, residual, swiglu: bool, out, out_f32: bool, rms
         return y if x.dim() == 2 or out is not None else y.view(*x.shape[:-1], y.shape[-1])
     if rms_w is not None:
         x = rmsnorm(x, rms_w, rms_eps)
-    return (linear_a8w8 if route == "a8w8" else linear_w4a8)(x, w, **kw)
+    return {"a8w8": linear_a8w8, "w4a8": linear_w4a8, "w4a4": linear_w4a4}[route](x, w, **kw)
 
 
 # ---- FP8 activations on FP8 weights: route "a8w8" ---------------------------------------------------------------------------------------
@@ -718,6 +719,20 @@ def w4a8_k_ok(K: int) -> bool:
     return K % A8W8_BK == 0 or K + (-K % A8W8_BK) < 2048
 
 
+def _mxfp4_kpadded(w: "Mxfp4Weight", Kp: int):
+    """(codes, scales) of w for a GEMM that walks Kp >= K in 128-code K-tiles: w's own, or -- K < 2048, tiny test models only -- the copy
+    padded with zero codes and the scale byte 127, made once and kept on the weight (linear_w4a8 and linear_w4a4 share it)."""
+    N, K = w.shape
+    if Kp == K:
+        return w.codes, w.scales
+    if w._kpad is None:                      # K < 2048: the row is in standard order, so padding appends
+        pc = torch.nn.functional.pad(w.codes, (0, (Kp - K) // 2)).contiguous()
+        ps = torch.full((N, Mxfp4Weight.scale_pitch(Kp)), 127, device=w.codes.device, dtype=torch.uint8)
+        ps[:, :K // 32] = w.scales[:, :K // 32]
+        w._kpad = (pc, ps)
+    return w._kpad
+
+
 def _quantize_rows_mxfp8(x: torch.Tensor, Kp: int):
     """(codes uint8 [M, Kp], scale bytes uint8 [M, Mxfp4Weight.scale_pitch(Kp)]) as ull_gemm_w4a8_bf16 reads them: the scale byte of block j
     sits where the resident MXFP4 layout puts a weight's (`_mx_perm`); columns past K are zero codes, and every scale byte that belongs to
@@ -766,17 +781,68 @@ def linear_w4a8(x: torch.Tensor, w: "Mxfp4Weight", residual: Optional[torch.Tens
     if not w4a8_k_ok(K):
         raise NotImplementedError(f"u-llava_amd.linear_w4a8: K = {K} is no multiple of 128 and cannot be padded (it would gain a superblock)")
     Kp = K + (-K % A8W8_BK)
-    wq, wsc = w.codes, w.scales
-    if Kp != K:
-        if w._kpad is None:                  # K < 2048: the row is in standard order, so padding appends
-            pc = torch.nn.functional.pad(wq, (0, (Kp - K) // 2)).contiguous()
-            ps = torch.full((N, Mxfp4Weight.scale_pitch(Kp)), 127, device=wq.device, dtype=torch.uint8)
-            ps[:, :K // 32] = wsc[:, :K // 32]
-            w._kpad = (pc, ps)
-        wq, wsc = w._kpad
+    wq, wsc = _mxfp4_kpadded(w, Kp)
     xq, xsc = _quantize_rows_mxfp8(x, Kp)
     out, flags, ldr = _epilogue(x, N, swiglu, out_f32, residual, out, BF16)
     _lib.call("ull_gemm_w4a8_bf16", _p(xq), xq.stride(0), _p(xsc), xsc.stride(0), _p(wq), wq.stride(0), _p(wsc), wsc.stride(0), _p(out),
+              _rows(out)[1], _p(residual), ldr, M, N, Kp, flags, _stream())
+    return out
+
+
+# ---- MXFP4 activations on MXFP4 weights: route "w4a4" -----------------------------------------------------------------------------------
+def _quantize_rows_mxfp4(x: torch.Tensor, Kp: int, layout: int):
+    """(codes uint8 [M, Kp / 2], scale bytes uint8 [M, Mxfp4Weight.scale_pitch(Kp)]) of ull_quantize_act_rows_mxfp4_bf16; layout 1: as
+    ull_gemm_w4a4_bf16 reads them (private to that pair).  Columns past K are zero codes, and every scale byte that belongs to no block of x
+    (padding blocks, spare bytes of the pitch) is 127 (2^0).  Kp != K only below 2048, where layout 1 stores the K-tiles in standard order."""
+    _chk(x, "x", BF16)
+    M, ldx = _rows(x)
+    K = x.shape[-1]
+    if K % 32:
+        raise RuntimeError(f"u-llava_amd.quantize_rows_mxfp4: K must be a multiple of 32, got {K}")
+    lds = Mxfp4Weight.scale_pitch(Kp)
+    codes = (torch.empty if Kp == K else torch.zeros)(M, Kp // 2, device=x.device, dtype=torch.uint8)
+    if lds == K // 32:
+        scales = torch.empty(M, lds, device=x.device, dtype=torch.uint8)
+    else:
+        scales = torch.full((M, lds), 127, device=x.device, dtype=torch.uint8)
+    _lib.call("ull_quantize_act_rows_mxfp4_bf16", _p(x), ldx, M, K, _p(codes), Kp // 2, _p(scales), lds, layout, _stream())
+    return codes, scales
+
+
+def quantize_rows_mxfp4(x: torch.Tensor):
+    """(codes uint8 [M, K / 2], scales uint8 [M, K / 32]) of bf16 rows x [..., K] (one row pitch, K % 32 == 0) in OCP MXFP4, the weights' rule
+    per row and block of 32 consecutive K elements: the E8M0 byte t + 127, t the smallest integer with amax|block| * 2^-t <= 6 (0 for an
+    all-zero block), clamped to [-125, 126]; codes = e2m1(x * 2^-t), nearest, ties to the even code -- bit for bit
+    `quantize_mxfp4(x).to_standard()`.  Standard layout (element 2i in the low nibble of byte i, scales in block order); the W4A4 GEMM reads
+    a private order (`_quantize_rows_mxfp4(x, K, 1)`)."""
+    K = x.shape[-1]
+    codes, raw = _quantize_rows_mxfp4(x, K, 0)
+    return codes, raw[:, :K // 32]
+
+
+def linear_w4a4(x: torch.Tensor, w: "Mxfp4Weight", residual: Optional[torch.Tensor] = None, swiglu: bool = False,
+                out: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
+    """y = epilogue(x @ w.T) with MXFP4 activations on the resident MXFP4 weight (ull_gemm_w4a4_bf16; the only call site of that entry):
+        xq, t = quantize_rows_mxfp4(x)                                         per row and block j of 32 K elements
+        y[m, n] = sum_j 2^(t[m, j] + s[n, j]) * sum_{k in j} e2m1(xq[m, k]) * e2m1(wq[n, k])      exact products, scales applied by the
+                                                                               instruction, fp32 accumulation in the kernel's fixed K order
+    then `linear`'s epilogue on y (residual / swiglu / out_f32, same rounding points).  A K below 2048 that is no multiple of 128 (tiny test
+    models) is padded with zero codes and the scale byte 127 on both sides, which adds 0 * 0 terms; the padded weight is the one linear_w4a8
+    keeps on the Mxfp4Weight."""
+    if not isinstance(w, Mxfp4Weight):
+        raise RuntimeError("u-llava_amd.linear_w4a4: w must be an Mxfp4Weight")
+    _chk(x, "x", BF16)
+    M, _ = _rows(x)
+    N, K = w.shape
+    if x.shape[-1] != K:
+        raise RuntimeError(f"u-llava_amd.linear_w4a4: K mismatch {x.shape[-1]} vs {K}")
+    if not w4a8_k_ok(K):
+        raise NotImplementedError(f"u-llava_amd.linear_w4a4: K = {K} is no multiple of 128 and cannot be padded (it would gain a superblock)")
+    Kp = K + (-K % A8W8_BK)
+    wq, wsc = _mxfp4_kpadded(w, Kp)
+    xq, xsc = _quantize_rows_mxfp4(x, Kp, 1)
+    out, flags, ldr = _epilogue(x, N, swiglu, out_f32, residual, out, BF16)
+    _lib.call("ull_gemm_w4a4_bf16", _p(xq), xq.stride(0), _p(xsc), xsc.stride(0), _p(wq), wq.stride(0), _p(wsc), wsc.stride(0), _p(out),
               _rows(out)[1], _p(residual), ldr, M, N, Kp, flags, _stream())
     return out
 
