@@ -290,6 +290,36 @@ int ull_quantize_act_rows_mxfp4_bf16(const void* X, int64_t ldx, int64_t M, int6
 int ull_gemm_w4a4_bf16(const void* Xq, int64_t ldxq, const void* x_scales, int64_t ldxs, const void* Q, int64_t ldq, const void* w_scales,
                        int64_t lds, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags, void* stream);
 
+/* ---- MXFP8 activations on MXFP4 weights in batched decode steps (bf16 build only: no *_f16 twins) ------------------------------------------
+ * UllavaCoreForCausalLM.quantize_weights("mxfp4", decode_activations="mxfp8_e4m3"): wherever ull_linear_route answers ULL_ROUTE_W4A8_SKINNY
+ * (5 to 32 rows against a LLaMA-sized weight, K % 128 == 0) the four LLaMA-layer Linears quantize their input rows to OCP MXFP8 and stream the
+ * resident MXFP4 codes and scale bytes through the block-scaled matrix instruction (u-llava_amd/csrc/w4a8_decode.hip).  For x [M, K] @ w^T:
+ *   xq, t = ull_quantize_rows_mxfp8_bf16(x)                 the per-block rule of the W4A8 section above
+ *   y[m, n] = sum_j 2^(t[m, j] + s[n, j]) * sum_{k in block j} float(xq[m, k]) * e2m1(wq[n, k])     every product exact in fp32, both scales
+ *                                                           applied by the instruction, fp32 accumulation
+ *   the summation order is a function of K alone -- not of M, N, the row index m or what the other rows hold.  The units are the super tiles
+ *   (b, t) of the whole 2048-element superblocks in ull_gemm_w4a8_bf16's visit order (b ascending, then t = 0 .. 3; inside one, the four K-tiles
+ *   at element b * 2048 + g * 512 + t * 128 with g = 0 .. 3 ascending), then the K-tiles after the last whole superblock ascending, one matrix
+ *   instruction per K-tile.  With nkt = K / 128 and p(u) the number of K-tiles in the units before unit u, partial sum w (w = 0 .. 7) adds the
+ *   units with nkt w / 8 <= p(u) < nkt (w + 1) / 8 (integer division) in ascending order from zero -- a partial sum without a unit is an exact
+ *   zero -- and the eight partial sums are added in ascending w.  (K = 4096: one super tile per partial sum.)  As in the W4A8 section the
+ *   definition covers inputs whose scaled terms are normal floats or zero.
+ * then the epilogue of ull_gemm_skinny_bf16 on y with its rounding points, as ull_gemm_skinny_a8w8_bf16 applies it (no scaling is left to it).
+ * ull_gemm_skinny_w4a8_bf16: ull_gemm_w4a8_bf16's operands and alignment rules -- (Xq, ldxq, x_scales, ldxs) from the MXFP8 row quantizer
+ * (codes in standard K order, scale bytes where it puts them), (Q, ldq, w_scales, lds) a resident MXFP4 weight; code pitches multiples of 16
+ * bytes and base pointers 16-byte aligned, scale pitches multiples of 4 bytes >= K / 32 and scale pointers 4-byte aligned; 1 <= M <= 32,
+ * K % 128 == 0.  flags: ULL_EPI_RESID, ULL_EPI_SWIGLU (Q rows in the gate|up interleave, N % 32 == 0), ULL_EPI_OUT_F32 only -- any other
+ * bit, or a null pointer: ULL_ERR_ARG; a shape or alignment it cannot take: ULL_ERR_SHAPE; nothing is launched in either case.
+ * ull_rmsnorm_quantize_rows_mxfp8_bf16: codes, scales = ull_quantize_rows_mxfp8_bf16(ull_rmsnorm_bf16(X; rms_w, eps)) bit for bit -- the same
+ * bf16 rounding of the normed row, the same scale rule, the same codes, the scale bytes in the same order -- without writing the normed rows.
+ * X [M, K] bf16 (row pitch ldx elements, 16-byte aligned rows), any M, K % 32 == 0; codes [M, K] (row pitch ldq bytes, a multiple of 8);
+ * scales: row pitch lds bytes >= K / 32 and a multiple of 4, pointer 4-byte aligned. */
+int ull_gemm_skinny_w4a8_bf16(const void* Xq, int64_t ldxq, const void* x_scales, int64_t ldxs, const void* Q, int64_t ldq, const void* w_scales,
+                              int64_t lds, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int flags,
+                              void* stream);
+int ull_rmsnorm_quantize_rows_mxfp8_bf16(const void* X, int64_t ldx, const void* rms_w, float eps, int64_t M, int64_t K, void* codes, int64_t ldq,
+                                         void* scales, int64_t lds, void* stream);
+
 /* ---- FP8 (e4m3) KV cache (bf16 build only) ------------------------------------------------------------------------------------------
  * KVCache(kv_dtype="fp8_e4m3") keeps, per layer, K codes [B, H, smax, hd] and V^T codes [B, H, hd, smax] (the key-permuted slot order of
  * ull_transpose_v) plus one fp32 scale 2^s per (batch, head, position) for the K row (k_scale [B, H, smax], by key) and one for the V column
@@ -782,6 +812,7 @@ int ull_sumsq_f32(const void* g, int grad_dtype, int64_t n, void* out, void* str
 #define ULL_ROUTE_W4A8 4        /* ull_gemm_w4a8_bf16 */
 #define ULL_ROUTE_A8W8_SKINNY 5 /* ull_gemm_skinny_a8w8_bf16 */
 #define ULL_ROUTE_W4A4 6        /* ull_gemm_w4a4_bf16 */
+#define ULL_ROUTE_W4A8_SKINNY 7 /* ull_gemm_skinny_w4a8_bf16 */
 /* activation quantization asked of the Linear: it takes effect only on the weight format it pairs with (fp8 + FP8, mxfp4 + MXFP8 or MXFP4) */
 #define ULL_AF_NONE 0
 #define ULL_AF_FP8 1   /* one power-of-two scale per token (ull_quantize_rows_fp8_bf16) */
@@ -789,8 +820,11 @@ int ull_sumsq_f32(const void* g, int grad_dtype, int64_t n, void* out, void* str
 #define ULL_AF_MXFP4 3 /* e2m1 codes, one E8M0 scale per block of 32 (ull_quantize_act_rows_mxfp4_bf16) */
 #define ULL_A8W8_BK 128          /* K-tile of the A8 kernels: one block-scaled matrix instruction */
 #define ULL_A8W8_SKINNY_MAX_M 32 /* ull_gemm_skinny_a8w8_bf16: two 16-row activation fragments */
+#define ULL_W4A8_SKINNY_MAX_M 32 /* ull_gemm_skinny_w4a8_bf16: two 16-row activation fragments */
 /* ULL_ROUTE_* in the low byte; bit 8: a LlamaRMSNorm asked in front of the Linear is a launch of its own (clear: the route's kernel fuses it).
- * wfmt: ULL_WF_*; afmt: ULL_AF_*, a_decode: also at the batched decode shapes; tune: the call's ULL_GEMM_TUNE_* bits. */
+ * wfmt: ULL_WF_*; afmt: ULL_AF_*; a_decode: the ULL_AF_* code of the activations at the batched decode shapes -- 0: none; ULL_AF_FP8: per-token
+ * fp8 there too (acts on fp8 weights with afmt == ULL_AF_FP8 only); ULL_AF_MXFP8: MXFP8 there (acts on ULL_WF_MXFP4 only, whatever afmt is);
+ * tune: the call's ULL_GEMM_TUNE_* bits. */
 int64_t ull_linear_route(int64_t M, int64_t N, int64_t K, int64_t ldw, int wfmt, int afmt, int a_decode, int tune);
 /* How ull_gemm_bf16 is to be called at this shape.  Bit 0: "big" -- the 256 x 256 kernel, which takes the weight's ULL_EPI_W_TILED copy; bit 1:
  * pass the workspace (the stream-K tail of a big GEMM from K >= min_k on, min_k < 0 = never; or, small_m: the caller's kernel has the split,

@@ -28,20 +28,26 @@ struct Route {
 // The GEMV's LDS staging holds the activations; a fused RMSNorm needs it.
 constexpr bool gemv_stages(int64_t M, int64_t K) { return M * K * 2 <= GEMV_STAGE_BYTES; }
 
-// wfmt: ULL_WF_*; afmt: ULL_AF_* with a_decode (activation quantization also at the batched decode shapes); tune: the ULL_GEMM_TUNE_* bits of the
-// call (a forced GEMM form keeps the Linear off the skinny kernels; the GEMV does not read it).
+// wfmt: ULL_WF_*; afmt: ULL_AF_*; a_decode: the ULL_AF_* code of the activations at the batched decode shapes (0: none); tune: the
+// ULL_GEMM_TUNE_* bits of the call (a forced GEMM form keeps the Linear off the skinny kernels; the GEMV does not read it).
 // An activation format on the weight format it pairs with (fp8 + per-token fp8, mxfp4 + mxfp8 or mxfp4; any other pair is weight-only) quantizes the
-// activations wherever the weight-only rule says GEMM.  a_decode on fp8 weights adds A8W8_SKINNY ahead of everything else: the skinny size rule,
-// starting above the rows the fused q|k|v + RoPE + cache-append GEMV takes and extended to that kernel's 32 rows (so at 17 .. 32 rows it replaces
-// A8W8), with K a whole number of 128-code K-tiles; it fuses the RMSNorm into its row quantization.
-constexpr Route route_of(int64_t M, int64_t N, int64_t K, int64_t ldw, int wfmt, int afmt, bool a_decode, int tune) {
+// activations wherever the weight-only rule says GEMM.  a_decode == ULL_AF_FP8 on fp8 weights with afmt == ULL_AF_FP8 adds A8W8_SKINNY ahead of
+// everything else: the skinny size rule, starting above the rows the fused q|k|v + RoPE + cache-append GEMV takes and extended to that kernel's
+// 32 rows (so at 17 .. 32 rows it replaces A8W8), with K a whole number of 128-code K-tiles; it fuses the RMSNorm into its row quantization.
+// a_decode == ULL_AF_MXFP8 on mxfp4 weights, whatever afmt is, adds W4A8_SKINNY the same way (at 17 .. 32 rows it replaces W4A8 / W4A4 / the
+// dequantizing GEMM); it acts on no other weight format, and ULL_AF_FP8 acts on no mxfp4 weight.
+constexpr Route route_of(int64_t M, int64_t N, int64_t K, int64_t ldw, int wfmt, int afmt, int a_decode, int tune) {
     const int a8 = wfmt == ULL_WF_FP8 && afmt == ULL_AF_FP8     ? ULL_ROUTE_A8W8
                    : wfmt == ULL_WF_MXFP4 && afmt == ULL_AF_MXFP8 ? ULL_ROUTE_W4A8
                    : wfmt == ULL_WF_MXFP4 && afmt == ULL_AF_MXFP4 ? ULL_ROUTE_W4A4
                                                                   : ULL_ROUTE_GEMM;
     const bool streams_large_weight = N * K >= LARGE_WEIGHT && ldw % 8 == 0 && tune == 0;
-    if (a8 == ULL_ROUTE_A8W8 && a_decode && M > GEMV_MAX_M && M <= ULL_A8W8_SKINNY_MAX_M && K % ULL_A8W8_BK == 0 && streams_large_weight)
+    if (a8 == ULL_ROUTE_A8W8 && a_decode == ULL_AF_FP8 && M > GEMV_MAX_M && M <= ULL_A8W8_SKINNY_MAX_M && K % ULL_A8W8_BK == 0 &&
+        streams_large_weight)
         return {ULL_ROUTE_A8W8_SKINNY, false};
+    if (wfmt == ULL_WF_MXFP4 && a_decode == ULL_AF_MXFP8 && M > GEMV_MAX_M && M <= ULL_W4A8_SKINNY_MAX_M && K % ULL_A8W8_BK == 0 &&
+        streams_large_weight)
+        return {ULL_ROUTE_W4A8_SKINNY, false};
     if (M >= SKINNY_MIN_M && M <= SKINNY_MAX_M && K % SKINNY_K_STEP == 0 && streams_large_weight) return {ULL_ROUTE_SKINNY, true};
     if (M <= GEMV_MAX_M && K % 8 == 0) return {ULL_ROUTE_GEMV, !gemv_stages(M, K)};
     return {a8, true};

@@ -2,7 +2,7 @@
 #include "linear_route.h"
 
 extern "C" int64_t ull_linear_route(int64_t M, int64_t N, int64_t K, int64_t ldw, int wfmt, int afmt, int a_decode, int tune) {
-    const ull_route::Route r = ull_route::route_of(M, N, K, ldw, wfmt, afmt, a_decode != 0, tune);
+    const ull_route::Route r = ull_route::route_of(M, N, K, ldw, wfmt, afmt, a_decode, tune);
     return r.kind | (r.rms_first ? 1 << 8 : 0);
 }
 

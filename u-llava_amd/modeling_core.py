@@ -194,6 +194,7 @@ class UllavaCoreForCausalLM(nn.Module):
     weight_quantization = None             # "fp8_e4m3" / "mxfp4" after quantize_weights()
     activation_quantization = None         # "fp8_e4m3" / "mxfp8_e4m3" / "mxfp4_e2m1" after quantize_weights(fmt, activations=...)
     activation_scope = "prefill"           # "prefill+decode" after quantize_weights(..., activation_scope="prefill+decode")
+    decode_activation_quantization = None  # "mxfp8_e4m3" after quantize_weights("mxfp4", decode_activations="mxfp8_e4m3")
 
     def __init__(self, config: UllavaCoreConfig, device=None, dtype=BF16):
         super().__init__()
@@ -386,7 +387,8 @@ class UllavaCoreForCausalLM(nn.Module):
                     mod.weight.data = torch.empty(0, device=mod.weight.device, dtype=mod.weight.dtype)
         return self
 
-    def quantize_weights(self, fmt: str = "fp8_e4m3", activations: Optional[str] = None, activation_scope: str = "prefill"):
+    def quantize_weights(self, fmt: str = "fp8_e4m3", activations: Optional[str] = None, activation_scope: str = "prefill",
+                         decode_activations: Optional[str] = None):
         """FP8 (e4m3) weight-only inference: store every LLaMA Linear (q/k/v/o/gate/up/down_proj of every layer) and lm_head as e4m3fn
         codes with one power-of-two fp32 scale per output row (ops.quantize_fp8); activations stay bf16, accumulation fp32.  Everything
         else (embeddings, norms, CLIP, projector) keeps its dtype.  Returns self.
@@ -438,7 +440,21 @@ class UllavaCoreForCausalLM(nn.Module):
         (ops.linear_a8w8_skinny) in place of the W8A16 skinny kernel (5 to 16 rows) or the 128 x 128 W8A8 GEMM (17 to 32 rows).  Steps of at
         most 4 tokens, lm_head and the coarse entries are untouched, so decoding at batch <= 4 is bit-identical to the weight-only model even
         under this scope.  Measured in profiles/a8_decode.txt.  May be switched on for a model that is already fp8 / A8-quantized;
-        `model.activation_scope` reports the setting."""
+        `model.activation_scope` reports the setting.
+
+        decode_activations="mxfp8_e4m3" (with fmt="mxfp4" only, and with any of activations=None / "mxfp8_e4m3" / "mxfp4_e2m1"; default None =
+        everything above, unchanged): MXFP8 activations in batched decode steps on mxfp4 weights (W4A8, DESIGN f20), chosen independently of the
+        prefill activations -- decode is bound by the weight stream, so 4-bit activations there would only cost accuracy.  Wherever the dispatch
+        rule (ops.linear_route) says "w4a8_skinny" -- 5 to 32 rows against a LLaMA-sized weight, K a multiple of 128 -- the four layer Linears
+        quantize their input rows to OCP MXFP8 (q|k|v and gate|up inside the RMSNorm launch they already pay, ops.rmsnorm_quantize_rows_mxfp8;
+        o_proj and down_proj in a launch of their own) and run the weight-streaming W4A8 kernel (ops.linear_w4a8_skinny) straight from the
+        resident codes and scale bytes, in place of the W4A16 skinny kernel (5 to 16 rows) or of whatever the prefill mode gives 17 to 32 rows
+        (dequantize + bf16 GEMM, or the 128 x 128 W4A8 / W4A4 GEMM).  The rule goes by the row count, so a prompt of 5 to 32 tokens takes the
+        route too (its q|k|v followed by the stand-alone RoPE kernel).  Steps of at most 4 tokens, lm_head, the coarse entries and every other
+        shape are untouched: decoding at batch <= 4 is bit-identical to the model without the keyword, and with activations=None a prefill of
+        more than 32 rows stays the bit-exact twin of the dequantized bf16 model.  This is the mxfp4 spelling of fp8's
+        activation_scope="prefill+decode", which stays refused on mxfp4.  Measured in profiles/w4a8_decode.txt.  May be switched on for a model
+        that is already mxfp4-quantized; no weight changes.  `model.decode_activation_quantization` reports the mode."""
         if fmt not in ("fp8_e4m3", "mxfp4"):
             raise ValueError(f"quantize_weights: unknown format {fmt!r} (supported: 'fp8_e4m3', 'mxfp4')")
         if activations not in (None, "fp8_e4m3", "mxfp8_e4m3", "mxfp4_e2m1"):
@@ -446,11 +462,16 @@ class UllavaCoreForCausalLM(nn.Module):
                              "'mxfp4_e2m1')")
         if activation_scope not in ("prefill", "prefill+decode"):
             raise ValueError(f"quantize_weights: unknown activation scope {activation_scope!r} (supported: 'prefill', 'prefill+decode')")
+        if decode_activations not in (None, "mxfp8_e4m3"):
+            raise ValueError(f"quantize_weights: unknown decode activation format {decode_activations!r} (supported: None, 'mxfp8_e4m3')")
         mx = fmt == "mxfp4"
+        if decode_activations is not None and not mx:
+            raise ValueError("quantize_weights('fp8_e4m3', decode_activations=...): decode_activations is the mxfp4 spelling; fp8_e4m3 weights "
+                             "take activations='fp8_e4m3', activation_scope=\"prefill+decode\"")
         if activation_scope == "prefill+decode":
             if mx:
-                raise NotImplementedError("quantize_weights('mxfp4', activation_scope='prefill+decode'): fp8 activations in decode steps are "
-                                          "implemented on fp8_e4m3 weights only; the mxfp4 (W4A8) lane map and resident layout differ")
+                raise NotImplementedError("quantize_weights('mxfp4', activation_scope='prefill+decode'): the scope is fp8_e4m3's spelling (one "
+                                          "scale per token); mxfp4 weights take decode_activations='mxfp8_e4m3'")
             if activations is None:
                 raise ValueError("quantize_weights: activation_scope='prefill+decode' needs activations='fp8_e4m3'")
         if activations == "fp8_e4m3" and mx:
@@ -462,11 +483,12 @@ class UllavaCoreForCausalLM(nn.Module):
         if activations == "mxfp4_e2m1" and not mx:
             raise NotImplementedError("quantize_weights('fp8_e4m3', activations='mxfp4_e2m1'): MXFP4 activations are implemented on mxfp4 weights "
                                       "only; fp8_e4m3 weights take activations='fp8_e4m3'")
-        if activations in ("mxfp8_e4m3", "mxfp4_e2m1"):  # (refused before any device work: the W4A8 / W4A4 kernels walk K in 128-code tiles; smaller K is padded)
+        if activations in ("mxfp8_e4m3", "mxfp4_e2m1") or decode_activations is not None:  # (refused before any device work: the W4A8 / W4A4 kernels walk K in 128-code tiles; smaller K is padded)
             cfg_ = self.config
             for k_ in (cfg_.hidden_size, cfg_.intermediate_size):
                 if k_ % 32 == 0 and not ops.w4a8_k_ok(k_):
-                    raise NotImplementedError(f"quantize_weights('mxfp4', activations='{activations}'): K = {k_} is not a multiple of 128 and cannot "
+                    mode_ = f"activations='{activations}'" if activations is not None else f"decode_activations='{decode_activations}'"
+                    raise NotImplementedError(f"quantize_weights('mxfp4', {mode_}): K = {k_} is not a multiple of 128 and cannot "
                                               "be padded (the resident layout of its first 2048 elements would change)")
         if self.weight_quantization is not None:
             if self.weight_quantization == fmt:
@@ -474,6 +496,8 @@ class UllavaCoreForCausalLM(nn.Module):
                     self.activation_quantization = activations
                 if activation_scope != "prefill":
                     self.activation_scope = activation_scope
+                if decode_activations is not None:
+                    self.decode_activation_quantization = decode_activations
                 return self
             self._refuse_quantized(f"quantize_weights({fmt!r})")
         if self.dtype != BF16:
@@ -539,6 +563,7 @@ class UllavaCoreForCausalLM(nn.Module):
         self.weight_quantization = fmt
         self.activation_quantization = activations
         self.activation_scope = activation_scope
+        self.decode_activation_quantization = decode_activations
         return self
 
     # The version tuples are read on EVERY forward (a decode step too): walking the module tree for them cost 0.5 ms of host time per step
@@ -975,8 +1000,8 @@ class UllavaCoreForCausalLM(nn.Module):
         wq = pk.get("fp8", False) or pk.get("mxfp4", False)      # quantize_weights(): the Linear weights are ops.Fp8Weight / ops.Mxfp4Weight
         # quantize_weights(activations=, activation_scope=): the layer Linears hand the mode to the dispatch rule (ops.linear(act_quant=))
         aq = None
-        if wq and self.activation_quantization is not None:
-            aq = ops.ActQuant(self.activation_quantization, self.activation_scope == "prefill+decode")
+        if wq and (self.activation_quantization is not None or self.decode_activation_quantization is not None):
+            aq = ops.ActQuant(self.activation_quantization, self.activation_scope == "prefill+decode", self.decode_activation_quantization)
         if aq is not None and fuse_rope and pk["llama"] and ops.linear_route(T, pk["llama"][0]["w_qkv"], aq) in ops.A8_ROUTES:
             fuse_rope = False                # A8 q|k|v: the plain projection, then the stand-alone RoPE kernel
         rope_cs = ops.rope_table(pos, inv_freq, x.dtype) if (fuse_rope or fuse_append) else None

@@ -73,11 +73,17 @@ class UllavaForCausalLM(nn.Module):
     def activation_quantization(self):
         return self.llm.activation_quantization
 
-    def quantize_weights(self, fmt: str = "fp8_e4m3", activations=None, activation_scope: str = "prefill"):
+    @property
+    def decode_activation_quantization(self):
+        return self.llm.decode_activation_quantization
+
+    def quantize_weights(self, fmt: str = "fp8_e4m3", activations=None, activation_scope: str = "prefill", decode_activations=None):
         """FP8 ("fp8_e4m3") or MXFP4 ("mxfp4") weight-only inference for the language model (UllavaCoreForCausalLM.quantize_weights); SAM and
         the heads keep their dtype.  activations="fp8_e4m3" (fp8 weights only) / "mxfp8_e4m3" / "mxfp4_e2m1" (mxfp4 weights only): fp8 / fp4 activations in the LLaMA
-        prefill as well; activation_scope="prefill+decode" (fp8 weights and activations only): also in decode steps of 5 to 32 tokens."""
-        self.llm.quantize_weights(fmt, activations=activations, activation_scope=activation_scope)
+        prefill as well; activation_scope="prefill+decode" (fp8 weights and activations only): also in decode steps of 5 to 32 tokens;
+        decode_activations="mxfp8_e4m3" (mxfp4 weights only, with any prefill mode): MXFP8 activations in decode steps of 5 to 32 tokens
+        (W4A8 from the resident codes); `decode_activation_quantization` reports it."""
+        self.llm.quantize_weights(fmt, activations=activations, activation_scope=activation_scope, decode_activations=decode_activations)
         return self
 
     @property

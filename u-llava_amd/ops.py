@@ -421,13 +421,16 @@ class streamk_policy:
 # ---- the Linear dispatch rule: every route of `linear` / `linear_qkv_rope` is decided here ------------------------------------------------
 class ActQuant(NamedTuple):
     """quantize_weights(activations=fmt, activation_scope=): "fp8_e4m3" (one scale per token, on an Fp8Weight) or "mxfp8_e4m3" / "mxfp4_e2m1" (one
-    per block of 32, on an Mxfp4Weight); decode: also at the batched decode shapes ("prefill+decode").  None in its place means weight-only."""
-    fmt: str
+    per block of 32, on an Mxfp4Weight); decode: also at the batched decode shapes ("prefill+decode", fp8 only).  decode_fmt:
+    quantize_weights(decode_activations=): the format of the activations at the batched decode shapes, chosen on its own ("mxfp8_e4m3" on an
+    Mxfp4Weight; fmt may then be None: a weight-only prefill with W4A8 decode steps).  None in its place means weight-only."""
+    fmt: Optional[str]
     decode: bool = False
+    decode_fmt: Optional[str] = None
 
 
-A8W8_BK, A8W8_SKINNY_MAX_M = _D["ULL_A8W8_BK"], _D["ULL_A8W8_SKINNY_MAX_M"]
-_ROUTES = {_D["ULL_ROUTE_" + r.upper()]: r for r in ("gemm", "gemv", "skinny", "a8w8", "w4a8", "a8w8_skinny", "w4a4")}
+A8W8_BK, A8W8_SKINNY_MAX_M, W4A8_SKINNY_MAX_M = _D["ULL_A8W8_BK"], _D["ULL_A8W8_SKINNY_MAX_M"], _D["ULL_W4A8_SKINNY_MAX_M"]
+_ROUTES = {_D["ULL_ROUTE_" + r.upper()]: r for r in ("gemm", "gemv", "skinny", "a8w8", "w4a8", "a8w8_skinny", "w4a4", "w4a8_skinny")}
 _WF = {None: _lib.WF_ELEM, "fp8": _lib.WF_FP8, "mxfp4": _lib.WF_MXFP4}
 _AF = {"fp8_e4m3": _D["ULL_AF_FP8"], "mxfp8_e4m3": _D["ULL_AF_MXFP8"], "mxfp4_e2m1": _D["ULL_AF_MXFP4"]}
 
@@ -439,10 +442,12 @@ def _linear_route(M: int, N: int, K: int, ldw: int, tune: int, wfmt: Optional[st
     """(route, rms_first) of a Linear x [M, K] @ w.T, w [N, K] with row pitch ldw; wfmt: None for a 16-bit weight, else its `fmt_name`.
     route "gemm": the tiled GEMM; "gemv": the weight-streaming GEMV at decode shapes; "skinny": batched decode steps against LLaMA-sized
     weights on the matrix cores; "a8w8" (linear_a8w8) / "w4a8" (linear_w4a8) / "w4a4" (linear_w4a4): quantized activations where aq pairs with the weight format and
-    the weight-only rule says "gemm"; "a8w8_skinny" (linear_a8w8_skinny): aq.decode on fp8 weights.
+    the weight-only rule says "gemm"; "a8w8_skinny" (linear_a8w8_skinny): aq.decode on fp8 weights; "w4a8_skinny" (linear_w4a8_skinny):
+    aq.decode_fmt "mxfp8_e4m3" on mxfp4 weights.
     rms_first: a requested RMSNorm is a launch of its own ahead of the Linear (False: the route's kernel fuses it)."""
     af = _D["ULL_AF_NONE"] if aq is None else _AF.get(aq.fmt, _D["ULL_AF_NONE"])
-    r = _lib.query("ull_linear_route", M, N, K, ldw, _WF[wfmt], af, bool(aq is not None and aq.decode), tune)
+    a_decode = 0 if aq is None else _AF[aq.decode_fmt] if aq.decode_fmt is not None else int(aq.decode)
+    r = _lib.query("ull_linear_route", M, N, K, ldw, _WF[wfmt], af, a_decode, tune)
     return _ROUTES[r & 255], bool(r >> 8)
 
 
@@ -457,6 +462,7 @@ a8w8_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("fp8_e4m3")) == "a8w
 w4a8_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("mxfp8_e4m3")) == "w4a8"                        # noqa: E731
 w4a4_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("mxfp4_e2m1")) == "w4a4"                        # noqa: E731
 a8w8_decode_takes = lambda M, N, K, w: linear_route(M, w, ActQuant("fp8_e4m3", True)) == "a8w8_skinny"      # noqa: E731
+w4a8_decode_takes = lambda M, N, K, w: linear_route(M, w, ActQuant(None, False, "mxfp8_e4m3")) == "w4a8_skinny"    # noqa: E731
 
 
 @functools.lru_cache(maxsize=None)
@@ -583,16 +589,21 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
 
 # ---- quantized activations on quantized weights (quantize_weights(activations=, activation_scope=)) ---------------------------------------
 # Which Linear takes which kernel is `_linear_route`'s decision alone; `linear(..., act_quant=)` carries it out (`_linear_a8`) through the
-# per-kernel wrappers linear_a8w8 / linear_w4a8 / linear_w4a4 / linear_a8w8_skinny, each the only call site of its entry.
-A8_ROUTES = ("a8w8", "w4a8", "a8w8_skinny", "w4a4")
+# per-kernel wrappers linear_a8w8 / linear_w4a8 / linear_w4a4 / linear_a8w8_skinny / linear_w4a8_skinny, each the only call site of its entry.
+A8_ROUTES = ("a8w8", "w4a8", "a8w8_skinny", "w4a4", "w4a8_skinny")
 
 
 def _linear_a8(route: str, x, w, residual, swiglu: bool, out, out_f32: bool, rms_w, rms_eps: float) -> torch.Tensor:
-    """`linear` on an A8 route: the RMSNorm rides in the row quantization ("a8w8_skinny") or is a launch of its own, then the route's wrapper."""
+    """`linear` on an A8 route: the RMSNorm rides in the row quantization ("a8w8_skinny", "w4a8_skinny") or is a launch of its own, then the
+    route's wrapper."""
     kw = dict(residual=residual, swiglu=swiglu, out=out, out_f32=out_f32)
-    if route == "a8w8_skinny":
-        xq, xs = quantize_rows_fp8(x) if rms_w is None else rmsnorm_quantize_rows_fp8(x, rms_w, rms_eps)
-        y = linear_a8w8_skinny(xq, xs, w, **kw)
+    if route in ("a8w8_skinny", "w4a8_skinny"):
+        if route == "a8w8_skinny":
+            xq, xs = quantize_rows_fp8(x) if rms_w is None else rmsnorm_quantize_rows_fp8(x, rms_w, rms_eps)
+            y = linear_a8w8_skinny(xq, xs, w, **kw)
+        else:
+            xq, xs = _quantize_rows_mxfp8(x, x.shape[-1]) if rms_w is None else rmsnorm_quantize_rows_mxfp8(x, rms_w, rms_eps)
+            y = linear_w4a8_skinny(xq, xs, w, **kw)
         return y if x.dim() == 2 or out is not None else y.view(*x.shape[:-1], y.shape[-1])
     if rms_w is not None:
         x = rmsnorm(x, rms_w, rms_eps)
@@ -786,6 +797,48 @@ def linear_w4a8(x: torch.Tensor, w: "Mxfp4Weight", residual: Optional[torch.Tens
     out, flags, ldr = _epilogue(x, N, swiglu, out_f32, residual, out, BF16)
     _lib.call("ull_gemm_w4a8_bf16", _p(xq), xq.stride(0), _p(xsc), xsc.stride(0), _p(wq), wq.stride(0), _p(wsc), wsc.stride(0), _p(out),
               _rows(out)[1], _p(residual), ldr, M, N, Kp, flags, _stream())
+    return out
+
+
+# ---- MXFP8 activations on MXFP4 weights at decode shapes: route "w4a8_skinny" -----------------------------------------------------------
+def rmsnorm_quantize_rows_mxfp8(x: torch.Tensor, w: torch.Tensor, eps: float):
+    """_quantize_rows_mxfp8(rmsnorm(x, w, eps), K) in one launch (ull_rmsnorm_quantize_rows_mxfp8_bf16), bit for bit: (codes uint8 [M, K], scale
+    bytes uint8 [M, Mxfp4Weight.scale_pitch(K)] in the order the W4A8 kernels read) of the normed bf16 rows, which are never written.
+    K % 32 == 0; scale bytes that belong to no block (spare bytes of the pitch) are 127."""
+    _chk(x, "x", BF16); _chk(w, "w", BF16)
+    M, ldx = _rows(x)
+    K = x.shape[-1]
+    if K % 32:
+        raise RuntimeError(f"u-llava_amd.rmsnorm_quantize_rows_mxfp8: K must be a multiple of 32, got {K}")
+    lds = Mxfp4Weight.scale_pitch(K)
+    codes = torch.empty(M, K, device=x.device, dtype=torch.uint8)
+    if lds == K // 32:
+        scales = torch.empty(M, lds, device=x.device, dtype=torch.uint8)
+    else:
+        scales = torch.full((M, lds), 127, device=x.device, dtype=torch.uint8)
+    _lib.call("ull_rmsnorm_quantize_rows_mxfp8_bf16", _p(x), ldx, _p(w), float(eps), M, K, _p(codes), K, _p(scales), lds, _stream())
+    return codes, scales
+
+
+def linear_w4a8_skinny(xq: torch.Tensor, xsc: torch.Tensor, w: "Mxfp4Weight", residual: Optional[torch.Tensor] = None, swiglu: bool = False,
+                       out: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
+    """y = epilogue(dequant(xq, xsc) @ w.T) at M <= 32 rows from MXFP8 activation codes xq uint8 [M, K] (rows contiguous, pitch a multiple of 16)
+    and their scale bytes xsc uint8 [M, >= K / 32] (`_quantize_rows_mxfp8` / rmsnorm_quantize_rows_mxfp8: the W4A8 pair's order), on the
+    weight-streaming W4A8 kernel (ull_gemm_skinny_w4a8_bf16; the only call site of that entry): linear_w4a8's arithmetic from the resident
+    MXFP4 codes and scale bytes with a summation order that depends on K alone, then `linear`'s skinny epilogue (residual / swiglu / out_f32,
+    same rounding points).  K % 128 == 0 (a padded K is the entry's to refuse)."""
+    if not isinstance(w, Mxfp4Weight):
+        raise RuntimeError("u-llava_amd.linear_w4a8_skinny: w must be an Mxfp4Weight")
+    if (xq.dtype != torch.uint8 or xq.dim() != 2 or xq.stride(1) != 1 or xsc.dtype != torch.uint8 or xsc.dim() != 2 or xsc.stride(1) != 1
+            or xsc.shape[0] != xq.shape[0]):
+        raise RuntimeError("u-llava_amd.linear_w4a8_skinny: xq uint8 [M, K] (rows contiguous), xsc uint8 [M, K / 32 or more] (rows contiguous)")
+    M, K = xq.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise RuntimeError(f"u-llava_amd.linear_w4a8_skinny: K mismatch {K} vs {w.shape[1]}")
+    out, flags, ldr = _epilogue(xq, N, swiglu, out_f32, residual, out, BF16)
+    _lib.call("ull_gemm_skinny_w4a8_bf16", _p(xq), xq.stride(0), _p(xsc), xsc.stride(0), _p(w.codes), w.codes.stride(0), _p(w.scales),
+              w.scales.stride(0), _p(out), _rows(out)[1], _p(residual), ldr, M, N, K, flags, _stream())
     return out
 
 
